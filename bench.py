@@ -2,6 +2,13 @@
 """Headline benchmark: SMO train time on the MNIST-60k one-vs-rest RBF config (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 60000] [--parallel auto|smo|cascade]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  Everything else the line can
+carry -- prediction time and accuracy on the test rows, the fits from FP64 host rows, the other solver,
+the cascades after a distributed headline, the single-GPU comparison of an N > 1 run -- runs after the
+timed steps and only with ``--full``.  ``--dump-outputs DIR`` writes the last timed fit's model (alpha, b,
+support, dual_coef) as ``DIR/<name>.npy``; the same arguments give the same inputs in every run.
 
 One "step" is one complete training run on the fixed synthetic 60k x 784 MNIST-shaped matrix
 (an SVM has no random init; the data are a deterministic synthetic draw of MNIST's shape and value
@@ -17,11 +24,11 @@ domain because MNIST itself is not available offline):
   workgroup; same support-vector set as the pairwise solve, b within the reference's own
   serial-vs-GPU spread.  ``--solver smo``: the reference's pairwise first-order trajectory, bit for
   bit the CPU oracle's (resident exact-integer Gram + persistent device SMO); the JSON line reports
-  the other solver's fit next to the headline either way.
+  the other solver's fit next to the headline either way (``--full``).
 * N > 1, ``--parallel auto`` with the decomposition solver (the default): the distributed
   decomposition solver (every GPU owns 1/N of the selection blocks and of f; one RCCL all-gather of
   candidate records per outer iteration); bit-identical to the one-GPU decomposition solver.  After
-  it, on the same ranks and under the same bracket (max over ranks), the star and the tree cascade
+  it (``--full``), on the same ranks and under the same bracket (max over ranks), the star and the tree cascade
   (BASELINE configs 5 and 4, every solve the warm-started decomposition): ``cascade_star_ms``,
   ``cascade_tree_ms`` and their rounds, SV history and critical path (``--cascade-steps``).
 * N > 1, ``--parallel smo`` (``auto`` with ``--solver smo``): ONE first-order SMO over the N GPUs
@@ -71,6 +78,37 @@ def ids_digest(ids) -> str:
 
     return hashlib.sha1(np.sort(np.asarray(ids, dtype=np.int64)).tobytes()).hexdigest()[:16]
 PREFLIGHT_ROWS = 4096
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def model_outputs(model) -> dict:
+    """What a caller of the timed fit receives: the dual variables, the threshold b, the support-vector
+    ids and their signed coefficients (a cascade returns them for its support vectors only)."""
+    r = getattr(model, "result", None)
+    if r is not None:  # CascadeSVM: the final support vectors by global id
+        return {"support": r.ids, "alpha": r.alpha, "dual_coef": np.asarray(r.alpha) * np.asarray(r.y), "b": [r.b]}
+    out = {"alpha": model.alpha_, "support": model.support_, "b": [model.b_]}
+    if hasattr(model, "dual_coef_"):
+        out["dual_coef"] = model.dual_coef_
+    return out
+
+
+def dump_outputs(directory, arrays: dict, seed: int) -> dict:
+    """Write every array as <directory>/<name>.npy in float64.  An array over its share of DUMP_MAX_BYTES
+    is cut to a fixed sample of its flattened elements (sorted indices drawn from ``seed``), the same from
+    run to run.  Returns {name: [elements written, elements in all]}."""
+    os.makedirs(directory, exist_ok=True)
+    budget = (DUMP_MAX_BYTES // max(1, len(arrays)) - 1024) // 8  # elements per file (1 KiB left for its header)
+    written = {}
+    for k, (name, v) in enumerate(sorted(arrays.items())):
+        v = np.ascontiguousarray(np.asarray(v), dtype=np.float64)
+        total = v.size
+        if total > budget:
+            idx = np.sort(np.random.default_rng(seed + k).choice(total, size=budget, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), v)
+        written[name] = [int(v.size), int(total)]
+    return written
 
 
 def main(argv=None):
@@ -103,11 +141,11 @@ def main(argv=None):
                          "exact-integer plan, every kernel value on FP64 MFMA; --parallel decomp / cascade)")
     ap.add_argument("--cascade", action="store_true", help="run the cascade even with one GPU")
     ap.add_argument("--cascade-steps", type=int, default=2,
-                    help="N > 1 with the distributed decomposition headline: the star and tree cascades (BASELINE "
+                    help="--full, N > 1 with the distributed decomposition headline: the star and tree cascades (BASELINE "
                          "configs 5 / 4) are timed after it with this many fits each, same bracket and max over "
                          "ranks (0 = skip)")
     ap.add_argument("--baseline-1gpu", type=int, default=3,
-                    help="N > 1: single-GPU fits timed after the run for speedup_vs_1gpu (0 = skip)")
+                    help="--full, N > 1: single-GPU fits timed after the run for speedup_vs_1gpu (0 = skip)")
     ap.add_argument("--wss", choices=["first", "second"], default="first",
                     help="working-set selection: first order (the reference; the headline) or the opt-in second-order")
     ap.add_argument("--solver", choices=["decomp", "smo"], default=None,
@@ -117,21 +155,31 @@ def main(argv=None):
     ap.add_argument("--max-iter", type=int, default=100000,
                     help="pair-update cap of every solve (the reference's 100,000; --rows beyond ~2M needs more)")
     ap.add_argument("--decomp-fits", "--other-solver-fits", dest="decomp_fits", type=int, default=3,
-                    help="N = 1: fits of the OTHER solver (pairwise when the headline is decomp, and vice versa) timed "
+                    help="--full, N = 1: fits of the OTHER solver (pairwise when the headline is decomp, and vice versa) timed "
                          "after the run and reported next to the headline (0 = skip)")
     ap.add_argument("--comm-timeout", type=float, default=120.0,
                     help="N > 1: seconds any rank waits on an exchange before every rank aborts its communicator "
                          "(a fit takes well under a second; a dead peer must not hang the run)")
     ap.add_argument("--f64-fits", type=int, default=3,
-                    help="N = 1: steady-state fits with FP64 host rows (the reference's H2D), reported next to the "
+                    help="--full, N = 1: steady-state fits with FP64 host rows (the reference's H2D), reported next to the "
                          "headline (0 = skip)")
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: the same launch paths on the C++ oracle (CPU tests of the torchrun / thread-rank "
                          "plumbing; N > 1 under torchrun exchanges over gloo); not a benchmark")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything that is not the headline: prediction and accuracy on "
+                         "the test rows, the FP64-row fits (--f64-fits), the other solver (--other-solver-fits), the "
+                         "cascades after a distributed headline (--cascade-steps) and the single-GPU comparison "
+                         "(--baseline-1gpu).  Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed fit returned (alpha, b, support, dual_coef) "
+                         "as DIR/<name>.npy in float64 (at most 64 MB in all: a fixed seeded sample of a larger array)")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0 or a.gpus < 1:
         ap.error("--steps must be >= 1, --warmup >= 0 and --gpus >= 1")
+    if not a.full:  # a plain run measures the headline only
+        a.f64_fits = a.decomp_fits = a.cascade_steps = a.baseline_1gpu = 0
 
     import torch
 
@@ -197,7 +245,7 @@ def main(argv=None):
         dist.init_process_group("gloo", timeout=datetime.timedelta(minutes=10))  # bootstrap store + timing max
 
     params = SVMParams(wss=2 if a.wss == "second" else 1, max_iter=a.max_iter)
-    te = synthetic_mnist(a.m, seed=a.seed, offset=a.n) if rank == 0 else None
+    te = synthetic_mnist(a.m, seed=a.seed, offset=a.n) if rank == 0 and a.full else None  # the parity fields' rows
     full = synthetic_mnist(a.n, seed=a.seed)  # every rank: the distributed SMO holds all rows on every GPU
     lo, hi = partition_bounds(a.n, world_env, rank) if multiproc else (0, a.n)
     part = full.subset(lo, hi)
@@ -467,6 +515,9 @@ def main(argv=None):
 
     ms = elapsed / a.steps * 1e3
     value = ms / 1e3
+    dumped = None
+    if a.dump_outputs and rank == 0:  # the last timed fit's model, before anything else runs
+        dumped = dump_outputs(a.dump_outputs, model_outputs(model), a.seed)
 
     # BASELINE configs 5 / 4 (the reference's multi-processor programs, mpi_svm_main2.cpp star and
     # mpi_svm_main3.cpp tree) on the same ranks after the headline: each timed like the headline steps
@@ -530,12 +581,14 @@ def main(argv=None):
         # Prediction on the 10k test rows (outside the timed region): H2D, scaling with the training
         # statistics, MFMA cross-kernel against the SVs, decision values back to the host.  The
         # reference's GPU "prediction" (38.3 s at 60k) also parses the test CSV.
-        sync()
-        tp = time.perf_counter()
-        model.decision_function(te.X)
-        sync()
-        pred_ms = (time.perf_counter() - tp) * 1e3
-        acc = model.score(te.X, te.y)
+        if a.full:
+            sync()
+            tp = time.perf_counter()
+            model.decision_function(te.X)
+            sync()
+            extra["prediction_ms_10k"] = round((time.perf_counter() - tp) * 1e3, 3)
+            extra["ref_gpu_prediction_s"] = REF_GPU_PRED_S
+            extra["accuracy"] = model.score(te.X, te.y)
         f64_ms = []
         if a.f64_fits > 0 and not cpu and a.input == "u8":  # the reference's FP64 host rows, same model
             X64 = full.X.astype(np.float64)
@@ -577,8 +630,7 @@ def main(argv=None):
                 extra["pairwise_solver"] = rec
         extra.update({
             "n_sv": int(len(model.support_)), "iterations": int(model.n_iter_), "b": float(model.b_),
-            "accuracy": acc, "stop_reason": model.stop_reason_, "timings_ms": model.timings_,
-            "prediction_ms_10k": round(pred_ms, 3), "ref_gpu_prediction_s": REF_GPU_PRED_S,
+            "stop_reason": model.stop_reason_, "timings_ms": model.timings_,
             "cold_fit_ms": warm_ms[0] if warm_ms else None, "warmup_fit_ms": warm_ms,
             "device_init_ms": device_init_ms, "solver": a.solver,
             "caveats": "timed fits reuse the library's grow-only device buffers and device context, allocated by the "
@@ -607,7 +659,7 @@ def main(argv=None):
                          "alpha replica, owns 1/N of the selection blocks and of f, and all-gathers its candidate "
                          "records once per outer iteration; the working-set solve is replicated.  Compared with "
                          "the one-GPU decomposition solver (single_gpu_s, bit_identical_to_1gpu)"}
-        if rank == 0:
+        if rank == 0 and a.full:
             extra["accuracy"] = model.score(te.X, te.y)
     elif mode == "smo":
         extra = {"n_sv": int(len(model.support_)), "iterations": int(model.n_iter_), "b": float(model.b_),
@@ -618,7 +670,7 @@ def main(argv=None):
                  "note": "one first-order SMO over all GPUs: each GPU holds 1/N of the points and its slab K(:, own) "
                          "of the exact-integer Gram; every iteration's candidates cross the GPUs over xGMI; same "
                          "iterations, alphas and b as the single-GPU trainer (bit_identical_to_1gpu)"}
-        if rank == 0:
+        if rank == 0 and a.full:
             extra["accuracy"] = model.score(te.X, te.y)
     else:
         r = model.result
@@ -646,7 +698,7 @@ def main(argv=None):
                  "note": "per_round_critical_path = [round, slowest local solve ms (tree: first layer), rank-0 "
                          "merge ms (tree: slowest rank of each later layer), their SMO iterations]; "
                          "the single-GPU trainer solves the same 60k problem in one 12,793-iteration SMO"}
-        if rank == 0:
+        if rank == 0 and a.full:
             extra["accuracy"] = model.score(te.X, te.y)
         ref = (REF_STAR_S if a.topology == "star" else REF_TREE_S).get(a.gpus)
         if ref:
@@ -735,6 +787,8 @@ def main(argv=None):
             "speedup_vs_serial": round(REF_SERIAL_S / value, 2) if a.n == 60000 else None,
             "speedup_vs_ref_gpu": round(REF_GPU_S / value, 2) if a.n == 60000 else None,
             "step_ms": step_ms,
+            "full": a.full,
+            **({"dumped_outputs": dumped} if dumped else {}),
             ("step_upload_alloc_gram_smo_fit_ms" if mode != "smo" else "step_upload_slab_smo_fit_ms"): parts,
             **extra,
         }

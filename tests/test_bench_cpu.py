@@ -6,6 +6,7 @@ import json
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
@@ -74,7 +75,7 @@ def test_bench_in_process_thread_ranks_json(capsys, topology, gpus):
 
     t0 = time.time()
     rc = bench.main(["--gpus", str(gpus), "--device", "cpu", "--rows", "1200", "--test-rows", "200", "--steps", "2",
-                     "--warmup", "1", "--topology", topology, "--baseline-1gpu", "1"])
+                     "--warmup", "1", "--topology", topology, "--full", "--baseline-1gpu", "1"])
     wall = time.time() - t0
     assert rc == 0
     line = json.loads([x for x in capsys.readouterr().out.splitlines() if x.startswith("{")][-1])
@@ -88,6 +89,47 @@ def test_bench_in_process_thread_ranks_json(capsys, topology, gpus):
     assert line["sv_history"] and len(line["per_round_critical_path"]) == line["rounds"]
     assert line["fallback_reason"] == "cpu device"  # --parallel auto: no distributed SMO on the CPU
     assert line["transport"] == "loopback"
+
+
+def test_plain_run_is_the_headline_only_and_full_adds_the_rest(capsys, tmp_path):
+    """Without --full the line carries the timed fit's own fields and nothing that takes a run of its
+    own, whatever the count options say; --full adds the parity fields.  --dump-outputs writes the last
+    timed fit's model in float64, the same from run to run."""
+    args = ["--device", "cpu", "--rows", "900", "--test-rows", "100", "--steps", "2", "--warmup", "1"]
+    assert bench.main(args + ["--baseline-1gpu", "2", "--dump-outputs", str(tmp_path / "a")]) == 0
+    plain = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+    assert plain["full"] is False and plain["steps"] == 2 and len(plain["step_ms"]) == 2
+    assert plain["ms_per_step"] > 0 and plain["stop_reason"] == "converged" and plain["n_sv"] > 0
+    for key in ("accuracy", "prediction_ms_10k", "pairwise_solver", "f64_input_fit_ms", "single_gpu_s"):
+        assert key not in plain
+    assert bench.main(args + ["--full", "--dump-outputs", str(tmp_path / "b")]) == 0
+    full = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+    assert full["full"] is True and full["accuracy"] > 0.9 and full["prediction_ms_10k"] > 0
+    assert (full["b"], full["n_sv"], full["iterations"]) == (plain["b"], plain["n_sv"], plain["iterations"])
+
+    from svm355 import SVC
+
+    tr = synthetic_mnist(900, seed=2024).compact()
+    ref = SVC(device="cpu").fit(tr.X, tr.y)
+    want = {"alpha": ref.alpha_, "support": ref.support_, "dual_coef": ref.dual_coef_, "b": [ref.b_]}
+    for d in ("a", "b"):
+        assert sorted(p.name for p in (tmp_path / d).iterdir()) == ["alpha.npy", "b.npy", "dual_coef.npy", "support.npy"]
+        for name, v in want.items():
+            got = np.load(tmp_path / d / f"{name}.npy")
+            assert got.dtype == np.float64 and np.array_equal(got, np.asarray(v, dtype=np.float64))
+    assert plain["dumped_outputs"]["alpha"] == [900, 900]
+
+
+def test_dump_outputs_samples_an_array_over_its_share(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * (1024 + 8 * 100))
+    big = np.arange(1000, dtype=np.int64)
+    w1 = bench.dump_outputs(tmp_path / "x", {"big": big, "small": [1.5]}, seed=3)
+    w2 = bench.dump_outputs(tmp_path / "y", {"big": big, "small": [1.5]}, seed=3)
+    assert w1 == w2 == {"big": [100, 1000], "small": [1, 1]}
+    a, b = np.load(tmp_path / "x" / "big.npy"), np.load(tmp_path / "y" / "big.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, b) and len(set(a.tolist())) == 100
+    assert np.all(np.diff(a) > 0) and set(a.tolist()) <= set(range(1000))
+    assert sum(p.stat().st_size for p in (tmp_path / "x").iterdir()) <= 2 * (1024 + 8 * 100)
 
 
 def test_bench_smo_refuses_cpu(capsys):
@@ -108,7 +150,7 @@ def test_bench_parallel_decomp_cpu_twin_thread_ranks(capsys):
     """--device cpu --parallel decomp: the distributed decomposition's CPU twin on thread ranks (strict
     loopback), bit-identical to the one-rank oracle solve."""
     assert bench.main(["--gpus", "2", "--device", "cpu", "--parallel", "decomp", "--rows", "600", "--steps", "1",
-                       "--baseline-1gpu", "1"]) == 0
+                       "--full", "--baseline-1gpu", "1"]) == 0
     out = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
     assert out["config"]["parallelism"] == "distributed-decomp-dp2"
     assert out["launch_form"] == "thread ranks on the CPU oracle (loopback)"

@@ -31,11 +31,38 @@ def _check_common(out, n_gpus, steps, wall_s):
     assert out["config"]["global_batch"] == 6000 and out["config"]["seq_len"] == 784
 
 
+def test_plain_one_gpu_run_times_the_steps_and_dumps_the_model(tmp_path):
+    """``bench.py --gpus 1 --steps K --warmup W`` without --full: K timed fits, the headline fields, none
+    of the extra measurements; --dump-outputs holds the model SVC.fit returns on the same rows."""
+    import numpy as np
+
+    from svm355 import SVC
+    from svm355.utils.data import synthetic_mnist
+
+    path = tmp_path / "b.json"
+    t0 = time.perf_counter()
+    rc = bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "6000", "--out", str(path),
+                     "--dump-outputs", str(tmp_path / "dump")])
+    wall = time.perf_counter() - t0
+    assert rc == 0
+    out = json.loads(path.read_text())
+    _check_common(out, 1, 3, wall)
+    assert out["full"] is False and len(out["step_ms"]) == 3 and out["stop_reason"] == "converged"
+    assert out["config"]["parallelism"] == "single-gpu" and out["solver"] == "decomp"
+    for key in ("accuracy", "prediction_ms_10k", "pairwise_solver", "f64_input_fit_ms"):
+        assert key not in out
+    tr = synthetic_mnist(6000, seed=2024).compact()
+    ref = SVC(device="cuda:0").fit(tr.X, tr.y)
+    for name, v in {"alpha": ref.alpha_, "support": ref.support_, "dual_coef": ref.dual_coef_, "b": [ref.b_]}.items():
+        got = np.load(tmp_path / "dump" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, np.asarray(v, dtype=np.float64))
+
+
 def test_bench_default_mode_two_ranks_with_the_cascades(tmp_path):
     path = tmp_path / "b.json"
     t0 = time.perf_counter()
     rc = bench.main(["--gpus", "2", "--transport", "loopback", "--steps", "1", "--warmup", "1", "--rows", "6000",
-                     "--test-rows", "1000", "--baseline-1gpu", "1", "--cascade-steps", "1", "--out", str(path)])
+                     "--test-rows", "1000", "--full", "--baseline-1gpu", "1", "--cascade-steps", "1", "--out", str(path)])
     wall = time.perf_counter() - t0
     assert rc == 0
     out = json.loads(path.read_text())
@@ -61,7 +88,7 @@ def test_torchrun_one_process_default_decomp():
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "1", "--parallel", "decomp",
-           "--rows", "6000", "--test-rows", "1000", "--steps", "2", "--warmup", "1", "--baseline-1gpu", "1",
+           "--rows", "6000", "--test-rows", "1000", "--steps", "2", "--warmup", "1", "--full", "--baseline-1gpu", "1",
            "--cascade-steps", "1"]
     t0 = time.perf_counter()
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
@@ -101,7 +128,7 @@ def test_torchrun_processes_share_one_gpu_over_hostcomm(nproc, rows):
     run on the same per-process ranks too."""
     casc = "1" if rows == 60000 else "0"
     p, wall = _torchrun(nproc, "--parallel", "decomp", "--transport", "hostcomm", "--rows", str(rows),
-                        "--test-rows", "1000", "--steps", "1", "--warmup", "1", "--baseline-1gpu", "1",
+                        "--test-rows", "1000", "--steps", "1", "--warmup", "1", "--full", "--baseline-1gpu", "1",
                         "--cascade-steps", casc)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
@@ -125,7 +152,7 @@ def test_torchrun_hostcomm_on_real_valued_rows(nproc):
     real-valued rows (FP64-MFMA kernel values), exchanging over gloo on the one GPU: the model equals the
     one-GPU FP64 decomposition bit for bit."""
     p, wall = _torchrun(nproc, "--parallel", "decomp", "--transport", "hostcomm", "--input", "f64-real", "--rows",
-                        "6000", "--test-rows", "500", "--steps", "1", "--warmup", "1", "--baseline-1gpu", "1",
+                        "6000", "--test-rows", "500", "--steps", "1", "--warmup", "1", "--full", "--baseline-1gpu", "1",
                         "--cascade-steps", "0")
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
@@ -140,7 +167,7 @@ def test_torchrun_world_not_dividing_8_converges_to_the_same_model():
     a multiple of 8 x world, another trajectory to the same optimum -- the preflight checks convergence,
     b and the SV count instead of bit identity, and the line says so (bit_identity_expected false)."""
     p, wall = _torchrun(3, "--parallel", "decomp", "--transport", "hostcomm", "--rows", "6000", "--test-rows", "500",
-                        "--steps", "1", "--warmup", "1", "--baseline-1gpu", "1", "--cascade-steps", "0")
+                        "--steps", "1", "--warmup", "1", "--full", "--baseline-1gpu", "1", "--cascade-steps", "0")
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
     out = json.loads(lines[0])
@@ -166,7 +193,7 @@ def test_a_failing_cascade_after_the_headline_is_reported_not_fatal():
     (SVM355_BENCH_CASCADE_FAIL) ends that cascade on every rank, the line still carries the headline and
     the error, and every process exits 0 (per-process launch, two ranks sharing the GPU)."""
     p, wall = _torchrun(2, "--parallel", "decomp", "--transport", "hostcomm", "--rows", "6000", "--test-rows", "500",
-                        "--steps", "1", "--warmup", "1", "--baseline-1gpu", "0", "--cascade-steps", "1",
+                        "--steps", "1", "--warmup", "1", "--full", "--baseline-1gpu", "0", "--cascade-steps", "1",
                         "--comm-timeout", "30", env_extra={"SVM355_BENCH_CASCADE_FAIL": "1,1"}, timeout=240)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
@@ -180,7 +207,7 @@ def test_torchrun_refuses_to_time_gloo_under_the_rccl_label():
     over another transport -- every process exits non-zero and rank 0 names the failing rank and step
     (VERDICT r5 weak #4: a SCALE run must never time gloo exchanges under an RCCL label)."""
     p, wall = _torchrun(1, "--parallel", "decomp", "--rows", "6000", "--test-rows", "500", "--steps", "1",
-                        "--warmup", "1", "--baseline-1gpu", "1", "--cascade-steps", "0",
+                        "--warmup", "1", "--full", "--baseline-1gpu", "1", "--cascade-steps", "0",
                         env_extra={"SVM355_RCCL_LIB": "/nonexistent/librccl.so"}, timeout=240)
     assert p.returncode != 0 and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     err = p.stdout + p.stderr
@@ -192,7 +219,7 @@ def test_torchrun_falls_back_to_gloo_when_allowed_and_says_so():
     transport before any timed fit, config.parallelism ends in -gloo, the line reports why, and the
     preflight solve equals the one-GPU solve."""
     p, wall = _torchrun(1, "--parallel", "decomp", "--rows", "6000", "--test-rows", "500", "--steps", "1",
-                        "--warmup", "1", "--baseline-1gpu", "1", "--cascade-steps", "0", "--allow-transport-fallback",
+                        "--warmup", "1", "--full", "--baseline-1gpu", "1", "--cascade-steps", "0", "--allow-transport-fallback",
                         env_extra={"SVM355_RCCL_LIB": "/nonexistent/librccl.so"}, timeout=240)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]

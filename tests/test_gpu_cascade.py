@@ -162,7 +162,8 @@ def test_torchrun_bench_per_process_rccl_rank(data):
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(root / "bench.py"), "--gpus", "1", "--cascade", "--rows", str(N),
-           "--test-rows", str(M), "--seed", "21", "--steps", "2", "--warmup", "1", "--baseline-1gpu", "1"]
+           "--test-rows", str(M), "--seed", "21", "--steps", "2", "--warmup", "1", "--full",
+           "--baseline-1gpu", "1"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=180)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]

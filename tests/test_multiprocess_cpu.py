@@ -178,7 +178,7 @@ def test_torchrun_decomp_ranks_match_one_rank(nproc):
     candidate records all-gathered per outer iteration.  alpha, b and the iteration counts must equal
     the one-rank solve (bench.py's bit_identical_to_1gpu compares every bit of alpha)."""
     out = _torchrun_bench(nproc, "--parallel", "decomp", "--rows", "1200", "--test-rows", "200", "--steps", "1",
-                          "--warmup", "0", "--baseline-1gpu", "1")
+                          "--warmup", "0", "--full", "--baseline-1gpu", "1")
     assert out["n_gpus"] == nproc and out["launch"].startswith("torchrun")
     assert out["config"]["parallelism"] == f"distributed-decomp-dp{nproc}"
     assert out["launch_form"] == "one rank per process (CPU oracle over gloo)"
