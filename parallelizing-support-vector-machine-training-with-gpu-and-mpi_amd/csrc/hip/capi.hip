@@ -54,6 +54,7 @@ int warm_copy_engine(DeviceCtx* ctx) {
 int tu_warm_capi(hipStream_t s);
 int tu_warm_cascade_dev(hipStream_t s);
 int tu_warm_decomp(hipStream_t s);
+int tu_warm_decomp_inner(hipStream_t s);
 int tu_warm_dsmo(hipStream_t s);
 int tu_warm_gram_mfma(hipStream_t s);
 int tu_warm_igram(hipStream_t s);
@@ -70,8 +71,8 @@ static bool first_context_on(int device) {
 }
 int tu_warm_all(hipStream_t s) {
   int bad = 0;
-  for (auto fn : {tu_warm_capi, tu_warm_cascade_dev, tu_warm_decomp, tu_warm_dsmo, tu_warm_gram_mfma, tu_warm_igram,
-                  tu_warm_prep_kernels, tu_warm_rowcache, tu_warm_smo})
+  for (auto fn : {tu_warm_capi, tu_warm_cascade_dev, tu_warm_decomp, tu_warm_decomp_inner, tu_warm_dsmo,
+                  tu_warm_gram_mfma, tu_warm_igram, tu_warm_prep_kernels, tu_warm_rowcache, tu_warm_smo})
     bad |= fn(s);
   return bad;
 }

@@ -86,6 +86,20 @@ struct DeviceCtx {
     ws_bytes = sz;
     return SVM_OK;
   }
+  // The library-owned buffer `gram` as a grow-only scratch of at least `bytes` (the decomposition solver's
+  // quantised rows or row norms); what it held is lost when it grows.
+  int ensure_gram_bytes(size_t bytes) {
+    if (bytes <= gram_bytes) return SVM_OK;
+    if (gram) {
+      SVMD_CHECK(hipStreamSynchronize(stream));
+      SVMD_CHECK(hipFree(gram));
+      gram = nullptr;
+      gram_bytes = 0;
+    }
+    SVMD_CHECK(hipMalloc(reinterpret_cast<void**>(&gram), bytes));
+    gram_bytes = bytes;
+    return SVM_OK;
+  }
   double* ensure_rc_cache(size_t bytes) {  // nullptr when the allocation fails
     if (bytes <= rc_cache_bytes) return rc_cache;
     if (rc_cache) {

@@ -1,5 +1,5 @@
-// Working-set decomposition SMO (decomp.hip): shapes and the host driver, shared by the one-GPU C ABI
-// (svmd_train_decomp_u8) and the distributed solve over a cascade group or process rank
+// Working-set decomposition SMO (decomp.hip; the inner solve: decomp_inner.hip): shapes and the host driver,
+// shared by the one-GPU C ABI (svmd_train_decomp_u8) and the distributed solve over a cascade group or process rank
 // (cascade_dev.hip: svmd_cascade_group_decomp / svmd_cascade_rank_decomp).
 #pragma once
 #include <cstdint>

@@ -12,7 +12,7 @@
 //                         main3.cpp:213), then the sorted, de-duplicated working set W (m <= q);
 //   3. K(W, W)            the working set's rows gathered, its m x m Gram on the exact-integer path
 //                         (the same kernel values as the full Gram, igram.hip);
-//   4. ws_inner_kernel    ONE workgroup runs first-order SMO on W with the reference's update
+//   4. ws_inner_kernel    (decomp_inner.hip) ONE workgroup runs first-order SMO on W with the reference's update
 //                         arithmetic (clip bounds, eta, stop reasons) -- an iteration is a workgroup
 //                         reduction and two L2-resident row reads, no grid exchange -- until W's own
 //                         gap is below max(tau, gap / 10);
@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "decomp.h"
+#include "decomp_dev.h"
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
 #include "persist.h"
@@ -42,57 +43,7 @@
 namespace svm355 {
 namespace {
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-struct DecompHost {  // pinned: the PROF build's phase totals (the loop state is DecompCtl, on the device)
-  int64_t prof[12];  // clock64 ticks per phase summed over iterations; [6] kernel clock64, [7] wall ticks;
-                     // [8..11] the second-order j phase split (row i, gains + wave reduction, publish +
-                     // barrier, fold)
-};
-
-// The outer loop's state on the device: the kernels of an outer iteration read and advance it, so the
-// host enqueues several outer iterations between synchronisations (a stopped solve turns the rest of
-// the batch into no-op launches).  stop = SVM_STOP_RUNNING (0) while running; kStopInternal: the working
-// set came out outside [2, kMaxWS] (a bug).
-struct DecompCtl {
-  int32_t stop, m;
-  double b_high, b_low;      // of the last working-set build
-  double tau_in;             // the next inner solve's stop tolerance
-  int64_t max_inner;         // and its iteration cap
-  int64_t outer, inner_total, changed_total, last_inner_it;
-  int32_t last_inner_reason;
-  int32_t shrunk;            // a shrink pass has run since the start or the last unshrink
-  int64_t n_active;          // this GPU's points not shrunk
-  int64_t passes;            // shrink passes run
-  int32_t last_m, pad2;      // the last inner solve's working-set size (the Newton polish's arming)
-  int64_t newton_steps;      // Newton polish steps applied (decomp_newton.h)
-};
-
-// The Newton polish's knobs on the device (NewtonCfg).
-struct NwDev {
-  int32_t on, every, per_solve, repeat, max_free, pad;
-  double frac;
-};
-constexpr int32_t kStopInternal = -100;
-
-// The control block's host copy, written by the kernel that last changes it in an outer iteration (the
-// inner solve, or the build when it stops the solve) with plain vector stores into pinned host memory:
-// visible to the host once the batch's event has completed, with no copy in the stream.
-__device__ __forceinline__ void publish_ctl(const DecompCtl& c, DecompCtl* __restrict__ pub) {
-  if (pub) *pub = c;
-}
-
-constexpr int kSelNT = 256, kSelE = 16;  // per-block selection: up to 4096 points per block
-constexpr int kMaxWS = 1024;             // working-set capacity (one 1024-thread inner workgroup)
-
-// A working-set candidate: global point id (-1 = none) and its f.  Candidates carry f because in the
-// distributed solve a GPU holds f only for its own points (every GPU holds alpha and y for all).
-struct CandRec {
-  double f;
-  int32_t id, pad;
-};
-
+// ---- select ---------------------------------------------------------------------------------------------
 // Per block b of `per` points of this GPU's slice (local rows [b per, (b + 1) per), global ids lo +
 // local): the T most violating points of I_high (smallest f) and of I_low (largest f) in wave_arg's
 // order (value, then lowest index): every wave's own T best by T wave arg-reductions (the winner
@@ -258,6 +209,7 @@ __global__ __launch_bounds__(kSelNT) void ws_select_wide_kernel(const double* __
   }
 }
 
+// ---- build and gather -----------------------------------------------------------------------------------
 // One workgroup over the L gathered candidates (Lr per GPU, GPU-major; the first Lh of each GPU's
 // are I_high picks, T per selection block, the rest I_low): b_high = min f over the I_high
 // candidates, b_low = max f over the I_low ones (the global extremes: every block's first pick is its
@@ -384,970 +336,6 @@ __global__ __launch_bounds__(64) void ws_gather_kernel(const int8_t* __restrict_
   }
 }
 
-// ---- Newton polish of the working set's free variables (decomp_newton.h) ---------------------------------
-// The inner workgroup's step on W's free set F (positions with c_lo < alpha < c_hi): the Cholesky of
-// K_FF with the right-hand sides f_F and 1 as two extra rows, the back substitution, b and u, the step
-// cut at the first bound, alpha and f of every position of W updated.  gA / gF: W's alpha and f by
-// position (the caller's registers spilled there around the call); Amat: (|F| + 2) x ldA scratch.
-// Every entry's arithmetic is newton_step_ref's, in its order (decomp_newton.h):
-//   * the factorisation is left-looking in panels of kNwPW columns: a row's panel entries first take the
-//     terms of every earlier column (ascending j, from the panel's own rows staged in LDS), then wave 0
-//     factors the panel in LDS column by column (the diagonal's sqrt, the divisions, the updates of the
-//     panel's later columns) with no workgroup barrier;
-//   * the back substitution goes by blocks of 64 columns from the last: wave 0 solves the block's
-//     triangle (staged in LDS) one column at a time, then every thread applies the block's 64 x to its
-//     entries below, in descending column order;
-//   * sums and the step's arg-min in the sequential order (thread 0; wave_arg's value-then-lowest-index).
-// Returns 0 (nothing changed), 1 (full step) or 2 (cut at a bound), the same in every thread.
-constexpr int kNwPW = 16;      // panel width
-constexpr int kNwMax = 512;    // |F| bound of the LDS buffers (NewtonCfg::max_free is clamped to it)
-// The factorisation's row updates for one panel (newton_wg): pb[r][c] = A[p0 + r][p0 + c] - sum_{j < p0}
-// L[p0 + r][j] L[p0 + c][j] (ascending j) for the panel's rows r < ract and columns c < pw (lower entries;
-// the right-hand-side rows nf, nf + 1 take every column), lp[j][c] = L[p0 + c][j] -- on FP64 MFMA
-// (v_mfma_f64_16x16x4f64): a wave per 16-row tile of the panel rows,
-// 16 columns, k-steps of 4 columns j..j+3.  The instruction sums its four products into the accumulator
-// as four fused multiply-adds in k order -- measured bit for bit against the chain c = fma(a0, b0, c);
-// ... fma(a3, b3, c) on 512,000 random entries (bench_kernels/mfma_f64_order.hip) -- so with A = -L (exact)
-// every entry takes exactly newton_step_ref's ascending fma chain.  Lane l: A = -L[p0 + row0 + (l & 15)]
-// [j + (l >> 4)], B = L[p0 + (l & 15)][j + (l >> 4)] (lp[j][c]); D: col = l & 15, row = (l >> 4) + 4 r.
-__device__ __forceinline__ void newton_rows_mfma(const double* __restrict__ Amat, int64_t ldA,
-                                                 const double* __restrict__ lp, double* __restrict__ pb, int p0, int pw,
-                                                 int nf, int ract, int lane, int w, int nw) {
-  const int col = lane & 15, g = lane >> 4;
-  const int ntile = (ract + 15) / 16;
-  for (int tile = w; tile < ntile; tile += nw) {
-    const int r0 = tile * 16;
-    const int ar = r0 + col;                 // the A operand's row (panel-local)
-    const bool arv = ar < ract;
-    const double* arow = Amat + int64_t(p0 + (arv ? ar : 0)) * ldA;
-    f64x4 acc;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rr = r0 + g + 4 * r, i = p0 + rr;
-      acc[r] = rr < ract && col < pw && (i >= nf || p0 + col <= i) ? Amat[int64_t(i) * ldA + p0 + col] : 0.0;
-    }
-    // A operands 16 k-steps (64 columns) at a time, the next 16 loaded while these run: one wave per SIMD,
-    // so only loads in flight hide their latency; k-steps at or beyond p0 are skipped (uniform), never
-    // run with zero operands (an added 0 could flip the sign of a zero)
-    // (the loads are unconditional -- columns up to p0 + 127 < kMaxWS stay inside Amat's row, and what
-    // lies beyond p0 is never used -- so all 16 are in flight together; a branch around each would make
-    // the compiler wait for every load before the next)
-    double nx[16];
-    auto load16 = [&](int j) {
-#pragma unroll
-      for (int s2 = 0; s2 < 16; ++s2) {
-        const double v = arow[j + 4 * s2 + g];
-        nx[s2] = arv ? -v : 0.0;
-      }
-    };
-    load16(0);
-    for (int j = 0; j < p0; j += 64) {
-      double av[16];
-#pragma unroll
-      for (int s2 = 0; s2 < 16; ++s2) av[s2] = nx[s2];
-      load16(j + 64);
-      if (j + 64 <= p0) {
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s2], lp[(j + 4 * s2 + g) * kNwPW + col], acc, 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2)
-          if (j + 4 * s2 < p0)
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s2], lp[(j + 4 * s2 + g) * kNwPW + col], acc, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rr = r0 + g + 4 * r;
-      if (rr < ract) pb[rr * kNwPW + col] = acc[r];
-    }
-  }
-}
-
-__device__ __forceinline__ int newton_wg(int m, const double* __restrict__ Kw, int64_t ldw, const int8_t* __restrict__ sy,
-                                      double* __restrict__ gA, double* __restrict__ gF, double* __restrict__ Amat,
-                                      double C, double eps, int max_free, int64_t* __restrict__ prof = nullptr) {
-  constexpr int64_t ldA = kMaxWS;
-  __shared__ int32_t fidx[kMaxWS];
-  __shared__ __attribute__((aligned(16))) double pb[(kNwMax + 2) * kNwPW];  // the panel's rows; later x1, x2, u
-  __shared__ __attribute__((aligned(16))) double lp[kNwMax * kNwPW];        // the panel's own rows of L (as [j][c]); later s1, s2, the diagonal blocks
-  __shared__ int32_t s_wc[16];
-  __shared__ int32_t s_fail, s_blk;
-  __shared__ double s_t, s_b;
-  __shared__ double s_wv[16];
-  __shared__ uint32_t s_wi[16];
-  const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, w = t >> 6, nw = nt >> 6;
-  const double c_hi = C - eps, c_lo = 0.0 + eps;
-  if (prof && t == 0) prof[7] = wall_clock64();
-  // 1. the free positions in ascending order
-  int base = 0;
-  for (int c0 = 0; c0 < m; c0 += nt) {
-    const int k = c0 + t;
-    const double ak = k < m ? gA[k] : 0.0;
-    const bool fr = k < m && ak > c_lo && ak < c_hi;
-    const unsigned long long bal = __ballot(fr);
-    if (lane == 0) s_wc[w] = __popcll(bal);
-    __syncthreads();
-    int r = __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
-    for (int q = 0; q < nw; ++q) {
-      if (q < w) r += s_wc[q];
-      tot += s_wc[q];
-    }
-    if (fr) fidx[base + r] = k;
-    base += tot;
-    __syncthreads();
-  }
-  const int nf = base;
-  if (nf < 2 || nf > min(max_free, kNwMax)) return 0;
-  if (prof && threadIdx.x == 0) prof[0] = wall_clock64();
-  // 2. A = K_FF (lower) and the right-hand sides f_F, 1 (rows nf, nf + 1); the lower triangle as one flat
-  // range of nf (nf + 1) / 2 entries (row i starts at i (i + 1) / 2), 32 independent gathers per thread
-  {
-    constexpr int U = 32;
-    const int64_t ne = int64_t(nf) * (nf + 1) / 2;
-    for (int64_t e0 = t; e0 < ne; e0 += U * int64_t(nt)) {
-      double v[U];
-      int64_t dst[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t e1 = e0 + int64_t(u) * nt, e = min(e1, ne - 1);  // clamped: the gathers are unconditional
-        int i = int((__builtin_sqrt(8.0 * double(e) + 1.0) - 1.0) * 0.5);
-        i = int64_t(i) * (i + 1) / 2 > e ? i - 1 : int64_t(i + 1) * (i + 2) / 2 <= e ? i + 1 : i;
-        const int k = int(e - int64_t(i) * (i + 1) / 2);
-        v[u] = Kw[int64_t(fidx[i]) * ldw + fidx[k]];
-        dst[u] = e1 < ne ? int64_t(i) * ldA + k : -1;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (dst[u] >= 0) Amat[dst[u]] = v[u];
-    }
-  }
-  for (int k = t; k < nf; k += nt) {
-    Amat[int64_t(nf) * ldA + k] = gF[fidx[k]];
-    Amat[int64_t(nf + 1) * ldA + k] = 1.0;
-  }
-  if (t == 0) s_fail = 0;
-  __threadfence_block();
-  __syncthreads();
-  if (prof && threadIdx.x == 0) prof[1] = wall_clock64();
-  // 3. the factorisation, a panel of kNwPW columns at a time: every panel row takes the terms of the earlier
-  // columns (newton_rows, ascending j; the panel's own rows of L staged in LDS as lp[j][c]) into pb, wave 0
-  // factors the panel's diagonal block in registers (a lane per row, readlane broadcasts), and a thread per
-  // row then solves the rows below the block against it (ascending kk) and stores the panel to Amat.
-  double* dblk = pb;  // the panel's diagonal block, kNwPW x kNwPW
-  int64_t pt0 = 0;
-  auto pstamp = [&](int k) {
-    if (prof && t == 0) {
-      const int64_t now = wall_clock64();
-      if (pt0) prof[k] += now - pt0;
-      pt0 = now;
-    }
-  };
-  if (prof && t == 0) prof[8] = prof[9] = prof[10] = prof[11] = 0;
-  for (int p0 = 0; p0 < nf; p0 += kNwPW) {
-    const int pw = min(kNwPW, nf - p0);
-    pstamp(11);
-    for (int e = t; e < kNwPW * p0; e += nt) {  // lp[j][c] = L[p0 + c][j], j < p0
-      const int j = e / kNwPW, c = e - j * kNwPW;
-      lp[e] = c < pw ? Amat[int64_t(p0 + c) * ldA + j] : 0.0;
-    }
-    __syncthreads();
-    // the earlier columns' terms on the panel's rows [p0, nf + 2), into pb[r][c] (r = row - p0): a thread per
-    // row below 129 rows... above 128 rows (up to 3 rows per thread), 2 threads per row (8 columns each)
-    // up to 128, 4 (4 columns each) up to 64 -- every lane busy however few rows are left
-    const int ract = nf + 2 - p0;
-    newton_rows_mfma(Amat, ldA, lp, pb, p0, pw, nf, ract, lane, w, nw);
-    pstamp(8);
-    __syncthreads();
-    if (w == 0) {  // the diagonal block in wave 0's registers: lane r = row p0 + r
-      double dr[kNwPW];
-#pragma unroll
-      for (int c = 0; c < kNwPW; ++c) dr[c] = lane < pw ? dblk[lane * kNwPW + c] : 0.0;
-      bool bad = false;
-#pragma unroll
-      for (int kk = 0; kk < kNwPW; ++kk) {
-        if (kk < pw) {
-          const double d = read_lane64(dr[kk], kk);  // row kk's updated diagonal
-          bad = bad || !(d > 1e-12);
-          const double lkk = d > 1e-12 ? __builtin_sqrt(d) : 1.0;
-          if (lane == kk) dr[kk] = lkk;
-          if (lane > kk) dr[kk] = dr[kk] / lkk;
-#pragma unroll
-          for (int k2 = kk + 1; k2 < kNwPW; ++k2)
-            if (k2 < pw) {
-              const double lk2 = read_lane64(dr[kk], k2);  // L[p0 + k2][p0 + kk]
-              if (lane >= k2) dr[k2] = __builtin_fma(-dr[kk], lk2, dr[k2]);
-            }
-        }
-      }
-      if (lane < pw)
-#pragma unroll
-        for (int c = 0; c < kNwPW; ++c) dblk[lane * kNwPW + c] = dr[c];
-      if (lane == 0 && bad) s_fail = 1;
-    }
-    __syncthreads();
-    pstamp(9);
-    if (s_fail) return 0;
-    // the rows below the block (and the two right-hand sides) against it, a thread per row; then every
-    // row to Amat
-    for (int r = t; r < ract; r += nt) {
-      const int i = p0 + r;
-      double sv[kNwPW];
-#pragma unroll
-      for (int c2 = 0; c2 < kNwPW / 2; ++c2) {
-        const f64x2 v = reinterpret_cast<const f64x2*>(pb + r * kNwPW)[c2];
-        sv[2 * c2] = v[0];
-        sv[2 * c2 + 1] = v[1];
-      }
-      if (r >= pw) {
-#pragma unroll
-        for (int kk = 0; kk < kNwPW; ++kk)
-          if (kk < pw) {
-            sv[kk] = sv[kk] / dblk[kk * kNwPW + kk];
-#pragma unroll
-            for (int k2 = kk + 1; k2 < kNwPW; ++k2)
-              if (k2 < pw) sv[k2] = __builtin_fma(-sv[kk], dblk[k2 * kNwPW + kk], sv[k2]);
-          }
-      }
-#pragma unroll
-      for (int c = 0; c < kNwPW; ++c)
-        if (c < pw && (i >= nf || p0 + c <= i)) Amat[int64_t(i) * ldA + p0 + c] = sv[c];
-    }
-    __threadfence_block();
-    __syncthreads();
-    pstamp(10);
-  }
-  if (prof && threadIdx.x == 0) prof[2] = wall_clock64();
-  // 4. back substitution: s1 / s2 = z (the right-hand-side rows), x = L^-T z, by blocks of 64 columns
-  double* s1 = lp;
-  double* s2 = lp + kNwMax;
-  double* dB = lp + 2 * kNwMax;  // the block's triangle, 64 x 64
-  double* x1 = pb;
-  double* x2 = pb + kNwMax;
-  for (int k = t; k < nf; k += nt) {
-    s1[k] = Amat[int64_t(nf) * ldA + k];
-    s2[k] = Amat[int64_t(nf + 1) * ldA + k];
-  }
-  for (int jb = (nf - 1) / 64 * 64; jb >= 0; jb -= 64) {
-    const int je = min(jb + 64, nf), bw = je - jb;
-    for (int e = t; e < 64 * 64; e += nt) {
-      const int r = e >> 6, c = e & 63;
-      dB[e] = r < bw && c <= r ? Amat[int64_t(jb + r) * ldA + jb + c] : 0.0;
-    }
-    __syncthreads();
-    if (w == 0) {  // the block's triangle in registers: lane i holds column i (L_ji, j >= i) and s_i
-      double col[64];
-#pragma unroll
-      for (int r = 0; r < 64; ++r) col[r] = dB[r * 64 + lane];
-      const int i = jb + lane;
-      double a1 = i < je ? s1[i] : 0.0, a2 = i < je ? s2[i] : 0.0;
-#pragma unroll
-      for (int r = 63; r >= 0; --r) {
-        if (r < bw) {  // j = jb + r, descending
-          const double ljj = read_lane64(col[r], r);
-          const double xa = read_lane64(a1, r) / ljj, xb = read_lane64(a2, r) / ljj;
-          if (lane == r) {
-            x1[jb + r] = xa;
-            x2[jb + r] = xb;
-          }
-          if (lane < r) {
-            a1 = __builtin_fma(-col[r], xa, a1);
-            a2 = __builtin_fma(-col[r], xb, a2);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    for (int i = t; i < jb; i += nt) {  // the block's columns on the entries below it, descending j
-      double a1 = s1[i], a2 = s2[i];
-      for (int j0 = je - 1; j0 >= jb; j0 -= 32) {
-        double l[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) l[u] = Amat[int64_t(max(j0 - u, jb)) * ldA + i];  // unconditional: all in flight
-#pragma unroll
-        for (int u = 0; u < 32; ++u)
-          if (j0 - u >= jb) {
-            a1 = __builtin_fma(-l[u], x1[j0 - u], a1);
-            a2 = __builtin_fma(-l[u], x2[j0 - u], a2);
-          }
-      }
-      s1[i] = a1;
-      s2[i] = a2;
-    }
-    __syncthreads();
-  }
-  if (prof && threadIdx.x == 0) prof[3] = wall_clock64();
-  // 5. b = sum x1 / sum x2 (ascending)
-  if (t == 0) {
-    double S1 = 0.0, S2 = 0.0;
-    for (int k = 0; k < nf; ++k) {
-      S1 += x1[k];
-      S2 += x2[k];
-    }
-    const bool ok = S2 > 0.0 && __builtin_isfinite(S1);
-    s_fail = ok ? 0 : 1;
-    s_b = ok ? S1 / S2 : 0.0;
-  }
-  __syncthreads();
-  if (s_fail) return 0;
-  // 6. the step's cut: min over k of the bound ratios (value, then lowest k)
-  const double b = s_b;
-  double* dal = lp;  // dalpha by F position (s1 / s2 are consumed)
-  VI best{__builtin_inf(), kSentinel};
-  for (int k = t; k < nf; k += nt) {
-    const double u = __builtin_fma(b, x2[k], -x1[k]);
-    const double dk = sy[fidx[k]] == 1 ? u : -u;
-    dal[k] = dk;
-    const double ak = gA[fidx[k]];
-    const double tk = dk > 0.0 ? (C - ak) / dk : dk < 0.0 ? (0.0 - ak) / dk : __builtin_inf();
-    if (tk < best.v) best = VI{tk, uint32_t(k)};  // ascending k within a thread: strict keeps the lowest
-  }
-  const VIL wb = wave_arg<true>(best);
-  if (lane == 0) {
-    s_wv[w] = wb.v;
-    s_wi[w] = wb.i;
-  }
-  __syncthreads();
-  if (t == 0) {
-    VI bb{s_wv[0], s_wi[0]};
-    for (int q = 1; q < nw; ++q) {
-      const VI c{s_wv[q], s_wi[q]};
-      if (beats<true>(c, bb)) bb = c;
-    }
-    s_t = bb.v < 1.0 ? bb.v : 1.0;
-    s_blk = bb.v < 1.0 ? int(bb.i) : -1;
-  }
-  __syncthreads();
-  // 7. alpha, and the realised changes (an - a) y
-  const double tt = s_t;
-  const int blk = s_blk;
-  double* ur = x1;  // x1 / x2 are consumed after the reads above
-  __syncthreads();
-  for (int k = t; k < nf; k += nt) {
-    const double ak = gA[fidx[k]], dk = dal[k];
-    double an = k == blk ? (dk > 0.0 ? C : 0.0) : __builtin_fma(tt, dk, ak);
-    an = fmin(C, fmax(0.0, an));
-    ur[k] = sy[fidx[k]] == 1 ? an - ak : ak - an;
-    gA[fidx[k]] = an;
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (prof && threadIdx.x == 0) prof[4] = wall_clock64();
-  // 8. f of every position of W: f_q += sum_k K(F_k, q) ur_k (ascending k), 16 loads per batch
-  for (int q0 = 0; q0 < m; q0 += 4 * nt) {  // four positions per thread at once: 4 x 16 loads in flight
-    double sacc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < nf; k0 += 16) {
-      double kv[4][16];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int q = min(q0 + v * nt + t, m - 1);  // clamped: the loads are unconditional, all in flight
-#pragma unroll
-        for (int u = 0; u < 16; ++u) kv[v][u] = Kw[int64_t(fidx[min(k0 + u, nf - 1)]) * ldw + q];
-      }
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-          if (k0 + u < nf) sacc[v] = __builtin_fma(kv[v][u], ur[k0 + u], sacc[v]);
-    }
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int q = q0 + v * nt + t;
-      if (q < m) gF[q] += sacc[v];
-    }
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (prof && t == 0) {
-    prof[5] = wall_clock64();
-    prof[6] = nf;
-  }
-  return blk >= 0 ? 2 : 1;
-}
-
-// One Newton step on a given working set (tests / timing, svmd_decomp_newton_probe): K(W, W) in Kw (m x
-// m, row stride ldw), alpha and f by position in gA / gF (updated), labels y; *code_out = the step's code.
-__global__ __launch_bounds__(256) void ws_newton_probe_kernel(int m, const double* __restrict__ Kw, int64_t ldw,
-                                                              const int32_t* __restrict__ y, double* __restrict__ gA,
-                                                              double* __restrict__ gF, double* __restrict__ Amat,
-                                                              double C, double eps, int max_free,
-                                                              int32_t* __restrict__ code_out, int64_t* __restrict__ prof) {
-  __shared__ int8_t sy[kMaxWS];
-  for (int k = threadIdx.x; k < kMaxWS; k += blockDim.x) sy[k] = k < m ? int8_t(y[k]) : int8_t(0);
-  __syncthreads();
-  const int code = newton_wg(m, Kw, ldw, sy, gA, gF, Amat, C, eps, max_free, prof);
-  if (threadIdx.x == 0) *code_out = code;
-}
-
-// First-order SMO on the working set in ONE workgroup of NT threads: thread t holds the PER contiguous
-// points W[t PER + e] (f, alpha, y in registers; its entries of a K(W, W) row are PER / 2 16-byte loads).
-// Per iteration:
-//   select   branch-free thread-local (value, lowest position) minimum over I_high and maximum over
-//            I_low, carrying the winner's alpha, then the wave64 arg-reductions (wave_arg);
-//   publish  lane 0 of every wave writes its two candidates to LDS (double-buffered by iteration
-//            parity) -- the iteration's ONE barrier;
-//   merge    every lane folds the NW per-wave candidates itself (LDS broadcast reads, the same serial
-//            order and tie rule everywhere), so all waves hold the identical (i_high, i_low, b_high,
-//            b_low, alpha_h, alpha_l) with no second barrier; the pair's labels come from LDS;
-//   rows     K12 and this thread's entries of the two rows of the L2-resident K(W, W);
-//   update   the reference's clip / eta / update arithmetic on the same inputs in every thread
-//            (persist_solve's sequence, main3.cpp:235-275) and f += ch K(i, .) + cl K(j, .).
-// Stops at W's own gap <= 2 tau_in, at max_inner, or on a reference stop reason.  Then the points
-// whose alpha changed are compacted in position order: cols[j] = their global ids, coef[j] =
-// (alpha_new - alpha_old) y, *mcount = how many -- the f update of all n points reads only those.
-// With packed rows (a shrunk solve, pos_of: local row -> packed position or -1), cdiag[j] = column j's
-// packed position on this GPU (-1: none), the f update's unit diagonal.
-//   DP (second order only): a second pair per iteration from the same selection -- i2 = the best
-//            I_high candidate of the waves other than i_high's, j2 = the first-order j (max f over
-//            I_low) -- whose rows load beside row i_high; after the first pair's update it is applied
-//            if it is still a violating pair (f_j2 > f_i2 + 2 tau_in) and feasible.  32 % fewer
-//            iterations of the chain at 60k for ~10 % more work per iteration.
-//   J2S (with DP): j2 by the second-order gain of row i2 instead of the first-order j (row i2 loads
-//            beside row i before the gains; both gains reduce in the same wave / barrier / fold).
-template <int NT, int PER, bool PROF = false, bool W2 = false, bool DP = false, bool J2S = false, bool NWT = false>
-__global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__ Kw, int64_t ldw,
-                                                      const int32_t* __restrict__ W, DecompCtl* __restrict__ ctl,
-                                                      const int32_t* __restrict__ y, double* __restrict__ alpha,
-                                                      const double* __restrict__ Wf, double C, double eps,
-                                                      int32_t* __restrict__ cols, double* __restrict__ coef,
-                                                      int32_t* __restrict__ mcount, DecompHost* __restrict__ hs,
-                                                      DecompCtl* __restrict__ pub, const int32_t* __restrict__ pos_of,
-                                                      int64_t lo, int64_t nloc, int32_t* __restrict__ cdiag,
-                                                      double* __restrict__ gAw, double* __restrict__ gFw,
-                                                      double* __restrict__ nAmat, NwDev nw) {
-  if (ctl->stop != SVM_STOP_RUNNING) return;
-  const int m = ctl->m;
-  const double tau_in = ctl->tau_in;
-  const int64_t max_inner = ctl->max_inner;
-  constexpr int NW = NT / 64;
-  static_assert(PER % 2 == 0, "row entries are loaded 16 bytes at a time");
-  __shared__ double pv[2][2][NW], pa[2][2][NW];
-  __shared__ uint32_t pi[2][2][NW];
-  __shared__ double qv[2][NW], qa[2][NW], qf[2][NW], qk[2][NW];  // W2: the second index's candidates
-  __shared__ uint32_t qi[2][NW];
-  __shared__ double rv[2][NW], ra[2][NW], rf[2][NW], rk[2][NW];  // J2S: the second pair's j candidates
-  __shared__ uint32_t ri2[2][NW];
-  __shared__ int8_t sy[NT * PER];
-  __shared__ int32_t wcnt[PER][NW];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  // position of this thread's element e: pair h = e / 2 of every lane is one 16-byte piece; a wave's 64
-  // pieces of pair h are one contiguous kilobyte, and the NT / 64 waves' kilobytes of pair h are adjacent
-  const int pbase = w * 128 + 2 * lane;
-  auto pos = [&](int e) { return pbase + (e >> 1) * (2 * NT) + (e & 1); };
-  double a[PER], a0[PER], ft[PER];
-  bool yp[PER], yn[PER];  // y = +1 / y = -1 (padding: neither, so in neither set)
-  int64_t gid[PER];
-#pragma unroll
-  for (int e = 0; e < PER; ++e) {
-    const int k = pos(e);
-    const bool valid = k < m;
-    gid[e] = valid ? W[k] : 0;
-    a[e] = valid ? alpha[gid[e]] : 0.0;
-    a0[e] = a[e];
-    const int32_t yk = valid ? y[gid[e]] : 0;
-    yp[e] = yk == 1;
-    yn[e] = yk == -1;
-    sy[k] = int8_t(yk);
-    ft[e] = valid ? Wf[k] : 0.0;
-  }
-  const double c_hi = C - eps, c_lo = 0.0 + eps, inf = __builtin_inf();
-  int64_t it = 0;
-  int32_t reason = SVM_STOP_CONVERGED;
-  // the Newton polish (decomp_newton.h): chain iterations with no bound-status change, starting at `every`
-  // after a long last inner solve (newton_since0)
-  int32_t since = NWT && ctl->last_m > 0 && double(ctl->last_inner_it) >= nw.frac * double(ctl->last_m) ? nw.every : 0;
-  int32_t ntrig = 0;
-  int64_t nsteps = 0;
-  // PROF: wave 0's clock at the phase boundaries (select | publish+barrier | merge | row loads | update)
-  int64_t pacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int64_t pt = PROF ? int64_t(clock64()) : 0;
-  const int64_t pc0 = pt, pw0 = PROF ? int64_t(wall_clock64()) : 0;
-  // this thread's PER contiguous entries of row r of K(W, W) as 16-byte loads (in bounds: t PER + e <
-  // NT PER <= ldw; the row base is 16-byte aligned: ldw even), zero beyond m
-  auto row = [&](int r, double* out) {
-    const double2* src = reinterpret_cast<const double2*>(Kw + int64_t(r) * ldw + pbase);
-#pragma unroll
-    for (int h = 0; h < PER / 2; ++h) {
-      const double2 v = src[NT * h];
-      out[2 * h] = pos(2 * h) < m ? v.x : 0.0;
-      out[2 * h + 1] = pos(2 * h + 1) < m ? v.y : 0.0;
-    }
-  };
-  // a wave-uniform element of K(W, W) through a VECTOR load (in order with the row loads on vmcnt): a
-  // scalar load would share lgkmcnt with the folds' LDS reads, which would then wait for it
-  auto kval = [&](int r, int c) {
-    int64_t off = int64_t(r) * ldw + c;
-    asm volatile("" : "+v"(off));
-    return Kw[off];
-  };
-  auto stamp = [&](int k) {
-    if constexpr (PROF) {
-      const int64_t now = int64_t(clock64());
-      pacc[k] += now - pt;
-      pt = now;
-    }
-  };
-  for (int par = 0;; par ^= 1) {
-    double hv = inf, lv = -inf, ha = 0.0, la = 0.0;
-    uint32_t hi = kSentinel, li = kSentinel;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {  // ascending position within a thread: strict compares keep the lowest
-      const bool below = a[e] < c_hi, above = a[e] > c_lo;
-      const bool in_high = (yp[e] && below) || (yn[e] && above);
-      const bool in_low = (yp[e] && above) || (yn[e] && below);
-      const bool ch = in_high && ft[e] < hv, cl = in_low && ft[e] > lv;
-      const uint32_t k = uint32_t(pos(e));
-      hv = ch ? ft[e] : hv;
-      ha = ch ? a[e] : ha;
-      hi = ch ? k : hi;
-      lv = cl ? ft[e] : lv;
-      la = cl ? a[e] : la;
-      li = cl ? k : li;
-    }
-    int lmn, lmx;  // the lanes holding the wave's winners publish them (no cross-lane reads)
-    wave_arg_pair_lanes(VI{hv, hi}, VI{lv, li}, lmn, lmx);
-    stamp(0);
-    if (lane == lmn) {
-      pv[par][0][w] = hv;
-      pi[par][0][w] = hi;
-      pa[par][0][w] = ha;
-    }
-    if (lane == lmx) {
-      pv[par][1][w] = lv;
-      pi[par][1][w] = li;
-      pa[par][1][w] = la;
-    }
-    __syncthreads();
-    stamp(1);
-    // the same pairwise tree fold in every lane (value, then lowest position): log2(NW) dependent steps
-    // fold (value, position) only, tracking the winning wave; its alpha is read from LDS afterwards
-    double fv[2][NW];
-    uint32_t fi[2][NW];
-    int fw[2][NW];
-#pragma unroll
-    for (int q = 0; q < NW; ++q)
-#pragma unroll
-      for (int sd = 0; sd < 2; ++sd) {
-        fv[sd][q] = pv[par][sd][q];
-        fi[sd][q] = pi[par][sd][q];
-        fw[sd][q] = q;
-      }
-#pragma unroll
-    for (int st = 1; st < NW; st <<= 1)
-#pragma unroll
-      for (int q = 0; q + st < NW; q += 2 * st) {
-        // bitwise, not short-circuit: the compiler turned || / && on these uniform values into branches
-        const bool th = (fv[0][q + st] < fv[0][q]) | ((fv[0][q + st] == fv[0][q]) & (fi[0][q + st] < fi[0][q]));
-        const bool tl = (fv[1][q + st] > fv[1][q]) | ((fv[1][q + st] == fv[1][q]) & (fi[1][q + st] < fi[1][q]));
-        fv[0][q] = th ? fv[0][q + st] : fv[0][q];
-        fi[0][q] = th ? fi[0][q + st] : fi[0][q];
-        fw[0][q] = th ? fw[0][q + st] : fw[0][q];
-        fv[1][q] = tl ? fv[1][q + st] : fv[1][q];
-        fi[1][q] = tl ? fi[1][q + st] : fi[1][q];
-        fw[1][q] = tl ? fw[1][q + st] : fw[1][q];
-      }
-    double bh = fv[0][0], bl = fv[1][0];
-    uint32_t uih = fi[0][0], uil = fi[1][0];
-    stamp(2);
-    if (uih == kSentinel || uil == kSentinel) {
-      reason = SVM_STOP_NO_CANDIDATE;
-      break;
-    }
-    if (bl <= bh + 2.0 * tau_in) break;  // W's own optimum (reason stays CONVERGED)
-    if (it >= max_inner) {
-      reason = SVM_STOP_MAX_ITER;
-      break;
-    }
-    if (NWT && since >= nw.every && ntrig < nw.per_solve) {  // uniform: the polish, then select again
-      ++ntrig;
-      since = 0;
-#pragma unroll
-      for (int e = 0; e < PER; ++e)
-        if (pos(e) < m) {
-          gAw[pos(e)] = a[e];
-          gFw[pos(e)] = ft[e];
-        }
-      __threadfence_block();
-      __syncthreads();
-      int steps = 0;
-      while (NWT && steps < nw.repeat) {
-        const int code = newton_wg(m, Kw, ldw, sy, gAw, gFw, nAmat, C, eps, nw.max_free);
-        if (code == 0) break;
-        ++steps;
-        if (code == 1) break;
-      }
-      if (steps > 0) {
-#pragma unroll
-        for (int e = 0; e < PER; ++e)
-          if (pos(e) < m) {
-            a[e] = gAw[pos(e)];
-            ft[e] = gFw[pos(e)];
-          }
-        it += steps;
-        nsteps += steps;
-        continue;
-      }
-    }
-    int ih = int(uih), il = int(uil);
-    double K12, bl_upd = bl, al;  // the second index's f in the update (first order: b_low)
-    double kh[PER], kl[PER];
-    // DP: the second pair (i2, j2) and what its update needs, from the same selection
-    int i2 = -1;
-    double f2h = 0.0, a2h = 0.0, f2l = bl, a2l = 0.0;
-    double2 r2h[PER / 2], r2l[PER / 2];  // DP: rows i2 and j2, raw, consumed by the second pair only
-    double Kh_i2 = 0.0, Kh_j2 = 0.0, Kl_i2 = 0.0, Kl_j2 = 0.0, K2_12 = 0.0;
-    bool dp_ok = false;
-    if constexpr (DP) {
-      const int wih = fw[0][0];
-      double bv = inf;
-      uint32_t bi = kSentinel;
-      int bq = 0;
-#pragma unroll
-      for (int q = 0; q < NW; ++q) {
-        const double v = pv[par][0][q];
-        const uint32_t ix = pi[par][0][q];
-        const bool take = (q != wih) & ((v < bv) | ((v == bv) & (ix < bi)));
-        bv = take ? v : bv;
-        bi = take ? ix : bi;
-        bq = take ? q : bq;
-      }
-      i2 = bi != kSentinel ? int(bi) : -1;
-      f2h = bv;
-      a2h = pa[par][0][bq];
-      a2l = pa[par][1][fw[1][0]];
-      dp_ok = J2S ? i2 >= 0 : i2 >= 0 && il != ih && i2 != il;  // (not J2S) il is still the first-order j = j2
-    }
-    int j2 = il;
-    double2 rj[PER / 2];  // second order: row j's raw pieces, consumed only after the clip arithmetic
-    if constexpr (!W2) {
-      // one memory round trip: K12 and this thread's entries of the two rows; the labels from LDS
-      K12 = Kw[int64_t(ih) * ldw + il];
-      row(ih, kh);
-      row(il, kl);
-      al = pa[par][1][fw[1][0]];
-    } else {
-      // second-order choice of the second index (smo_cpu.cpp / persist_solve WSS2): row i_high, then
-      // the maximum of (f_t - b_high)^2 / a_t over I_low points above b_high (a_t = 2 - 2 K(i, t),
-      // floored at eps; reciprocal approximation: only the choice depends on it), a second barrier
-      // and fold, then row j
-      row(ih, kh);  // unconditional loads (no exec-mask branch per load)
-      if constexpr (J2S) {  // row i2 now (its gains need it); row j2 and the K values after the fold
-        const int ri = dp_ok ? i2 : ih;
-        const double2* s2h = reinterpret_cast<const double2*>(Kw + int64_t(ri) * ldw + pbase);
-#pragma unroll
-        for (int h = 0; h < PER / 2; ++h) r2h[h] = s2h[NT * h];
-        Kh_i2 = kval(ih, ri);
-      } else if constexpr (DP) {
-        {  // issued after row i (unconditionally -- row i again when there is no second pair: no branch
-           // around loads, whose merge made the compiler wait for all of them before the gains)
-          const int ri = dp_ok ? i2 : ih, rj2 = dp_ok ? j2 : ih;
-          const double2* s2h = reinterpret_cast<const double2*>(Kw + int64_t(ri) * ldw + pbase);
-          const double2* s2l = reinterpret_cast<const double2*>(Kw + int64_t(rj2) * ldw + pbase);
-#pragma unroll
-          for (int h = 0; h < PER / 2; ++h) r2h[h] = s2h[NT * h];
-#pragma unroll
-          for (int h = 0; h < PER / 2; ++h) r2l[h] = s2l[NT * h];
-          Kh_i2 = kval(ih, ri);
-          Kh_j2 = kval(ih, rj2);
-          K2_12 = kval(ri, rj2);
-        }
-      }
-      if constexpr (PROF) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp(8);
-      }
-      double gv = inf;
-      int ge = 0;  // the element of the thread's best gain: its alpha, f and K(i, j) are read by the winner
-#pragma unroll
-      for (int e = 0; e < PER; ++e) {
-        const bool below = a[e] < c_hi, above = a[e] > c_lo;
-        const bool in_low = (yp[e] && above) || (yn[e] && below);
-        const double bb = ft[e] - bh;
-        double at = 2.0 - 2.0 * kh[e];
-        at = at <= 0.0 ? eps : at;
-        // IEEE division (not v_rcp_f64): the choice is then reproducible on the host bit for bit
-        // (svm_decomp_train_gram, the CPU oracle)
-        const double gain = -(bb * bb) / at;
-        const bool c = in_low && ft[e] > bh && gain < gv;
-        gv = c ? gain : gv;
-        ge = c ? e : ge;
-      }
-      const uint32_t gi = gv < inf ? uint32_t(pos(ge)) : kSentinel;
-      double gv2 = inf;
-      int ge2 = 0;
-      if constexpr (J2S) {  // the same gain over I_low points above f(i2), on row i2 (f2h = inf: none)
-#pragma unroll
-        for (int e = 0; e < PER; ++e) {
-          const bool below = a[e] < c_hi, above = a[e] > c_lo;
-          const bool in_low = (yp[e] && above) || (yn[e] && below);
-          const double bb = ft[e] - f2h;
-          const double k2 = pos(e) < m ? ((e & 1) ? r2h[e >> 1].y : r2h[e >> 1].x) : 0.0;
-          double at = 2.0 - 2.0 * k2;
-          at = at <= 0.0 ? eps : at;
-          const double gain = -(bb * bb) / at;
-          const bool c = in_low && ft[e] > f2h && gain < gv2;
-          gv2 = c ? gain : gv2;
-          ge2 = c ? e : ge2;
-        }
-      }
-      const uint32_t gi2 = gv2 < inf ? uint32_t(pos(ge2)) : kSentinel;
-      const int lc = wave_arg_lane<true>(VI{gv, gi});
-      const int lc2 = J2S ? wave_arg_lane<true>(VI{gv2, gi2}) : -1;
-      stamp(9);
-      if (lane == lc) {
-        double ga = a[0], gf = ft[0], gk = kh[0];
-#pragma unroll
-        for (int e = 1; e < PER; ++e) {
-          ga = ge == e ? a[e] : ga;
-          gf = ge == e ? ft[e] : gf;
-          gk = ge == e ? kh[e] : gk;
-        }
-        qv[par][w] = gv;
-        qi[par][w] = gi;
-        qa[par][w] = ga;
-        qf[par][w] = gf;
-        qk[par][w] = gk;
-      }
-      if (J2S && lane == lc2) {
-        double ga = a[0], gf = ft[0], gk = r2h[0].x;
-#pragma unroll
-        for (int e = 1; e < PER; ++e) {
-          ga = ge2 == e ? a[e] : ga;
-          gf = ge2 == e ? ft[e] : gf;
-          gk = ge2 == e ? ((e & 1) ? r2h[e >> 1].y : r2h[e >> 1].x) : gk;
-        }
-        rv[par][w] = gv2;
-        ri2[par][w] = gi2;
-        ra[par][w] = ga;
-        rf[par][w] = gf;
-        rk[par][w] = gk;
-      }
-      __syncthreads();
-      stamp(10);
-      // the same (value, lowest position) order as a serial fold, as a tree over (value, position);
-      // the winner's alpha, f and K(i, j) are read from its wave's slot afterwards
-      double cv[NW];
-      uint32_t cj[NW];
-      int cw[NW];
-#pragma unroll
-      for (int q = 0; q < NW; ++q) {
-        cv[q] = qv[par][q];
-        cj[q] = qi[par][q];
-        cw[q] = q;
-      }
-#pragma unroll
-      for (int st = 1; st < NW; st <<= 1)
-#pragma unroll
-        for (int q = 0; q + st < NW; q += 2 * st) {
-          const bool tk = (cv[q + st] < cv[q]) | ((cv[q + st] == cv[q]) & (cj[q + st] < cj[q]));
-          cv[q] = tk ? cv[q + st] : cv[q];
-          cj[q] = tk ? cj[q + st] : cj[q];
-          cw[q] = tk ? cw[q + st] : cw[q];
-        }
-      if (cj[0] == kSentinel) {  // no I_low point above b_high (cannot happen while the gap is open)
-        reason = SVM_STOP_NO_CANDIDATE;
-        break;
-      }
-      il = int(cj[0]);
-      stamp(11);
-      {  // issued now, consumed after the clip / division below, which then runs under the loads' latency
-        const double2* src = reinterpret_cast<const double2*>(Kw + int64_t(il) * ldw + pbase);
-#pragma unroll
-        for (int h = 0; h < PER / 2; ++h) rj[h] = src[NT * h];
-      }
-      if constexpr (J2S) {  // the second pair's j: the same fold over the second gains
-        double dv[NW];
-        uint32_t dj[NW];
-        int dw[NW];
-#pragma unroll
-        for (int q = 0; q < NW; ++q) {
-          dv[q] = rv[par][q];
-          dj[q] = ri2[par][q];
-          dw[q] = q;
-        }
-#pragma unroll
-        for (int st = 1; st < NW; st <<= 1)
-#pragma unroll
-          for (int q = 0; q + st < NW; q += 2 * st) {
-            const bool tk = (dv[q + st] < dv[q]) | ((dv[q + st] == dv[q]) & (dj[q + st] < dj[q]));
-            dv[q] = tk ? dv[q + st] : dv[q];
-            dj[q] = tk ? dj[q + st] : dj[q];
-            dw[q] = tk ? dw[q + st] : dw[q];
-          }
-        const bool jok = dj[0] != kSentinel;
-        j2 = jok ? int(dj[0]) : ih;
-        dp_ok = dp_ok && jok && j2 != ih && il != j2 && il != i2;
-        f2l = rf[par][dw[0]];
-        a2l = ra[par][dw[0]];
-        K2_12 = rk[par][dw[0]];
-        const int rj2 = dp_ok ? j2 : ih;
-        const double2* s2l = reinterpret_cast<const double2*>(Kw + int64_t(rj2) * ldw + pbase);
-#pragma unroll
-        for (int h = 0; h < PER / 2; ++h) r2l[h] = s2l[NT * h];
-        Kh_j2 = kval(ih, rj2);
-        Kl_i2 = kval(il, dp_ok ? i2 : il);
-        Kl_j2 = kval(il, rj2);
-      } else if constexpr (DP) {
-        dp_ok = dp_ok && il != j2 && il != i2;  // the second-order j must leave the second pair alone
-        Kl_i2 = kval(il, dp_ok ? i2 : il);
-        Kl_j2 = kval(il, dp_ok ? j2 : il);
-      }
-      al = qa[par][cw[0]];
-      bl_upd = qf[par][cw[0]];
-      K12 = qk[par][cw[0]];
-    }
-    const double ah = pa[par][0][fw[0][0]];
-    const int32_t yh = sy[ih], yl = sy[il];
-    if constexpr (PROF) {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      stamp(3);
-    }
-    const double K11 = 1.0, K22 = 1.0;  // the Gram's unit diagonal
-    const int s = yh * yl;
-    const double eta = K11 + K22 - 2.0 * K12;
-    double U, V;
-    if (s == -1) {
-      U = fmax(0.0, al - ah);
-      V = fmin(C, C + al - ah);
-    } else {
-      U = fmax(0.0, al + ah - C);
-      V = fmin(C, al + ah);
-    }
-    if (!(U <= V + 1e-12)) {
-      reason = SVM_STOP_INFEASIBLE;
-      break;
-    }
-    if (eta <= eps) {
-      reason = SVM_STOP_NONPOS_ETA;
-      break;
-    }
-    double al_new = al + double(yl) * (bh - bl_upd) / eta;
-    if (al_new > V) al_new = V;
-    if (al_new < U) al_new = U;
-    const double ah_new = ah + double(s) * (al - al_new);
-    const double ch = (ah_new - ah) * double(yh);
-    const double cl = (al_new - al) * double(yl);
-    // a bound-status change of an updated point (bound_status): the Newton polish waits for a settled set
-    auto bst = [&](double v) { return v <= c_lo ? 0 : v >= c_hi ? 2 : 1; };
-    bool moved_status = NWT && (bst(ah_new) != bst(ah) || bst(al_new) != bst(al));
-    if constexpr (W2) {
-#pragma unroll
-      for (int h = 0; h < PER / 2; ++h) {
-        double x = rj[h].x, z = rj[h].y;
-        // an empty asm reading cl: the wait for row j's data lands here, after the division, not inside it
-        asm volatile("" : "+v"(x), "+v"(z) : "v"(cl));
-        kl[2 * h] = pos(2 * h) < m ? x : 0.0;
-        kl[2 * h + 1] = pos(2 * h + 1) < m ? z : 0.0;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int k = pos(e);
-      ft[e] += ch * kh[e] + cl * kl[e];  // main3.cpp:274 operation order
-      a[e] = k == ih ? ah_new : k == il ? al_new : a[e];
-    }
-    ++it;
-    if constexpr (DP) {
-      if (dp_ok && it < max_inner) {
-        // the second pair's f after the first update, as its owner thread computed it just now
-        const double fi2 = f2h + (ch * Kh_i2 + cl * Kl_i2);
-        const double fj2 = f2l + (ch * Kh_j2 + cl * Kl_j2);
-        const int32_t yh2 = sy[i2], yl2 = sy[j2];
-        const int s2 = yh2 * yl2;
-        const double eta2 = K11 + K22 - 2.0 * K2_12;
-        double U2, V2;
-        if (s2 == -1) {
-          U2 = fmax(0.0, a2l - a2h);
-          V2 = fmin(C, C + a2l - a2h);
-        } else {
-          U2 = fmax(0.0, a2l + a2h - C);
-          V2 = fmin(C, a2l + a2h);
-        }
-        if (fj2 > fi2 + 2.0 * tau_in && U2 <= V2 + 1e-12 && !(eta2 <= eps)) {  // still violating, feasible
-          double al2 = a2l + double(yl2) * (fi2 - fj2) / eta2;
-          if (al2 > V2) al2 = V2;
-          if (al2 < U2) al2 = U2;
-          const double ah2 = a2h + double(s2) * (a2l - al2);
-          const double ch2 = (ah2 - a2h) * double(yh2);
-          const double cl2 = (al2 - a2l) * double(yl2);
-          double k2h[PER], k2l[PER];
-#pragma unroll
-          for (int h = 0; h < PER / 2; ++h) {
-            double x = r2h[h].x, z = r2h[h].y, u = r2l[h].x, v = r2l[h].y;
-            asm volatile("" : "+v"(x), "+v"(z), "+v"(u), "+v"(v) : "v"(cl2));  // consumed here, not at the load
-            k2h[2 * h] = pos(2 * h) < m ? x : 0.0;
-            k2h[2 * h + 1] = pos(2 * h + 1) < m ? z : 0.0;
-            k2l[2 * h] = pos(2 * h) < m ? u : 0.0;
-            k2l[2 * h + 1] = pos(2 * h + 1) < m ? v : 0.0;
-          }
-#pragma unroll
-          for (int e = 0; e < PER; ++e) {
-            const int k = pos(e);
-            ft[e] += ch2 * k2h[e] + cl2 * k2l[e];
-            a[e] = k == i2 ? ah2 : k == j2 ? al2 : a[e];
-          }
-          ++it;
-          if constexpr (NWT) moved_status = moved_status || bst(ah2) != bst(a2h) || bst(al2) != bst(a2l);
-        }
-      }
-    }
-    if constexpr (NWT) since = moved_status ? 0 : since + 1;
-    stamp(4);
-  }
-  // compaction in position order: pair h, then wave, then lane, then e & 1
-  bool chg[PER];
-  int below[PER / 2];
-#pragma unroll
-  for (int e = 0; e < PER; ++e) {
-    chg[e] = pos(e) < m && a[e] != a0[e];
-    if (chg[e]) alpha[gid[e]] = a[e];
-  }
-#pragma unroll
-  for (int h = 0; h < PER / 2; ++h) {
-    const unsigned long long b0 = __ballot(chg[2 * h]), b1 = __ballot(chg[2 * h + 1]);
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    below[h] = __popcll(b0 & lt) + __popcll(b1 & lt);
-    if (lane == 0) wcnt[h][w] = __popcll(b0) + __popcll(b1);
-  }
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int h = 0; h < PER / 2; ++h) {
-    int j = base + below[h];
-    for (int q = 0; q < NW; ++q) {
-      if (q < w) j += wcnt[h][q];
-      base += wcnt[h][q];
-    }
-#pragma unroll
-    for (int e = 2 * h; e < 2 * h + 2; ++e)
-      if (chg[e]) {
-        cols[j] = int32_t(gid[e]);
-        coef[j] = (a[e] - a0[e]) * (yp[e] ? 1.0 : -1.0);
-        // packed rows (shrinking): the column's row in the packed list, for the unit diagonal of the update
-        if (cdiag) cdiag[j] = gid[e] >= lo && gid[e] < lo + nloc ? pos_of[gid[e] - lo] : -1;
-        ++j;
-      }
-  }
-  if (PROF && t == 0) {
-    for (int k = 0; k < 5; ++k) hs->prof[k] += pacc[k];
-    for (int k = 8; k < 12; ++k) hs->prof[k] += pacc[k];
-    hs->prof[6] += int64_t(clock64()) - pc0;
-    hs->prof[7] += int64_t(wall_clock64()) - pw0;
-  }
-  if (t == 0) {
-    *mcount = base;
-    ctl->outer += 1;
-    ctl->inner_total += it;
-    ctl->changed_total += base;
-    ctl->last_inner_it = it;
-    ctl->last_m = m;
-    ctl->newton_steps += nsteps;
-    ctl->last_inner_reason = reason;
-    publish_ctl(*ctl, pub);
-  }
-}
-
 // FP64 rows (real-valued data): Xo[k] = X[ids[k]] (ld doubles) and no[k] = nrm[ids[k]] for k < *count,
 // one workgroup per row; no-op when gated (a stopped solve's remaining launches).
 __global__ __launch_bounds__(64) void ws_gather_f64_kernel(const double* __restrict__ X, const double* __restrict__ nrm,
@@ -1364,6 +352,7 @@ __global__ __launch_bounds__(64) void ws_gather_f64_kernel(const double* __restr
   if (threadIdx.x == 0) no[k] = nrm[src];
 }
 
+// ---- cache plan and sums --------------------------------------------------------------------------------
 // FP64 rows: f[i] += sum_{k < *count} coef[k] Kc[i][k] (the block K(rows, moved columns)), one wave
 // per row, lane-strided then a fixed butterfly (deterministic).
 __global__ __launch_bounds__(256) void ws_rowsum_f64_kernel(const double* __restrict__ Kc, int64_t ldc,
@@ -1611,6 +600,79 @@ __global__ __launch_bounds__(256) void ws_fsum_count_kernel(const double* __rest
   f[act ? int64_t(act[i]) : i] += s;
 }
 
+// ---- init and warm start --------------------------------------------------------------------------------
+// pos_of = the identity (the packed list before any repack, or after an unshrink).
+__global__ void ws_iota_kernel(int32_t* __restrict__ v, int64_t n) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) v[i] = int32_t(i);
+}
+
+__global__ void ws_init_kernel(const int32_t* __restrict__ y, double* __restrict__ alpha, double* __restrict__ f,
+                               int64_t lo, int64_t nloc, int64_t n, int warm, DecompCtl* __restrict__ ctl) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n && !warm) alpha[i] = 0.0;
+  if (i < nloc) f[i] = -static_cast<double>(y[lo + i]);  // main3.cpp:165-172
+  if (i == 0 && ctl) ctl->n_active = nloc;
+}
+
+// Warm start: the ascending ids j with alpha_j != 0 into cols, alpha_j y_j into coef, their number to
+// *count (device) and *count_h (pinned host).  One 1024-thread workgroup; each thread takes 8
+// consecutive points of a 8192-point chunk, a workgroup exclusive scan of the per-thread counts
+// places them (ascending order preserved).
+__global__ __launch_bounds__(1024) void ws_nz_compact_kernel(const double* __restrict__ alpha,
+                                                             const int32_t* __restrict__ y, int64_t n,
+                                                             int32_t* __restrict__ cols, double* __restrict__ coef,
+                                                             int32_t* __restrict__ count, int64_t* __restrict__ count_h) {
+  constexpr int E = 8, NW = 1024 / 64;
+  __shared__ int32_t wtot[NW];
+  __shared__ int64_t base;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  if (t == 0) base = 0;
+  __syncthreads();
+  for (int64_t c0 = 0; c0 < n; c0 += int64_t(1024) * E) {
+    const int64_t i0 = c0 + int64_t(t) * E;
+    int cnt = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) cnt += (i0 + e < n && alpha[i0 + e] != 0.0) ? 1 : 0;
+    int incl = cnt;  // inclusive wave scan
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int v = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += v;
+    }
+    if (lane == 63) wtot[w] = incl;
+    __syncthreads();
+    int64_t pos = base + incl - cnt;
+    for (int q = 0; q < w; ++q) pos += wtot[q];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int64_t i = i0 + e;
+      if (i < n && alpha[i] != 0.0) {
+        cols[pos] = int32_t(i);
+        coef[pos] = alpha[i] * double(y[i]);
+        ++pos;
+      }
+    }
+    __syncthreads();
+    if (t == 0) {
+      int64_t tot = 0;
+      for (int q = 0; q < NW; ++q) tot += wtot[q];
+      base += tot;
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    *count = int32_t(base);
+    *count_h = base;
+  }
+}
+
+// counts[c] = the columns of warm-start chunk c (kMaxWS per chunk; the last one partial).
+__global__ void ws_chunk_counts_kernel(const int32_t* __restrict__ count, int32_t* __restrict__ counts, int nchunks) {
+  const int c = int(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (c < nchunks) counts[c] = max(0, min(kMaxWS, *count - c * kMaxWS));
+}
+
 // ---- shrinking (decomp_shrink.h) ----------------------------------------------------------------------
 // The shrink pass after an outer iteration: every active row of this GPU (the packed list act[0 ..
 // *nrows), or all nloc rows) that the rule drops gets shr = 1; ctl->n_active counts what is left and
@@ -1761,78 +823,6 @@ __global__ void ws_unshrink_ctl_kernel(DecompCtl* __restrict__ ctl, int64_t nloc
   }
 }
 
-// pos_of = the identity (the packed list before any repack, or after an unshrink).
-__global__ void ws_iota_kernel(int32_t* __restrict__ v, int64_t n) {
-  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = int32_t(i);
-}
-
-__global__ void ws_init_kernel(const int32_t* __restrict__ y, double* __restrict__ alpha, double* __restrict__ f,
-                               int64_t lo, int64_t nloc, int64_t n, int warm, DecompCtl* __restrict__ ctl) {
-  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i < n && !warm) alpha[i] = 0.0;
-  if (i < nloc) f[i] = -static_cast<double>(y[lo + i]);  // main3.cpp:165-172
-  if (i == 0 && ctl) ctl->n_active = nloc;
-}
-
-// Warm start: the ascending ids j with alpha_j != 0 into cols, alpha_j y_j into coef, their number to
-// *count (device) and *count_h (pinned host).  One 1024-thread workgroup; each thread takes 8
-// consecutive points of a 8192-point chunk, a workgroup exclusive scan of the per-thread counts
-// places them (ascending order preserved).
-__global__ __launch_bounds__(1024) void ws_nz_compact_kernel(const double* __restrict__ alpha,
-                                                             const int32_t* __restrict__ y, int64_t n,
-                                                             int32_t* __restrict__ cols, double* __restrict__ coef,
-                                                             int32_t* __restrict__ count, int64_t* __restrict__ count_h) {
-  constexpr int E = 8, NW = 1024 / 64;
-  __shared__ int32_t wtot[NW];
-  __shared__ int64_t base;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  if (t == 0) base = 0;
-  __syncthreads();
-  for (int64_t c0 = 0; c0 < n; c0 += int64_t(1024) * E) {
-    const int64_t i0 = c0 + int64_t(t) * E;
-    int cnt = 0;
-#pragma unroll
-    for (int e = 0; e < E; ++e) cnt += (i0 + e < n && alpha[i0 + e] != 0.0) ? 1 : 0;
-    int incl = cnt;  // inclusive wave scan
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int v = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += v;
-    }
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    int64_t pos = base + incl - cnt;
-    for (int q = 0; q < w; ++q) pos += wtot[q];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int64_t i = i0 + e;
-      if (i < n && alpha[i] != 0.0) {
-        cols[pos] = int32_t(i);
-        coef[pos] = alpha[i] * double(y[i]);
-        ++pos;
-      }
-    }
-    __syncthreads();
-    if (t == 0) {
-      int64_t tot = 0;
-      for (int q = 0; q < NW; ++q) tot += wtot[q];
-      base += tot;
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    *count = int32_t(base);
-    *count_h = base;
-  }
-}
-
-// counts[c] = the columns of warm-start chunk c (kMaxWS per chunk; the last one partial).
-__global__ void ws_chunk_counts_kernel(const int32_t* __restrict__ count, int32_t* __restrict__ counts, int nchunks) {
-  const int c = int(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (c < nchunks) counts[c] = max(0, min(kMaxWS, *count - c * kMaxWS));
-}
-
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -1861,23 +851,319 @@ DecompShape decomp_shape(int64_t n, int qws, int world) {
   return d;
 }
 
-// Decomposition solve on quantised rows (Q, N0, WN: all n rows; the plan's step weights in stw on the
-// device).  alpha: n doubles (cold start: zeroed here).  q: working-set size (<= 1024).
-// Distributed (world > 1): this GPU owns the blocks [rank NB / world, (rank + 1) NB / world) of the
-// selection's global block partition, keeps f for their points only, and exchanges its candidate
-// records once per outer iteration through `allgather`; every GPU then builds the same working set and
-// runs the same inner solve on the same inputs (alpha is replicated and updated identically), and
-// updates f for its own points.  With world dividing 8 the trajectory is the one-GPU trajectory.
-// stats (kDecompStats int64): outer iterations, inner iterations, working-set capacity, solve
-// microseconds, columns of the f updates (points moved, summed over the outer iterations), inner
-// workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA), warm-start columns.
-int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n, const svm_params& p,
-               int qws, svm_result* r, int64_t* stats, const DecompOpts& o) {
-  const auto t0 = std::chrono::steady_clock::now();
-  hipStream_t s = ctx->stream;
+// ---- the driver -----------------------------------------------------------------------------------------
+namespace {
+
+constexpr int64_t kLdw = kMaxWS;              // K(W, W) row stride
+constexpr int64_t kLdp = 2 * (kMaxWS / 128);  // column halves of the f update
+
+// Every environment switch a solve reads (docs/KNOBS.md), parsed at the top of each solve and never kept
+// between solves: the tests change them between fits of one process.
+struct DecompKnobs {
+  bool wide_select = false, prof = false, kww_sym = false, shrink_log = false;  // _WIDE_SELECT, _PROF, _KWW, _SHRINK_LOG
+  bool wss2 = true, dp = true, j2s = false;                                     // _WSS = 1 | 2 | 3 | 4
+  bool pack = true, cache_evict = true;                                         // _PACK=0, _CCACHE_EVICT=0
+  int inner_nt = 256, batch = 1;                                                // _NT, _BATCH
+  double tau_frac = 0.1, repack_frac = 0.75;                                    // _TAU_FRAC, _REPACK
+  int fail_rank = -1;                                                           // _FAIL_RANK (-1: none)
+  int64_t fail_outer = 0;                                                       // _FAIL_OUTER
+  int ccache = -1;                                                              // _CCACHE: 0 off, 1 on, -1 by size
+  double ccache_frac = -1.0;                                                    // _CCACHE_FRAC (< 0: not set)
+  bool ccache_slots_set = false;                                                // _CCACHE_SLOTS
+  int64_t ccache_slots = 0;
+  int local_world = 0;                                                          // LOCAL_WORLD_SIZE (0: not set)
+};
+
+int read_knobs(const DecompShape& sh, DecompKnobs* out) {
+  DecompKnobs k;
+  auto is1 = [](const char* name) {
+    const char* v = getenv(name);
+    return v && atoi(v) == 1;
+  };
+  k.wide_select = is1("SVM355_DECOMP_WIDE_SELECT");
+  // inner workgroup: NT threads x PER points (NT * PER = 1024); SVM355_DECOMP_NT = 64 | 128 | 256 | 512
+  if (const char* v = getenv("SVM355_DECOMP_NT")) k.inner_nt = atoi(v);
+  if (k.inner_nt != 64 && k.inner_nt != 128 && k.inner_nt != 512 && k.inner_nt != 65) k.inner_nt = 256;
+  // 65: one wave x 6 points (A/B probe of a one-wave inner solve; needs a working set of <= 384)
+  if (k.inner_nt == 65 && sh.L > 384) {
+    set_error("decomposition SMO: SVM355_DECOMP_NT=65 needs a working set of <= 384 points");
+    return SVM_ERR_ARG;
+  }
+  // inner stop: the working set's own gap <= max(2 tau, 2 tau_frac gap) (SVM355_DECOMP_TAU_FRAC)
+  if (const char* v = getenv("SVM355_DECOMP_TAU_FRAC")) k.tau_frac = atof(v);
+  // at 0.5 and above the working set's stop (its gap <= tau_frac x 2 gap) holds before any update, so the
+  // solve could make no progress (it would stop at once with a zero model)
+  if (!(k.tau_frac >= 0.0 && k.tau_frac < 0.5)) {
+    set_error("decomposition SMO: SVM355_DECOMP_TAU_FRAC must be in [0, 0.5), got %g", k.tau_frac);
+    return SVM_ERR_ARG;
+  }
+  // SVM355_DECOMP_PROF=1: clock64 phase totals of the inner solves on stderr (diagnostic build)
+  k.prof = is1("SVM355_DECOMP_PROF");
+  // inner pair selection: second order for j (default; fewer, longer iterations: 8,206 vs 14,334 at
+  // 60k, 12% faster) or first order (SVM355_DECOMP_WSS=1)
+  k.wss2 = !is1("SVM355_DECOMP_WSS");
+  // SVM355_DECOMP_WSS = 3 (the default): second order plus the second pair per iteration (DP); 2: one
+  // pair (40k 17.0 -> 15.5 ms, 60k 20.8 -> 19.2, 120k 43.9 -> 42.7, 250k 84.9 -> 83.1, 1M 296 -> 289)
+  const char* wss = getenv("SVM355_DECOMP_WSS");
+  k.dp = k.wss2 && (wss ? atoi(wss) >= 3 : true);
+  // SVM355_DECOMP_WSS = 4: the second pair's j by the second-order gain of row i2 (opt-in)
+  k.j2s = k.dp && wss && atoi(wss) == 4;
+  // with one batch always queued ahead, 1 already hides the host; more only adds no-op tail
+  if (const char* v = getenv("SVM355_DECOMP_BATCH")) k.batch = std::max(1, atoi(v));
+  const char* kww = getenv("SVM355_DECOMP_KWW");  // "sym": the triangular Gram launch (A/B)
+  k.kww_sym = kww && std::strcmp(kww, "sym") == 0;
+  const char* pk = getenv("SVM355_DECOMP_PACK");
+  k.pack = !(pk && atoi(pk) == 0);
+  // repack when the active rows are at most this share of the packed ones
+  if (const char* v = getenv("SVM355_DECOMP_REPACK")) k.repack_frac = std::min(1.0, std::max(0.0, atof(v)));
+  k.shrink_log = is1("SVM355_DECOMP_SHRINK_LOG");
+  // fault injection (tests, world > 1): rank SVM355_DECOMP_FAIL_RANK fails when it is about to enqueue
+  // outer iteration SVM355_DECOMP_FAIL_OUTER (default 0: before the first selection), while its peers
+  // wait in their candidate all-gathers (decomp_cpu.cpp has the same hook)
+  if (const char* fr = getenv("SVM355_DECOMP_FAIL_RANK")) {
+    const char* fo = getenv("SVM355_DECOMP_FAIL_OUTER");
+    k.fail_rank = atoi(fr);
+    k.fail_outer = fo ? std::max(0, atoi(fo)) : 0;
+  }
+  if (const char* cc = getenv("SVM355_DECOMP_CCACHE")) k.ccache = atoi(cc) != 0 ? 1 : 0;
+  // evict by CLOCK once the slots are taken (SVM355_DECOMP_CCACHE_EVICT=0: fill-only, the round-4 cache)
+  const char* ev = getenv("SVM355_DECOMP_CCACHE_EVICT");
+  k.cache_evict = !(ev && atoi(ev) == 0);
+  if (const char* v = getenv("SVM355_DECOMP_CCACHE_FRAC")) k.ccache_frac = std::min(0.9, std::max(0.0, atof(v)));
+  if (const char* v = getenv("SVM355_DECOMP_CCACHE_SLOTS")) {  // tests: a small cache (its scratch path)
+    k.ccache_slots_set = true;
+    k.ccache_slots = atoll(v);
+  }
+  if (const char* lw = getenv("LOCAL_WORLD_SIZE")) k.local_world = std::max(1, atoi(lw));
+  *out = k;
+  return SVM_OK;
+}
+
+// A bump allocator over the context's workspace, 256-byte aligned: `layout` names every buffer once and
+// runs twice, first against no base for the total size, then against the (grown) workspace.
+struct WsCarver {
+  char* base;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t count, bool on = true) {
+    if (!on) return nullptr;
+    const size_t o = off;
+    off += (count * sizeof(T) + 255) & ~size_t(255);
+    return base ? reinterpret_cast<T*>(base + o) : nullptr;
+  }
+};
+template <class Layout>
+int carve_ws(DeviceCtx* ctx, Layout&& layout) {
+  WsCarver size{nullptr};
+  layout(size);
+  const int rc = ctx->ensure_ws(size.off);
+  if (rc) return rc;
+  WsCarver c{static_cast<char*>(ctx->ws)};
+  layout(c);
+  return SVM_OK;
+}
+
+// A solve's buffers in the context's workspace (nullptr: not part of this solve).
+struct DecompWs {
+  double* f = nullptr;                     // this GPU's rows
+  CandRec *own = nullptr, *all = nullptr;  // this GPU's candidate records, every GPU's
+  int32_t* W = nullptr;
+  double *Wf = nullptr, *Kw = nullptr;  // the working set's f (the inner solve's, the Newton polish's), K(W, W)
+  double* coef = nullptr;               // the moved columns: (alpha_new - alpha_old) y, ids, their number
+  int32_t *cols = nullptr, *mcount = nullptr;
+  DecompCtl* ctl = nullptr;
+  // exact-integer rows: the working set's quantised rows and the GEMV's column-half partials;
+  // FP64 rows: the working set's and the moved columns' rows (+ norms) and the block K(rows, columns)
+  int8_t* Qw = nullptr;
+  int32_t* N0w = nullptr;
+  double *WNw = nullptr, *part = nullptr, *Xw = nullptr, *nw = nullptr, *Xc = nullptr, *nc = nullptr, *Kc = nullptr;
+  // column cache state: slot per point (-1 = none), the update's slots, its misses, {next free, misses},
+  // the CLOCK metadata (fill-only: none)
+  int32_t *cslot = nullptr, *crd = nullptr, *cmid = nullptr, *cmsl = nullptr, *cst = nullptr, *cmeta = nullptr;
+  int32_t* wid = nullptr;  // K(W, W) through the narrow column store: the ids 0 .. kMaxWS - 1, then the count kMaxWS
+  // warm start (and the recomputation of f when a shrunk solve unshrinks): the nonzero alphas' ids and
+  // alpha y (all n at most), the per-chunk column counts
+  int32_t *wcols = nullptr, *wcnt = nullptr;
+  double* wcoef = nullptr;
+  uint8_t* shr = nullptr;  // shrinking (decomp_shrink.h): the per-row flags
+  // the Newton polish (decomp_newton.h): W's alpha by position and the factorisation's scratch
+  double *gAw = nullptr, *nAmat = nullptr;
+  // packing (shrinking on exact-integer rows): the packed lists of active rows (two buffers), the selection
+  // blocks' offsets into them (two), the blocks' counts, the rows' packed positions, the device-side packed
+  // row count, the moved columns' (and misses') packed positions for the unit diagonal, and the packed
+  // copies of the quantised rows
+  int32_t *act[2] = {nullptr, nullptr}, *boff[2] = {nullptr, nullptr};
+  int32_t *bcnt = nullptr, *pos_of = nullptr, *nrows = nullptr, *cdiag = nullptr, *mdiag = nullptr, *N0a = nullptr;
+  int8_t* Qa = nullptr;
+  double* WNa = nullptr;
+};
+
+// The f update's kernel columns K(this GPU's rows, j) kept in HBM (size_col_cache); slab null: no cache.
+struct ColCache {
+  double* slab = nullptr;
+  int32_t cap = 0;  // persistent slots (kMaxWS scratch slots follow them)
+  int64_t ld = 0;   // slot stride in doubles
+};
+
+// What every stage of a solve reads: the problem, this GPU's slice of it, the knobs, the buffers.
+struct Solve {
+  DeviceCtx* ctx = nullptr;
+  hipStream_t s = nullptr;
+  DecompRows R;
+  bool f64 = false;
+  int kq = 0;  // the quantised rows' bytes (exact-integer rows)
+  const int32_t* y = nullptr;
+  double* alpha = nullptr;
+  svm_params p{};
+  DecompShape sh;
+  int world = 1, rank = 0;
+  // all rows; this GPU's selection blocks, rows [lo, lo + nloc) and candidate records; warm-start chunks
+  int64_t n = 0, NBr = 0, lo = 0, nloc = 0, Lr = 0, nchunks = 0;
+  DecompKnobs k;
+  bool wide_select = false, kww_narrow = false, pack_on = false;
+  ShrinkCfg shc;
+  InnerVariant inner;
+  NwDev nwd{};
+  const DecompAllGather* allgather = nullptr;
+  svm_decomp_trace* tr = nullptr;
+  ColCache cc;
+  DecompWs w;
+  // pinned: the PROF totals, the two published control blocks (and their device address), the warm start's count
+  DecompHost* hs = nullptr;
+  DecompCtl *ctl_h = nullptr, *ctl_pub = nullptr;
+  int64_t* nz_h = nullptr;
+  std::chrono::steady_clock::time_point t0;
+};
+
+// The packed rows of a shrunk solve and the host's view of the shrinking: pk = the current list's buffer
+// (-1: none, the rows in place -- before the first repack and after an unshrink), pk_bound = an upper bound
+// of the device's packed row count (the active count the host last read: passes only drop rows); o_dev =
+// the device's outer-iteration count when the next enqueued one runs (exact: only a stop or an unshrink
+// turns launches into no-ops, and the host re-reads the count at an unshrink), origin = the outer count at
+// the start or the last unshrink, seen_active = the active rows the host last read back.
+struct PackState {
+  int pk = -1;
+  int64_t pk_bound = 0, seen_active = 0, min_active = 0;
+  int64_t o_dev = 0, origin = 0, unshrinks = 0, repacks = 0;
+  explicit PackState(int64_t nloc) : pk_bound(nloc), seen_active(nloc), min_active(nloc) {}
+};
+
+// Column cache (exact-integer rows): the f update's kernel columns K(this GPU's rows, j) stay in HBM
+// per point for the rest of the fit, so a column moved again is a read, not an int8-MFMA
+// recomputation (64 / 75 / 85 % of the column uses at 60k / 250k / 1M repeat an earlier one,
+// profiles/r4_decomp_column_cache.txt); bit-identical to the GEMV path (ws_cache_fsum_kernel).
+// SVM355_DECOMP_CCACHE = 0 off, 1 on; default on once this GPU's int8 rows (nloc x kq bytes, read by
+// every recomputation) outgrow the 256 MB last-level cache: the recomputation then streams them from
+// HBM (192 MiB: 60k MNIST rows, 46 MB, are 4 % faster without the cache, 250k rows 2 % with it).
+// Runs under the lock that also covers the workspace allocation (alloc_solve).
+int size_col_cache(const Solve& S, bool warm, ColCache* out) {
+  DeviceCtx* ctx = S.ctx;
+  const DecompKnobs& k = S.k;
+  const int64_t n = S.n, nloc = S.nloc;
+  *out = ColCache{};
+  if (S.f64 || nloc <= 0) return SVM_OK;
+  if (!(k.ccache >= 0 ? k.ccache != 0 : nloc * int64_t(S.kq) > (int64_t(192) << 20))) return SVM_OK;
+  // slots: twice the distinct columns measured per fit (~1,686 (n / 60k)^0.46), within half the free
+  // HBM, plus kMaxWS scratch slots (moved columns beyond a full cache, this update only)
+  int64_t cap = int64_t(2.0 * 1686.0 * std::pow(double(n) / 60000.0, 0.46));
+  cap = std::min<int64_t>(std::max<int64_t>(cap, 1024), n);
+  size_t free_b = 0, total_b = 0;
+  SVMD_CHECK(hipMemGetInfo(&free_b, &total_b));
+  const int64_t ld = (nloc + 3) & ~int64_t(3);  // a multiple of 4: 16-byte row pairs (or quads) in the reader
+  const size_t slot_b = size_t(ld) * 8;
+  // the workspace allocated next (f, the GEMV partials, the per-point slot map, a warm start's columns
+  // and ~64 MB of fixed parts) comes out of the same free memory
+  const size_t ws_need = size_t(nloc + 1) * 8 * size_t(1 + kLdp) + size_t(n) * (warm ? 16 : 4) + (size_t(64) << 20);
+  const size_t ws_grow = ws_need > ctx->ws_bytes ? ws_need - ctx->ws_bytes : 0;
+  const size_t avail = free_b + ctx->rc_cache_bytes > ws_grow ? free_b + ctx->rc_cache_bytes - ws_grow : 0;
+  cap = std::min<int64_t>(cap, int64_t(avail / 2 / slot_b) - kMaxWS);
+  // and at most a quarter of the GPU's HBM (SVM355_DECOMP_CCACHE_FRAC): the slab is a grow-only
+  // buffer of the context, kept for the next fit, that PyTorch's allocator cannot see -- it must leave
+  // room for the caller's tensors and other contexts on the device.  At 1M rows that is
+  // ~8,000 slots of 8 MB for ~6,100 distinct columns a fit moves, so no fit of n <= 1M loses a hit.
+  // (a context's own share when several solve side by side, svmd_set_ccache_frac; the env var overrides)
+  double frac = ctx->ccache_frac >= 0.0 ? ctx->ccache_frac : 0.25;
+  // processes sharing this GPU (torchrun ranks over host-staged gloo on one device; the lock orders the
+  // sizing within a process only): each takes its share of the quarter
+  if (ctx->ccache_frac < 0.0 && k.local_world > 0) {
+    int ndev = 1;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) ndev = 1;
+    const int sharing = (k.local_world + ndev - 1) / ndev;
+    frac /= double(sharing);
+  }
+  if (k.ccache_frac >= 0.0) frac = k.ccache_frac;
+  cap = std::min<int64_t>(cap, int64_t(double(total_b) * frac / double(slot_b)) - kMaxWS);
+  int64_t min_cap = 256;
+  if (k.ccache_slots_set) {
+    cap = std::min<int64_t>(cap, k.ccache_slots);
+    min_cap = 1;
+  }
+  if (cap >= min_cap && cap < int64_t(INT32_MAX) - kMaxWS) out->slab = ctx->ensure_rc_cache(size_t(cap + kMaxWS) * slot_b);
+  if (!out->slab) {
+    (void)hipGetLastError();  // a failed allocation is not sticky: the GEMV path runs
+    return SVM_OK;
+  }
+  out->cap = int32_t(cap);
+  out->ld = ld;
+  return SVM_OK;
+}
+
+// The solve's workspace, in this order (the layout is part of what a fit's speed was measured on).
+void layout_ws(Solve& S, bool warm, WsCarver& c) {
+  DecompWs& w = S.w;
+  const size_t nl1 = size_t(std::max<int64_t>(S.nloc, 1)), n = size_t(S.n), kq = size_t(S.kq), ld = size_t(S.R.ld);
+  const bool f64 = S.f64, q8 = !f64, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
+  w.f = c.take<double>(nl1);
+  w.own = c.take<CandRec>(size_t(S.Lr));
+  w.all = c.take<CandRec>(size_t(S.sh.L));
+  w.W = c.take<int32_t>(kMaxWS);
+  w.Wf = c.take<double>(kMaxWS);
+  w.Kw = c.take<double>(size_t(kMaxWS) * kLdw);
+  w.coef = c.take<double>(kMaxWS);
+  w.cols = c.take<int32_t>(kMaxWS);
+  w.mcount = c.take<int32_t>(64);
+  w.ctl = c.take<DecompCtl>(1);
+  w.Qw = c.take<int8_t>(size_t(kMaxWS) * kq, q8);
+  w.N0w = c.take<int32_t>(kMaxWS, q8);
+  w.WNw = c.take<double>(kMaxWS, q8);
+  w.part = c.take<double>(nl1 * kLdp, q8);
+  w.Xw = c.take<double>(size_t(kMaxWS) * ld, f64);
+  w.nw = c.take<double>(kMaxWS, f64);
+  w.Xc = c.take<double>(size_t(kMaxWS) * ld, f64);
+  w.nc = c.take<double>(kMaxWS, f64);
+  w.Kc = c.take<double>(nl1 * kMaxWS, f64);
+  w.cslot = c.take<int32_t>(n, cache);
+  w.crd = c.take<int32_t>(kMaxWS, cache);
+  w.cmid = c.take<int32_t>(kMaxWS, cache);
+  w.cmsl = c.take<int32_t>(kMaxWS, cache);
+  w.cst = c.take<int32_t>(16, cache);
+  w.cmeta = c.take<int32_t>(size_t(S.cc.cap) * 3, cache && S.k.cache_evict);  // owner, last, ref per slot
+  w.wid = c.take<int32_t>(kMaxWS + 16, q8);
+  w.wcols = c.take<int32_t>(n, nzbuf);
+  w.wcoef = c.take<double>(n, nzbuf);
+  w.wcnt = c.take<int32_t>(size_t(S.nchunks + 1), nzbuf);
+  w.shr = c.take<uint8_t>(nl1, S.shc.on);
+  w.gAw = c.take<double>(kMaxWS);
+  w.nAmat = c.take<double>(size_t(kMaxWS + 2) * kMaxWS, S.nwd.on != 0);
+  w.act[0] = c.take<int32_t>(nl1 * 2, pack);
+  w.act[1] = w.act[0] ? w.act[0] + nl1 : nullptr;
+  w.boff[0] = c.take<int32_t>(size_t(S.NBr + 1) * 2, pack);
+  w.boff[1] = w.boff[0] ? w.boff[0] + (S.NBr + 1) : nullptr;
+  w.bcnt = c.take<int32_t>(size_t(S.NBr + 1), pack);
+  w.pos_of = c.take<int32_t>(nl1, pack);
+  w.nrows = c.take<int32_t>(16, pack);
+  w.cdiag = c.take<int32_t>(kMaxWS, pack);
+  w.mdiag = c.take<int32_t>(kMaxWS, pack);
+  w.Qa = c.take<int8_t>(nl1 * kq, pack);
+  w.N0a = c.take<int32_t>(nl1, pack);
+  w.WNa = c.take<double>(nl1, pack);
+}
+
+// The checks, the shape and this GPU's slice of it, the knobs and what follows from them.
+int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n,
+                const svm_params& p, int qws, const DecompOpts& o) {
   const int world = o.world, rank = o.rank;
-  const DecompAllGather& allgather = o.allgather;
-  if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allgather)) {
+  if (world < 1 || rank < 0 || rank >= world || (world > 1 && !o.allgather)) {
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
   }
@@ -1886,11 +1172,6 @@ int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* al
     set_error("decomposition SMO: bad row source");
     return SVM_ERR_ARG;
   }
-  static const QuantPlan kNoPlan;
-  const QuantPlan& P = f64 ? kNoPlan : *R.P;
-  const int8_t* Q = R.Q;
-  const int32_t* N0 = R.N0;
-  const double *WN = R.WN, *stw = R.stw;
   svm_decomp_trace* tr = o.trace;
   if (tr && (world != 1 || tr->cap < 0 || (tr->n != 0 && tr->n != n))) {
     set_error("decomposition SMO: a trace needs one GPU and snapshots of n = %lld", (long long)n);
@@ -1902,661 +1183,529 @@ int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* al
               "world <= 64)", (long long)n, (long long)sh.L, kMaxWS);
     return SVM_ERR_ARG;
   }
-  const int64_t NBr = sh.NB / world, b0 = rank * NBr;
-  const int64_t lo = std::min<int64_t>(n, b0 * sh.per), hi = std::min<int64_t>(n, (b0 + NBr) * sh.per);
-  const int64_t nloc = hi - lo;
-  const int T = sh.T;
-  const int64_t Lr = 2 * NBr * T;  // this GPU's candidate records (I_high picks, then I_low)
-  const char* wide_env = getenv("SVM355_DECOMP_WIDE_SELECT");
-  const bool wide_select = sh.per > int64_t(kSelNT) * kSelE || T > 64 || (wide_env && atoi(wide_env) == 1);
-  // inner workgroup: NT threads x PER points (NT * PER = 1024); SVM355_DECOMP_NT = 64 | 128 | 256 | 512
-  int inner_nt = 256;
-  if (const char* v = getenv("SVM355_DECOMP_NT")) inner_nt = atoi(v);
-  if (inner_nt != 64 && inner_nt != 128 && inner_nt != 512 && inner_nt != 65) inner_nt = 256;
-  // 65: one wave x 6 points (A/B probe of a one-wave inner solve; needs a working set of <= 384)
-  if (inner_nt == 65 && sh.L > 384) {
-    set_error("decomposition SMO: SVM355_DECOMP_NT=65 needs a working set of <= 384 points");
-    return SVM_ERR_ARG;
-  }
-  // inner stop: the working set's own gap <= max(2 tau, 2 tau_frac gap) (SVM355_DECOMP_TAU_FRAC)
-  double tau_frac = 0.1;
-  if (const char* v = getenv("SVM355_DECOMP_TAU_FRAC")) tau_frac = atof(v);
-  // at 0.5 and above the working set's stop (its gap <= tau_frac x 2 gap) holds before any update, so the
-  // solve could make no progress (it would stop at once with a zero model)
-  if (!(tau_frac >= 0.0 && tau_frac < 0.5)) {
-    set_error("decomposition SMO: SVM355_DECOMP_TAU_FRAC must be in [0, 0.5), got %g", tau_frac);
-    return SVM_ERR_ARG;
-  }
-  // SVM355_DECOMP_PROF=1: clock64 phase totals of the inner solves on stderr (diagnostic build)
-  const bool prof = getenv("SVM355_DECOMP_PROF") && atoi(getenv("SVM355_DECOMP_PROF")) == 1;
-  // inner pair selection: second order for j (default; fewer, longer iterations: 8,206 vs 14,334 at
-  // 60k, 12% faster) or first order (SVM355_DECOMP_WSS=1)
-  const bool inner_wss2 = !(getenv("SVM355_DECOMP_WSS") && atoi(getenv("SVM355_DECOMP_WSS")) == 1);
-  // SVM355_DECOMP_WSS = 3 (the default): second order plus the second pair per iteration (DP); 2: one
-  // pair (40k 17.0 -> 15.5 ms, 60k 20.8 -> 19.2, 120k 43.9 -> 42.7, 250k 84.9 -> 83.1, 1M 296 -> 289)
-  const char* wss_env = getenv("SVM355_DECOMP_WSS");
-  const bool inner_dp = inner_wss2 && (wss_env ? atoi(wss_env) >= 3 : true);
-  // SVM355_DECOMP_WSS = 4: the second pair's j by the second-order gain of row i2 (opt-in)
-  const bool inner_j2s = inner_dp && wss_env && atoi(wss_env) == 4;
-  const int64_t ldw = kMaxWS;              // K(W, W) row stride
-  const int64_t ldp = 2 * (kMaxWS / 128);  // column halves of the f update
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += al(bytes);
-    return o;
-  };
-  // Column cache (exact-integer rows): the f update's kernel columns K(this GPU's rows, j) stay in HBM
-  // per point for the rest of the fit, so a column moved again is a read, not an int8-MFMA
-  // recomputation (64 / 75 / 85 % of the column uses at 60k / 250k / 1M repeat an earlier one,
-  // profiles/r4_decomp_column_cache.txt); bit-identical to the GEMV path (ws_cache_fsum_kernel).
-  // SVM355_DECOMP_CCACHE = 0 off, 1 on; default on once this GPU's int8 rows (nloc x kq bytes, read by
-  // every recomputation) outgrow the 256 MB last-level cache: the recomputation then streams them from
-  // HBM (192 MiB: 60k MNIST rows, 46 MB, are 4 % faster without the cache, 250k rows 2 % with it).
-  bool use_cache = false;
-  int32_t cache_cap = 0;
-  // Sizing and allocating the cache and the workspace is one step per process: thread ranks sharing a
-  // GPU (the loopback rehearsal) would otherwise read the same free memory, each take half of it, and
-  // leave a later rank without room for its workspace.
-  static std::mutex alloc_mu;
-  std::unique_lock<std::mutex> alloc_lock(alloc_mu);
-  // evict by CLOCK once the slots are taken (SVM355_DECOMP_CCACHE_EVICT=0: fill-only, the round-4 cache)
-  const char* ev_env = getenv("SVM355_DECOMP_CCACHE_EVICT");
-  const bool cache_evict = !(ev_env && atoi(ev_env) == 0);
-  int64_t ldc_cache = 0;
-  double* cache = nullptr;
-  if (!f64 && nloc > 0) {
-    const char* cc = getenv("SVM355_DECOMP_CCACHE");
-    use_cache = cc ? atoi(cc) != 0 : nloc * int64_t(P.kq) > (int64_t(192) << 20);
-  }
-  if (use_cache) {
-    // slots: twice the distinct columns measured per fit (~1,686 (n / 60k)^0.46), within half the free
-    // HBM, plus kMaxWS scratch slots (moved columns beyond a full cache, this update only)
-    int64_t cap = int64_t(2.0 * 1686.0 * std::pow(double(n) / 60000.0, 0.46));
-    cap = std::min<int64_t>(std::max<int64_t>(cap, 1024), n);
-    size_t free_b = 0, total_b = 0;
-    SVMD_CHECK(hipMemGetInfo(&free_b, &total_b));
-    ldc_cache = (nloc + 3) & ~int64_t(3);  // a multiple of 4: 16-byte row pairs (or quads) in the reader
-    const size_t slot_b = size_t(ldc_cache) * 8;
-    // the workspace allocated below (f, the GEMV partials, the per-point slot map, a warm start's columns
-    // and ~64 MB of fixed parts) comes out of the same free memory
-    const size_t ws_need = size_t(nloc + 1) * 8 * size_t(1 + ldp) + size_t(n) * (o.warm ? 16 : 4) + (size_t(64) << 20);
-    const size_t ws_grow = ws_need > ctx->ws_bytes ? ws_need - ctx->ws_bytes : 0;
-    const size_t avail = free_b + ctx->rc_cache_bytes > ws_grow ? free_b + ctx->rc_cache_bytes - ws_grow : 0;
-    cap = std::min<int64_t>(cap, int64_t(avail / 2 / slot_b) - kMaxWS);
-    // and at most a quarter of the GPU's HBM (SVM355_DECOMP_CCACHE_FRAC): the slab is a grow-only
-    // buffer of the context, kept for the next fit, that PyTorch's allocator cannot see -- it must leave
-    // room for the caller's tensors and other contexts on the device.  At 1M rows that is
-    // ~8,000 slots of 8 MB for ~6,100 distinct columns a fit moves, so no fit of n <= 1M loses a hit.
-    // (a context's own share when several solve side by side, svmd_set_ccache_frac; the env var overrides)
-    double frac = ctx->ccache_frac >= 0.0 ? ctx->ccache_frac : 0.25;
-    // processes sharing this GPU (torchrun ranks over host-staged gloo on one device; alloc_mu orders the
-    // sizing within a process only): each takes its share of the quarter
-    if (ctx->ccache_frac < 0.0)
-      if (const char* lw = getenv("LOCAL_WORLD_SIZE")) {
-        int ndev = 1;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) ndev = 1;
-        const int sharing = (std::max(1, atoi(lw)) + ndev - 1) / ndev;
-        frac /= double(sharing);
-      }
-    if (const char* v = getenv("SVM355_DECOMP_CCACHE_FRAC")) frac = std::min(0.9, std::max(0.0, atof(v)));
-    cap = std::min<int64_t>(cap, int64_t(double(total_b) * frac / double(slot_b)) - kMaxWS);
-    int64_t min_cap = 256;
-    if (const char* v = getenv("SVM355_DECOMP_CCACHE_SLOTS")) {  // tests: a small cache (its scratch path)
-      cap = std::min<int64_t>(cap, atoll(v));
-      min_cap = 1;
-    }
-    if (cap >= min_cap && cap < int64_t(INT32_MAX) - kMaxWS) {
-      cache = ctx->ensure_rc_cache(size_t(cap + kMaxWS) * slot_b);
-      cache_cap = int32_t(cap);
-    }
-    use_cache = cache != nullptr;
-    if (!use_cache) (void)hipGetLastError();  // a failed allocation is not sticky: the GEMV path runs
-  }
-  const size_t nl1 = size_t(std::max<int64_t>(nloc, 1));
-  const size_t o_f = take(nl1 * 8), o_own = take(size_t(Lr) * sizeof(CandRec)),
-               o_all = take(size_t(sh.L) * sizeof(CandRec)), o_W = take(kMaxWS * 4), o_Wf = take(kMaxWS * 8),
-               o_Kw = take(size_t(kMaxWS) * ldw * 8), o_coef = take(kMaxWS * 8), o_cols = take(kMaxWS * 4),
-               o_mcount = take(256), o_ctl = take(sizeof(DecompCtl));
-  // exact-integer rows: the working set's quantised rows and the GEMV's column-half partials;
-  // FP64 rows: the working set's and the moved columns' rows (+ norms) and the block K(rows, columns)
-  const size_t o_Qw = f64 ? 0 : take(size_t(kMaxWS) * P.kq), o_N0w = f64 ? 0 : take(kMaxWS * 4),
-               o_WNw = f64 ? 0 : take(kMaxWS * 8), o_part = f64 ? 0 : take(nl1 * ldp * 8),
-               o_Xw = f64 ? take(size_t(kMaxWS) * R.ld * 8) : 0, o_nw = f64 ? take(kMaxWS * 8) : 0,
-               o_Xc = f64 ? take(size_t(kMaxWS) * R.ld * 8) : 0, o_nc = f64 ? take(kMaxWS * 8) : 0,
-               o_Kc = f64 ? take(nl1 * kMaxWS * 8) : 0;
-  // column cache state: slot per point (-1 = none), the update's slots, its misses, {next free, misses}
-  const size_t o_cslot = use_cache ? take(size_t(n) * 4) : 0, o_crd = use_cache ? take(kMaxWS * 4) : 0,
-               o_cmid = use_cache ? take(kMaxWS * 4) : 0, o_cmsl = use_cache ? take(kMaxWS * 4) : 0,
-               o_cst = use_cache ? take(64) : 0,
-               o_cmeta = use_cache && cache_evict ? take(size_t(cache_cap) * 12) : 0;
-  // K(W, W) through the narrow column store: the identity ids 0 .. kMaxWS - 1 and the column count
-  const size_t o_wid = f64 ? 0 : take(kMaxWS * 4 + 64);
-  // warm start (and the recomputation of f when a shrunk solve unshrinks): the nonzero alphas' ids and
-  // alpha y (all n at most), the per-chunk column counts
-  const ShrinkCfg shc = shrink_cfg(p);
-  const bool nzbuf = o.warm || shc.on;
-  const int64_t nchunks = (n + kMaxWS - 1) / kMaxWS;
-  const size_t o_wcols = nzbuf ? take(size_t(n) * 4) : 0, o_wcoef = nzbuf ? take(size_t(n) * 8) : 0,
-               o_wcnt = nzbuf ? take(size_t(nchunks + 1) * 4) : 0;
-  // shrinking (decomp_shrink.h): the per-row flags; with packing (exact-integer rows) the packed lists of
-  // active rows (two buffers), the selection blocks' offsets into them (two), the blocks' counts, the
-  // rows' packed positions, the device-side packed row count, the moved columns' (and misses') packed
-  // positions for the unit diagonal, and the packed copies of the quantised rows
-  const char* pk_env = getenv("SVM355_DECOMP_PACK");
-  const bool pack_on = shc.on && !f64 && nloc > 0 && !(pk_env && atoi(pk_env) == 0);
-  double repack_frac = 0.75;  // repack when the active rows are at most this share of the packed ones
-  if (const char* v = getenv("SVM355_DECOMP_REPACK")) repack_frac = std::min(1.0, std::max(0.0, atof(v)));
-  const size_t o_shr = shc.on ? take(nl1) : 0;
-  // the Newton polish (decomp_newton.h): W's alpha by position and the factorisation's scratch
+  const int rc = read_knobs(sh, &S.k);
+  if (rc) return rc;
+  S.ctx = ctx;
+  S.s = ctx->stream;
+  S.R = R;
+  S.f64 = f64;
+  S.kq = f64 ? 0 : R.P->kq;
+  S.y = y;
+  S.alpha = alpha;
+  S.n = n;
+  S.p = p;
+  S.sh = sh;
+  S.world = world;
+  S.rank = rank;
+  S.NBr = sh.NB / world;
+  const int64_t b0 = rank * S.NBr;
+  S.lo = std::min<int64_t>(n, b0 * sh.per);
+  S.nloc = std::min<int64_t>(n, (b0 + S.NBr) * sh.per) - S.lo;
+  S.Lr = 2 * S.NBr * sh.T;  // this GPU's candidate records (I_high picks, then I_low)
+  S.nchunks = (n + kMaxWS - 1) / kMaxWS;
+  S.wide_select = sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select;
+  S.kww_narrow = !f64 && !S.k.kww_sym && S.kq <= 1536;
+  S.shc = shrink_cfg(p);
+  S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
   const NewtonCfg nwc = newton_cfg(p);
-  const NwDev nwd{nwc.on ? 1 : 0, nwc.every, nwc.per_solve, nwc.repeat, nwc.max_free, 0, nwc.frac};
-  const size_t o_gaw = take(kMaxWS * 8), o_namat = nwc.on ? take(size_t(kMaxWS + 2) * kMaxWS * 8) : 0;
-  const size_t o_act = pack_on ? take(nl1 * 4 * 2) : 0, o_boff = pack_on ? take(size_t(NBr + 1) * 4 * 2) : 0,
-               o_bcnt = pack_on ? take(size_t(NBr + 1) * 4) : 0, o_pos = pack_on ? take(nl1 * 4) : 0,
-               o_nrows = pack_on ? take(64) : 0, o_cdiag = pack_on ? take(kMaxWS * 4) : 0,
-               o_mdiag = pack_on ? take(kMaxWS * 4) : 0, o_Qa = pack_on ? take(nl1 * size_t(P.kq)) : 0,
-               o_N0a = pack_on ? take(nl1 * 4) : 0, o_WNa = pack_on ? take(nl1 * 8) : 0;
-  int rc = ctx->ensure_ws(off);
+  S.nwd = NwDev{nwc.on ? 1 : 0, nwc.every, nwc.per_solve, nwc.repeat, nwc.max_free, 0, nwc.frac};
+  S.inner = InnerVariant{S.k.inner_nt, S.k.prof, S.k.wss2, S.k.dp, S.k.j2s, nwc.on};
+  S.allgather = &o.allgather;
+  S.tr = tr;
+  return SVM_OK;
+}
+
+// Sizing and allocating the cache and the workspace is one step per process: thread ranks sharing a
+// GPU (the loopback rehearsal) would otherwise read the same free memory, each take half of it, and
+// leave a later rank without room for its workspace.
+int alloc_solve(Solve& S, bool warm) {
+  static std::mutex alloc_mu;
+  std::lock_guard<std::mutex> alloc_lock(alloc_mu);
+  int rc = size_col_cache(S, warm, &S.cc);
   if (rc) return rc;
-  rc = ctx->ensure_pinned(sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl) + 64);
-  if (rc) return rc;
-  alloc_lock.unlock();
-  char* ws = static_cast<char*>(ctx->ws);
-  auto* f = reinterpret_cast<double*>(ws + o_f);
-  auto* cown = reinterpret_cast<CandRec*>(ws + o_own);
-  auto* call = world > 1 ? reinterpret_cast<CandRec*>(ws + o_all) : cown;
-  auto* W = reinterpret_cast<int32_t*>(ws + o_W);
-  auto* Wf = reinterpret_cast<double*>(ws + o_Wf);
-  auto* Qw = reinterpret_cast<int8_t*>(ws + o_Qw);
-  auto* N0w = reinterpret_cast<int32_t*>(ws + o_N0w);
-  auto* WNw = reinterpret_cast<double*>(ws + o_WNw);
-  auto* Kw = reinterpret_cast<double*>(ws + o_Kw);
-  auto* coef = reinterpret_cast<double*>(ws + o_coef);
-  auto* cols = reinterpret_cast<int32_t*>(ws + o_cols);
-  auto* mcount = reinterpret_cast<int32_t*>(ws + o_mcount);
-  auto* part = reinterpret_cast<double*>(ws + o_part);
-  auto* Xw = reinterpret_cast<double*>(ws + o_Xw);
-  auto* nw = reinterpret_cast<double*>(ws + o_nw);
-  auto* Xc = reinterpret_cast<double*>(ws + o_Xc);
-  auto* nc = reinterpret_cast<double*>(ws + o_nc);
-  auto* Kc = reinterpret_cast<double*>(ws + o_Kc);
-  auto* cslot = reinterpret_cast<int32_t*>(ws + o_cslot);
-  auto* crd = reinterpret_cast<int32_t*>(ws + o_crd);
-  auto* cmid = reinterpret_cast<int32_t*>(ws + o_cmid);
-  auto* cmsl = reinterpret_cast<int32_t*>(ws + o_cmsl);
-  auto* cst = reinterpret_cast<int32_t*>(ws + o_cst);
-  auto* cmeta = use_cache && cache_evict ? reinterpret_cast<int32_t*>(ws + o_cmeta) : nullptr;
-  auto* wid = reinterpret_cast<int32_t*>(ws + o_wid);  // [kMaxWS] identity, then the count kMaxWS
-  auto* ctl = reinterpret_cast<DecompCtl*>(ws + o_ctl);
-  auto* shr = shc.on ? reinterpret_cast<uint8_t*>(ws + o_shr) : nullptr;
-  auto* gAw = reinterpret_cast<double*>(ws + o_gaw);
-  auto* nAmat = nwc.on ? reinterpret_cast<double*>(ws + o_namat) : nullptr;
-  double* Wfw = Wf;  // the inner solve's W-local f, also the Newton polish's
-  int32_t* pact[2] = {reinterpret_cast<int32_t*>(ws + o_act), reinterpret_cast<int32_t*>(ws + o_act) + nl1};
-  int32_t* pboff[2] = {reinterpret_cast<int32_t*>(ws + o_boff), reinterpret_cast<int32_t*>(ws + o_boff) + (NBr + 1)};
-  auto* pbcnt = reinterpret_cast<int32_t*>(ws + o_bcnt);
-  auto* pos_of = reinterpret_cast<int32_t*>(ws + o_pos);
-  auto* pk_rows = reinterpret_cast<int32_t*>(ws + o_nrows);
-  auto* cdiag = reinterpret_cast<int32_t*>(ws + o_cdiag);
-  auto* mdiag = reinterpret_cast<int32_t*>(ws + o_mdiag);
-  auto* Qa = reinterpret_cast<int8_t*>(ws + o_Qa);
-  auto* N0a = reinterpret_cast<int32_t*>(ws + o_N0a);
-  auto* WNa = reinterpret_cast<double*>(ws + o_WNa);
-  // the packed state (host side): pk = the current list's buffer (-1: none, the rows in place -- before
-  // the first repack and after an unshrink), pk_bound = an upper bound of the device's packed row count
-  // (the active count the host last read: passes only drop rows)
-  int pk = -1;
-  int64_t pk_bound = nloc;
-  // f += K(this GPU's rows, cols[0:*cnt]) coef: the exact-integer GEMV (column-half partials summed in
-  // order) or, for FP64 rows, the moved columns' rows gathered, their block on FP64 MFMA and a row sum
-  // tiled: also launch the tiled column store for updates of more than 64 misses (it exits at once
-  // otherwise, but a launch over every row tile costs ~5-8 us); off after the first outer iterations,
-  // where the narrow store takes any count itself (only the cold start misses hundreds of columns)
-  // Packed rows (a shrunk solve, pk >= 0): the row operand is the packed copy (Qa, N0a, WNa) of the active
-  // rows, pk_bound of them by the host's bound (the device count pk_rows gates the sums), the unit
-  // diagonal from the columns' packed positions (the inner solve's cdiag), and the sums go to f[act[k]].
-  auto f_update = [&](const int32_t* cl, const double* cf, const int32_t* cnt, bool tiled = true) -> int {
-    if (nloc <= 0) return SVM_OK;
-    const bool packed = pk >= 0;
-    const int8_t* Qr = packed ? Qa : Q + lo * int64_t(P.kq);
-    const int32_t* N0r = packed ? N0a : N0 + lo;
-    const double* WNr = packed ? WNa : WN + lo;
-    const int64_t nr = packed ? pk_bound : nloc, roff = packed ? 0 : lo;
-    const int32_t* pa = packed ? pact[pk] : nullptr;
-    const int32_t* pn = packed ? pk_rows : nullptr;
-    if (nr <= 0) return SVM_OK;
-    if (use_cache) {  // plan the slots, compute and store the missing columns, sum every column from the cache
-      hipLaunchKernelGGL(ws_cache_plan_kernel, dim3(1), dim3(kMaxWS), 0, s, cl, cnt, cslot, cache_cap, cst, crd, cmid,
-                         cmsl, cmeta, packed ? cdiag : nullptr, mdiag);
-      SVMD_LAUNCH_CHECK();
-      const int rc2 = launch_igram_colstore(s, Qr, N0r, WNr, stw, nr, roff, Q, N0, WN, cmid, cmsl, cst + 1, kMaxWS, P,
-                                            p.gamma, cache, ldc_cache, cst + 2, tiled, packed ? mdiag : nullptr);
-      if (rc2) return rc2;
-      hipLaunchKernelGGL((ws_cache_fsum_kernel<2>), dim3(unsigned((nr + 511) / 512)), dim3(256), 0, s, cache,
-                         ldc_cache, crd, cf, cnt, f, nr, pa, pn);
-      SVMD_LAUNCH_CHECK();
-      return SVM_OK;
-    }
-    if (!f64) {
-      const int rc2 = launch_igram_gemv(s, Qr, N0r, WNr, stw, nr, roff, Q, N0, WN, cl, cf, cnt, kMaxWS, P, p.gamma, part,
-                                        ldp, packed ? cdiag : nullptr);
-      if (rc2) return rc2;
-      hipLaunchKernelGGL(ws_fsum_count_kernel, dim3(unsigned((nr + 255) / 256)), dim3(256), 0, s, part, ldp, cnt, f, nr,
-                         pa, pn);
-      SVMD_LAUNCH_CHECK();
-      return SVM_OK;
-    }
+  if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
+  if ((rc = S.ctx->ensure_pinned(sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl) + 64))) return rc;
+  char* pin = static_cast<char*>(S.ctx->pinned);
+  S.hs = reinterpret_cast<DecompHost*>(pin);
+  S.ctl_h = reinterpret_cast<DecompCtl*>(pin + sizeof(DecompHost) * 2);
+  S.nz_h = reinterpret_cast<int64_t*>(pin + sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl));
+  SVMD_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&S.ctl_pub), S.ctl_h, 0));  // as the device addresses it
+  return SVM_OK;
+}
+
+// f += K(this GPU's rows, cols[0:*cnt]) coef: the exact-integer GEMV (column-half partials summed in
+// order) or, for FP64 rows, the moved columns' rows gathered, their block on FP64 MFMA and a row sum
+// tiled: also launch the tiled column store for updates of more than 64 misses (it exits at once
+// otherwise, but a launch over every row tile costs ~5-8 us); off after the first outer iterations,
+// where the narrow store takes any count itself (only the cold start misses hundreds of columns)
+// Packed rows (a shrunk solve, pk >= 0): the row operand is the packed copy (Qa, N0a, WNa) of the active
+// rows, pk_bound of them by the host's bound (the device count nrows gates the sums), the unit
+// diagonal from the columns' packed positions (the inner solve's cdiag), and the sums go to f[act[k]].
+int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const double* cf, const int32_t* cnt,
+             bool tiled = true) {
+  const DecompWs& w = S.w;
+  const DecompRows& R = S.R;
+  hipStream_t s = S.s;
+  const int64_t lo = S.lo, nloc = S.nloc;
+  if (nloc <= 0) return SVM_OK;
+  if (S.f64) {
     hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, cl, cnt,
-                       nullptr, Xc, nc);
+                       nullptr, w.Xc, w.nc);
     SVMD_LAUNCH_CHECK();
-    const int rc2 = launch_rbf_block_dev(s, R.X + lo * R.ld, R.nrm + lo, nloc, R.ld, Xc, nc, kMaxWS, R.ld, R.ld,
-                                         p.gamma, Kc, kMaxWS, false, nullptr, cnt, cl, lo);
-    if (rc2) return rc2;
-    hipLaunchKernelGGL(ws_rowsum_f64_kernel, dim3(unsigned((nloc + 3) / 4)), dim3(256), 0, s, Kc, int64_t(kMaxWS), cf,
-                       cnt, f, nloc);
+    const int rc = launch_rbf_block_dev(s, R.X + lo * R.ld, R.nrm + lo, nloc, R.ld, w.Xc, w.nc, kMaxWS, R.ld, R.ld,
+                                        S.p.gamma, w.Kc, kMaxWS, false, nullptr, cnt, cl, lo);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ws_rowsum_f64_kernel, dim3(unsigned((nloc + 3) / 4)), dim3(256), 0, s, w.Kc, int64_t(kMaxWS), cf,
+                       cnt, w.f, nloc);
     SVMD_LAUNCH_CHECK();
     return SVM_OK;
-  };
-  auto* hs = static_cast<DecompHost*>(ctx->pinned);
-  auto* ctl_h = reinterpret_cast<DecompCtl*>(static_cast<char*>(ctx->pinned) + sizeof(DecompHost) * 2);
-  std::memset(hs, 0, sizeof(DecompHost));
-  SVMD_CHECK(hipMemsetAsync(ctl, 0, sizeof(DecompCtl), s));  // stop = SVM_STOP_RUNNING, counters 0
-  if (f64) SVMD_CHECK(hipMemsetAsync(Xw, 0, size_t(kMaxWS) * R.ld * 8, s));  // rows beyond m stay finite
-  const char* kww = getenv("SVM355_DECOMP_KWW");  // "sym": the triangular Gram launch (A/B)
-  const bool kww_narrow = !f64 && !(kww && std::strcmp(kww, "sym") == 0) && P.kq <= 1536;
-  if (kww_narrow) {
+  }
+  const QuantPlan& P = *R.P;
+  const bool packed = ps.pk >= 0;
+  const int8_t* Qr = packed ? w.Qa : R.Q + lo * int64_t(P.kq);
+  const int32_t* N0r = packed ? w.N0a : R.N0 + lo;
+  const double* WNr = packed ? w.WNa : R.WN + lo;
+  const int64_t nr = packed ? ps.pk_bound : nloc, roff = packed ? 0 : lo;
+  const int32_t* pa = packed ? w.act[ps.pk] : nullptr;
+  const int32_t* pn = packed ? w.nrows : nullptr;
+  if (nr <= 0) return SVM_OK;
+  if (S.cc.slab) {  // plan the slots, compute and store the missing columns, sum every column from the cache
+    hipLaunchKernelGGL(ws_cache_plan_kernel, dim3(1), dim3(kMaxWS), 0, s, cl, cnt, w.cslot, S.cc.cap, w.cst, w.crd,
+                       w.cmid, w.cmsl, w.cmeta, packed ? w.cdiag : nullptr, w.mdiag);
+    SVMD_LAUNCH_CHECK();
+    const int rc = launch_igram_colstore(s, Qr, N0r, WNr, R.stw, nr, roff, R.Q, R.N0, R.WN, w.cmid, w.cmsl, w.cst + 1,
+                                         kMaxWS, P, S.p.gamma, S.cc.slab, S.cc.ld, w.cst + 2, tiled,
+                                         packed ? w.mdiag : nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL((ws_cache_fsum_kernel<2>), dim3(unsigned((nr + 511) / 512)), dim3(256), 0, s, S.cc.slab, S.cc.ld,
+                       w.crd, cf, cnt, w.f, nr, pa, pn);
+    SVMD_LAUNCH_CHECK();
+    return SVM_OK;
+  }
+  const int rc = launch_igram_gemv(s, Qr, N0r, WNr, R.stw, nr, roff, R.Q, R.N0, R.WN, cl, cf, cnt, kMaxWS, P, S.p.gamma,
+                                   w.part, kLdp, packed ? w.cdiag : nullptr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ws_fsum_count_kernel, dim3(unsigned((nr + 255) / 256)), dim3(256), 0, s, w.part, kLdp, cnt, w.f, nr,
+                     pa, pn);
+  SVMD_LAUNCH_CHECK();
+  return SVM_OK;
+}
+
+int cache_reset(const Solve& S) {  // no point has a slot, the first free slot is 0
+  if (!S.cc.slab) return SVM_OK;
+  const DecompWs& w = S.w;
+  SVMD_CHECK(hipMemsetAsync(w.cslot, 0xFF, size_t(S.n) * 4, S.s));
+  SVMD_CHECK(hipMemsetAsync(w.cst, 0, 64, S.s));
+  if (w.cmeta) {  // owners and stamps -1, CLOCK bits clear
+    SVMD_CHECK(hipMemsetAsync(w.cmeta, 0xFF, size_t(S.cc.cap) * 8, S.s));
+    SVMD_CHECK(hipMemsetAsync(w.cmeta + 2 * int64_t(S.cc.cap), 0, size_t(S.cc.cap) * 4, S.s));
+  }
+  return SVM_OK;
+}
+
+// f += K(:, nz) (alpha y)_nz: the nonzero alphas compacted (ascending ids), then the GEMV in chunks of
+// kMaxWS columns, each summed into f in order (svm_decomp_train_gram does the same): a warm start, and
+// the recomputation of f when a shrunk solve unshrinks.  The one host read: how many chunks.
+int nz_update(const Solve& S, const PackState& ps, int64_t* nz_out) {
+  const DecompWs& w = S.w;
+  hipStream_t s = S.s;
+  *S.nz_h = -1;
+  hipLaunchKernelGGL(ws_nz_compact_kernel, dim3(1), dim3(1024), 0, s, S.alpha, S.y, S.n, w.wcols, w.wcoef,
+                     w.wcnt + S.nchunks, S.nz_h);
+  SVMD_LAUNCH_CHECK();
+  SVMD_CHECK(hipStreamSynchronize(s));
+  const int64_t nz = *S.nz_h;
+  if (nz < 0 || nz > S.n) {
+    set_error("decomposition SMO: the nonzero-alpha compaction returned no count");
+    return SVM_ERR_INTERNAL;
+  }
+  const int nch = int((nz + kMaxWS - 1) / kMaxWS);
+  if (nch > 0) {
+    hipLaunchKernelGGL(ws_chunk_counts_kernel, dim3(unsigned((nch + 255) / 256)), dim3(256), 0, s, w.wcnt + S.nchunks,
+                       w.wcnt, nch);
+    SVMD_LAUNCH_CHECK();
+  }
+  for (int c = 0; c < nch; ++c) {
+    const int rc = f_update(S, ps, w.wcols + int64_t(c) * kMaxWS, w.wcoef + int64_t(c) * kMaxWS, w.wcnt + c);
+    if (rc) return rc;
+  }
+  if (nz_out) *nz_out = nz;
+  return SVM_OK;
+}
+
+// The start of a solve on the stream: the control block running with its counters 0, a fresh cache,
+// alpha (cold start) and f = -y, and a warm start's f (*warm_cols = its columns).
+int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_cols) {
+  const DecompWs& w = S.w;
+  hipStream_t s = S.s;
+  std::memset(S.hs, 0, sizeof(DecompHost));
+  SVMD_CHECK(hipMemsetAsync(w.ctl, 0, sizeof(DecompCtl), s));  // stop = SVM_STOP_RUNNING, counters 0
+  if (S.f64) SVMD_CHECK(hipMemsetAsync(w.Xw, 0, size_t(kMaxWS) * S.R.ld * 8, s));  // rows beyond m stay finite
+  if (S.kww_narrow) {
     static const std::vector<int32_t> ident = [] {
       std::vector<int32_t> v(kMaxWS + 1);
       for (int k = 0; k < kMaxWS; ++k) v[k] = k;
       v[kMaxWS] = kMaxWS;
       return v;
     }();
-    SVMD_CHECK(hipMemcpyAsync(wid, ident.data(), ident.size() * 4, hipMemcpyHostToDevice, s));
+    SVMD_CHECK(hipMemcpyAsync(w.wid, ident.data(), ident.size() * 4, hipMemcpyHostToDevice, s));
   }
-  auto cache_reset = [&]() -> int {  // no point has a slot, the first free slot is 0
-    if (!use_cache) return SVM_OK;
-    SVMD_CHECK(hipMemsetAsync(cslot, 0xFF, size_t(n) * 4, s));
-    SVMD_CHECK(hipMemsetAsync(cst, 0, 64, s));
-    if (cmeta) {  // owners and stamps -1, CLOCK bits clear
-      SVMD_CHECK(hipMemsetAsync(cmeta, 0xFF, size_t(cache_cap) * 8, s));
-      SVMD_CHECK(hipMemsetAsync(cmeta + 2 * int64_t(cache_cap), 0, size_t(cache_cap) * 4, s));
-    }
-    return SVM_OK;
-  };
-  if ((rc = cache_reset())) return rc;  // a fresh cache per fit
-  if (shr) SVMD_CHECK(hipMemsetAsync(shr, 0, nl1, s));
-  hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, y, alpha, f, lo, nloc, n,
-                     int(o.warm), ctl);
+  int rc = cache_reset(S);  // a fresh cache per fit
+  if (rc) return rc;
+  if (w.shr) SVMD_CHECK(hipMemsetAsync(w.shr, 0, size_t(std::max<int64_t>(S.nloc, 1)), s));
+  hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo, S.nloc,
+                     S.n, int(warm), w.ctl);
   SVMD_LAUNCH_CHECK();
-  // f += K(:, nz) (alpha y)_nz: the nonzero alphas compacted (ascending ids), then the GEMV in chunks of
-  // kMaxWS columns, each summed into f in order (svm_decomp_train_gram does the same): a warm start, and
-  // the recomputation of f when a shrunk solve unshrinks.  The one host read: how many chunks.
-  auto nz_update = [&](int64_t* nz_out) -> int {
-    auto* wcols = reinterpret_cast<int32_t*>(ws + o_wcols);
-    auto* wcoef = reinterpret_cast<double*>(ws + o_wcoef);
-    auto* wcnt = reinterpret_cast<int32_t*>(ws + o_wcnt);
-    auto* nz_h = reinterpret_cast<int64_t*>(static_cast<char*>(ctx->pinned) + sizeof(DecompHost) * 2 +
-                                            2 * sizeof(DecompCtl));
-    *nz_h = -1;
-    hipLaunchKernelGGL(ws_nz_compact_kernel, dim3(1), dim3(1024), 0, s, alpha, y, n, wcols, wcoef, wcnt + nchunks,
-                       nz_h);
-    SVMD_LAUNCH_CHECK();
+  if (warm && (rc = nz_update(S, ps, warm_cols))) return rc;
+  return SVM_OK;
+}
+
+// repack: the active rows (not shrunk) into the other list buffer, their quantised rows copied, the
+// column cache (whose rows are the packed ones) cleared
+int repack(const Solve& S, PackState& ps) {
+  const DecompWs& w = S.w;
+  const DecompRows& R = S.R;
+  const int nb = ps.pk < 0 ? 0 : ps.pk ^ 1;
+  const int32_t* ca = ps.pk < 0 ? nullptr : w.act[ps.pk];
+  const int32_t* cb = ps.pk < 0 ? nullptr : w.boff[ps.pk];
+  hipLaunchKernelGGL(ws_pack_count_kernel, dim3(unsigned(S.NBr)), dim3(256), 0, S.s, ca, cb, S.sh.per, S.nloc, w.shr,
+                     w.bcnt);
+  SVMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ws_pack_write_kernel, dim3(unsigned(S.NBr)), dim3(256), 0, S.s, ca, cb, S.sh.per, S.nloc, w.shr,
+                     w.bcnt, w.boff[nb], w.nrows, w.act[nb], w.pos_of, R.Q, R.N0, R.WN, S.lo, S.kq, w.Qa, w.N0a, w.WNa);
+  SVMD_LAUNCH_CHECK();
+  ps.pk = nb;
+  ps.pk_bound = ps.seen_active;
+  ++ps.repacks;
+  return cache_reset(S);
+}
+
+// The wait for an event of the solver's stream: under the exchange's deadline / abort policy when the
+// distributed solve has one, else here.
+int wait_event(const Solve& S, hipEvent_t ev) {
+  if (!(S.world > 1 && S.allgather->wait && S.allgather->wait(ev))) SVMD_CHECK(hipEventSynchronize(ev));
+  return SVM_OK;
+}
+
+// The unshrink (decomp_shrink.h), when a readback shows kStopUnshrink: the queued batch ran as no-ops and
+// `ev` (recorded after it) is waited for under the exchange's policy; then every row is active again, the
+// rows are in place again (no packed list), the column cache is cleared, f is recomputed from alpha (the
+// warm start's chunked update), and the outer loop resumes at the device's outer count.
+int unshrink(const Solve& S, PackState& ps, const DecompCtl& seen, hipEvent_t ev) {
+  const DecompWs& w = S.w;
+  hipStream_t s = S.s;
+  int rc = ev ? wait_event(S, ev) : SVM_OK;
+  if (rc) return rc;
+  hipLaunchKernelGGL(ws_unshrink_ctl_kernel, dim3(1), dim3(64), 0, s, w.ctl, S.nloc);
+  SVMD_LAUNCH_CHECK();
+  SVMD_CHECK(hipMemsetAsync(w.shr, 0, size_t(std::max<int64_t>(S.nloc, 1)), s));
+  ps.pk = -1;
+  ps.pk_bound = S.nloc;
+  ps.seen_active = S.nloc;
+  if ((rc = cache_reset(S))) return rc;
+  hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo, S.nloc,
+                     S.n, 1, w.ctl);
+  SVMD_LAUNCH_CHECK();
+  if ((rc = nz_update(S, ps, nullptr))) return rc;
+  ps.o_dev = ps.origin = seen.outer;
+  ++ps.unshrinks;
+  if (S.k.shrink_log) {
     SVMD_CHECK(hipStreamSynchronize(s));
-    const int64_t nz = *nz_h;
-    if (nz < 0 || nz > n) {
-      set_error("decomposition SMO: the nonzero-alpha compaction returned no count");
-      return SVM_ERR_INTERNAL;
-    }
-    const int nch = int((nz + kMaxWS - 1) / kMaxWS);
-    if (nch > 0) {
-      hipLaunchKernelGGL(ws_chunk_counts_kernel, dim3(unsigned((nch + 255) / 256)), dim3(256), 0, s, wcnt + nchunks,
-                         wcnt, nch);
-      SVMD_LAUNCH_CHECK();
-    }
-    for (int c = 0; c < nch; ++c) {
-      const int rc2 = f_update(wcols + int64_t(c) * kMaxWS, wcoef + int64_t(c) * kMaxWS, wcnt + c);
-      if (rc2) return rc2;
-    }
-    if (nz_out) *nz_out = nz;
-    return SVM_OK;
-  };
-  int64_t warm_cols = 0;
-  if (o.warm && (rc = nz_update(&warm_cols))) return rc;
-  // shrinking, host side: o_dev = the device's outer-iteration count when the next enqueued one runs
-  // (exact: only a stop or an unshrink turns launches into no-ops, and the host re-reads the count at
-  // an unshrink), origin = the outer count at the start or the last unshrink, seen_active = the active
-  // rows the host last read back
-  int64_t o_dev = 0, origin = 0, seen_active = nloc, min_active = nloc, unshrinks = 0, repacks = 0;
-  // repack: the active rows (not shrunk) into the other list buffer, their quantised rows copied, the
-  // column cache (whose rows are the packed ones) cleared
-  auto repack = [&]() -> int {
-    const int nb = pk < 0 ? 0 : pk ^ 1;
-    const int32_t* ca = pk < 0 ? nullptr : pact[pk];
-    const int32_t* cb = pk < 0 ? nullptr : pboff[pk];
-    hipLaunchKernelGGL(ws_pack_count_kernel, dim3(unsigned(NBr)), dim3(256), 0, s, ca, cb, sh.per, nloc, shr, pbcnt);
-    SVMD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ws_pack_write_kernel, dim3(unsigned(NBr)), dim3(256), 0, s, ca, cb, sh.per, nloc, shr, pbcnt,
-                       pboff[nb], pk_rows, pact[nb], pos_of, Q, N0, WN, lo, P.kq, Qa, N0a, WNa);
-    SVMD_LAUNCH_CHECK();
-    pk = nb;
-    pk_bound = seen_active;
-    ++repacks;
-    return cache_reset();
-  };
-  if (tr) tr->count = 0;
-  // Outer iterations are enqueued `batch` at a time (SVM355_DECOMP_BATCH, default 1): every kernel reads
-  // the device control block, so after the stop the rest are no-op launches.  Each batch ends with a
-  // readback of the control block and an event; the host waits for batch k's event only after it has
-  // enqueued batch k + 1, so the GPU always has the next batch queued (no idle host round trip).
-  int batch = 1;  // with one batch always queued ahead, 1 already hides the host; more only adds no-op tail
-  if (const char* v = getenv("SVM355_DECOMP_BATCH")) batch = std::max(1, atoi(v));
-  if (tr) batch = 1;  // the trace reads every outer iteration back
-  int32_t* gate = &ctl->stop;
-  // fault injection (tests, world > 1): rank SVM355_DECOMP_FAIL_RANK fails when it is about to enqueue
-  // outer iteration SVM355_DECOMP_FAIL_OUTER (default 0: before the first selection), while its peers
-  // wait in their candidate all-gathers (decomp_cpu.cpp has the same hook)
-  int64_t fail_outer = -1;
-  if (const char* fr = getenv("SVM355_DECOMP_FAIL_RANK"); fr && world > 1 && atoi(fr) == rank) {
-    const char* fo = getenv("SVM355_DECOMP_FAIL_OUTER");
-    fail_outer = fo ? std::max(0, atoi(fo)) : 0;
+    fprintf(stderr, "decomp: rank %d unshrink at outer %lld (%.3f ms)\n", S.rank, (long long)seen.outer, ms_since(S.t0));
   }
-  const int64_t max_batches = p.max_iter / std::max(1, batch) + 64;  // a stop comes well before: never spin
-#define SVM_WS_INNER_(NT, PER, PR, S2)                                                                            \
-  do {                                                                                                             \
-    if (inner_j2s && S2)                                                                                           \
-      hipLaunchKernelGGL((ws_inner_kernel<NT, PER, PR, S2, S2, S2>), dim3(1), dim3(NT), 0, s, Kw, ldw, W, ctl, y,  \
-                         alpha, Wf, p.C, p.eps, cols, coef, mcount, hs, pub, ipos, lo, nloc, icdiag, gAw, Wfw, nAmat, \
-                         nwd);                                                                                     \
-    else if (inner_dp && S2 && nwc.on)                                                                             \
-      hipLaunchKernelGGL((ws_inner_kernel<NT, PER, PR, S2, S2, false, true>), dim3(1), dim3(NT), 0, s, Kw, ldw, W,  \
-                         ctl, y, alpha, Wf, p.C, p.eps, cols, coef, mcount, hs, pub, ipos, lo, nloc, icdiag, gAw, Wfw, \
-                         nAmat, nwd);                                                                              \
-    else if (inner_dp && S2)                                                                                       \
-      hipLaunchKernelGGL((ws_inner_kernel<NT, PER, PR, S2, S2>), dim3(1), dim3(NT), 0, s, Kw, ldw, W, ctl, y,      \
-                         alpha, Wf, p.C, p.eps, cols, coef, mcount, hs, pub, ipos, lo, nloc, icdiag, gAw, Wfw, nAmat, \
-                         nwd);                                                                                     \
-    else                                                                                                           \
-      hipLaunchKernelGGL((ws_inner_kernel<NT, PER, PR, S2>), dim3(1), dim3(NT), 0, s, Kw, ldw, W, ctl, y, alpha,   \
-                         Wf, p.C, p.eps, cols, coef, mcount, hs, pub, ipos, lo, nloc, icdiag, gAw, Wfw, nAmat, nwd); \
-  } while (0)
-#define SVM_WS_INNER(NT, PER)                \
-  if (prof && inner_wss2)                    \
-    SVM_WS_INNER_(NT, PER, true, true);      \
-  else if (prof)                             \
-    SVM_WS_INNER_(NT, PER, true, false);     \
-  else if (inner_wss2)                       \
-    SVM_WS_INNER_(NT, PER, false, true);     \
-  else                                       \
-    SVM_WS_INNER_(NT, PER, false, false)
-  // solo timing (DecompSolo): the two device segments of an outer iteration under the shared mutex,
-  // each timed alone and waited for before the mutex is released
-  DecompSolo* solo = (world > 1 && !tr) ? o.solo : nullptr;
-  hipEvent_t sev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct SoloEvents {
-    hipEvent_t* e;
-    ~SoloEvents() {
-      for (int i = 0; i < 4; ++i)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-  } sev_guard{sev};
-  if (solo)
-    for (auto& e : sev) SVMD_CHECK(hipEventCreate(&e));
-  std::unique_lock<std::mutex> solo_lk;
-  auto solo_begin = [&](int k) -> int {
-    if (!solo) return SVM_OK;
-    solo_lk = std::unique_lock<std::mutex>(*solo->mu);
-    SVMD_CHECK(hipEventRecord(sev[2 * k], s));
+  return SVM_OK;
+}
+
+// solo timing (DecompSolo): the two device segments of an outer iteration under the shared mutex,
+// each timed alone and waited for before the mutex is released
+struct SoloTimer {
+  DecompSolo* solo;
+  hipStream_t s;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  std::unique_lock<std::mutex> lk;
+  ~SoloTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int init() {
+    if (solo)
+      for (auto& e : ev) SVMD_CHECK(hipEventCreate(&e));
     return SVM_OK;
-  };
-  auto solo_end = [&](int k) -> int {
+  }
+  int begin(int k) {
     if (!solo) return SVM_OK;
-    SVMD_CHECK(hipEventRecord(sev[2 * k + 1], s));
-    SVMD_CHECK(hipEventSynchronize(sev[2 * k + 1]));
+    lk = std::unique_lock<std::mutex>(*solo->mu);
+    SVMD_CHECK(hipEventRecord(ev[2 * k], s));
+    return SVM_OK;
+  }
+  int end(int k) {
+    if (!solo) return SVM_OK;
+    SVMD_CHECK(hipEventRecord(ev[2 * k + 1], s));
+    SVMD_CHECK(hipEventSynchronize(ev[2 * k + 1]));
     float ms = 0.0f;
-    SVMD_CHECK(hipEventElapsedTime(&ms, sev[2 * k], sev[2 * k + 1]));
+    SVMD_CHECK(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
     (k == 0 ? solo->sel_ms : solo->rest_ms).push_back(double(ms));
-    solo_lk.unlock();
+    lk.unlock();
+    return SVM_OK;
+  }
+};
+
+// K(W, W) of the working set the build left: its rows gathered, then the exact-integer Gram over the full
+// capacity (the narrow column store, else the triangular launch) or the FP64-MFMA block.
+int enqueue_kww(const Solve& S) {
+  const DecompWs& w = S.w;
+  const DecompRows& R = S.R;
+  hipStream_t s = S.s;
+  int32_t* gate = &w.ctl->stop;
+  if (S.f64) {
+    hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W, &w.ctl->m,
+                       gate, w.Xw, w.nw);
+    SVMD_LAUNCH_CHECK();
+    // K(W, W) on FP64 MFMA, columns bounded by m, unit diagonal; skipped once stopped
+    return launch_rbf_block_dev(s, w.Xw, w.nw, kMaxWS, R.ld, w.Xw, w.nw, kMaxWS, R.ld, R.ld, S.p.gamma, w.Kw, kLdw, true,
+                                gate, &w.ctl->m, nullptr, 0);
+  }
+  const QuantPlan& P = *R.P;
+  hipLaunchKernelGGL(ws_gather_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.Q, R.N0, R.WN, P.kq, w.W, w.ctl, w.Qw,
+                     w.N0w, w.WNw);
+  SVMD_LAUNCH_CHECK();
+  // K(W, W) over the full capacity (rows beyond m are never read); skipped once stopped
+  bool ww = false;
+  int rc = SVM_OK;
+  if (S.kww_narrow && (rc = launch_igram_ww(s, w.Qw, w.N0w, w.WNw, R.stw, kMaxWS, w.wid, w.wid + kMaxWS, P, S.p.gamma,
+                                            w.Kw, kLdw, gate, &ww)))
+    return rc;
+  if (!ww)
+    rc = launch_igram_sym(s, w.Qw, w.N0w, w.WNw, const_cast<double*>(R.stw), kMaxWS, P, S.p.gamma, w.Kw, kLdw, false,
+                          gate);
+  return rc;
+}
+
+// One outer iteration on the stream, the `index`-th enqueued: (repack,) select, all-gather, build, gather,
+// K(W, W), inner solve, f update, shrink pass.  Every kernel reads the device control block, so after the
+// stop these are no-op launches.  pub: where the last kernel to change the control block publishes it.
+int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index, bool first_of_batch, DecompCtl* pub) {
+  const DecompWs& w = S.w;
+  const svm_params& p = S.p;
+  hipStream_t s = S.s;
+  const int64_t NBr = S.NBr, lo = S.lo, nloc = S.nloc;
+  const int T = S.sh.T;
+  int rc;
+  if (S.world > 1 && S.k.fail_rank == S.rank && index == S.k.fail_outer) {
+    set_error("injected failure of rank %d at outer iteration %lld", S.rank, (long long)S.k.fail_outer);
+    return SVM_ERR_INTERNAL;
+  }
+  if ((rc = solo.begin(0))) return rc;
+  // repack once the active rows the host last read are at most repack_frac of the packed ones
+  if (S.pack_on && NBr > 0 && first_of_batch && ps.seen_active < ps.pk_bound &&
+      double(ps.seen_active) <= S.k.repack_frac * double(ps.pk_bound))
+    if ((rc = repack(S, ps))) return rc;
+  const bool packed = ps.pk >= 0;
+  const int32_t* act = packed ? w.act[ps.pk] : nullptr;
+  if (NBr > 0)
+    hipLaunchKernelGGL(S.wide_select ? ws_select_wide_kernel : ws_select_kernel, dim3(unsigned(NBr)), dim3(kSelNT), 0, s,
+                       w.f, S.alpha, S.y, lo, nloc, S.sh.per, T, p.C, p.eps, w.own, w.own + NBr * T, w.ctl, act,
+                       packed ? w.boff[ps.pk] : nullptr, w.shr);
+  SVMD_LAUNCH_CHECK();
+  if ((rc = solo.end(0))) return rc;
+  CandRec* all = S.world > 1 ? w.all : w.own;
+  if (S.world > 1) S.allgather->gather(w.own, int64_t(S.Lr * sizeof(CandRec)), all);  // stream-ordered
+  if ((rc = solo.begin(1))) return rc;
+  hipLaunchKernelGGL(ws_build_kernel, dim3(1), dim3(kMaxWS), 0, s, all, int(S.sh.L), int(S.Lr), int(NBr * T), int(T),
+                     p.tau, S.k.tau_frac, int64_t(p.max_iter), w.W, w.Wf, w.ctl, w.mcount, pub);
+  SVMD_LAUNCH_CHECK();
+  if ((rc = enqueue_kww(S))) return rc;
+  launch_ws_inner(s, S.inner,
+                  InnerArgs{w.Kw, kLdw, w.W, w.ctl, S.y, S.alpha, w.Wf, p.C, p.eps, w.cols, w.coef, w.mcount, S.hs, pub,
+                            packed ? w.pos_of : nullptr, lo, nloc, packed ? w.cdiag : nullptr, w.gAw, w.Wf, w.nAmat,
+                            S.nwd});
+  SVMD_LAUNCH_CHECK();
+  if ((rc = f_update(S, ps, w.cols, w.coef, w.mcount, index < 4))) return rc;
+  ++ps.o_dev;  // this outer iteration's count once it has run
+  if (S.shc.pass_after(ps.o_dev, ps.origin) && nloc > 0) {  // the shrink pass, with this outer iteration's bounds
+    const int64_t np = packed ? ps.pk_bound : nloc;
+    hipLaunchKernelGGL(ws_shrink_pass_kernel, dim3(unsigned((np + 255) / 256)), dim3(256), 0, s, w.f, S.alpha, S.y, lo,
+                       nloc, act, w.nrows, w.shr, p.C, p.eps, S.shc.margin, w.ctl);
+    SVMD_LAUNCH_CHECK();
+  }
+  return solo.end(1);
+}
+
+// The trace's record of the outer iteration the control block `c` was read back after (one GPU).
+int record_trace(const Solve& S, const DecompCtl& c) {
+  svm_decomp_trace* tr = S.tr;
+  const DecompWs& w = S.w;
+  const int64_t n = S.n;
+  if (tr->count >= tr->cap) return SVM_OK;
+  const int64_t oi = tr->count++;
+  const int m = c.m;
+  int32_t mv = 0;
+  SVMD_CHECK(hipMemcpy(&mv, w.mcount, 4, hipMemcpyDeviceToHost));
+  if (tr->m) tr->m[oi] = m;
+  // the first `cnt` of a device array into the record's kMaxWS entries, the rest `fill`
+  auto padded = [&](auto* dst, const auto* src, int cnt, auto fill) -> int {
+    if (!dst) return SVM_OK;
+    SVMD_CHECK(hipMemcpy(dst + oi * kMaxWS, src, size_t(cnt) * sizeof(*dst), hipMemcpyDeviceToHost));
+    std::fill(dst + oi * kMaxWS + cnt, dst + (oi + 1) * kMaxWS, fill);
     return SVM_OK;
   };
-  const DecompCtl* fin = nullptr;  // the readback that saw the stop
-  DecompCtl* ctl_pub = nullptr;  // ctl_h as the device addresses it
-  SVMD_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&ctl_pub), ctl_h, 0));
-  // The unshrink (decomp_shrink.h), when a readback shows kStopUnshrink: the queued batch ran as no-ops and
-  // `ev` (recorded after it) is waited for under the exchange's policy; then every row is active again, the
-  // rows are in place again (no packed list), the column cache is cleared, f is recomputed from alpha (the
-  // warm start's chunked update), and the outer loop resumes at the device's outer count.
-  const bool shrink_log = getenv("SVM355_DECOMP_SHRINK_LOG") && atoi(getenv("SVM355_DECOMP_SHRINK_LOG")) == 1;
-  auto unshrink = [&](const DecompCtl& seen, hipEvent_t ev) -> int {
-    if (ev && !(world > 1 && allgather.wait && allgather.wait(ev))) SVMD_CHECK(hipEventSynchronize(ev));
-    hipLaunchKernelGGL(ws_unshrink_ctl_kernel, dim3(1), dim3(64), 0, s, ctl, nloc);
-    SVMD_LAUNCH_CHECK();
-    SVMD_CHECK(hipMemsetAsync(shr, 0, nl1, s));
-    pk = -1;
-    pk_bound = nloc;
-    seen_active = nloc;
-    int rc2 = cache_reset();
-    if (rc2) return rc2;
-    hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, y, alpha, f, lo, nloc, n, 1,
-                       ctl);
-    SVMD_LAUNCH_CHECK();
-    if ((rc2 = nz_update(nullptr))) return rc2;
-    o_dev = origin = seen.outer;
-    ++unshrinks;
-    if (shrink_log) {
-      SVMD_CHECK(hipStreamSynchronize(s));
-      fprintf(stderr, "decomp: rank %d unshrink at outer %lld (%.3f ms)\n", rank, (long long)seen.outer, ms_since(t0));
-    }
-    return SVM_OK;
-  };
-  bool queued = false;  // a batch is in flight whose readback the host has not checked
-  for (int64_t bt = 0;; ++bt) {
-    DecompCtl* pub = tr ? nullptr : ctl_pub + (bt & 1);  // the trace path copies the block itself
-    for (int bi = 0; bi < batch; ++bi) {
-      if (bt * batch + bi == fail_outer) {
-        set_error("injected failure of rank %d at outer iteration %lld", rank, (long long)fail_outer);
-        return SVM_ERR_INTERNAL;
-      }
-      if ((rc = solo_begin(0))) return rc;
-      // repack once the active rows the host last read are at most repack_frac of the packed ones
-      if (pack_on && NBr > 0 && bi == 0 && seen_active < pk_bound && double(seen_active) <= repack_frac * double(pk_bound))
-        if ((rc = repack())) return rc;
-      const int32_t* sact = pk >= 0 ? pact[pk] : nullptr;
-      const int32_t* sboff = pk >= 0 ? pboff[pk] : nullptr;
-      if (NBr > 0)
-        hipLaunchKernelGGL(wide_select ? ws_select_wide_kernel : ws_select_kernel, dim3(unsigned(NBr)), dim3(kSelNT),
-                           0, s, f, alpha, y, lo, nloc, sh.per, T, p.C, p.eps, cown, cown + NBr * T, ctl, sact, sboff,
-                           shr);
-      SVMD_LAUNCH_CHECK();
-      if ((rc = solo_end(0))) return rc;
-      if (world > 1) allgather.gather(cown, int64_t(Lr * sizeof(CandRec)), call);  // stream-ordered
-      if ((rc = solo_begin(1))) return rc;
-      hipLaunchKernelGGL(ws_build_kernel, dim3(1), dim3(kMaxWS), 0, s, call, int(sh.L), int(Lr), int(NBr * T), int(T),
-                         p.tau, tau_frac, int64_t(p.max_iter), W, Wf, ctl, mcount, pub);
-      SVMD_LAUNCH_CHECK();
-      if (!f64) {
-        hipLaunchKernelGGL(ws_gather_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, Q, N0, WN, P.kq, W, ctl, Qw, N0w,
-                           WNw);
-        SVMD_LAUNCH_CHECK();
-        // K(W, W) over the full capacity (rows beyond m are never read); skipped once stopped
-        bool ww = false;
-        if (kww_narrow && (rc = launch_igram_ww(s, Qw, N0w, WNw, stw, kMaxWS, wid, wid + kMaxWS, P, p.gamma, Kw, ldw,
-                                                gate, &ww)))
-          return rc;
-        if (!ww) {
-          rc = launch_igram_sym(s, Qw, N0w, WNw, const_cast<double*>(stw), kMaxWS, P, p.gamma, Kw, ldw, false, gate);
-          if (rc) return rc;
-        }
-      } else {
-        hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, W, &ctl->m,
-                           gate, Xw, nw);
-        SVMD_LAUNCH_CHECK();
-        // K(W, W) on FP64 MFMA, columns bounded by m, unit diagonal; skipped once stopped
-        rc = launch_rbf_block_dev(s, Xw, nw, kMaxWS, R.ld, Xw, nw, kMaxWS, R.ld, R.ld, p.gamma, Kw, ldw, true, gate,
-                                  &ctl->m, nullptr, 0);
-        if (rc) return rc;
-      }
-      const int32_t* ipos = pk >= 0 ? pos_of : nullptr;
-      int32_t* icdiag = pk >= 0 ? cdiag : nullptr;
-      if (inner_nt == 65)
-        SVM_WS_INNER(64, 6);
-      else if (inner_nt == 64)
-        SVM_WS_INNER(64, 16);
-      else if (inner_nt == 128)
-        SVM_WS_INNER(128, 8);
-      else if (inner_nt == 256)
-        SVM_WS_INNER(256, 4);
-      else
-        SVM_WS_INNER(512, 2);
-      SVMD_LAUNCH_CHECK();
-      rc = f_update(cols, coef, mcount, bt * batch + bi < 4);
-      if (rc) return rc;
-      ++o_dev;  // this outer iteration's count once it has run
-      if (shc.pass_after(o_dev, origin) && nloc > 0) {  // the shrink pass, with this outer iteration's bounds
-        const int64_t np = pk >= 0 ? pk_bound : nloc;
-        hipLaunchKernelGGL(ws_shrink_pass_kernel, dim3(unsigned((np + 255) / 256)), dim3(256), 0, s, f, alpha, y, lo,
-                           nloc, pk >= 0 ? pact[pk] : nullptr, pk_rows, shr, p.C, p.eps, shc.margin, ctl);
-        SVMD_LAUNCH_CHECK();
-      }
-      if ((rc = solo_end(1))) return rc;
-#undef SVM_WS_INNER
-#undef SVM_WS_INNER_
-    }
-    if (tr) {  // trace: every outer iteration is read back before the next is enqueued
-      SVMD_CHECK(hipMemcpyAsync(ctl_h, ctl, sizeof(DecompCtl), hipMemcpyDeviceToHost, s));
-      SVMD_CHECK(hipStreamSynchronize(s));
-      if (ctl_h->stop == kStopUnshrink) {
-        const DecompCtl seen = *ctl_h;
-        if ((rc = unshrink(seen, nullptr))) return rc;
-        continue;
-      }
-      if (ctl_h->stop != SVM_STOP_RUNNING) {
-        fin = ctl_h;
-        break;
-      }
-      seen_active = ctl_h->n_active;
-      min_active = std::min(min_active, seen_active);
-      if (tr->count < tr->cap) {
-        const int64_t oi = tr->count++;
-        const int m = ctl_h->m;
-        int32_t mv = 0;
-        SVMD_CHECK(hipMemcpy(&mv, mcount, 4, hipMemcpyDeviceToHost));
-        if (tr->m) tr->m[oi] = m;
-        if (tr->W) {
-          SVMD_CHECK(hipMemcpy(tr->W + oi * kMaxWS, W, size_t(m) * 4, hipMemcpyDeviceToHost));
-          for (int k = m; k < kMaxWS; ++k) tr->W[oi * kMaxWS + k] = -1;
-        }
-        if (tr->moved) tr->moved[oi] = mv;
-        if (tr->cols) {
-          SVMD_CHECK(hipMemcpy(tr->cols + oi * kMaxWS, cols, size_t(mv) * 4, hipMemcpyDeviceToHost));
-          for (int k = mv; k < kMaxWS; ++k) tr->cols[oi * kMaxWS + k] = -1;
-        }
-        if (tr->coef) {
-          SVMD_CHECK(hipMemcpy(tr->coef + oi * kMaxWS, coef, size_t(mv) * 8, hipMemcpyDeviceToHost));
-          for (int k = mv; k < kMaxWS; ++k) tr->coef[oi * kMaxWS + k] = 0.0;
-        }
-        if (tr->inner) tr->inner[oi] = ctl_h->last_inner_it;
-        if (tr->bounds) {
-          tr->bounds[2 * oi] = ctl_h->b_high;
-          tr->bounds[2 * oi + 1] = ctl_h->b_low;
-        }
-        if (tr->n == n && tr->alpha)
-          SVMD_CHECK(hipMemcpy(tr->alpha + oi * n, alpha, size_t(n) * 8, hipMemcpyDeviceToHost));
-        if (tr->n == n && tr->f) {
-          SVMD_CHECK(hipMemcpy(tr->f + oi * n, f, size_t(n) * 8, hipMemcpyDeviceToHost));
-          if (shr) {  // shrunk rows: NaN (their f is not part of the trajectory; the oracle's trace agrees)
-            std::vector<uint8_t> sh_h(static_cast<size_t>(n));
-            SVMD_CHECK(hipMemcpy(sh_h.data(), shr, size_t(n), hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < n; ++i)
-              if (sh_h[size_t(i)]) tr->f[oi * n + i] = __builtin_nan("");
-          }
-        }
-      }
-      if (bt >= max_batches) {
-        set_error("decomposition SMO: no stop after %lld outer iterations", (long long)ctl_h->outer);
-        return SVM_ERR_INTERNAL;
-      }
-      continue;
-    }
-    SVMD_CHECK(hipEventRecord(ctx->ev_ctl[bt & 1], s));  // the batch's kernels published into ctl_h[bt & 1]
-    if (!queued) {  // keep one batch queued ahead of the wait
-      queued = true;
-      continue;
-    }
-    const int64_t pb = bt - 1;
-    hipEvent_t ev = ctx->ev_ctl[pb & 1];
-    const auto tw = std::chrono::steady_clock::now();
-    if (!(world > 1 && allgather.wait && allgather.wait(ev))) SVMD_CHECK(hipEventSynchronize(ev));
-    if (o.host_wait_ms) *o.host_wait_ms += ms_since(tw);
-    if (ctl_h[pb & 1].stop == kStopUnshrink) {  // batch bt ran as no-ops: drain it, unshrink, restart the pipeline
-      const DecompCtl seen = ctl_h[pb & 1];
-      if ((rc = unshrink(seen, ctx->ev_ctl[bt & 1]))) return rc;
-      queued = false;
-      continue;
-    }
-    if (ctl_h[pb & 1].stop != SVM_STOP_RUNNING) {
-      fin = ctl_h + (pb & 1);  // batch bt (queued) runs as no-ops; the state is final
-      break;
-    }
-    seen_active = ctl_h[pb & 1].n_active;
-    min_active = std::min(min_active, seen_active);
-    if (shrink_log)
-      fprintf(stderr, "decomp: rank %d outer %lld gap %.6g active %lld packed %lld (%.3f ms)\n", rank,
-              (long long)ctl_h[pb & 1].outer, ctl_h[pb & 1].b_low - ctl_h[pb & 1].b_high, (long long)seen_active,
-              (long long)(pk >= 0 ? pk_bound : nloc), ms_since(t0));
-    if (bt >= max_batches) {
-      set_error("decomposition SMO: no stop after %lld outer iterations", (long long)ctl_h[pb & 1].outer);
-      return SVM_ERR_INTERNAL;
+  if (tr->moved) tr->moved[oi] = mv;
+  if (padded(tr->W, w.W, m, -1) || padded(tr->cols, w.cols, mv, -1) || padded(tr->coef, w.coef, mv, 0.0))
+    return SVM_ERR_DEVICE;
+  if (tr->inner) tr->inner[oi] = c.last_inner_it;
+  if (tr->bounds) {
+    tr->bounds[2 * oi] = c.b_high;
+    tr->bounds[2 * oi + 1] = c.b_low;
+  }
+  if (tr->n == n && tr->alpha) SVMD_CHECK(hipMemcpy(tr->alpha + oi * n, S.alpha, size_t(n) * 8, hipMemcpyDeviceToHost));
+  if (tr->n == n && tr->f) {
+    SVMD_CHECK(hipMemcpy(tr->f + oi * n, w.f, size_t(n) * 8, hipMemcpyDeviceToHost));
+    if (w.shr) {  // shrunk rows: NaN (their f is not part of the trajectory; the oracle's trace agrees)
+      std::vector<uint8_t> sh_h(static_cast<size_t>(n));
+      SVMD_CHECK(hipMemcpy(sh_h.data(), w.shr, size_t(n), hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < n; ++i)
+        if (sh_h[size_t(i)]) tr->f[oi * n + i] = __builtin_nan("");
     }
   }
-  if (fin->stop == kStopInternal) {
+  return SVM_OK;
+}
+
+// The stopped solve's result, statistics (see run_decomp) and, from the PROF build, its phase totals.
+int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int64_t warm_cols, svm_result* r,
+                 int64_t* stats) {
+  if (fin.stop == kStopInternal) {
     set_error("decomposition SMO: working set outside [2, %d] points", kMaxWS);
     return SVM_ERR_INTERNAL;
   }
-  const int64_t outer = fin->outer, inner_total = fin->inner_total, changed_total = fin->changed_total;
-  const int32_t stop = fin->stop;
-  const double bh = fin->b_high, bl = fin->b_low;
-  if (prof && inner_total > 0) {
-    const double it = double(inner_total);
+  const DecompHost* hs = S.hs;
+  if (S.k.prof && fin.inner_total > 0) {
+    const double it = double(fin.inner_total);
     fprintf(stderr, "decomp prof (clock64 ticks / inner iteration): select %.0f  publish+barrier %.0f  merge %.0f  "
             "row loads %.0f  update %.0f  (%lld iterations; inner kernels %.3f ms wall = %lld clock64 ticks)\n",
             hs->prof[0] / it, hs->prof[1] / it, hs->prof[2] / it,
             (hs->prof[3] + hs->prof[8] + hs->prof[9] + hs->prof[10] + hs->prof[11]) / it, hs->prof[4] / it,
-            (long long)inner_total, hs->prof[7] / 1e5, (long long)hs->prof[6]);
-    if (inner_wss2)
+            (long long)fin.inner_total, hs->prof[7] / 1e5, (long long)hs->prof[6]);
+    if (S.k.wss2)
       fprintf(stderr, "decomp prof second-order j (inside row loads): row i %.0f  gains + wave reduction %.0f  "
               "publish + barrier %.0f  fold %.0f  row j %.0f\n", hs->prof[8] / it, hs->prof[9] / it,
               hs->prof[10] / it, hs->prof[11] / it, hs->prof[3] / it);
   }
   if (stats) {
-    stats[0] = outer;
-    stats[1] = inner_total;
-    stats[2] = sh.L;  // the working-set capacity actually used (see decomp_shape)
-    stats[3] = int64_t(ms_since(t0) * 1000.0);
-    stats[4] = changed_total;
-    stats[5] = inner_nt;
-    stats[6] = f64 ? 1 : 0;
+    stats[0] = fin.outer;
+    stats[1] = fin.inner_total;
+    stats[2] = S.sh.L;  // the working-set capacity actually used (see decomp_shape)
+    stats[3] = int64_t(ms_since(S.t0) * 1000.0);
+    stats[4] = fin.changed_total;
+    stats[5] = S.k.inner_nt;
+    stats[6] = S.f64 ? 1 : 0;
     stats[7] = warm_cols;
-    stats[8] = unshrinks;
-    stats[9] = fin->passes;
-    stats[10] = min_active;
-    stats[11] = repacks;
-    stats[12] = fin->newton_steps;
+    stats[8] = ps.unshrinks;
+    stats[9] = fin.passes;
+    stats[10] = ps.min_active;
+    stats[11] = ps.repacks;
+    stats[12] = fin.newton_steps;
   }
   if (r) {
-    r->iterations = inner_total + 1;
-    r->b_high = bh;
-    r->b_low = bl;
-    r->b = (bh + bl) / 2;
-    r->stop_reason = stop;
+    r->iterations = fin.inner_total + 1;
+    r->b_high = fin.b_high;
+    r->b_low = fin.b_low;
+    r->b = (fin.b_high + fin.b_low) / 2;
+    r->stop_reason = fin.stop;
     r->reserved = 0;
     r->n_sv = -1;
-    r->seconds = ms_since(t0) / 1e3;
+    r->seconds = ms_since(S.t0) / 1e3;
   }
   return SVM_OK;
 }
 
+}  // namespace
+
+// Decomposition solve on quantised rows (Q, N0, WN: all n rows; the plan's step weights in stw on the
+// device) or on FP64 rows (DecompRows).  alpha: n doubles (cold start: zeroed here).  q: working-set size
+// (<= 1024).
+// Distributed (world > 1): this GPU owns the blocks [rank NB / world, (rank + 1) NB / world) of the
+// selection's global block partition, keeps f for their points only, and exchanges its candidate
+// records once per outer iteration through `allgather`; every GPU then builds the same working set and
+// runs the same inner solve on the same inputs (alpha is replicated and updated identically), and
+// updates f for its own points.  With world dividing 8 the trajectory is the one-GPU trajectory.
+// stats (kDecompStats = SVM_DECOMP_STATS int64, 13 written): outer iterations, inner iterations, working-set
+// capacity, solve microseconds, columns of the f updates (points moved, summed over the outer iterations),
+// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA), warm-start columns,
+// unshrinks, shrink passes, the fewest active rows, repacks, Newton polish steps.
+int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n, const svm_params& p,
+               int qws, svm_result* r, int64_t* stats, const DecompOpts& o) {
+  Solve S;
+  S.t0 = std::chrono::steady_clock::now();
+  int rc = setup_solve(S, ctx, R, y, alpha, n, p, qws, o);
+  if (rc) return rc;
+  if ((rc = alloc_solve(S, o.warm))) return rc;
+  hipStream_t s = S.s;
+  svm_decomp_trace* tr = S.tr;
+  PackState ps(S.nloc);
+  int64_t warm_cols = 0;
+  if ((rc = start_solve(S, ps, o.warm, &warm_cols))) return rc;
+  if (tr) tr->count = 0;
+  // Outer iterations are enqueued `batch` at a time (SVM355_DECOMP_BATCH, default 1): every kernel reads
+  // the device control block, so after the stop the rest are no-op launches.  Each batch's last kernel
+  // publishes the control block to the host and an event follows it; the host waits for batch k's event
+  // only after it has enqueued batch k + 1, so the GPU always has the next batch queued (no idle host
+  // round trip).  The trace reads every outer iteration back itself.
+  const int batch = tr ? 1 : S.k.batch;
+  const int64_t max_batches = p.max_iter / std::max(1, batch) + 64;  // a stop comes well before: never spin
+  SoloTimer solo{(S.world > 1 && !tr) ? o.solo : nullptr, s};
+  if ((rc = solo.init())) return rc;
+  const DecompCtl* fin = nullptr;  // the readback that saw the stop
+  bool queued = false;             // a batch is in flight whose readback the host has not checked
+  for (int64_t bt = 0;; ++bt) {
+    DecompCtl* pub = tr ? nullptr : S.ctl_pub + (bt & 1);  // the trace path copies the block itself
+    for (int bi = 0; bi < batch; ++bi)
+      if ((rc = enqueue_outer(S, ps, solo, bt * batch + bi, bi == 0, pub))) return rc;
+    const DecompCtl* seen = S.ctl_h;
+    hipEvent_t drain = nullptr;  // what an unshrink waits for first: the batch queued behind the one read
+    if (tr) {  // trace: every outer iteration is read back before the next is enqueued
+      SVMD_CHECK(hipMemcpyAsync(S.ctl_h, S.w.ctl, sizeof(DecompCtl), hipMemcpyDeviceToHost, s));
+      SVMD_CHECK(hipStreamSynchronize(s));
+    } else {
+      SVMD_CHECK(hipEventRecord(ctx->ev_ctl[bt & 1], s));  // the batch's kernels published into ctl_h[bt & 1]
+      if (!queued) {  // keep one batch queued ahead of the wait
+        queued = true;
+        continue;
+      }
+      const int64_t pb = bt - 1;
+      const auto tw = std::chrono::steady_clock::now();
+      if ((rc = wait_event(S, ctx->ev_ctl[pb & 1]))) return rc;
+      if (o.host_wait_ms) *o.host_wait_ms += ms_since(tw);
+      seen = S.ctl_h + (pb & 1);
+      drain = ctx->ev_ctl[bt & 1];
+    }
+    if (seen->stop == kStopUnshrink) {  // batch bt ran as no-ops: drain it, unshrink, restart the pipeline
+      const DecompCtl at = *seen;
+      if ((rc = unshrink(S, ps, at, drain))) return rc;
+      queued = false;
+      continue;
+    }
+    if (seen->stop != SVM_STOP_RUNNING) {
+      fin = seen;  // batch bt (queued) runs as no-ops; the state is final
+      break;
+    }
+    ps.seen_active = seen->n_active;
+    ps.min_active = std::min(ps.min_active, ps.seen_active);
+    if (tr) {
+      if ((rc = record_trace(S, *seen))) return rc;
+    } else if (S.k.shrink_log) {
+      fprintf(stderr, "decomp: rank %d outer %lld gap %.6g active %lld packed %lld (%.3f ms)\n", S.rank,
+              (long long)seen->outer, seen->b_low - seen->b_high, (long long)ps.seen_active,
+              (long long)(ps.pk >= 0 ? ps.pk_bound : S.nloc), ms_since(S.t0));
+    }
+    if (bt >= max_batches) {
+      set_error("decomposition SMO: no stop after %lld outer iterations", (long long)seen->outer);
+      return SVM_ERR_INTERNAL;
+    }
+  }
+  return finish_solve(S, ps, *fin, warm_cols, r, stats);
+}
+
+// ---- the fit entries ------------------------------------------------------------------------------------
 namespace {
 
 // The solve after quantisation: step weights to the device, the decomposition, the SV count.
@@ -2578,42 +1727,43 @@ int decomp_solve(DeviceCtx* ctx, const DecompRows& R, const int32_t* y_d, double
 
 // The context's grow-only buffer holds the quantised rows (the solver's workspace is ctx->ws):
 // Q (n x kq), N0, WN, the step weights and the quantiser's column tables (aux_bytes).
-int decomp_quant_buffers(DeviceCtx* ctx, int64_t n, const QuantPlan& P, size_t aux_bytes, int8_t** Q, int32_t** N0,
-                         double** WN, double** stw, void** aux) {
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t need = al(size_t(n) * P.kq) + al(size_t(n) * 4) + al(size_t(n) * 8) + al(P.step_w.size() * 8) +
-                      al(aux_bytes);
-  if (need > ctx->gram_bytes) {
-    if (ctx->gram) {
-      SVMD_CHECK(hipStreamSynchronize(ctx->stream));
-      SVMD_CHECK(hipFree(ctx->gram));
-      ctx->gram = nullptr;
-      ctx->gram_bytes = 0;
-    }
-    SVMD_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->gram), need));
-    ctx->gram_bytes = need;
+struct QuantBufs {
+  int8_t* Q = nullptr;
+  int32_t* N0 = nullptr;
+  double *WN = nullptr, *stw = nullptr;
+  void* aux = nullptr;
+  DecompRows rows(const QuantPlan& P) const {  // as a solve's row source
+    DecompRows R;
+    R.Q = Q;
+    R.N0 = N0;
+    R.WN = WN;
+    R.stw = stw;
+    R.P = &P;
+    return R;
   }
-  char* base = reinterpret_cast<char*>(ctx->gram);
-  *Q = reinterpret_cast<int8_t*>(base);
-  *N0 = reinterpret_cast<int32_t*>(base + al(size_t(n) * P.kq));
-  *WN = reinterpret_cast<double*>(reinterpret_cast<char*>(*N0) + al(size_t(n) * 4));
-  *stw = reinterpret_cast<double*>(reinterpret_cast<char*>(*WN) + al(size_t(n) * 8));
-  *aux = reinterpret_cast<char*>(*stw) + al(P.step_w.size() * 8);
+};
+int decomp_quant_buffers(DeviceCtx* ctx, int64_t n, const QuantPlan& P, size_t aux_bytes, QuantBufs* b) {
+  auto layout = [&](WsCarver& c) {
+    b->Q = c.take<int8_t>(size_t(n) * P.kq);
+    b->N0 = c.take<int32_t>(size_t(n));
+    b->WN = c.take<double>(size_t(n));
+    b->stw = c.take<double>(P.step_w.size());
+    b->aux = c.take<char>(aux_bytes);
+  };
+  WsCarver size{nullptr};
+  layout(size);
+  const int rc = ctx->ensure_gram_bytes(size.off);
+  if (rc) return rc;
+  WsCarver c{reinterpret_cast<char*>(ctx->gram)};
+  layout(c);
   return SVM_OK;
 }
 
 // The quantised rows' solve: the step weights to the device, then the decomposition.
-int decomp_after_quant(DeviceCtx* ctx, const int8_t* Q, const int32_t* N0, const double* WN, double* stw,
-                       const QuantPlan& P, const int32_t* y_d, double* alpha_d, int64_t n, const svm_params& p, int q,
-                       svm_result* r, int64_t* stats, const DecompOpts& o) {
-  SVMD_CHECK(hipMemcpyAsync(stw, P.step_w.data(), P.step_w.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  DecompRows R;
-  R.Q = Q;
-  R.N0 = N0;
-  R.WN = WN;
-  R.stw = stw;
-  R.P = &P;
-  return decomp_solve(ctx, R, y_d, alpha_d, n, p, q, r, stats, o);
+int decomp_after_quant(DeviceCtx* ctx, const QuantBufs& b, const QuantPlan& P, const int32_t* y_d, double* alpha_d,
+                       int64_t n, const svm_params& p, int q, svm_result* r, int64_t* stats, const DecompOpts& o) {
+  SVMD_CHECK(hipMemcpyAsync(b.stw, P.step_w.data(), P.step_w.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  return decomp_solve(ctx, b.rows(P), y_d, alpha_d, n, p, q, r, stats, o);
 }
 
 }  // namespace
@@ -2634,21 +1784,18 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
   const bool force_f64 = fe && atoi(fe) == 1;
   QuantPlan P;
   if (!force_f64 && mn_h && mx_h && plan_quant(mn_h, mx_h, d, &P) && P.kq <= 32 * 128) {
-    int8_t* Q;
-    int32_t* N0;
-    double *WN, *stw;
-    void* aux;
-    int rc = decomp_quant_buffers(ctx, n, P, quantize_aux_bytes(P), &Q, &N0, &WN, &stw, &aux);
+    QuantBufs b;
+    int rc = decomp_quant_buffers(ctx, n, P, quantize_aux_bytes(P), &b);
     if (rc) return rc;
     bool ok = false;
     {
       TraceRange tr("svm355:quantise");
-      rc = quantize_rows(ctx->stream, X_d, n, ld, P, aux, Q, N0, WN, &ok);
+      rc = quantize_rows(ctx->stream, X_d, n, ld, P, b.aux, b.Q, b.N0, b.WN, &ok);
       if (rc) return rc;
     }
     if (ok) {
       if (prep_ms) *prep_ms = ms_since(t0);
-      rc = decomp_after_quant(ctx, Q, N0, WN, stw, P, y_d, alpha_d, n, p, q, r, stats, o);
+      rc = decomp_after_quant(ctx, b, P, y_d, alpha_d, n, p, q, r, stats, o);
       if (rc) return rc;
       *used = true;
       return SVM_OK;
@@ -2667,19 +1814,10 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
     if (need > 0.8 * double(free_b + ctx->ws_bytes)) return SVM_OK;
   }
   // FP64 rows: their squared norms in the context's grow-only buffer, then the solve
-  const size_t need = size_t(n) * 8;
-  if (need > ctx->gram_bytes) {
-    if (ctx->gram) {
-      SVMD_CHECK(hipStreamSynchronize(ctx->stream));
-      SVMD_CHECK(hipFree(ctx->gram));
-      ctx->gram = nullptr;
-      ctx->gram_bytes = 0;
-    }
-    SVMD_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->gram), need));
-    ctx->gram_bytes = need;
-  }
+  int rc = ctx->ensure_gram_bytes(size_t(n) * 8);
+  if (rc) return rc;
   auto* nrm = reinterpret_cast<double*>(ctx->gram);
-  int rc = launch_scale_norms(ctx->stream, const_cast<double*>(X_d), n, d, ld, nullptr, nullptr, nrm);
+  rc = launch_scale_norms(ctx->stream, const_cast<double*>(X_d), n, d, ld, nullptr, nullptr, nrm);
   if (rc) return rc;
   if (prep_ms) *prep_ms = ms_since(t0);
   DecompRows R;
@@ -2702,44 +1840,30 @@ int decomp_fit_u8(DeviceCtx* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, con
   if (!decomp_shape(n, q, o.world).ok) return SVM_OK;
   QuantPlan P;
   if (!plan_quant(mn_h, mx_h, d, &P) || P.kq > 32 * 128) return SVM_OK;  // igram's LDS table bound
-  int8_t* Q;
-  int32_t* N0;
-  double *WN, *stw;
-  void* aux;
-  int rc = decomp_quant_buffers(ctx, n, P, quantize_u8_aux_bytes(P), &Q, &N0, &WN, &stw, &aux);
+  QuantBufs b;
+  int rc = decomp_quant_buffers(ctx, n, P, quantize_u8_aux_bytes(P), &b);
   if (rc) return rc;
   bool ok = false;
   {
     TraceRange tr("svm355:quantise");
-    rc = quantize_u8_rows(ctx->stream, Xu_d, n, d, mn_h, mx_h, P, aux, Q, N0, WN, &ok);
+    rc = quantize_u8_rows(ctx->stream, Xu_d, n, d, mn_h, mx_h, P, b.aux, b.Q, b.N0, b.WN, &ok);
     if (rc) return rc;
   }
   if (!ok) return SVM_OK;
   if (prep_ms) *prep_ms = ms_since(t0);
-  rc = decomp_after_quant(ctx, Q, N0, WN, stw, P, y_d, alpha_d, n, p, q, r, stats, o);
+  rc = decomp_after_quant(ctx, b, P, y_d, alpha_d, n, p, q, r, stats, o);
   if (rc) return rc;
   *used = true;
   return SVM_OK;
 }
 
-}  // namespace svm355
+namespace {
 
-using namespace svm355;
-
-extern "C" {
-
-// Decomposition SMO straight from uint8 pixel rows (exact-integer kernel values, no stored Gram).
-// *used = 0 and nothing done when the rows' statistics do not admit the integer plan.  stats
-// (optional, 8 int64): see run_decomp.
-SVM_API int svmd_train_decomp_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
-                                 const double* mx_h, const int32_t* y_d, double* alpha_d, const svm_params* pp,
-                                 int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used_out) {
-  SVMD_CTX(h);
-  if (used_out) *used_out = 0;
-  if (!Xu_d || n < 2 || d <= 0 || !mn_h || !mx_h || !y_d || !alpha_d) {
-    set_error("svmd_train_decomp_u8: bad arguments");
-    return SVM_ERR_ARG;
-  }
+// The C entries' one body after their argument checks: uint8 rows (X_d n x d) or min-max scaled FP64 rows
+// (X_d n x ld), the parameters or the defaults, the fit between the context's stream joins, the timing.
+int train_decomp(DeviceCtx* ctx, const void* X_d, bool is_u8, int64_t n, int64_t ld, int64_t d, const double* mn_h,
+                 const double* mx_h, const int32_t* y_d, double* alpha_d, const svm_params* pp, int32_t q,
+                 const DecompOpts& o, svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used_out) {
   svm_params p;
   if (pp)
     p = *pp;
@@ -2750,15 +1874,42 @@ SVM_API int svmd_train_decomp_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_
   if (rc) return rc;
   bool used = false;
   double prep = 0.0;
-  rc = decomp_fit_u8(ctx, Xu_d, n, d, mn_h, mx_h, y_d, alpha_d, p, q, r, stats, &used, &prep);
+  rc = is_u8 ? decomp_fit_u8(ctx, static_cast<const uint8_t*>(X_d), n, d, mn_h, mx_h, y_d, alpha_d, p, q, r, stats,
+                             &used, &prep, o)
+             : decomp_fit_rows(ctx, static_cast<const double*>(X_d), n, ld, d, mn_h, mx_h, y_d, alpha_d, p, q, r,
+                               stats, &used, &prep, o);
   if (rc) return rc;
   if (used && timing) {
     timing->gram_ms = prep;  // quantisation only: no Gram is stored
-    timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timing->total_ms = ms_since(t0);
     timing->smo_ms = timing->total_ms - prep;
   }
   if (used_out) *used_out = used ? 1 : 0;
   return ctx->end();
+}
+
+}  // namespace
+
+}  // namespace svm355
+
+using namespace svm355;
+
+// ---- the C ABI ------------------------------------------------------------------------------------------
+extern "C" {
+
+// Decomposition SMO straight from uint8 pixel rows (exact-integer kernel values, no stored Gram).
+// *used = 0 and nothing done when the rows' statistics do not admit the integer plan.  stats
+// (optional, SVM_DECOMP_STATS int64): see run_decomp.
+SVM_API int svmd_train_decomp_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
+                                 const double* mx_h, const int32_t* y_d, double* alpha_d, const svm_params* pp,
+                                 int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used_out) {
+  SVMD_CTX(h);
+  if (used_out) *used_out = 0;
+  if (!Xu_d || n < 2 || d <= 0 || !mn_h || !mx_h || !y_d || !alpha_d) {
+    set_error("svmd_train_decomp_u8: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  return train_decomp(ctx, Xu_d, true, n, 0, d, mn_h, mx_h, y_d, alpha_d, pp, q, {}, r, timing, stats, used_out);
 }
 
 // The same solve from min-max scaled FP64 rows on the device (X_d: n x ld; mn_h / mx_h the training
@@ -2773,25 +1924,7 @@ SVM_API int svmd_train_decomp_rows(void* h, const double* X_d, int64_t n, int64_
     set_error("svmd_train_decomp_rows: bad arguments");
     return SVM_ERR_ARG;
   }
-  svm_params p;
-  if (pp)
-    p = *pp;
-  else
-    svm_default_params(&p);
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = ctx->begin();
-  if (rc) return rc;
-  bool used = false;
-  double prep = 0.0;
-  rc = decomp_fit_rows(ctx, X_d, n, ld, d, mn_h, mx_h, y_d, alpha_d, p, q, r, stats, &used, &prep);
-  if (rc) return rc;
-  if (used && timing) {
-    timing->gram_ms = prep;
-    timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    timing->smo_ms = timing->total_ms - prep;
-  }
-  if (used_out) *used_out = used ? 1 : 0;
-  return ctx->end();
+  return train_decomp(ctx, X_d, false, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, {}, r, timing, stats, used_out);
 }
 
 // The general entry: uint8 rows (is_u8, X_d n x d) or min-max scaled FP64 rows (X_d n x ld), cold or
@@ -2807,37 +1940,18 @@ SVM_API int svmd_train_decomp(void* h, const void* X_d, int32_t is_u8, int64_t n
     set_error("svmd_train_decomp: bad arguments");
     return SVM_ERR_ARG;
   }
-  svm_params p;
-  if (pp)
-    p = *pp;
-  else
-    svm_default_params(&p);
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = ctx->begin();
-  if (rc) return rc;
-  bool used = false;
-  double prep = 0.0;
   DecompOpts o;
   o.warm = warm != 0;
   o.trace = trace;
-  rc = is_u8 ? decomp_fit_u8(ctx, static_cast<const uint8_t*>(X_d), n, d, mn_h, mx_h, y_d, alpha_d, p, q, r, stats,
-                             &used, &prep, o)
-             : decomp_fit_rows(ctx, static_cast<const double*>(X_d), n, ld, d, mn_h, mx_h, y_d, alpha_d, p, q, r,
-                               stats, &used, &prep, o);
-  if (rc) return rc;
-  if (used && timing) {
-    timing->gram_ms = prep;
-    timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    timing->smo_ms = timing->total_ms - prep;
-  }
-  if (used_out) *used_out = used ? 1 : 0;
-  return ctx->end();
+  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, o, r, timing, stats, used_out);
 }
 
-// The decomposition solver's f-update GEMV alone (tests): the uint8 rows quantised as a solve would,
-// then f_out[i] = sum_k coef[k] K(lo + i, cols[k]) over k < m for the rows [lo, lo + nloc) -- the GEMV
-// kernel with the device-side count m, its partial halves summed in order (the f update of a solve,
-// from f = 0).  cols / coef / f_out are host arrays; m <= 1024.  *used = 0 without an exact plan.
+// The decomposition solver's f update alone (tests): the uint8 rows quantised as a solve would, then
+// f_out[i] = sum_k coef[k] K(lo + i, cols[k]) over k < m for the rows [lo, lo + nloc) -- the solver's own
+// f_update from f = 0 with the device-side count m, on the GEMV (its partial halves summed in order) or,
+// with SVM355_GEMV_VIA_CACHE set, on a fresh column cache of m persistent slots (every column a miss: the
+// narrow store up to 64 columns, the tiled one beyond; then the reader).  cols / coef / f_out are host
+// arrays; m <= 1024.  *used = 0 without an exact plan.
 SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
                                 const double* mx_h, double gamma, int64_t lo, int64_t nloc, const int32_t* cols_h,
                                 const double* coef_h, int32_t m, double* f_out, int32_t* used_out) {
@@ -2858,81 +1972,55 @@ SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t
   hipStream_t s = ctx->stream;
   QuantPlan P;
   if (!plan_quant(mn_h, mx_h, d, &P) || P.kq > 32 * 128) return ctx->end();
-  int8_t* Q;
-  int32_t* N0;
-  double *WN, *stw;
-  void* aux;
-  rc = decomp_quant_buffers(ctx, n, P, quantize_u8_aux_bytes(P), &Q, &N0, &WN, &stw, &aux);
+  QuantBufs b;
+  rc = decomp_quant_buffers(ctx, n, P, quantize_u8_aux_bytes(P), &b);
   if (rc) return rc;
   bool ok = false;
-  rc = quantize_u8_rows(s, Xu_d, n, d, mn_h, mx_h, P, aux, Q, N0, WN, &ok);
+  rc = quantize_u8_rows(s, Xu_d, n, d, mn_h, mx_h, P, b.aux, b.Q, b.N0, b.WN, &ok);
   if (rc) return rc;
   if (!ok) return ctx->end();
-  SVMD_CHECK(hipMemcpyAsync(stw, P.step_w.data(), P.step_w.size() * 8, hipMemcpyHostToDevice, s));
-  const int64_t ldp = 2 * (kMaxWS / 128);
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_cols = 0, o_coef = al(kMaxWS * 4), o_cnt = o_coef + al(kMaxWS * 8), o_f = o_cnt + 256,
-               o_part = o_f + al(size_t(nloc) * 8), need = o_part + size_t(nloc) * ldp * 8;
-  rc = ctx->ensure_ws(need);
-  if (rc) return rc;
-  char* ws = static_cast<char*>(ctx->ws);
-  auto* cols = reinterpret_cast<int32_t*>(ws + o_cols);
-  auto* coef = reinterpret_cast<double*>(ws + o_coef);
-  auto* cnt = reinterpret_cast<int32_t*>(ws + o_cnt);
-  auto* f = reinterpret_cast<double*>(ws + o_f);
-  auto* part = reinterpret_cast<double*>(ws + o_part);
-  SVMD_CHECK(hipMemcpyAsync(cols, cols_h, size_t(m) * 4, hipMemcpyHostToDevice, s));
-  SVMD_CHECK(hipMemcpyAsync(coef, coef_h, size_t(m) * 8, hipMemcpyHostToDevice, s));
-  SVMD_CHECK(hipMemcpyAsync(cnt, &m, 4, hipMemcpyHostToDevice, s));
-  SVMD_CHECK(hipMemsetAsync(f, 0, size_t(nloc) * 8, s));
+  SVMD_CHECK(hipMemcpyAsync(b.stw, P.step_w.data(), P.step_w.size() * 8, hipMemcpyHostToDevice, s));
+  Solve S;  // what f_update reads of a solve: the rows, the slice, gamma, the cache and the update's buffers
+  S.ctx = ctx;
+  S.s = s;
+  S.R = b.rows(P);
+  S.kq = P.kq;
+  S.n = n;
+  S.lo = lo;
+  S.nloc = nloc;
+  S.p.gamma = gamma;
   const char* vc = getenv("SVM355_GEMV_VIA_CACHE");
-  if (vc && atoi(vc) != 0) {
-    // the column-cache form of the same update (tests / timing): a fresh cache of m persistent slots
-    // (every column a miss: the narrow store up to 64 columns, the tiled one beyond), then the reader
-    const int64_t ldc = (nloc + 3) & ~int64_t(3);
-    double* cache = ctx->ensure_rc_cache(size_t(m + kMaxWS) * ldc * 8);
-    if (!cache) {
+  const bool via_cache = vc && atoi(vc) != 0;
+  if (via_cache) {
+    S.cc.cap = m;
+    S.cc.ld = (nloc + 3) & ~int64_t(3);
+    S.cc.slab = ctx->ensure_rc_cache(size_t(m + kMaxWS) * S.cc.ld * 8);
+    if (!S.cc.slab) {
       set_error("svmd_decomp_gemv_u8: no memory for the column cache");
       return SVM_ERR_DEVICE;
     }
-    const size_t o_cs = need, o_rd = o_cs + al(size_t(n) * 4), o_mid = o_rd + al(kMaxWS * 4),
-                 o_msl = o_mid + al(kMaxWS * 4), o_st = o_msl + al(kMaxWS * 4), need2 = o_st + 256;
-    rc = ctx->ensure_ws(need2);
-    if (rc) return rc;
-    ws = static_cast<char*>(ctx->ws);  // (re)allocated: every pointer again
-    cols = reinterpret_cast<int32_t*>(ws + o_cols);
-    coef = reinterpret_cast<double*>(ws + o_coef);
-    cnt = reinterpret_cast<int32_t*>(ws + o_cnt);
-    f = reinterpret_cast<double*>(ws + o_f);
-    auto* cslot = reinterpret_cast<int32_t*>(ws + o_cs);
-    auto* crd = reinterpret_cast<int32_t*>(ws + o_rd);
-    auto* cmid = reinterpret_cast<int32_t*>(ws + o_mid);
-    auto* cmsl = reinterpret_cast<int32_t*>(ws + o_msl);
-    auto* cst = reinterpret_cast<int32_t*>(ws + o_st);
-    SVMD_CHECK(hipMemcpyAsync(cols, cols_h, size_t(m) * 4, hipMemcpyHostToDevice, s));
-    SVMD_CHECK(hipMemcpyAsync(coef, coef_h, size_t(m) * 8, hipMemcpyHostToDevice, s));
-    SVMD_CHECK(hipMemcpyAsync(cnt, &m, 4, hipMemcpyHostToDevice, s));
-    SVMD_CHECK(hipMemsetAsync(f, 0, size_t(nloc) * 8, s));
-    SVMD_CHECK(hipMemsetAsync(cslot, 0xFF, size_t(n) * 4, s));
-    SVMD_CHECK(hipMemsetAsync(cst, 0, 256, s));
-    hipLaunchKernelGGL(ws_cache_plan_kernel, dim3(1), dim3(kMaxWS), 0, s, cols, cnt, cslot, m, cst, crd, cmid, cmsl,
-                       nullptr, nullptr, nullptr);
-    SVMD_LAUNCH_CHECK();
-    rc = launch_igram_colstore(s, Q + lo * int64_t(P.kq), N0 + lo, WN + lo, stw, nloc, lo, Q, N0, WN, cmid, cmsl,
-                               cst + 1, kMaxWS, P, gamma, cache, ldc, cst + 2);
-    if (rc) return rc;
-    hipLaunchKernelGGL((ws_cache_fsum_kernel<2>), dim3(unsigned((nloc + 511) / 512)), dim3(256), 0, s, cache, ldc, crd,
-                       coef, cnt, f, nloc);
-    SVMD_LAUNCH_CHECK();
-  } else {
-    rc = launch_igram_gemv(s, Q + lo * int64_t(P.kq), N0 + lo, WN + lo, stw, nloc, lo, Q, N0, WN, cols, coef, cnt,
-                           kMaxWS, P, gamma, part, ldp);
-    if (rc) return rc;
-    hipLaunchKernelGGL(ws_fsum_count_kernel, dim3(unsigned((nloc + 255) / 256)), dim3(256), 0, s, part, ldp, cnt, f,
-                       nloc);
-    SVMD_LAUNCH_CHECK();
   }
-  SVMD_CHECK(hipMemcpyAsync(f_out, f, size_t(nloc) * 8, hipMemcpyDeviceToHost, s));
+  DecompWs& w = S.w;
+  rc = carve_ws(ctx, [&](WsCarver& c) {
+    w.cols = c.take<int32_t>(kMaxWS);
+    w.coef = c.take<double>(kMaxWS);
+    w.mcount = c.take<int32_t>(64);
+    w.f = c.take<double>(size_t(nloc));
+    w.part = c.take<double>(size_t(nloc) * kLdp, !via_cache);
+    w.cslot = c.take<int32_t>(size_t(n), via_cache);
+    w.crd = c.take<int32_t>(kMaxWS, via_cache);
+    w.cmid = c.take<int32_t>(kMaxWS, via_cache);
+    w.cmsl = c.take<int32_t>(kMaxWS, via_cache);
+    w.cst = c.take<int32_t>(64, via_cache);
+  });
+  if (rc) return rc;
+  SVMD_CHECK(hipMemcpyAsync(w.cols, cols_h, size_t(m) * 4, hipMemcpyHostToDevice, s));
+  SVMD_CHECK(hipMemcpyAsync(w.coef, coef_h, size_t(m) * 8, hipMemcpyHostToDevice, s));
+  SVMD_CHECK(hipMemcpyAsync(w.mcount, &m, 4, hipMemcpyHostToDevice, s));
+  SVMD_CHECK(hipMemsetAsync(w.f, 0, size_t(nloc) * 8, s));
+  if ((rc = cache_reset(S))) return rc;
+  if ((rc = f_update(S, PackState(nloc), w.cols, w.coef, w.mcount))) return rc;
+  SVMD_CHECK(hipMemcpyAsync(f_out, w.f, size_t(nloc) * 8, hipMemcpyDeviceToHost, s));
   SVMD_CHECK(hipStreamSynchronize(s));
   if (used_out) *used_out = 1;
   return ctx->end();
@@ -2953,21 +2041,21 @@ SVM_API int svmd_decomp_newton_probe(void* h, const double* Kw_h, const int32_t*
   int rc = ctx->begin();
   if (rc) return rc;
   hipStream_t s = ctx->stream;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t o_k = 0, o_y = al(size_t(kMaxWS) * kMaxWS * 8), o_a = o_y + al(kMaxWS * 4), o_f = o_a + al(kMaxWS * 8),
-               o_a0 = o_f + al(kMaxWS * 8), o_f0 = o_a0 + al(kMaxWS * 8), o_c = o_f0 + al(kMaxWS * 8), o_p = o_c + 256,
-               o_A = o_p + 256, need = o_A + size_t(kMaxWS + 2) * kMaxWS * 8;
-  if ((rc = ctx->ensure_ws(need))) return rc;
-  char* ws = static_cast<char*>(ctx->ws);
-  auto* Kw = reinterpret_cast<double*>(ws + o_k);
-  auto* yd = reinterpret_cast<int32_t*>(ws + o_y);
-  auto* ad = reinterpret_cast<double*>(ws + o_a);
-  auto* fd = reinterpret_cast<double*>(ws + o_f);
-  auto* a0 = reinterpret_cast<double*>(ws + o_a0);
-  auto* f0 = reinterpret_cast<double*>(ws + o_f0);
-  auto* cd = reinterpret_cast<int32_t*>(ws + o_c);
-  auto* pd = reinterpret_cast<int64_t*>(ws + o_p);
-  auto* Ad = reinterpret_cast<double*>(ws + o_A);
+  double *Kw = nullptr, *ad = nullptr, *fd = nullptr, *a0 = nullptr, *f0 = nullptr, *Ad = nullptr;
+  int32_t *yd = nullptr, *cd = nullptr;
+  int64_t* pd = nullptr;
+  rc = carve_ws(ctx, [&](WsCarver& c) {
+    Kw = c.take<double>(size_t(kMaxWS) * kMaxWS);
+    yd = c.take<int32_t>(kMaxWS);
+    ad = c.take<double>(kMaxWS);
+    fd = c.take<double>(kMaxWS);
+    a0 = c.take<double>(kMaxWS);
+    f0 = c.take<double>(kMaxWS);
+    cd = c.take<int32_t>(64);
+    pd = c.take<int64_t>(32);
+    Ad = c.take<double>(size_t(kMaxWS + 2) * kMaxWS);
+  });
+  if (rc) return rc;
   SVMD_CHECK(hipMemcpy2DAsync(Kw, kMaxWS * 8, Kw_h, size_t(m) * 8, size_t(m) * 8, size_t(m), hipMemcpyHostToDevice, s));
   SVMD_CHECK(hipMemcpyAsync(yd, y_h, size_t(m) * 4, hipMemcpyHostToDevice, s));
   SVMD_CHECK(hipMemcpyAsync(a0, a_h, size_t(m) * 8, hipMemcpyHostToDevice, s));
@@ -2980,8 +2068,7 @@ SVM_API int svmd_decomp_newton_probe(void* h, const double* Kw_h, const int32_t*
     SVMD_CHECK(hipMemcpyAsync(ad, a0, size_t(m) * 8, hipMemcpyDeviceToDevice, s));
     SVMD_CHECK(hipMemcpyAsync(fd, f0, size_t(m) * 8, hipMemcpyDeviceToDevice, s));
     SVMD_CHECK(hipEventRecord(e0, s));
-    hipLaunchKernelGGL(ws_newton_probe_kernel, dim3(1), dim3(256), 0, s, m, Kw, int64_t(kMaxWS), yd, ad, fd, Ad, C, eps,
-                       max_free, cd, pd);
+    launch_ws_newton_probe(s, m, Kw, int64_t(kMaxWS), yd, ad, fd, Ad, C, eps, max_free, cd, pd);
     SVMD_LAUNCH_CHECK();
     SVMD_CHECK(hipEventRecord(e1, s));
     SVMD_CHECK(hipEventSynchronize(e1));

@@ -53,11 +53,12 @@ SVM_API int svmd_train_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, 
                           const double* mx_h, const int32_t* y_d, double* alpha_d, int32_t warm,
                           const svm_params* p, svm_result* r, double* K_d, int64_t ldk, svmd_timing* timing,
                           int32_t* used);
-// Working-set decomposition SMO (decomp.hip, opt-in): working sets of up to q <= 1024 points solved
+// Working-set decomposition SMO (decomp.hip, decomp_inner.hip): working sets of up to q <= 1024 points solved
 // in one workgroup, f updated by the exact-integer kernel values against the working set; no stored
-// Gram.  *used = 0 when the rows are not integer pixels.  stats (optional, 8 int64): outer
-// iterations, inner iterations, working-set size, solve microseconds, f-update columns (points
-// moved, summed over the outer iterations), inner workgroup size.
+// Gram.  *used = 0 when the rows are not integer pixels.  stats (optional, SVM_DECOMP_STATS
+// int64, 13 written): outer iterations, inner iterations, working-set size, solve microseconds, f-update
+// columns (points moved, summed over the outer iterations), inner workgroup size, kernel-value path,
+// warm-start columns, unshrinks, shrink passes, fewest active rows, repacks, Newton polish steps.
 SVM_API int svmd_train_decomp_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
                                  const double* mx_h, const int32_t* y_d, double* alpha_d, const svm_params* p,
                                  int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used);
@@ -214,7 +215,8 @@ SVM_API int svmd_cascade_group_exercise(void* group, const char* script, double 
 // every rank's GPU holds all n uint8 rows (host X, n x d) and labels, owns a block range of f, and
 // all-gathers its candidate records once per outer iteration; the working set, inner solve and alpha
 // are replicated.  With 1, 2, 4 or 8 ranks the trajectory equals svmd_train_decomp_u8's.  alpha_out
-// (n), r, stats (8 int64, see svmd_train_decomp_u8) and mm_out (2 d: column min / max) may be null.
+// (n), r, stats (SVM_DECOMP_STATS int64, see svmd_train_decomp_u8) and mm_out (2 d: column min / max) may
+// be null.
 SVM_API int svmd_cascade_group_decomp(void* group, const uint8_t* X, const int32_t* y, int64_t n, int64_t d,
                                       const svm_params* p, int32_t q, double* alpha_out, svm_result* r,
                                       int64_t* stats, double* rank_ms, double* mm_out);

@@ -12,6 +12,8 @@ import torch
 from svm355 import SVC, SVMParams
 from svm355.utils.data import synthetic_mnist
 
+from decomp_checks import kkt_gap_fp64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -162,6 +164,31 @@ def test_decomp_rejects_an_inner_stop_that_cannot_progress(monkeypatch):
     monkeypatch.setenv("SVM355_DECOMP_TAU_FRAC", "0.3")
     m = SVC(device="cuda:0", solver="decomp").fit(tr.X, tr.y)
     assert m.stop_reason_ == "converged" and len(m.support_) > 0
+
+
+@pytest.mark.parametrize("env,q,threads", [({"SVM355_DECOMP_NT": "64", "SVM355_DECOMP_WSS": "2"}, 1024, 64),
+                                           ({"SVM355_DECOMP_NT": "128", "SVM355_DECOMP_WSS": "2"}, 1024, 128),
+                                           ({"SVM355_DECOMP_NT": "512", "SVM355_DECOMP_WSS": "2"}, 1024, 512),
+                                           ({"SVM355_DECOMP_NT": "65", "SVM355_DECOMP_WSS": "2"}, 256, 65),
+                                           ({"SVM355_DECOMP_PROF": "1"}, 1024, 256)])
+def test_inner_kernel_dispatch_arms(env, q, threads, monkeypatch):
+    """The inner kernel's other workgroup shapes (SVM355_DECOMP_NT, at the one-pair second-order rule: the
+    second pair of WSS=3 is defined on the 256-thread wave layout) and its profiling build: each converges
+    with the requested workgroup and meets the reference's stop test on all points from an independent FP64
+    kernel.  n = 2000 in 784 columns: 32 selection blocks, a working set that fills all 1,024 slots (every
+    PER slot of every shape).  The profiling build only adds clocks: the default build's alpha and b."""
+    tr = synthetic_mnist(2000, seed=91)
+    p = SVMParams()
+    base = SVC(device="cuda:0", solver="decomp", working_set=q).fit(tr.X, tr.y) if "SVM355_DECOMP_PROF" in env else None
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    m = SVC(device="cuda:0", solver="decomp", working_set=q).fit(tr.X, tr.y)
+    assert m.stop_reason_ == "converged"
+    assert m.timings_["inner_threads"] == threads
+    assert kkt_gap_fp64(tr.X, tr.y.astype(np.float64), m.alpha_, p) <= 2 * p.tau + 1e-9
+    if base is not None:
+        assert m.b_ == base.b_
+        np.testing.assert_array_equal(m.alpha_, base.alpha_)
 
 
 @pytest.mark.parametrize("n,world,ccache", [(6000, 2, None), (6000, 8, None), (20000, 4, None), (6000, 2, "1"),

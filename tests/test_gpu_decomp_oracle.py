@@ -18,6 +18,8 @@ from svm355.ops import cpu as C
 from svm355.ops import device as D
 from svm355.utils.data import synthetic_mnist
 
+from decomp_checks import kkt_gap_fp64
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
@@ -87,8 +89,9 @@ def _compare(dt, ot):
 
 
 @pytest.mark.parametrize("n,q,wss", [(2000, 1024, 3), (2000, 64, 3), (6000, 512, 3), (6000, 1024, 3),
-                                     (2000, 1024, 4), (6000, 1024, 4)])
+                                     (2000, 1024, 4), (6000, 1024, 4), (2000, 1024, 1), (2000, 1024, 2)])
 def test_device_trajectory_equals_the_cpu_oracle(n, q, wss, monkeypatch):
+    # wss 1 / 2: the first-order and the one-pair second-order inner kernels (oracle inner_wss 1 / 2)
     # wss 4: the second pair's j by the second-order gain of row i2 (SVM355_DECOMP_WSS=4, oracle inner_wss 4)
     monkeypatch.setenv("SVM355_DECOMP_WSS", str(wss))
     tr = synthetic_mnist(n, seed=41 + q).compact()
@@ -282,25 +285,6 @@ def test_shrinking_trajectory_equals_the_oracle(monkeypatch, mode, cache, repack
                 assert tm["repacks"] >= 1
 
 
-def _kkt_gap_fp64(X, y, a, p):
-    """b_low - b_high over ALL points from an independent FP64 RBF (torch, min-max scaled rows)."""
-    Xs = torch.from_numpy(X.astype(np.float64)).to(DEV)
-    mn, mx = Xs.min(0).values, Xs.max(0).values
-    rng = torch.where(mx - mn < 1e-12, torch.ones_like(mx), mx - mn)
-    Xs = (Xs - mn) / rng
-    sq = (Xs * Xs).sum(1)
-    ay = torch.from_numpy(a * y).to(DEV)
-    f = torch.empty(len(y), dtype=torch.float64, device=DEV)
-    for i0 in range(0, len(y), 4096):
-        B = Xs[i0:i0 + 4096] @ Xs.T
-        Kb = torch.exp(-p.gamma * torch.clamp(sq[i0:i0 + 4096, None] + sq[None, :] - 2.0 * B, min=0.0))
-        f[i0:i0 + 4096] = Kb @ ay
-    f = f.cpu().numpy() - y
-    hi = ((y == 1) & (a < p.C - p.eps)) | ((y == -1) & (a > p.eps))
-    lo = ((y == 1) & (a > p.eps)) | ((y == -1) & (a < p.C - p.eps))
-    return f[lo].max() - f[hi].min()
-
-
 @pytest.mark.parametrize("n", [60000])
 def test_shrunk_solve_meets_the_stop_test_on_all_points(n):
     """The headline shape with shrinking=True against the default (off): the same support
@@ -315,7 +299,7 @@ def test_shrunk_solve_meets_the_stop_test_on_all_points(n):
     assert on.timings_["shrink_passes"] >= 1 and on.timings_["min_active"] < n
     assert off.timings_["shrink_passes"] == 0
     y = tr.y.astype(np.float64)
-    assert _kkt_gap_fp64(tr.X, y, on.alpha_, p) <= 2 * p.tau + 1e-9
+    assert kkt_gap_fp64(tr.X, y, on.alpha_, p) <= 2 * p.tau + 1e-9
 
 
 @pytest.mark.parametrize("env", [{"SVM355_DECOMP_NEWTON": "1", "SVM355_DECOMP_NEWTON_EVERY": "5", "SVM355_DECOMP_NEWTON_FRAC": "0"},
