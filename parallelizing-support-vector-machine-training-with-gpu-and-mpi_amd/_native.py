@@ -46,6 +46,8 @@ class SvmParams(ctypes.Structure):
         ("verbose", c_int32),
         ("wss", c_int32),
         ("shrink", c_int32),
+        ("weight_pos", c_double),
+        ("weight_neg", c_double),
     ]
 
 
@@ -420,6 +422,6 @@ def shrink_stats(st) -> dict:
 
 
 def params_struct(C=10.0, gamma=0.00125, tau=1e-5, eps=1e-12, sv_tol=1e-8, max_iter=100000,
-                  n_threads=1, verbose=0, wss=1, shrink=0) -> SvmParams:
+                  n_threads=1, verbose=0, wss=1, shrink=0, weight_pos=1.0, weight_neg=1.0) -> SvmParams:
     return SvmParams(float(C), float(gamma), float(tau), float(eps), float(sv_tol), int(max_iter),
-                     int(n_threads), int(verbose), int(wss), int(shrink))
+                     int(n_threads), int(verbose), int(wss), int(shrink), float(weight_pos), float(weight_neg))

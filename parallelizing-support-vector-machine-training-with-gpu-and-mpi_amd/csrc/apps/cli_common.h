@@ -47,7 +47,9 @@ inline void usage(const char* prog) {
           "usage: %s [--dataset P | --train F --test F | --synthetic N[,M] [--seed S]] [--n-limit N]\n"
           "          [--C 10] [--gamma 0.00125] [--tau 1e-5] [--eps 1e-12] [--sv-tol 1e-8]\n"
           "          [--max-iter 100000] [--positive-label 1] [--threads T] [--model-dir D] [--json F]\n"
-          "          [--gram auto|fp64|int] [--warmup W] [--wss first|second] [--solver auto|decomp|smo]\n",
+          "          [--gram auto|fp64|int] [--warmup W] [--wss first|second] [--solver auto|decomp|smo]\n"
+          "          [--weight-pos W] [--weight-neg W]   class weights (> 0, default 1): the box of the positive /\n"
+          "                                              negative rows is C * W (svm_serial; svm_gpu's decomposition)\n",
           prog);
 }
 
@@ -89,6 +91,14 @@ inline bool parse(int argc, char** argv, Options& o, int default_threads) {
     auto count = [&](const char* what, const char* v, bool until_comma = false) {
       return parse_int(what, v, until_comma);
     };
+    // a class weight: finite and > 0 (0 in the C struct reads as 1, so it is refused here, not passed on)
+    auto weight = [&](double& w, const char* what) {
+      w = num(what);
+      if (!(w > 0) || !std::isfinite(w)) {
+        fprintf(stderr, "%s must be finite and > 0, got %g\n", what, w);
+        exit(2);
+      }
+    };
     if (a == "--dataset") o.dataset = next("--dataset");
     else if (a == "--train") o.train = next("--train");
     else if (a == "--test") o.test = next("--test");
@@ -109,6 +119,8 @@ inline bool parse(int argc, char** argv, Options& o, int default_threads) {
     else if (a == "--tau") o.p.tau = num("--tau");
     else if (a == "--eps") o.p.eps = num("--eps");
     else if (a == "--sv-tol") o.p.sv_tol = num("--sv-tol");
+    else if (a == "--weight-pos") weight(o.p.weight_pos, "--weight-pos");
+    else if (a == "--weight-neg") weight(o.p.weight_neg, "--weight-neg");
     else if (a == "--max-iter") o.p.max_iter = count("--max-iter", next("--max-iter"));
     else if (a == "--positive-label") o.positive_label = (int)count("--positive-label", next("--positive-label"));
     else if (a == "--threads") o.p.n_threads = (int)count("--threads", next("--threads"));
@@ -219,10 +231,10 @@ inline void write_json(const std::string& path, const char* program, const Optio
   }
   fprintf(f,
           "{\"program\": \"%s\", \"n\": %lld, \"n_features\": %lld, \"C\": %.17g, \"gamma\": %.17g, "
-          "\"tau\": %.17g, \"iterations\": %lld, \"b\": %.17g, \"b_high\": %.17g, \"b_low\": %.17g, "
+          "\"tau\": %.17g, \"weight_pos\": %.17g, \"weight_neg\": %.17g, \"iterations\": %lld, \"b\": %.17g, \"b_high\": %.17g, \"b_low\": %.17g, "
           "\"stop_reason\": \"%s\", \"n_sv\": %lld, \"test_correct\": %lld, \"test_m\": %lld, "
           "\"accuracy\": %.17g, \"training_ms\": %.3f, \"prediction_ms\": %.3f, \"total_ms\": %.3f%s%s}\n",
-          program, n, d, o.p.C, o.p.gamma, o.p.tau, (long long)r.iterations, r.b, r.b_high, r.b_low,
+          program, n, d, o.p.C, o.p.gamma, o.p.tau, o.p.weight_pos, o.p.weight_neg, (long long)r.iterations, r.b, r.b_high, r.b_low,
           svm_stop_message(r.stop_reason), (long long)r.n_sv, correct, m, m ? double(correct) / double(m) : 0.0,
           train_ms, pred_ms, total_ms, extra && *extra ? ", " : "", extra ? extra : "");
   fclose(f);

@@ -77,6 +77,11 @@ int main(int argc, char** argv) {
   }
   cli::Options o;
   if (!cli::parse(int(rest.size()), rest.data(), o, 0)) return 2;
+  if (o.p.weight_pos != 1.0 || o.p.weight_neg != 1.0) {
+    fprintf(stderr, "svm_cascade: --weight-pos / --weight-neg are not supported by the cascade trainers (svm_serial, "
+                    "or svm_gpu's decomposition solver)\n");
+    return 2;
+  }
   if ((topology != "star" && topology != "tree") || P < 1 || max_rounds < 1 || !(timeout > 0) ||
       (transport != "auto" && transport != "rccl" && transport != "loopback")) {
     usage(argv[0]);

@@ -43,6 +43,13 @@ struct Dev {
 int main(int argc, char** argv) {
   cli::Options o;
   if (!cli::parse(argc, argv, o, 0)) return 2;
+  // class weights: the decomposition solver has per-class boxes; the pairwise SMO (--solver smo, or what
+  // --gram / --wss second route to) has one box and refuses them
+  if ((o.p.weight_pos != 1.0 || o.p.weight_neg != 1.0) && (o.solver == 0 || o.gram_mode != 0 || o.p.wss == 2)) {
+    fprintf(stderr, "svm_gpu: --weight-pos / --weight-neg need the decomposition solver (not --solver smo, --gram or "
+                    "--wss second)\n");
+    return 2;
+  }
   int32_t ndev = 0;
   svmd_device_count(&ndev);
   if (ndev < 1) {

@@ -105,6 +105,23 @@ SVM_API void svm_default_params(svm_params* p) {
   p->verbose = 0;
   p->wss = 1;
   p->shrink = 0;
+  p->weight_pos = 1.0;
+  p->weight_neg = 1.0;
+}
+
+SVM_API int svm_class_boxes(const svm_params* p, double* c_pos, double* c_neg) {
+  if (!p || !c_pos || !c_neg) {
+    set_error("svm_class_boxes: null argument");
+    return SVM_ERR_ARG;
+  }
+  const double wp = p->weight_pos == 0.0 ? 1.0 : p->weight_pos, wn = p->weight_neg == 0.0 ? 1.0 : p->weight_neg;
+  if (!(wp > 0.0) || !(wn > 0.0) || !std::isfinite(wp) || !std::isfinite(wn)) {
+    set_error("class weights must be finite and > 0 (weight_pos = %g, weight_neg = %g)", p->weight_pos, p->weight_neg);
+    return SVM_ERR_ARG;
+  }
+  *c_pos = p->C * wp;
+  *c_neg = p->C * wn;
+  return SVM_OK;
 }
 
 SVM_API const char* svm_stop_message(int32_t reason) {

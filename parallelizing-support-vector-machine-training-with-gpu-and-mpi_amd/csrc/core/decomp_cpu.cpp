@@ -19,6 +19,9 @@
 //     the warm start's chunked GEMV) -- which points are active is part of the trajectory; which rows the
 //     device also keeps updating (its packed list lags the flags) is not, so the trace shows f only
 //     for active points (NaN elsewhere).
+//   * class weights (svm_params.weight_pos / weight_neg): per-class boxes in the set membership of every
+//     selection and in the clip of both pairs (smo_cpu.cpp has the expressions); shrinking and the Newton
+//     polish are unweighted and refuse them.
 // The kernel values themselves come from the caller (the device Gram on the exact-integer path).
 #include <chrono>
 #include <climits>
@@ -125,6 +128,13 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     set_error("svm_decomp_train_gram: a trace needs one rank");
     return SVM_ERR_ARG;
   }
+  double Cp, Cn;  // the boxes of the y = +1 / y = -1 rows
+  if (const int rc = svm_class_boxes(&p, &Cp, &Cn)) return rc;
+  if (Cp != Cn && (shrink_cfg(p).on || newton_cfg(p).on)) {
+    set_error("svm_decomp_train_gram: class weights are not supported with %s (unweighted)",
+              shrink_cfg(p).on ? "shrinking" : "the Newton polish (SVM355_DECOMP_NEWTON)");
+    return SVM_ERR_ARG;
+  }
   const Shape sh = shape(n, qws > 0 ? qws : kMaxWS, world);
   if (!sh.ok) {
     set_error("svm_decomp_train_gram: n = %lld is outside the solver's shapes", (long long)n);
@@ -142,10 +152,10 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   }
   const auto t0 = std::chrono::steady_clock::now();
   WorkerTeam team(std::max<int32_t>(1, std::min<int32_t>(resolve_threads(p.n_threads), int32_t(n / 256) + 1)));
-  const double C = p.C, eps = p.eps, tau = p.tau, c_hi = C - eps, c_lo = 0.0 + eps;
+  const double C = p.C, eps = p.eps, tau = p.tau, chp = Cp - eps, chn = Cn - eps, c_lo = 0.0 + eps;
   const double inf = std::numeric_limits<double>::infinity();
-  auto in_high = [&](int32_t yi, double a) { return (yi == 1 && a < c_hi) || (yi == -1 && a > c_lo); };
-  auto in_low = [&](int32_t yi, double a) { return (yi == 1 && a > c_lo) || (yi == -1 && a < c_hi); };
+  auto in_high = [&](int32_t yi, double a) { return (yi == 1 && a < chp) || (yi == -1 && a > c_lo); };
+  auto in_low = [&](int32_t yi, double a) { return (yi == 1 && a > c_lo) || (yi == -1 && a < chn); };
 
   // ---- start: cold (alpha = 0, f = -y: ws_init_kernel) or warm (f = -y + K (alpha y) over the
   // nonzero alphas, ascending, in chunks of kMaxWS columns: decomp.hip's warm start); f of this
@@ -407,13 +417,14 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       const int32_t yh = yw[size_t(ih)], yl = yw[size_t(il)];
       const int s = yh * yl;
       const double eta = 1.0 + 1.0 - 2.0 * K12;
+      const double Ch = yh == 1 ? Cp : Cn, Cl = yl == 1 ? Cp : Cn;
       double U, V;
       if (s == -1) {
         U = std::fmax(0.0, al - ah);
-        V = std::fmin(C, C + al - ah);
+        V = std::fmin(Cl, Ch + al - ah);
       } else {
-        U = std::fmax(0.0, al + ah - C);
-        V = std::fmin(C, al + ah);
+        U = std::fmax(0.0, al + ah - Ch);
+        V = std::fmin(Cl, al + ah);
       }
       if (!(U <= V + 1e-12)) {
         reason = SVM_STOP_INFEASIBLE;
@@ -430,8 +441,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       const double ch = (ah_new - ah) * double(yh);
       const double cl = (al_new - al) * double(yl);
       for (int k = 0; k < m; ++k) ft[size_t(k)] += ch * kh[size_t(k)] + cl * kl[size_t(k)];
-      bool moved_status = bound_status(ah_new, C, eps) != bound_status(ah, C, eps) ||
-                          bound_status(al_new, C, eps) != bound_status(al, C, eps);
+      bool moved_status = bound_status(ah_new, Ch, eps) != bound_status(ah, Ch, eps) ||
+                          bound_status(al_new, Cl, eps) != bound_status(al, Cl, eps);
       a[size_t(ih)] = ah_new;
       a[size_t(il)] = al_new;
       ++it;
@@ -441,13 +452,14 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         const int32_t yh2 = yw[size_t(i2)], yl2 = yw[size_t(j2)];
         const int s2 = yh2 * yl2;
         const double eta2 = 1.0 + 1.0 - 2.0 * K[int64_t(W[size_t(i2)]) * ldk + W[size_t(j2)]];
+        const double Ch2 = yh2 == 1 ? Cp : Cn, Cl2 = yl2 == 1 ? Cp : Cn;
         double U2, V2;
         if (s2 == -1) {
           U2 = std::fmax(0.0, a2l - a2h);
-          V2 = std::fmin(C, C + a2l - a2h);
+          V2 = std::fmin(Cl2, Ch2 + a2l - a2h);
         } else {
-          U2 = std::fmax(0.0, a2l + a2h - C);
-          V2 = std::fmin(C, a2l + a2h);
+          U2 = std::fmax(0.0, a2l + a2h - Ch2);
+          V2 = std::fmin(Cl2, a2l + a2h);
         }
         if (fj2 > fi2 + 2.0 * tau_in && U2 <= V2 + 1e-12 && !(eta2 <= eps)) {
           double al2 = a2l + double(yl2) * (fi2 - fj2) / eta2;
@@ -459,8 +471,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
           const double* Ki2 = K + int64_t(W[size_t(i2)]) * ldk;
           const double* Kj2 = K + int64_t(W[size_t(j2)]) * ldk;
           for (int k = 0; k < m; ++k) ft[size_t(k)] += ch2 * Ki2[W[size_t(k)]] + cl2 * Kj2[W[size_t(k)]];
-          moved_status = moved_status || bound_status(ah2, C, eps) != bound_status(a2h, C, eps) ||
-                         bound_status(al2, C, eps) != bound_status(a2l, C, eps);
+          moved_status = moved_status || bound_status(ah2, Ch2, eps) != bound_status(a2h, Ch2, eps) ||
+                         bound_status(al2, Cl2, eps) != bound_status(a2l, Cl2, eps);
           a[size_t(i2)] = ah2;
           a[size_t(j2)] = al2;
           ++it;

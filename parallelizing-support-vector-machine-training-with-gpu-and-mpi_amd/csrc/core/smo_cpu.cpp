@@ -6,6 +6,10 @@
 //   I_low  = {y=+1, a>eps}   U {y=-1, a<C-eps}, i_low  = argmax f over I_low  (lowest index on ties)
 //   stop when b_low <= b_high + 2*tau, no candidate, infeasible [U,V], eta <= eps, or iterations
 //   exceed max_iter; b = (b_high + b_low)/2.
+// Class weights (svm_params.weight_pos / weight_neg, LIBSVM's -wi): row i's box is [0, C_i] with C_i =
+// C weight_pos for y_i = +1 and C weight_neg for y_i = -1; the sets test a < C_i - eps and the pair
+// clip is  s = -1: U = max(0, al - ah), V = min(C_l, C_h + al - ah);  s = +1: U = max(0, al + ah - C_h),
+// V = min(C_l, al + ah)  -- with equal weights of 1 the reference's expressions, operation for operation.
 // Kernel rows of i_high / i_low are recomputed only when the index changes (main3.cpp:216-232).
 //
 // Opt-in (svm_params.wss = 2, not the reference): second-order selection of the second index
@@ -68,6 +72,8 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
     set_error("svm_smo_train: empty problem");
     return SVM_ERR_EMPTY;
   }
+  double Cp, Cn;  // the boxes of the y = +1 / y = -1 rows
+  if (const int rc = svm_class_boxes(&p, &Cp, &Cn)) return rc;
   const auto t0 = std::chrono::steady_clock::now();
   // Worker count: the requested threads, but at least kMinPerThread elements each (the passes are
   // a few ns per element; below that the fork/join of a pass costs more than it saves).  The
@@ -75,7 +81,7 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
   constexpr int64_t kMinPerThread = 256;
   const int32_t nt = int32_t(std::max<int64_t>(1, std::min<int64_t>(std::max(1, p.n_threads), n / kMinPerThread)));
   WorkerTeam team(nt);
-  const double C = p.C, eps = p.eps, tau = p.tau;
+  const double eps = p.eps, tau = p.tau, chp = Cp - eps, chn = Cn - eps;
   std::vector<double> f(size_t(n), 0.0);
 
   if (!warm) {
@@ -114,8 +120,8 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
       Pick l{-std::numeric_limits<double>::infinity(), n};
       for (int64_t i = lo; i < hi; ++i) {
         const double a = alpha[i], fi = f[size_t(i)];
-        const bool in_high = (y[i] == 1 && a < C - eps) || (y[i] == -1 && a > 0.0 + eps);
-        const bool in_low = (y[i] == 1 && a > 0.0 + eps) || (y[i] == -1 && a < C - eps);
+        const bool in_high = (y[i] == 1 && a < chp) || (y[i] == -1 && a > 0.0 + eps);
+        const bool in_low = (y[i] == 1 && a > 0.0 + eps) || (y[i] == -1 && a < chn);
         if (in_high && fi < h.v) h = {fi, i};
         if (in_low && fi > l.v) l = {fi, i};
       }
@@ -159,7 +165,7 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
         Pick g{std::numeric_limits<double>::infinity(), n};
         for (int64_t t = lo; t < hi; ++t) {
           const double a = alpha[t], ft = f[size_t(t)];
-          const bool in_low = (y[t] == 1 && a > 0.0 + eps) || (y[t] == -1 && a < C - eps);
+          const bool in_low = (y[t] == 1 && a > 0.0 + eps) || (y[t] == -1 && a < chn);
           if (!in_low || !(ft > b_high)) continue;
           const double bb = ft - b_high;
           double at = K11 + 1.0 - 2.0 * Kh[size_t(t)];
@@ -193,13 +199,14 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
     const double K12 = Kh[size_t(i_low_upd)];
     const double eta = K11 + K22 - 2.0 * K12;
     const double ah = alpha[i_high], al = alpha[i_low_upd];
+    const double Ch = y[i_high] == 1 ? Cp : Cn, Cl = y[i_low_upd] == 1 ? Cp : Cn;
     double U, V;
     if (s == -1) {
       U = std::max(0.0, al - ah);
-      V = std::min(C, C + al - ah);
+      V = std::min(Cl, Ch + al - ah);
     } else {
-      U = std::max(0.0, al + ah - C);
-      V = std::min(C, al + ah);
+      U = std::max(0.0, al + ah - Ch);
+      V = std::min(Cl, al + ah);
     }
     if (!(U <= V + 1e-12)) {
       stop = SVM_STOP_INFEASIBLE;

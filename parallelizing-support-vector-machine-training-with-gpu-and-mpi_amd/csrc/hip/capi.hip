@@ -31,6 +31,20 @@ svm_params resolve(const svm_params* p) {
 }  // namespace
 
 namespace svm355 {
+// The solvers without per-class boxes (the pairwise device solvers, the distributed and cascade trainers)
+// refuse class weights that differ from 1 -- none solves the unweighted problem in their place.  SVM_OK
+// when both weights are 1 (or 0, which reads as 1).
+int refuse_class_weights(const svm_params& p, const char* who) {
+  double cp, cn;
+  const int rc = svm_class_boxes(&p, &cp, &cn);
+  if (rc) return rc;
+  if (cp != p.C || cn != p.C) {
+    set_error("%s: class weights (weight_pos = %g, weight_neg = %g) are supported by the decomposition solver on one "
+              "GPU and the CPU solvers only", who, p.weight_pos, p.weight_neg);
+    return SVM_ERR_ARG;
+  }
+  return SVM_OK;
+}
 // The process's first LARGE host-to-device copy sets up the copy-engine path: ~8 ms, paid by whichever
 // copy comes first -- the first fit's 47 MB row upload (profiles/r5_cold_fit_trace.txt: the cold upload
 // 8.0 ms against 0.9 ms, and 1.1 ms after a 32 MB copy at start-up, from pinned or pageable memory
@@ -357,8 +371,9 @@ SVM_API int svmd_smo(void* h, const double* K_d, int64_t ldk, const int32_t* y_d
   SVMD_CTX(h);
   TraceRange tr("svm355:smo");
   const svm_params q = resolve(p);
-  int rc = ctx->begin();
+  int rc = refuse_class_weights(q, "svmd_smo");
   if (rc) return rc;
+  if ((rc = ctx->begin())) return rc;
   rc = run_smo(ctx, K_d, ldk, y_d, n, alpha_d, warm, q, r, trace_host, trace_cap);
   if (rc) return rc;
   if (r) {
@@ -375,8 +390,9 @@ SVM_API int svmd_smo_multi(void* h, const double* K_d, int64_t ldk, const int32_
   SVMD_CTX(h);
   TraceRange tr("svm355:smo_multi");
   const svm_params q = resolve(p);
-  int rc = ctx->begin();
+  int rc = refuse_class_weights(q, "svmd_smo_multi");
   if (rc) return rc;
+  if ((rc = ctx->begin())) return rc;
   rc = run_smo_multi(ctx, K_d, ldk, Y_d, n, nclass, A_d, q, r, batched);
   if (rc) return rc;
   if (r) {
@@ -505,6 +521,7 @@ SVM_API int svmd_train(void* h, const double* X_d, const double* sqn_d, int64_t 
                        const int32_t* y_d, double* alpha_d, int32_t warm, const svm_params* p,
                        svm_result* r, double* K_d, int64_t ldk, svmd_timing* timing) {
   SVMD_CTX(h);
+  if (const int rc = refuse_class_weights(resolve(p), "svmd_train")) return rc;
   return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, resolve(p), r, K_d, ldk, timing, nullptr,
                     nullptr, 0, 1, nullptr);
 }
@@ -514,6 +531,7 @@ SVM_API int svmd_train_q(void* h, const double* X_d, const double* sqn_d, int64_
                          double* K_d, int64_t ldk, svmd_timing* timing, const double* mn_h, const double* mx_h,
                          int64_t d, int32_t gram_mode, int32_t* gram_used) {
   SVMD_CTX(h);
+  if (const int rc = refuse_class_weights(resolve(p), "svmd_train_q")) return rc;
   return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, resolve(p), r, K_d, ldk, timing, mn_h, mx_h,
                     d, gram_mode, gram_used);
 }
@@ -533,9 +551,10 @@ SVM_API int svmd_train_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, co
     return SVM_ERR_ARG;
   }
   const svm_params q = resolve(p);
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = ctx->begin();
+  int rc = refuse_class_weights(q, "svmd_train_u8");
   if (rc) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = ctx->begin())) return rc;
   QuantPlan P;
   if (!plan_quant(mn_h, mx_h, d, &P)) return ctx->end();
   bool used = false;
@@ -630,8 +649,9 @@ SVM_API int svmd_train_rows(void* h, const double* X_d, const double* sqn_d, int
                             int32_t* gram_used, int64_t* trace_host, int64_t trace_cap) {
   SVMD_CTX(h);
   const svm_params q = resolve(p);
-  int rc = ctx->begin();
+  int rc = refuse_class_weights(q, "svmd_train_rows");
   if (rc) return rc;
+  if ((rc = ctx->begin())) return rc;
   QuantPlan P;
   if (gram_mode != 1 && mn_h && mx_h) plan_quant(mn_h, mx_h, d, &P);
   if (cache_bytes <= 0) {

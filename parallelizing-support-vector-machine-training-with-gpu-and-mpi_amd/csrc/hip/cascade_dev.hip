@@ -1049,6 +1049,7 @@ SVM_API svm_cascade_out* svmd_cascade_group_fit(void* h, const void* X, int32_t 
     set_error("svmd_cascade_group_fit: bad arguments");
     return nullptr;
   }
+  if (c && refuse_class_weights(c->params, "svmd_cascade_group_fit")) return nullptr;
   std::lock_guard<std::mutex> lk(g->mu);
   if (g->broken) {
     set_error("svmd_cascade_group_fit: the group's communicators were aborted by an earlier failure; create a new group");
@@ -1148,6 +1149,7 @@ static int group_decomp(void* h, const void* X, bool u8, const int32_t* y, int64
     p = *pp;
   else
     svm_default_params(&p);
+  if (const int rc = refuse_class_weights(p, "svmd_cascade_group_decomp")) return rc;
   const int P = g->world;
   auto token = std::make_shared<AbortToken>();
   const WaitPolicy wp{token, g->timeout_s};
@@ -1271,6 +1273,7 @@ static int rank_decomp(void* h, const void* X, bool u8, const int32_t* y, int64_
     p = *pp;
   else
     svm_default_params(&p);
+  if (const int rc = refuse_class_weights(p, "svmd_cascade_rank_decomp")) return rc;
   try {
     (void)hipSetDevice(pr->device);
     pr->set_policy(WaitPolicy{nullptr, pr->timeout_s});
@@ -1415,6 +1418,7 @@ SVM_API svm_cascade_out* svmd_cascade_rank_fit(void* h, const void* X, int32_t u
     set_error("svmd_cascade_rank_fit: bad arguments");
     return nullptr;
   }
+  if (c && refuse_class_weights(c->params, "svmd_cascade_rank_fit")) return nullptr;
   if (p->broken) {
     set_error("svmd_cascade_rank_fit: the communicator was aborted by an earlier failure");
     return nullptr;

@@ -137,6 +137,10 @@ struct DeviceCtx {
     return SVM_ERR_ARG;                                          \
   }
 
+// SVM_ERR_ARG (with the error set) when p's class weights differ from 1: the check of every solver
+// without per-class boxes (capi.hip).
+int refuse_class_weights(const svm_params& p, const char* who);
+
 // Load every translation unit's code object on s (hip_util.h SVMD_TU_WARM): svmd_create.
 int tu_warm_all(hipStream_t s);
 

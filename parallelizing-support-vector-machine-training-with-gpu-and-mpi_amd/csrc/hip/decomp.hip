@@ -56,7 +56,7 @@ namespace {
 __global__ __launch_bounds__(kSelNT) void ws_select_kernel(const double* __restrict__ f,
                                                            const double* __restrict__ alpha,
                                                            const int32_t* __restrict__ y, int64_t lo, int64_t nloc,
-                                                           int64_t per, int T, double C, double eps,
+                                                           int64_t per, int T, double C, double Cn, double eps,
                                                            CandRec* __restrict__ cand_h, CandRec* __restrict__ cand_l,
                                                            const DecompCtl* __restrict__ ctl,
                                                            const int32_t* __restrict__ act,
@@ -67,7 +67,8 @@ __global__ __launch_bounds__(kSelNT) void ws_select_kernel(const double* __restr
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int64_t b0 = act ? int64_t(boff[blockIdx.x]) : int64_t(blockIdx.x) * per;
   const int64_t b1 = act ? int64_t(boff[blockIdx.x + 1]) : std::min<int64_t>(nloc, b0 + per);
-  const double c_hi = C - eps, c_lo = 0.0 + eps, inf = __builtin_inf();
+  // class weights: C is the box of the y = +1 rows, Cn of the y = -1 rows (equal without weights)
+  const double c_hi = C - eps, c_hin = Cn - eps, c_lo = 0.0 + eps, inf = __builtin_inf();
   double fh[kSelE], fl[kSelE];
   uint32_t gi[kSelE];  // global ids, ascending in e
 #pragma unroll
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(kSelNT) void ws_select_kernel(const double* __restr
       const double a = alpha[lo + i], fi = f[i];
       const int32_t yi = y[lo + i];
       if ((yi == 1 && a < c_hi) || (yi == -1 && a > c_lo)) fh[e] = fi;
-      if ((yi == 1 && a > c_lo) || (yi == -1 && a < c_hi)) fl[e] = fi;
+      if ((yi == 1 && a > c_lo) || (yi == -1 && a < c_hin)) fl[e] = fi;
     }
   }
   // Every wave takes its own T best of each side with wave reductions only (no barrier per pick), then
@@ -149,7 +150,8 @@ __global__ __launch_bounds__(kSelNT) void ws_select_kernel(const double* __restr
 __global__ __launch_bounds__(kSelNT) void ws_select_wide_kernel(const double* __restrict__ f,
                                                                 const double* __restrict__ alpha,
                                                                 const int32_t* __restrict__ y, int64_t lo,
-                                                                int64_t nloc, int64_t per, int T, double C, double eps,
+                                                                int64_t nloc, int64_t per, int T, double C, double Cn,
+                                                                double eps,
                                                                 CandRec* __restrict__ cand_h,
                                                                 CandRec* __restrict__ cand_l,
                                                                 const DecompCtl* __restrict__ ctl,
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(kSelNT) void ws_select_wide_kernel(const double* __
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int64_t b0 = act ? int64_t(boff[blockIdx.x]) : int64_t(blockIdx.x) * per;
   const int64_t b1 = act ? int64_t(boff[blockIdx.x + 1]) : std::min<int64_t>(nloc, b0 + per);
-  const double c_hi = C - eps, c_lo = 0.0 + eps, inf = __builtin_inf();
+  const double c_hi = C - eps, c_hin = Cn - eps, c_lo = 0.0 + eps, inf = __builtin_inf();
   __shared__ double wv[2][NW];
   __shared__ uint32_t wi[2][NW];
   VI ph{-inf, 0}, pl{inf, 0};  // the previous round's block picks (round 0: nothing excluded)
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(kSelNT) void ws_select_wide_kernel(const double* __
       const int32_t yi = y[lo + i];
       const uint32_t gi = uint32_t(lo + i);
       const bool up = (yi == 1 && a < c_hi) || (yi == -1 && a > c_lo);
-      const bool dn = (yi == 1 && a > c_lo) || (yi == -1 && a < c_hi);
+      const bool dn = (yi == 1 && a > c_lo) || (yi == -1 && a < c_hin);
       const bool eh = k == 0 || fi > ph.v || (fi == ph.v && gi > ph.i);
       const bool el = k == 0 || fi < pl.v || (fi == pl.v && gi > pl.i);
       if (up && eh && fi < mn.v) mn = VI{fi, gi};
@@ -1015,6 +1017,7 @@ struct Solve {
   const int32_t* y = nullptr;
   double* alpha = nullptr;
   svm_params p{};
+  double Cp = 0.0, Cn = 0.0;  // the boxes of the y = +1 / y = -1 rows (svm_class_boxes)
   DecompShape sh;
   int world = 1, rank = 0;
   // all rows; this GPU's selection blocks, rows [lo, lo + nloc) and candidate records; warm-start chunks
@@ -1183,8 +1186,9 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
               "world <= 64)", (long long)n, (long long)sh.L, kMaxWS);
     return SVM_ERR_ARG;
   }
-  const int rc = read_knobs(sh, &S.k);
+  int rc = read_knobs(sh, &S.k);
   if (rc) return rc;
+  if ((rc = svm_class_boxes(&p, &S.Cp, &S.Cn))) return rc;
   S.ctx = ctx;
   S.s = ctx->stream;
   S.R = R;
@@ -1209,7 +1213,24 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
   const NewtonCfg nwc = newton_cfg(p);
   S.nwd = NwDev{nwc.on ? 1 : 0, nwc.every, nwc.per_solve, nwc.repeat, nwc.max_free, 0, nwc.frac};
-  S.inner = InnerVariant{S.k.inner_nt, S.k.prof, S.k.wss2, S.k.dp, S.k.j2s, nwc.on};
+  S.inner = InnerVariant{S.k.inner_nt, S.k.prof, S.k.wss2, S.k.dp, S.k.j2s, nwc.on, S.Cp != S.Cn};
+  if (S.inner.weighted) {
+    // class weights: what is unweighted refuses them -- it never solves another problem in silence
+    const char* what = world > 1     ? "the distributed solve (world > 1)"
+                       : S.shc.on    ? "shrinking"
+                       : nwc.on      ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                     : nullptr;
+    if (what) {
+      set_error("decomposition SMO: class weights are not supported with %s", what);
+      return SVM_ERR_ARG;
+    }
+    if (!ws_inner_weighted_built(S.inner)) {
+      set_error("decomposition SMO: the weighted inner solve is not built for SVM355_DECOMP_NT=%d SVM355_DECOMP_WSS=%d "
+                "SVM355_DECOMP_PROF=%d (built: NT=256 with WSS=1, 2 or 3, PROF=0)",
+                S.k.inner_nt, S.k.j2s ? 4 : S.k.dp ? 3 : S.k.wss2 ? 2 : 1, S.k.prof ? 1 : 0);
+      return SVM_ERR_ARG;
+    }
+  }
   S.allgather = &o.allgather;
   S.tr = tr;
   return SVM_OK;
@@ -1504,7 +1525,7 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
   const int32_t* act = packed ? w.act[ps.pk] : nullptr;
   if (NBr > 0)
     hipLaunchKernelGGL(S.wide_select ? ws_select_wide_kernel : ws_select_kernel, dim3(unsigned(NBr)), dim3(kSelNT), 0, s,
-                       w.f, S.alpha, S.y, lo, nloc, S.sh.per, T, p.C, p.eps, w.own, w.own + NBr * T, w.ctl, act,
+                       w.f, S.alpha, S.y, lo, nloc, S.sh.per, T, S.Cp, S.Cn, p.eps, w.own, w.own + NBr * T, w.ctl, act,
                        packed ? w.boff[ps.pk] : nullptr, w.shr);
   SVMD_LAUNCH_CHECK();
   if ((rc = solo.end(0))) return rc;
@@ -1515,10 +1536,11 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
                      p.tau, S.k.tau_frac, int64_t(p.max_iter), w.W, w.Wf, w.ctl, w.mcount, pub);
   SVMD_LAUNCH_CHECK();
   if ((rc = enqueue_kww(S))) return rc;
-  launch_ws_inner(s, S.inner,
-                  InnerArgs{w.Kw, kLdw, w.W, w.ctl, S.y, S.alpha, w.Wf, p.C, p.eps, w.cols, w.coef, w.mcount, S.hs, pub,
-                            packed ? w.pos_of : nullptr, lo, nloc, packed ? w.cdiag : nullptr, w.gAw, w.Wf, w.nAmat,
-                            S.nwd});
+  if ((rc = launch_ws_inner(s, S.inner,
+                            InnerArgs{w.Kw, kLdw, w.W, w.ctl, S.y, S.alpha, w.Wf, S.Cp, p.eps, w.cols, w.coef, w.mcount,
+                                      S.hs, pub, packed ? w.pos_of : nullptr, lo, nloc, packed ? w.cdiag : nullptr,
+                                      w.gAw, w.Wf, w.nAmat, S.nwd, S.Cn})))
+    return rc;
   SVMD_LAUNCH_CHECK();
   if ((rc = f_update(S, ps, w.cols, w.coef, w.mcount, index < 4))) return rc;
   ++ps.o_dev;  // this outer iteration's count once it has run
@@ -1869,9 +1891,11 @@ int train_decomp(DeviceCtx* ctx, const void* X_d, bool is_u8, int64_t n, int64_t
     p = *pp;
   else
     svm_default_params(&p);
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = ctx->begin();
+  double cp, cn;  // the class weights' range check, before anything runs
+  int rc = svm_class_boxes(&p, &cp, &cn);
   if (rc) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = ctx->begin())) return rc;
   bool used = false;
   double prep = 0.0;
   rc = is_u8 ? decomp_fit_u8(ctx, static_cast<const uint8_t*>(X_d), n, d, mn_h, mx_h, y_d, alpha_d, p, q, r, stats,

@@ -67,10 +67,11 @@ struct CandRec {
 
 // Which ws_inner_kernel instantiation an inner solve runs: nt threads (64 / 128 / 256 / 512 with
 // 1024 / nt points each; 65: one wave x 6 points), the profiling build, second-order j (wss2), the second
-// pair per iteration (dp), its j by second-order gain (j2s), the Newton polish compiled in (newton).
+// pair per iteration (dp), its j by second-order gain (j2s), the Newton polish compiled in (newton), per-class
+// boxes (weighted: class weights that differ; built for some shapes and rules only, ws_inner_weighted_built).
 struct InnerVariant {
   int nt = 256;
-  bool prof = false, wss2 = true, dp = true, j2s = false, newton = false;
+  bool prof = false, wss2 = true, dp = true, j2s = false, newton = false, weighted = false;
 };
 
 // ws_inner_kernel's arguments, in its parameter order.  (The control blocks above are file-local types, as
@@ -83,7 +84,7 @@ struct InnerArgs {
   const int32_t* y;
   double* alpha;
   const double* Wf;
-  double C, eps;
+  double C, eps;  // C: the box of the y = +1 rows (every row's without class weights)
   int32_t* cols;
   double* coef;
   int32_t* mcount;
@@ -94,10 +95,15 @@ struct InnerArgs {
   int32_t* cdiag;
   double *gAw, *gFw, *nAmat;
   NwDev nw;
+  double Cn;  // the box of the y = -1 rows (read by the weighted variants only)
 };
 
-// One inner solve on stream s (one workgroup; the caller checks the launch).
-void launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a);
+// Whether the weighted inner solve is built for v's workgroup shape and selection rule: 256 threads x 4
+// points with SVM355_DECOMP_WSS = 1, 2 or 3, no profiling build, no Newton polish.
+bool ws_inner_weighted_built(const InnerVariant& v);
+// One inner solve on stream s (one workgroup; the caller checks the launch).  SVM_ERR_ARG, with nothing
+// launched, for a weighted variant that is not built -- never the unweighted kernel in its place.
+int launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a);
 // ws_newton_probe_kernel (one 256-thread workgroup): one Newton step on a given working set.
 void launch_ws_newton_probe(hipStream_t s, int m, const double* Kw, int64_t ldw, const int32_t* y, double* gA, double* gF,
                             double* Amat, double C, double eps, int max_free, int32_t* code_out, int64_t* prof);

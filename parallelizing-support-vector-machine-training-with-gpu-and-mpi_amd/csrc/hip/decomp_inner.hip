@@ -430,7 +430,12 @@ __global__ __launch_bounds__(256) void ws_newton_probe_kernel(int m, const doubl
 //            iterations of the chain at 60k for ~10 % more work per iteration.
 //   J2S (with DP): j2 by the second-order gain of row i2 instead of the first-order j (row i2 loads
 //            beside row i before the gains; both gains reduce in the same wave / barrier / fold).
-template <int NT, int PER, bool PROF = false, bool W2 = false, bool DP = false, bool J2S = false, bool NWT = false>
+//   CW (class weights): C is the box of the y = +1 points and Cn of the y = -1 points -- an element's own
+//            upper bound in the set membership of every selection, and the pair's two boxes in the clip
+//            of both pairs (smo_cpu.cpp has the expressions).  Without CW, Cn is not read and the code is
+//            the unweighted kernel's.  Not built with the Newton polish (newton_wg is unweighted).
+template <int NT, int PER, bool PROF = false, bool W2 = false, bool DP = false, bool J2S = false, bool NWT = false,
+          bool CW = false>
 __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__ Kw, int64_t ldw,
                                                       const int32_t* __restrict__ W, DecompCtl* __restrict__ ctl,
                                                       const int32_t* __restrict__ y, double* __restrict__ alpha,
@@ -440,7 +445,8 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
                                                       DecompCtl* __restrict__ pub, const int32_t* __restrict__ pos_of,
                                                       int64_t lo, int64_t nloc, int32_t* __restrict__ cdiag,
                                                       double* __restrict__ gAw, double* __restrict__ gFw,
-                                                      double* __restrict__ nAmat, NwDev nw) {
+                                                      double* __restrict__ nAmat, NwDev nw, double Cn) {
+  static_assert(!(CW && NWT), "the Newton polish is unweighted");
   if (ctl->stop != SVM_STOP_RUNNING) return;
   const int m = ctl->m;
   const double tau_in = ctl->tau_in;
@@ -477,6 +483,21 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
     ft[e] = valid ? Wf[k] : 0.0;
   }
   const double c_hi = C - eps, c_lo = 0.0 + eps, inf = __builtin_inf();
+  const double c_hin = CW ? Cn - eps : c_hi;  // CW: c_hi is the y = +1 points' bound, c_hin the y = -1 points'
+  // element e's upper bound (padding has neither label and is in neither set)
+  auto chi = [&](int e) {
+    if constexpr (CW)
+      return yp[e] ? c_hi : c_hin;
+    else
+      return c_hi;
+  };
+  // the box of a point of W by its label
+  auto box = [&](int32_t yk) {
+    if constexpr (CW)
+      return yk == 1 ? C : Cn;
+    else
+      return C;
+  };
   int64_t it = 0;
   int32_t reason = SVM_STOP_CONVERGED;
   // the Newton polish (decomp_newton.h): chain iterations with no bound-status change, starting at `every`
@@ -518,7 +539,7 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
     uint32_t hi = kSentinel, li = kSentinel;
 #pragma unroll
     for (int e = 0; e < PER; ++e) {  // ascending position within a thread: strict compares keep the lowest
-      const bool below = a[e] < c_hi, above = a[e] > c_lo;
+      const bool below = a[e] < chi(e), above = a[e] > c_lo;
       const bool in_high = (yp[e] && below) || (yn[e] && above);
       const bool in_low = (yp[e] && above) || (yn[e] && below);
       const bool ch = in_high && ft[e] < hv, cl = in_low && ft[e] > lv;
@@ -686,7 +707,7 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
       int ge = 0;  // the element of the thread's best gain: its alpha, f and K(i, j) are read by the winner
 #pragma unroll
       for (int e = 0; e < PER; ++e) {
-        const bool below = a[e] < c_hi, above = a[e] > c_lo;
+        const bool below = a[e] < chi(e), above = a[e] > c_lo;
         const bool in_low = (yp[e] && above) || (yn[e] && below);
         const double bb = ft[e] - bh;
         double at = 2.0 - 2.0 * kh[e];
@@ -704,7 +725,7 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
       if constexpr (J2S) {  // the same gain over I_low points above f(i2), on row i2 (f2h = inf: none)
 #pragma unroll
         for (int e = 0; e < PER; ++e) {
-          const bool below = a[e] < c_hi, above = a[e] > c_lo;
+          const bool below = a[e] < chi(e), above = a[e] > c_lo;
           const bool in_low = (yp[e] && above) || (yn[e] && below);
           const double bb = ft[e] - f2h;
           const double k2 = pos(e) < m ? ((e & 1) ? r2h[e >> 1].y : r2h[e >> 1].x) : 0.0;
@@ -831,13 +852,14 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
     const double K11 = 1.0, K22 = 1.0;  // the Gram's unit diagonal
     const int s = yh * yl;
     const double eta = K11 + K22 - 2.0 * K12;
+    const double Ch = box(yh), Cl = box(yl);
     double U, V;
     if (s == -1) {
       U = fmax(0.0, al - ah);
-      V = fmin(C, C + al - ah);
+      V = fmin(Cl, Ch + al - ah);
     } else {
-      U = fmax(0.0, al + ah - C);
-      V = fmin(C, al + ah);
+      U = fmax(0.0, al + ah - Ch);
+      V = fmin(Cl, al + ah);
     }
     if (!(U <= V + 1e-12)) {
       reason = SVM_STOP_INFEASIBLE;
@@ -881,13 +903,14 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
         const int32_t yh2 = sy[i2], yl2 = sy[j2];
         const int s2 = yh2 * yl2;
         const double eta2 = K11 + K22 - 2.0 * K2_12;
+        const double Ch2 = box(yh2), Cl2 = box(yl2);
         double U2, V2;
         if (s2 == -1) {
           U2 = fmax(0.0, a2l - a2h);
-          V2 = fmin(C, C + a2l - a2h);
+          V2 = fmin(Cl2, Ch2 + a2l - a2h);
         } else {
-          U2 = fmax(0.0, a2l + a2h - C);
-          V2 = fmin(C, a2l + a2h);
+          U2 = fmax(0.0, a2l + a2h - Ch2);
+          V2 = fmin(Cl2, a2l + a2h);
         }
         if (fj2 > fi2 + 2.0 * tau_in && U2 <= V2 + 1e-12 && !(eta2 <= eps)) {  // still violating, feasible
           double al2 = a2l + double(yl2) * (fi2 - fj2) / eta2;
@@ -980,7 +1003,7 @@ template <int NT, int PER, bool PR, bool S2>
 void launch_rule(hipStream_t s, const InnerVariant& v, const InnerArgs& a) {
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(1), dim3(NT), 0, s, a.Kw, a.ldw, a.W, a.ctl, a.y, a.alpha, a.Wf, a.C, a.eps, a.cols,
-                       a.coef, a.mcount, a.hs, a.pub, a.pos_of, a.lo, a.nloc, a.cdiag, a.gAw, a.gFw, a.nAmat, a.nw);
+                       a.coef, a.mcount, a.hs, a.pub, a.pos_of, a.lo, a.nloc, a.cdiag, a.gAw, a.gFw, a.nAmat, a.nw, a.Cn);
   };
   if (v.j2s && S2)
     go(ws_inner_kernel<NT, PER, PR, S2, S2, S2>);
@@ -1004,9 +1027,34 @@ void launch_shape(hipStream_t s, const InnerVariant& v, const InnerArgs& a) {
     launch_rule<NT, PER, false, false>(s, v, a);
 }
 
+// The weighted instantiations (per-class boxes): 256 x 4 under the second-order rule with the second pair
+// (the default), the second-order rule alone and the first-order rule.
+void launch_weighted(hipStream_t s, const InnerVariant& v, const InnerArgs& a) {
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(256), 0, s, a.Kw, a.ldw, a.W, a.ctl, a.y, a.alpha, a.Wf, a.C, a.eps, a.cols,
+                       a.coef, a.mcount, a.hs, a.pub, a.pos_of, a.lo, a.nloc, a.cdiag, a.gAw, a.gFw, a.nAmat, a.nw, a.Cn);
+  };
+  if (v.wss2 && v.dp)
+    go(ws_inner_kernel<256, 4, false, true, true, false, false, true>);
+  else if (v.wss2)
+    go(ws_inner_kernel<256, 4, false, true, false, false, false, true>);
+  else
+    go(ws_inner_kernel<256, 4, false, false, false, false, false, true>);
+}
+
 }  // namespace
 
-void launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a) {
+bool ws_inner_weighted_built(const InnerVariant& v) { return v.nt == 256 && !v.prof && !v.j2s && !v.newton; }
+
+int launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a) {
+  if (v.weighted) {
+    if (!ws_inner_weighted_built(v)) {
+      set_error("decomposition SMO: the weighted inner solve is not built for this variant");
+      return SVM_ERR_ARG;
+    }
+    launch_weighted(s, v, a);
+    return SVM_OK;
+  }
   if (v.nt == 65)  // one wave x 6 points (a working set of <= 384)
     launch_shape<64, 6>(s, v, a);
   else if (v.nt == 64)
@@ -1017,6 +1065,7 @@ void launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a) {
     launch_shape<256, 4>(s, v, a);
   else
     launch_shape<512, 2>(s, v, a);
+  return SVM_OK;
 }
 
 void launch_ws_newton_probe(hipStream_t s, int m, const double* Kw, int64_t ldw, const int32_t* y, double* gA, double* gF,

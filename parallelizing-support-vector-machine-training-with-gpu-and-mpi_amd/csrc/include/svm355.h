@@ -53,6 +53,9 @@ typedef struct svm_params {
   int32_t wss;       // working-set selection: 0 / 1 = first order (reference), 2 = second-order j
   int32_t shrink;    // decomposition solver shrinking: 0 = default (off), -1 = off, k > 0 = every k outer
                      // iterations (decomp_shrink.h)
+  double weight_pos; // class weights: row i's box is [0, C * weight_pos] where y_i = +1 and
+  double weight_neg; //   [0, C * weight_neg] where y_i = -1 (LIBSVM's -wi); 0 reads as 1 (a zero-filled
+                     //   struct from an older caller), negative or non-finite values are SVM_ERR_ARG
 } svm_params;
 
 typedef struct svm_result {
@@ -69,6 +72,9 @@ typedef struct svm_result {
 SVM_API const char* svm_last_error(void);
 SVM_API void svm_default_params(svm_params* p);
 SVM_API const char* svm_stop_message(int32_t reason);
+// The two classes' box constraints C * weight_pos / C * weight_neg of p (a weight of 0 reads as 1);
+// SVM_ERR_ARG for a negative or non-finite weight.  Equal weights of 1 give C itself, bit for bit.
+SVM_API int svm_class_boxes(const svm_params* p, double* c_pos, double* c_neg);
 
 // ---------------------------------------------------------------- data I/O (L0)
 // Loads a CSV with a header row; the last column is the integer label.

@@ -111,14 +111,26 @@ class OneVsRestSVC:
     def __init__(self, C: float = 10.0, gamma: float = 0.00125, tol: float = 1e-5, eps: float = 1e-12,
                  sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
                  gram: str = "auto", concurrent_solves: Optional[int] = None, solver: str = "auto",
-                 wss: str = "first"):
+                 wss: str = "first", class_weight=None):
         """``solver`` (GPU): "auto" = "decomp" unless ``wss="second"`` or a ``gram`` is forced, then
         "batched".  "batched" runs all pairwise class solves in ONE kernel launch over the shared Gram, a team
         of workgroups per XCD pulling classes from a queue; "streams" runs one persistent solve per
         class on ``concurrent_solves`` streams (default 8).  Results are identical either way.  "decomp":
         the working-set decomposition solver per class with no Gram, ``concurrent_solves`` classes at a time
         (default: all, or 2 past 192 MiB of pixel rows, where the solves are bound by passes over the rows).
-        ``wss="second"``: the opt-in second-order working-set selection (as ``SVC(wss="second")``) in every class solve."""
+        ``wss="second"``: the opt-in second-order working-set selection (as ``SVC(wss="second")``) in every class solve.
+        ``class_weight="balanced"``: every class solve weighs its two sides by n / (2 n_c), as
+        ``SVC(class_weight="balanced")`` on that class's labels (``class_weight_``: the resolved weights per
+        class); on the CPU and with ``solver="decomp"`` (what "auto" then resolves to on a GPU)."""
+        if class_weight not in (None, "balanced"):
+            raise ValueError("class_weight must be None or 'balanced'")
+        if class_weight is not None and solver in ("batched", "streams"):
+            raise ValueError(f"class_weight is not supported by solver={solver!r} (the GPU pairwise solvers are "
+                             "unweighted): use solver='decomp' or device='cpu'")
+        if class_weight is not None and solver == "auto" and (wss == "second" or gram != "auto"):
+            raise ValueError("class_weight is not supported with wss='second' or a forced gram (they route to the "
+                             "unweighted GPU pairwise solvers)")
+        self.class_weight = class_weight
         if solver not in ("auto", "batched", "streams", "decomp"):
             raise ValueError("solver must be auto, batched, streams or decomp")
         if solver == "decomp" and wss == "second":
@@ -164,7 +176,15 @@ class OneVsRestSVC:
         return self
 
     def _ys(self, labels):
-        return [np.where(labels == c, 1, -1).astype(np.int32) for c in self.classes_]
+        ys = [np.where(labels == c, 1, -1).astype(np.int32) for c in self.classes_]
+        # the class solves' parameters: the resolved class weights of each one-vs-rest problem
+        from ..utils.data import resolve_class_weight
+
+        self._class_params = [self.params.replace(**dict(zip(("weight_pos", "weight_neg"),
+                                                             resolve_class_weight(self.class_weight, y))))
+                              for y in ys]
+        self.class_weight_ = [{1: p.weight_pos, -1: p.weight_neg} for p in self._class_params]
+        return ys
 
     def _mine(self, k: int) -> bool:
         t = self._transport
@@ -204,7 +224,7 @@ class OneVsRestSVC:
         for k, y in enumerate(ys):
             if not self._mine(k):
                 continue
-            a, r, _ = C.smo_train_gram(K, y, self.params)
+            a, r, _ = C.smo_train_gram(K, y, self._class_params[k])
             alphas[k], bs[k], iters[k], stops[k] = a, r.b, r.iterations, r.stop_reason
         alphas, bs, iters, stops = self._combine(alphas, bs, iters, stops)
         Y = np.stack(ys, 0)
@@ -221,6 +241,8 @@ class OneVsRestSVC:
         device = torch.device(self._dev())
         if self.solver == "decomp" or (self.solver == "auto" and self.params.wss == 1 and self.gram == "auto"):
             return self._fit_cuda_decomp(X, labels, device)
+        if self.class_weight is not None:
+            raise ValueError("class_weight is not supported by the GPU pairwise solvers (batched / streams)")
         t0 = time.perf_counter()
         d = X.shape[1]
         Xu = K = None
@@ -350,7 +372,7 @@ class OneVsRestSVC:
             ctx = D.DeviceContext.get(device)
             N.check(ctx.lib.svmd_set_ccache_frac(ctx.handle, frac), "svmd_set_ccache_frac")
             with torch.cuda.stream(s):
-                out = D.train_decomp(rows, ys_d[k], alphas[k], self.params, mn_h, mx_h)
+                out = D.train_decomp(rows, ys_d[k], alphas[k], self._class_params[k], mn_h, mx_h)
             s.synchronize()
             if out is None:
                 raise N.NativeError(f"class {self.classes_[k]}: the decomposition solver declined these rows "

@@ -25,7 +25,7 @@ from typing import Optional
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
-from ..utils.data import MinMaxScaler, check_finite_bounds, check_warm_start
+from ..utils.data import MinMaxScaler, check_finite_bounds, check_warm_start, resolve_class_weight
 
 
 def _resolve_device(device: str) -> str:
@@ -44,7 +44,8 @@ class SVC:
     def __init__(self, C: float = 10.0, gamma: float = 0.00125, tol: float = 1e-5, eps: float = 1e-12,
                  sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
                  scale: bool = True, zero_is_positive: bool = False, gram: str = "auto", kcache: str = "auto",
-                 wss: str = "first", solver: str = "auto", working_set: int = 1024, shrinking=False):
+                 wss: str = "first", solver: str = "auto", working_set: int = 1024, shrinking=False,
+                 class_weight=None):
         if wss not in ("first", "second"):
             raise ValueError("wss must be 'first' (the reference's selection) or 'second'")
         if solver not in ("auto", "smo", "decomp"):
@@ -53,6 +54,12 @@ class SVC:
         self.params = SVMParams(C=C, gamma=gamma, tau=tol, eps=eps, sv_tol=sv_tol, max_iter=max_iter,
                                 n_threads=n_threads if n_threads > 0 else default_threads(),
                                 wss=2 if wss == "second" else 1, shrinking=shrinking)
+        # class weights (scikit-learn's class_weight, LIBSVM's -wi): None, "balanced" (n / (2 n_c), resolved
+        # per fit from the labels) or {1: w_pos, -1: w_neg}; row i's box is [0, C * w(y_i)].  The CPU oracle
+        # and the GPU decomposition solver take them; the pairwise GPU solver, shrinking and the knobs that
+        # route to the pairwise solver (gram=, kcache=, wss="second") raise with them.
+        resolve_class_weight(class_weight)  # the option's form; the weights themselves per fit
+        self.class_weight = class_weight
         self.device = device
         self.scale = scale
         self.zero_is_positive = zero_is_positive
@@ -82,8 +89,13 @@ class SVC:
             raise ValueError("X must be (n, d) and y (n,)")
         if not np.all(np.abs(y) == 1):
             raise ValueError("labels must be +1/-1 (use svm355.utils.data.one_vs_rest)")
+        wp, wn = resolve_class_weight(self.class_weight, y)
+        self.params = self.params.replace(weight_pos=wp, weight_neg=wn)
+        self.class_weight_ = {1: wp, -1: wn}
+        if self.params.weighted:
+            self._check_weighted(dev)
         if alpha0 is not None:
-            alpha0 = check_warm_start(alpha0, y, self.params.C)
+            alpha0 = check_warm_start(alpha0, y, self.params.box(y) if self.params.weighted else self.params.C)
         t0 = time.perf_counter()
         if dev == "cpu":
             self._fit_cpu(X, y, alpha0)
@@ -91,6 +103,21 @@ class SVC:
             self._fit_cuda(X, y, alpha0, dev)
         self.fit_time_ = time.perf_counter() - t0
         return self
+
+    def _check_weighted(self, dev: str) -> None:
+        """Class weights run on the CPU oracle and on the GPU decomposition solver (no shrinking); everything
+        else raises here, before any device work."""
+        p = self.params
+        if p._shrink_code() > 0:
+            p.refuse_weights("shrinking")
+        if dev == "cpu":
+            return
+        if self.solver == "smo":
+            p.refuse_weights("the GPU pairwise solver (solver='smo')")
+        for name, on in (("wss='second'", p.wss == 2), (f"gram={self.gram!r}", self.gram != "auto"),
+                         (f"kcache={self.kcache!r}", self.kcache != "auto"), ("scale=False", not self.scale)):
+            if on:
+                p.refuse_weights(f"{name} (the GPU pairwise solver)")
 
     def _finish(self, alpha: np.ndarray, y: np.ndarray, res) -> None:
         self.alpha_ = alpha
@@ -132,6 +159,7 @@ class SVC:
         # selection, a forced Gram path or the row cache)
         decomp = self.solver == "decomp" or (self.solver == "auto" and self.params.wss != 2 and self.gram == "auto"
                                              and self.kcache == "auto")
+        weighted = self.params.weighted  # then the decomposition or an error: never the pairwise solver
         if decomp:
             if not self.scale:
                 if self.solver == "decomp":
@@ -176,6 +204,9 @@ class SVC:
                                  "not fit the device")
         if out is not None:
             res, tm = out
+        elif weighted:
+            self.params.refuse_weights("the GPU pairwise solver, which this fit falls back to (the decomposition "
+                                       "solver does not cover these rows)")
         else:  # the pairwise solver (also solver="auto" when the decomposition's workspace does not fit)
             res, tm = D.train(Xd, sqn, yd, alpha, self.params, warm=alpha0 is not None, mn=mn, mx=mx, gram=self.gram,
                               kcache=self.kcache)
@@ -327,7 +358,10 @@ class SVC:
         m = load_model(directory)
         p = m["params"]
         svc = cls(C=p.C, gamma=p.gamma, tol=p.tau, eps=p.eps, sv_tol=p.sv_tol, max_iter=p.max_iter, device=device,
-                  scale=m["scaler"] is not None)
+                  scale=m["scaler"] is not None,
+                  class_weight={1: p.weight_pos, -1: p.weight_neg} if p.weighted else None)
+        svc.params = svc.params.replace(weight_pos=p.weight_pos, weight_neg=p.weight_neg)
+        svc.class_weight_ = {1: p.weight_pos, -1: p.weight_neg}
         svc.scaler_ = m["scaler"]
         svc.support_ = m["ids"]
         svc.support_labels_ = m["labels"]

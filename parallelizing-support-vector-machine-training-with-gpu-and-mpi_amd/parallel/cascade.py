@@ -114,6 +114,8 @@ class CascadeSVM:
     def fit(self, X, y, world: int = 1, device: str = "cpu", transport: str = "auto", group=None) -> "CascadeSVM":
         """Thread-ranks of this process over contiguous ceil(n / world) partitions with global ids."""
         self._check_world(world)
+        if device != "cpu":
+            self.params.refuse_weights("the cascade on the device backend")
         self._set_solver(device == "cpu")
         y = np.ascontiguousarray(y, dtype=np.int32)
         if device == "cpu":
@@ -141,6 +143,8 @@ class CascadeSVM:
         """This process's rank trains on its partition (raw rows, global ids): ``RcclRank`` (its GPU,
         RCCL) or ``HostCommRank`` (the CPU oracle over a gloo group, the multi-process CPU tests)."""
         self._check_world(rank.world)
+        if rank.device != "cpu":
+            self.params.refuse_weights("the cascade on the device backend")
         self._set_solver(rank.device == "cpu")
         if rank.device == "cpu":
             self.device = "cpu"

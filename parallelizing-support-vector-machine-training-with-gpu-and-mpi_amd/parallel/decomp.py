@@ -114,6 +114,7 @@ def cpu_fit(X: np.ndarray, y: np.ndarray, params: Optional[SVMParams] = None, q:
 def group_fit(group, X: np.ndarray, y: np.ndarray, params: Optional[SVMParams] = None, q: int = 1024) -> dict:
     """One distributed decomposition solve over a ``DeviceGroup`` (its ranks are this process's
     threads; RCCL or the loopback rehearsal)."""
+    (params or SVMParams()).refuse_weights("the distributed decomposition solver")
     lib = N.hip()
     X, u8 = _rows(X)
     fn = lib.svmd_cascade_group_decomp if u8 else lib.svmd_cascade_group_decomp_rows
@@ -132,6 +133,7 @@ def group_fit(group, X: np.ndarray, y: np.ndarray, params: Optional[SVMParams] =
 
 def rank_fit(rank, X: np.ndarray, y: np.ndarray, params: Optional[SVMParams] = None, q: int = 1024) -> dict:
     """This process's rank of a distributed decomposition solve (every rank passes all rows)."""
+    (params or SVMParams()).refuse_weights("the distributed decomposition solver")
     lib = N.hip()
     X, u8 = _rows(X)
     fn = lib.svmd_cascade_rank_decomp if u8 else lib.svmd_cascade_rank_decomp_rows
@@ -146,8 +148,13 @@ class DistributedDecompSVC:
 
     def __init__(self, world: int = 1, transport: str = "auto", C: float = 10.0, gamma: float = 0.00125,
                  tol: float = 1e-5, eps: float = 1e-12, sv_tol: float = 1e-8, max_iter: int = 100000,
-                 working_set: int = 1024, group=None, rank=None):
+                 working_set: int = 1024, group=None, rank=None, class_weight=None):
+        from ..utils.data import resolve_class_weight
+
         self.params = SVMParams(C=C, gamma=gamma, tau=tol, eps=eps, sv_tol=sv_tol, max_iter=max_iter)
+        if class_weight is not None and resolve_class_weight(class_weight) != (1.0, 1.0):
+            raise ValueError("class_weight is not supported by the distributed decomposition solver: use "
+                             "SVC(solver='decomp') on one GPU or device='cpu'")
         self.world, self.transport, self.group, self.rank = world, transport, group, rank
         self.working_set = int(working_set)
 

@@ -67,6 +67,7 @@ class DsmoGroup:
         n, d = X.shape
         y = check_labels(y, n)
         params = params or SVMParams()
+        params.refuse_weights("the distributed SMO")  # svmd_dsmo_* has one box for both classes
         p = params.to_struct()
         alpha = np.empty(n, dtype=np.float64)
         r = N.SvmResult()
@@ -205,6 +206,7 @@ class DsmoRank:
 
         from ..utils.data import check_labels, pixel_rows
 
+        (params or SVMParams()).refuse_weights("the distributed SMO")  # before any collective: every rank alike
         p = (params or SVMParams()).to_struct()
         lib, err = N.hip(), ""
         ok = torch.ones(1, dtype=torch.int32)

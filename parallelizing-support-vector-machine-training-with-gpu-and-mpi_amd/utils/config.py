@@ -50,6 +50,11 @@ class SVMParams:
     # int k > 0 = a pass every k outer iterations.  The stop test is still the reference's, on all n
     # points (f recomputed when the solve unshrinks).
     shrinking: object = False
+    # class weights (LIBSVM's -wi, scikit-learn's class_weight): row i's box is [0, C * weight_pos] where
+    # y_i = +1 and [0, C * weight_neg] where y_i = -1.  The CPU solvers and the one-GPU decomposition
+    # solver take them; everything else refuses weights that differ from 1.
+    weight_pos: float = 1.0
+    weight_neg: float = 1.0
 
     def __post_init__(self):
         # the reference hard-codes these; as parameters they must keep the problem well posed:
@@ -60,11 +65,30 @@ class SVMParams:
                                               ("max_iter", self.max_iter, self.max_iter >= 1),
                                               ("n_threads", self.n_threads, self.n_threads >= 0),
                                               ("wss", self.wss, self.wss in (1, 2)),
-                                              ("shrinking", self._shrink_code(), self._shrink_code() >= -1))
+                                              ("shrinking", self._shrink_code(), self._shrink_code() >= -1),
+                                              ("weight_pos", self.weight_pos, self.weight_pos > 0),
+                                              ("weight_neg", self.weight_neg, self.weight_neg > 0))
                if not (ok and np.isfinite(v))]
         if bad:
             raise ValueError("SVM parameters out of range: " + ", ".join(bad) +
-                             " (C, gamma, tau > 0; eps, sv_tol >= 0; max_iter >= 1; wss 1 or 2)")
+                             " (C, gamma, tau > 0; eps, sv_tol >= 0; max_iter >= 1; wss 1 or 2; "
+                             "weight_pos, weight_neg finite and > 0)")
+
+    @property
+    def weighted(self) -> bool:
+        """Class weights that differ from 1 (the two boxes may still be equal)."""
+        return self.weight_pos != 1.0 or self.weight_neg != 1.0
+
+    def box(self, y) -> np.ndarray:
+        """Every row's box constraint C_i for labels y in {+1, -1}."""
+        return np.where(np.asarray(y) == 1, self.C * self.weight_pos, self.C * self.weight_neg)
+
+    def refuse_weights(self, what: str) -> None:
+        """ValueError when class weights are set: ``what`` solves the unweighted problem only."""
+        if self.weighted:
+            raise ValueError(f"class weights (weight_pos={self.weight_pos}, weight_neg={self.weight_neg}) are not "
+                             f"supported by {what}: use the CPU solvers or the one-GPU decomposition solver "
+                             "(SVC(solver='decomp'))")
 
     def _shrink_code(self) -> int:
         s = self.shrinking
@@ -78,7 +102,8 @@ class SVMParams:
 
     def to_struct(self, verbose: int = 0):
         return params_struct(self.C, self.gamma, self.tau, self.eps, self.sv_tol, self.max_iter,
-                             self.n_threads, verbose, self.wss, self._shrink_code())
+                             self.n_threads, verbose, self.wss, self._shrink_code(), self.weight_pos,
+                             self.weight_neg)
 
     def replace(self, **kw) -> "SVMParams":
         return dataclasses.replace(self, **kw)

@@ -74,9 +74,36 @@ def check_labels(y, n: int) -> np.ndarray:
     return y.astype(np.int32, copy=False)
 
 
-def check_warm_start(alpha0, y: np.ndarray, C: float) -> np.ndarray:
+def resolve_class_weight(class_weight, y: np.ndarray = None):
+    """(weight_pos, weight_neg) of a ``class_weight`` option: None -> (1, 1); a dict with exactly the keys
+    1 and -1 -> its values; "balanced" -> n / (2 n_c) from the labels y (scikit-learn's rule; an absent
+    class is an error).  y = None validates the option's form only (and returns None for "balanced")."""
+    if class_weight is None:
+        return 1.0, 1.0
+    if isinstance(class_weight, str):
+        if class_weight != "balanced":
+            raise ValueError(f"class_weight must be None, 'balanced' or {{1: w_pos, -1: w_neg}}, got {class_weight!r}")
+        if y is None:
+            return None
+        y = np.asarray(y)
+        n, n_pos, n_neg = int(y.shape[0]), int(np.sum(y == 1)), int(np.sum(y == -1))
+        for label, cnt in ((1, n_pos), (-1, n_neg)):
+            if cnt == 0:
+                raise ValueError(f"class_weight='balanced': class {label:+d} is absent from y")
+        return n / (2.0 * n_pos), n / (2.0 * n_neg)
+    if not isinstance(class_weight, dict) or set(class_weight.keys()) != {1, -1}:
+        raise ValueError(f"class_weight must be None, 'balanced' or a dict with exactly the keys 1 and -1, got "
+                         f"{class_weight!r}")
+    w = (float(class_weight[1]), float(class_weight[-1]))
+    if not all(np.isfinite(v) and v > 0 for v in w):
+        raise ValueError(f"class weights must be finite and > 0, got {class_weight!r}")
+    return w
+
+
+def check_warm_start(alpha0, y: np.ndarray, C) -> np.ndarray:
     """alpha0 as float64 (n,) that is a feasible point of the dual: finite, inside the box [0, C] (to rounding) and on
-    the equality constraint sum(alpha y) = 0 (to rounding).  ValueError otherwise: the solvers assume a
+    the equality constraint sum(alpha y) = 0 (to rounding).  C: the box constraint, or every row's own (n,)
+    under class weights.  ValueError otherwise: the solvers assume a
     feasible start, and from an infeasible one they stop on a "converged" model that is not a solution."""
     a = np.ascontiguousarray(alpha0, dtype=np.float64)
     n = y.shape[0]
@@ -84,9 +111,11 @@ def check_warm_start(alpha0, y: np.ndarray, C: float) -> np.ndarray:
         raise ValueError(f"alpha0 must have shape ({n},), got {a.shape}")
     # the solvers' own alphas may sit a few ulps outside the box (a_i moves by the rounded step of a_j,
     # as in the reference's update, gpu_svm_main3.cu:441-448): a previous solution must stay a valid start
-    tol = 1e-9 * max(1.0, C)
-    if not np.all(np.isfinite(a)) or a.min(initial=0.0) < -tol or a.max(initial=0.0) > C + tol:
-        raise ValueError(f"alpha0 must be finite and inside [0, C = {C}]")
+    box = np.broadcast_to(np.asarray(C, dtype=np.float64), (n,))
+    tol = 1e-9 * np.maximum(1.0, box)
+    if not np.all(np.isfinite(a)) or np.any(a < -tol) or np.any(a > box + tol):
+        raise ValueError("alpha0 must be finite and inside [0, C = %s]"
+                         % (C if np.ndim(C) == 0 else "its class's box, %s" % sorted(set(box.tolist()))))
     s = float(np.dot(a, y.astype(np.float64)))
     if abs(s) > 1e-9 * max(1.0, float(a.sum())):
         raise ValueError(f"alpha0 must satisfy sum(alpha0 * y) = 0 (the dual's equality constraint), got {s:.3g}")
