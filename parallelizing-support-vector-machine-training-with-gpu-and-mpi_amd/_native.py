@@ -281,6 +281,8 @@ _HIP_SIGS = {
                                     POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
     "svmd_decomp_newton_probe": (c_int32, [c_void_p, _P, _P, c_int32, _P, _P, c_double, c_double, c_int32, c_int32,
                                             POINTER(c_int32), _P, POINTER(c_double)]),
+    "svmd_decomp_newton_probe_nt": (c_int32, [c_void_p, _P, _P, c_int32, _P, _P, c_double, c_double, c_int32, c_int32,
+                                               c_int32, POINTER(c_int32), _P, POINTER(c_double)]),
     "svmd_decomp_gemv_u8": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, c_double, c_int64, c_int64, _P, _P,
                                       c_int32, _P, POINTER(c_int32)]),
     "svmd_minmax_u8": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P]),
@@ -401,7 +403,8 @@ def ptr(a) -> int:
 
 def newton_step_probe(Kw, y, a, f, C=10.0, eps=1e-12, max_free=1024):
     """One Newton polish step (decomp_newton.h newton_step_ref) on a working set: Kw (m x m), labels,
-    alpha, f by position.  Returns (alpha, f, code: 0 none, 1 full step, 2 cut at a bound)."""
+    alpha, f by position.  Returns (alpha, f, code: 0 none, 1 full step, 2 cut at a bound).  max_free is
+    capped at kNewtonMaxFree (512, the device step's bound): a larger free set takes no step."""
     import numpy as np
 
     Kw = np.ascontiguousarray(Kw, dtype=np.float64)

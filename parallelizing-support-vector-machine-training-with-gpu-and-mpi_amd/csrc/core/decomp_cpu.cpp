@@ -41,7 +41,15 @@ namespace {
 
 constexpr int kMaxWS = SVM_DECOMP_MAX_WS;
 constexpr int64_t kSelPts = 256 * 16;  // points per selection block below the block cap (ws_select_kernel)
-constexpr int kInnerNT = 256;           // the device's inner workgroup (ws_inner_kernel<256, 4>)
+
+// The device's inner workgroup (ws_inner_kernel<NT, 1024 / NT>): 256 threads, or SVM355_DECOMP_NT = 64 | 128 |
+// 512 as the device reads it (decomp.hip; its one-wave probe shape 65 is not modelled).  Only the second
+// pair's "outside i_high's wave" rule depends on it: position k lies in wave (k mod 2 NT) / 128.
+int inner_nt() {
+  const char* v = getenv("SVM355_DECOMP_NT");
+  const int nt = v ? atoi(v) : 256;
+  return nt == 64 || nt == 128 || nt == 512 ? nt : 256;
+}
 
 struct Shape {
   bool ok = false;
@@ -193,6 +201,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   int64_t outer = 0, inner_total = 0, changed_total = 0, last_inner_it = 0, newton_steps = 0;
   int64_t chain_it = 0;  // inner-solve loop iterations (each one or more pair updates)
   int last_m = 0;
+  const int inner_threads = inner_nt();
   NewtonCfg nwc = newton_cfg(p);
   nwc.on = nwc.on && inner_wss == 3;  // the device polishes in its default inner solve (second order + second pair)
   int32_t last_reason = SVM_STOP_CONVERGED, stop = SVM_STOP_RUNNING;
@@ -353,16 +362,16 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         }
       }
       // inner_wss 3: the second pair from the same selection (ws_inner_kernel DP): i2 = the best I_high
-      // point outside i_high's wave of the 256-thread inner workgroup (position k lies in wave
-      // (k mod 512) / 128), j2 = the first-order j.  inner_wss 4 (ws_inner_kernel J2S): j2 by the
+      // point outside i_high's wave of the inner workgroup (inner_nt threads, 256 by default: position k lies
+      // in wave (k mod 512) / 128), j2 = the first-order j.  inner_wss 4 (ws_inner_kernel J2S): j2 by the
       // second-order gain of row i2 over I_low points above f(i2), from the same snapshot
       int i2 = -1;
       int j2 = il;
       if (inner_wss >= 3) {
-        const int wih = (ih % (2 * kInnerNT)) / 128;
+        const int wih = (ih % (2 * inner_threads)) / 128;
         double v2 = inf;
         for (int k = 0; k < m; ++k)
-          if ((k % (2 * kInnerNT)) / 128 != wih && in_high(yw[size_t(k)], a[size_t(k)]) && ft[size_t(k)] < v2) {
+          if ((k % (2 * inner_threads)) / 128 != wih && in_high(yw[size_t(k)], a[size_t(k)]) && ft[size_t(k)] < v2) {
             v2 = ft[size_t(k)];
             i2 = k;
           }

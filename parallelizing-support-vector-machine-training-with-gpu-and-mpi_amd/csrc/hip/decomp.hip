@@ -2053,13 +2053,15 @@ SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t
 // One Newton polish step (decomp_newton.h) on the device for a host working set (tests / timing): Kw_h
 // (m x m), y_h, a_h / f_h by position (overwritten with the result); *code = 0 / 1 / 2; prof (optional, 8
 // int64): wall-clock stamps of the phases (free set, K_FF, factorisation, back substitution, step, f) of
-// the last of `reps` runs (each from the same inputs), ticks at 100 MHz; ms_out: the mean time per step.
-SVM_API int svmd_decomp_newton_probe(void* h, const double* Kw_h, const int32_t* y_h, int32_t m, double* a_h,
-                                     double* f_h, double C, double eps, int32_t max_free, int32_t reps, int32_t* code,
-                                     int64_t* prof_h, double* ms_out) {
+// the last of `reps` runs (each from the same inputs), ticks at 100 MHz, then |F| (prof[6]; the stamps are
+// zeroed before every run, so a refused step leaves |F| = 0); ms_out: the mean time per step.  threads: the
+// workgroup's size, 64 / 128 / 256 / 512 (the inner solve's shapes); max_free above kNewtonMaxFree is capped.
+SVM_API int svmd_decomp_newton_probe_nt(void* h, const double* Kw_h, const int32_t* y_h, int32_t m, double* a_h,
+                                        double* f_h, double C, double eps, int32_t max_free, int32_t reps,
+                                        int32_t threads, int32_t* code, int64_t* prof_h, double* ms_out) {
   SVMD_CTX(h);
-  if (!Kw_h || !y_h || !a_h || !f_h || !code || m < 1 || m > kMaxWS || reps < 1) {
-    set_error("svmd_decomp_newton_probe: bad arguments (1 <= m <= %d)", kMaxWS);
+  if (!Kw_h || !y_h || !a_h || !f_h || !code || m < 1 || m > kMaxWS || reps < 1 || !ws_newton_probe_built(threads)) {
+    set_error("svmd_decomp_newton_probe: bad arguments (1 <= m <= %d, threads 64 / 128 / 256 / 512)", kMaxWS);
     return SVM_ERR_ARG;
   }
   int rc = ctx->begin();
@@ -2091,8 +2093,10 @@ SVM_API int svmd_decomp_newton_probe(void* h, const double* Kw_h, const int32_t*
   for (int r = 0; r < reps; ++r) {
     SVMD_CHECK(hipMemcpyAsync(ad, a0, size_t(m) * 8, hipMemcpyDeviceToDevice, s));
     SVMD_CHECK(hipMemcpyAsync(fd, f0, size_t(m) * 8, hipMemcpyDeviceToDevice, s));
+    SVMD_CHECK(hipMemsetAsync(pd, 0, 32 * sizeof(int64_t), s));
     SVMD_CHECK(hipEventRecord(e0, s));
-    launch_ws_newton_probe(s, m, Kw, int64_t(kMaxWS), yd, ad, fd, Ad, C, eps, max_free, cd, pd);
+    if ((rc = launch_ws_newton_probe(s, threads, m, Kw, int64_t(kMaxWS), yd, ad, fd, Ad, C, eps, max_free, cd, pd)))
+      return rc;
     SVMD_LAUNCH_CHECK();
     SVMD_CHECK(hipEventRecord(e1, s));
     SVMD_CHECK(hipEventSynchronize(e1));
@@ -2109,6 +2113,13 @@ SVM_API int svmd_decomp_newton_probe(void* h, const double* Kw_h, const int32_t*
   SVMD_CHECK(hipStreamSynchronize(s));
   if (ms_out) *ms_out = double(tot) / reps;
   return ctx->end();
+}
+
+// The probe in a 256-thread workgroup (the inner solve's default shape).
+SVM_API int svmd_decomp_newton_probe(void* h, const double* Kw_h, const int32_t* y_h, int32_t m, double* a_h,
+                                     double* f_h, double C, double eps, int32_t max_free, int32_t reps, int32_t* code,
+                                     int64_t* prof_h, double* ms_out) {
+  return svmd_decomp_newton_probe_nt(h, Kw_h, y_h, m, a_h, f_h, C, eps, max_free, reps, 256, code, prof_h, ms_out);
 }
 
 }  // extern "C"

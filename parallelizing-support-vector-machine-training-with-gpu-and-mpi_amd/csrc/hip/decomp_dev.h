@@ -104,8 +104,11 @@ bool ws_inner_weighted_built(const InnerVariant& v);
 // One inner solve on stream s (one workgroup; the caller checks the launch).  SVM_ERR_ARG, with nothing
 // launched, for a weighted variant that is not built -- never the unweighted kernel in its place.
 int launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a);
-// ws_newton_probe_kernel (one 256-thread workgroup): one Newton step on a given working set.
-void launch_ws_newton_probe(hipStream_t s, int m, const double* Kw, int64_t ldw, const int32_t* y, double* gA, double* gF,
-                            double* Amat, double C, double eps, int max_free, int32_t* code_out, int64_t* prof);
+// ws_newton_probe_kernel (one workgroup of nt threads): one Newton step on a given working set.  Built for
+// nt = 64, 128, 256 and 512, the inner solve's shapes (ws_newton_probe_built); SVM_ERR_ARG, with nothing
+// launched, for any other nt.
+bool ws_newton_probe_built(int nt);
+int launch_ws_newton_probe(hipStream_t s, int nt, int m, const double* Kw, int64_t ldw, const int32_t* y, double* gA,
+                           double* gF, double* Amat, double C, double eps, int max_free, int32_t* code_out, int64_t* prof);
 
 }  // namespace svm355

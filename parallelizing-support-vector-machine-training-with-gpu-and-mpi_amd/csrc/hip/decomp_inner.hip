@@ -3,6 +3,7 @@
 // translation unit: the instantiations of the inner kernel are most of the solver's compile time.  The
 // driver (decomp.hip) reaches it through launch_ws_inner / launch_ws_newton_probe only.
 #include "decomp_dev.h"
+#include "decomp_newton.h"
 #include "persist.h"
 #include "svm355_device.h"
 
@@ -25,7 +26,10 @@ namespace {
 //   * sums and the step's arg-min in the sequential order (thread 0; wave_arg's value-then-lowest-index).
 // Returns 0 (nothing changed), 1 (full step) or 2 (cut at a bound), the same in every thread.
 constexpr int kNwPW = 16;      // panel width
-constexpr int kNwMax = 512;    // |F| bound of the LDS buffers (NewtonCfg::max_free is clamped to it)
+constexpr int kNwMax = kNewtonMaxFree;  // |F| bound of the LDS buffers: the cap shared with newton_step_ref,
+                                        // which newton_cfg clamps NewtonCfg::max_free to (decomp_newton.h)
+static_assert(2 * kNwMax + 64 * 64 <= kNwMax * kNwPW && kNwMax + 127 < kMaxWS,
+              "lp also holds the back substitution's s1, s2 and 64 x 64 block; the row updates read 127 columns ahead");
 // The factorisation's row updates for one panel (newton_wg): pb[r][c] = A[p0 + r][p0 + c] - sum_{j < p0}
 // L[p0 + r][j] L[p0 + c][j] (ascending j) for the panel's rows r < ract and columns c < pw (lower entries;
 // the right-hand-side rows nf, nf + 1 take every column), lp[j][c] = L[p0 + c][j] -- on FP64 MFMA
@@ -393,11 +397,14 @@ __device__ __forceinline__ int newton_wg(int m, const double* __restrict__ Kw, i
 
 // One Newton step on a given working set (tests / timing, svmd_decomp_newton_probe): K(W, W) in Kw (m x
 // m, row stride ldw), alpha and f by position in gA / gF (updated), labels y; *code_out = the step's code.
-__global__ __launch_bounds__(256) void ws_newton_probe_kernel(int m, const double* __restrict__ Kw, int64_t ldw,
-                                                              const int32_t* __restrict__ y, double* __restrict__ gA,
-                                                              double* __restrict__ gF, double* __restrict__ Amat,
-                                                              double C, double eps, int max_free,
-                                                              int32_t* __restrict__ code_out, int64_t* __restrict__ prof) {
+// One workgroup of NT threads, the inner solve's shapes (launch_ws_inner): newton_wg strides its tiles and
+// rows by the NT / 64 waves it runs in.
+template <int NT>
+__global__ __launch_bounds__(NT) void ws_newton_probe_kernel(int m, const double* __restrict__ Kw, int64_t ldw,
+                                                             const int32_t* __restrict__ y, double* __restrict__ gA,
+                                                             double* __restrict__ gF, double* __restrict__ Amat,
+                                                             double C, double eps, int max_free,
+                                                             int32_t* __restrict__ code_out, int64_t* __restrict__ prof) {
   __shared__ int8_t sy[kMaxWS];
   for (int k = threadIdx.x; k < kMaxWS; k += blockDim.x) sy[k] = k < m ? int8_t(y[k]) : int8_t(0);
   __syncthreads();
@@ -1068,10 +1075,27 @@ int launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a) {
   return SVM_OK;
 }
 
-void launch_ws_newton_probe(hipStream_t s, int m, const double* Kw, int64_t ldw, const int32_t* y, double* gA, double* gF,
-                            double* Amat, double C, double eps, int max_free, int32_t* code_out, int64_t* prof) {
-  hipLaunchKernelGGL(ws_newton_probe_kernel, dim3(1), dim3(256), 0, s, m, Kw, ldw, y, gA, gF, Amat, C, eps, max_free,
-                     code_out, prof);
+bool ws_newton_probe_built(int nt) { return nt == 64 || nt == 128 || nt == 256 || nt == 512; }
+
+int launch_ws_newton_probe(hipStream_t s, int nt, int m, const double* Kw, int64_t ldw, const int32_t* y, double* gA,
+                           double* gF, double* Amat, double C, double eps, int max_free, int32_t* code_out, int64_t* prof) {
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(unsigned(nt)), 0, s, m, Kw, ldw, y, gA, gF, Amat, C, eps, max_free, code_out,
+                       prof);
+  };
+  if (nt == 64)
+    go(ws_newton_probe_kernel<64>);
+  else if (nt == 128)
+    go(ws_newton_probe_kernel<128>);
+  else if (nt == 256)
+    go(ws_newton_probe_kernel<256>);
+  else if (nt == 512)
+    go(ws_newton_probe_kernel<512>);
+  else {
+    set_error("decomposition SMO: the Newton probe is built for 64, 128, 256 or 512 threads, not %d", nt);
+    return SVM_ERR_ARG;
+  }
+  return SVM_OK;
 }
 
 }  // namespace svm355

@@ -1,5 +1,5 @@
 // Newton polish of a working set's free variables: the decomposition solver's end-game step, shared
-// by the device solver (csrc/hip/decomp.hip, ws_newton_kernel) and its CPU oracle
+// by the device solver (csrc/hip/decomp_inner.hip, newton_wg) and its CPU oracle
 // (csrc/core/decomp_cpu.cpp), which must stay bit-identical.
 //
 // Why.  The reference's SMO (main3.cpp:162-294) moves two variables per iteration.  Near the optimum
@@ -20,7 +20,8 @@
 // When.  Inside the inner solve, once `every` iterations of the pairwise chain have passed without any
 // updated point changing its bound status (the free set has settled), at most per_solve times; a step
 // cut at a bound is repeated up to `repeat` steps; and right at the start of the inner solve when the
-// previous one needed at least frac x m pair updates (the end game).  F must have 2 <= |F| <= max_free.
+// previous one needed at least frac x m pair updates (the end game).  F must have 2 <= |F| <= max_free,
+// and max_free <= kNewtonMaxFree on both sides (the device step's LDS buffers hold that many columns).
 // On the 60k headline (CPU oracle) this takes the pair updates from 9,760 to ~4,200-4,700 with 14-20
 // steps, in the last five working sets.
 //
@@ -43,13 +44,17 @@
 
 namespace svm355 {
 
+// The largest free set a step may have: the bound of the device step's LDS buffers (newton_wg), and so of
+// the reference too -- a working set with more free points takes no step on either side.
+constexpr int32_t kNewtonMaxFree = 512;
+
 struct NewtonCfg {
   bool on = false;         // opt-in (SVM355_DECOMP_NEWTON=1): a net loss on the headline, see below
   double frac = 0.5;       // a step at the start of the inner solve when the last one needed >= frac x m
   int32_t every = 50;      // a step after `every` chain iterations with no point changing its bound status
   int32_t per_solve = 8;   // at most this many triggers per inner solve
   int32_t repeat = 2;      // a trigger repeats the step while it is cut at a bound, up to this many steps
-  int32_t max_free = 640;  // |F| above this: no step (the factorisation costs |F|^3 / 6 FMAs)
+  int32_t max_free = kNewtonMaxFree;  // |F| above this: no step (|F|^3 / 6 FMAs); at most kNewtonMaxFree
 };
 
 // Off by default.  The device step (newton_wg) costs ~0.67 ms at |F| = 302 (probe; ~0.86 ms in situ), and
@@ -66,7 +71,8 @@ inline NewtonCfg newton_cfg(const svm_params& p) {
   if (const char* v = std::getenv("SVM355_DECOMP_NEWTON_EVERY")) c.every = std::max(1, std::atoi(v));
   if (const char* v = std::getenv("SVM355_DECOMP_NEWTON_PER_SOLVE")) c.per_solve = std::max(0, std::atoi(v));
   if (const char* v = std::getenv("SVM355_DECOMP_NEWTON_REPEAT")) c.repeat = std::max(1, std::atoi(v));
-  if (const char* v = std::getenv("SVM355_DECOMP_NEWTON_MAX")) c.max_free = std::max(2, std::min(1024, std::atoi(v)));
+  if (const char* v = std::getenv("SVM355_DECOMP_NEWTON_MAX"))
+    c.max_free = std::max(2, std::min(kNewtonMaxFree, std::atoi(v)));
   return c;
 }
 
@@ -83,6 +89,7 @@ inline int bound_status(double a, double C, double eps) { return a <= 0.0 + eps 
 // working set's alpha, f and labels by position; Kw(q, k) the kernel value of positions q and k (row q,
 // column k of K(W, W): the device reads rows F_i for K_FF and rows F_k for the f update).
 // Returns 0 when no step was applied, 1 for a full step, 2 for a step cut at a bound (a and f updated).
+// No step when |F| < 2 or |F| > min(max_free, kNewtonMaxFree): a larger max_free is capped, as on the device.
 template <class KFn>
 int newton_step_ref(int m, double* a, double* f, const int32_t* yw, KFn&& Kw, double C, double eps, int32_t max_free) {
   const double c_hi = C - eps, c_lo = 0.0 + eps;
@@ -90,7 +97,7 @@ int newton_step_ref(int m, double* a, double* f, const int32_t* yw, KFn&& Kw, do
   for (int k = 0; k < m; ++k)
     if (a[k] > c_lo && a[k] < c_hi) F.push_back(k);
   const int nf = int(F.size());
-  if (nf < 2 || nf > max_free) return 0;
+  if (nf < 2 || nf > std::min(max_free, kNewtonMaxFree)) return 0;
   // rows 0 .. nf-1: K_FF (lower); rows nf, nf+1: the right-hand sides f_F and 1
   std::vector<double> A(size_t(nf + 2) * nf, 0.0);
   for (int i = 0; i < nf; ++i)

@@ -489,10 +489,12 @@ def decomp_gemv_u8(Xu: torch.Tensor, mn, mx, gamma: float, cols: np.ndarray, coe
 
 
 def decomp_newton_probe(Kw: np.ndarray, y: np.ndarray, a: np.ndarray, f: np.ndarray, C: float = 10.0,
-                        eps: float = 1e-12, max_free: int = 1024, reps: int = 1, device="cuda:0"):
+                        eps: float = 1e-12, max_free: int = 1024, reps: int = 1, device="cuda:0", threads: int = 256):
     """One Newton polish step (decomp_newton.h) on the device for a host working set: returns (alpha, f,
     code, phase stamps (100 MHz ticks: free set, K_FF, factorisation, back substitution, step, f; then
-    |F|), mean ms per step)."""
+    |F|, 0 when the step was refused), mean ms per step).  max_free is capped at kNewtonMaxFree (512): a
+    larger free set takes no step.  threads: the workgroup's size, 64, 128, 256 or 512 (the inner solve's
+    shapes); any other value is an argument error."""
     Kw = np.ascontiguousarray(Kw, dtype=np.float64)
     y = np.ascontiguousarray(y, dtype=np.int32)
     a = np.array(a, dtype=np.float64)
@@ -500,9 +502,9 @@ def decomp_newton_probe(Kw: np.ndarray, y: np.ndarray, a: np.ndarray, f: np.ndar
     prof = np.zeros(16, dtype=np.int64)
     code, ms = ctypes.c_int32(0), ctypes.c_double(0.0)
     ctx = _ctx_for(torch.empty(1, device=device))
-    N.check(ctx.lib.svmd_decomp_newton_probe(ctx.bind(), N.ptr(Kw), N.ptr(y), len(y), N.ptr(a), N.ptr(f), float(C),
-                                             float(eps), int(max_free), int(reps), ctypes.byref(code), N.ptr(prof),
-                                             ctypes.byref(ms)), "svmd_decomp_newton_probe")
+    N.check(ctx.lib.svmd_decomp_newton_probe_nt(ctx.bind(), N.ptr(Kw), N.ptr(y), len(y), N.ptr(a), N.ptr(f), float(C),
+                                                float(eps), int(max_free), int(reps), int(threads), ctypes.byref(code),
+                                                N.ptr(prof), ctypes.byref(ms)), "svmd_decomp_newton_probe")
     return a, f, int(code.value), prof, float(ms.value)
 
 

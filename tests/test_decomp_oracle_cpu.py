@@ -11,6 +11,8 @@ from svm355 import SVMParams
 from svm355.ops import cpu as C
 from svm355.utils.data import MinMaxScaler, synthetic_mnist
 
+from decomp_checks import NEWTON_C, NEWTON_SIZES, NEWTON_SIZES_ABOVE_CAP, newton_case
+
 
 def _problem(n, seed):
     tr = synthetic_mnist(n, seed=seed)
@@ -258,3 +260,97 @@ def test_newton_step_solves_the_free_subproblem():
     a3, f3, code3 = newton_step_probe(Kw, y, a * 0.1, Kw @ (0.1 * a * y) - y, C=0.15)
     assert code3 == 2 and np.sum((a3 == 0.0) | (a3 == 0.15)) >= 1
     np.testing.assert_allclose(f3, Kw @ (a3 * y) - y, rtol=0, atol=1e-12)
+
+
+# ---- one step of the reference against plain mathematics ---------------------------------------------------------
+# The device step is held to newton_step_ref bit for bit (tests/test_gpu_newton_step.py, the same cases); a
+# mistake shared by both -- the header is -- would pass that.  Here the reference is held to the bordered
+# linear system itself.  A backward-stable Cholesky solve is within cond(K_FF) 2^-52 of the solution, relative.
+_EPS52 = 2.0 ** -52
+
+
+def _step_bound(case, scale):
+    return float(np.linalg.cond(case.KFF)) * _EPS52 * max(1.0, float(np.abs(scale).max()))
+
+
+@pytest.mark.parametrize("m,nf", NEWTON_SIZES)
+def test_newton_full_step_is_the_constructed_solution(m, nf):
+    """Kind "full": the realised (alpha' - alpha) y on F is the constructed u, and f' is equal on F, both to
+    cond(K_FF) 2^-52 max(1, max|u|); sum y alpha is unchanged; nothing outside F moves.  (Measured: the error
+    is 0.02-0.08 of the bound at 3 <= |F| <= 512 and 0.25-0.31 at |F| = 2; profiles/newton.md.)"""
+    from svm355._native import newton_step_probe
+
+    case = newton_case(m, nf, "full")
+    a2, f2, code = newton_step_probe(case.K, case.y, case.a, case.f, C=NEWTON_C)
+    F, yF = case.free, case.y[case.free]
+    assert code == 1 and np.count_nonzero((a2 > 1e-12) & (a2 < NEWTON_C - 1e-12)) == nf
+    bound = _step_bound(case, case.u)
+    err = np.abs((a2 - case.a)[F] * yF - case.u).max()
+    print(f"m={m} |F|={nf}: error {err:.3g}, ptp(f'_F) {np.ptp(f2[F]):.3g}, bound {bound:.3g}, ratio {err / bound:.3g}")
+    assert err <= bound
+    assert np.ptp(f2[F]) <= bound
+    assert abs(float(a2 @ case.y) - float(case.a @ case.y)) <= 1e-12 * case.a.sum()
+    rest = np.ones(m, dtype=bool)
+    rest[F] = False
+    np.testing.assert_array_equal(a2[rest], case.a[rest])
+
+
+def _assert_cut_step(case, a2, code):
+    """One free variable exactly on a bound; every free alpha moved along the full step's direction d (the
+    refined LU solve of the bordered system) by one fraction t in (0, 1), the least-squares t over F.  With
+    the reference's d within E = cond 2^-52 max(1, max|d|) of that d in every entry, the residual of entry k
+    is at most t (E + |d_k| sqrt(|F|) E / |d|_2) <= t (1 + sqrt(|F|)) E, plus the rounding of alpha + t d and
+    of the difference (2 ulp of C)."""
+    F, nf = case.free, len(case.free)
+    d, _ = case.direction()
+    da = (a2 - case.a)[F]
+    assert code == 2
+    assert np.count_nonzero((a2[F] == 0.0) | (a2[F] == NEWTON_C)) == 1
+    t = float(da @ d) / float(d @ d)
+    assert 0.0 < t < 1.0
+    bound = t * (1.0 + np.sqrt(nf)) * _step_bound(case, d) + 4.0 * _EPS52 * NEWTON_C
+    res = np.abs(da - t * d).max()
+    print(f"m={len(case.a)} |F|={nf}: t {t:.4g}, residual {res:.3g}, bound {bound:.3g}")
+    assert res <= bound
+    return da
+
+
+@pytest.mark.parametrize("m,nf", [s for s in NEWTON_SIZES if s[1] >= 3])
+def test_newton_cut_step_stops_at_the_first_bound(m, nf):
+    """Kind "cut" (f = K (alpha y) - y): the step lands one variable on its bound, moves the others by the same
+    fraction of the full step, and f' is the kernel's f of the new alpha to 1e-11."""
+    from svm355._native import newton_step_probe
+
+    case = newton_case(m, nf, "cut")
+    a2, f2, code = newton_step_probe(case.K, case.y, case.a, case.f, C=NEWTON_C)
+    _assert_cut_step(case, a2, code)
+    np.testing.assert_allclose(f2, case.K @ (a2 * case.y) - case.y, rtol=0, atol=1e-11)
+
+
+@pytest.mark.parametrize("where", [0, -1])
+def test_newton_cut_lands_on_the_forced_position(where):
+    from svm355._native import newton_step_probe
+
+    case = newton_case(600, 257, "cut", cut_at=where)
+    a2, f2, code = newton_step_probe(case.K, case.y, case.a, case.f, C=NEWTON_C)
+    da = _assert_cut_step(case, a2, code)
+    k = case.free[where]
+    assert a2[k] in (0.0, NEWTON_C) and abs(a2[k] - case.a[k]) < 1e-8
+    ur = da * case.y[case.free]  # f moves by the realised changes (this case's f is not the kernel's f of alpha)
+    np.testing.assert_allclose(f2 - case.f, case.K[:, case.free] @ ur, rtol=0, atol=1e-11)
+
+
+@pytest.mark.parametrize("kind", ["full", "cut"])
+@pytest.mark.parametrize("m,nf", NEWTON_SIZES_ABOVE_CAP)
+def test_newton_reference_takes_no_step_above_the_cap(m, nf, kind):
+    """The device step holds at most kNewtonMaxFree = 512 free points in LDS; the reference has the same cap,
+    whatever max_free asks for (before the shared cap it stepped at |F| = 513 and the device did not)."""
+    from svm355._native import newton_step_probe
+
+    case = newton_case(m, nf, kind)
+    for kw in ({}, {"max_free": 1024}):
+        a2, f2, code = newton_step_probe(case.K, case.y, case.a, case.f, C=NEWTON_C, **kw)
+        assert code == 0
+        np.testing.assert_array_equal(a2, case.a)
+        np.testing.assert_array_equal(f2, case.f)
+

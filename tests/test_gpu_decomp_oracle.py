@@ -306,17 +306,27 @@ def test_shrunk_solve_meets_the_stop_test_on_all_points(n):
                                  {"SVM355_DECOMP_NEWTON": "1", "SVM355_DECOMP_NEWTON_EVERY": "20", "SVM355_DECOMP_NEWTON_REPEAT": "4",
                                   "SVM355_DECOMP_SHRINK": "1", "SVM355_DECOMP_SHRINK_START": "1"},
                                  {"SVM355_DECOMP_NEWTON": "1", "SVM355_DECOMP_NEWTON_EVERY": "10", "SVM355_DECOMP_CCACHE": "1",
-                                  "SVM355_DECOMP_NEWTON_FRAC": "0", "SVM355_DECOMP_NEWTON_MAX": "150"}])
+                                  "SVM355_DECOMP_NEWTON_FRAC": "0", "SVM355_DECOMP_NEWTON_MAX": "150"},
+                                 {"SVM355_DECOMP_NEWTON": "1", "SVM355_DECOMP_NEWTON_EVERY": "5", "SVM355_DECOMP_NEWTON_FRAC": "0",
+                                  "SVM355_DECOMP_NT": "64"},
+                                 {"SVM355_DECOMP_NEWTON": "1", "SVM355_DECOMP_NEWTON_EVERY": "5", "SVM355_DECOMP_NEWTON_FRAC": "0",
+                                  "SVM355_DECOMP_NT": "128"},
+                                 {"SVM355_DECOMP_NEWTON": "1", "SVM355_DECOMP_NEWTON_EVERY": "5", "SVM355_DECOMP_NEWTON_FRAC": "0",
+                                  "SVM355_DECOMP_NT": "512"}])
 def test_newton_polish_trajectory_equals_the_oracle(monkeypatch, env):
     """The Newton polish of the working set's free variables (decomp_newton.h, newton_wg in the inner
     solve: a left-looking panel Cholesky of K_FF with two right-hand-side rows, the back substitution in
     one wave, the cut at the first bound) against the oracle's sequential reference, bit for bit: every
     working set, moved column, coefficient, alpha and f; forced often here (every 5-20 quiet chain
-    iterations, from the first working set), with shrinking, with the column cache and a small |F| cap."""
+    iterations, from the first working set), with shrinking, with the column cache and a small |F| cap, and
+    in the inner solve's one-, two- and eight-wave shapes (SVM355_DECOMP_NT=64 / 128 / 512, at n = 2000 only;
+    the oracle reads the same variable: the second pair's i2 comes from outside i_high's wave, so the
+    trajectory depends on the shape.  The step alone at every shape and free-set edge:
+    test_gpu_newton_step.py)."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     fired = 0
-    for n, seed in ((2000, 5), (6000, 61)):
+    for n, seed in ((2000, 5), (6000, 61)) if "SVM355_DECOMP_NT" not in env else ((2000, 5),):
         tr = synthetic_mnist(n, seed=seed).compact()
         Xu, mn, mx = _dev_rows(tr)
         K = _exact_gram_host(Xu, mn, mx, n)
