@@ -209,6 +209,7 @@ _CORE_SIGS = {
     "svm_crash_handler_install": (c_int32, [c_char_p]),
     "svm_decomp_gemv_ref": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int64, _P]),
     "svm_decomp_newton_step": (c_int32, [_P, c_int64, _P, c_int32, _P, _P, c_double, c_double, c_int32, POINTER(c_int32)]),
+    "svm_smo_plan": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P]),
     "svm_decomp_rank_train_gram": (c_int32, [_P, _P, c_int64, _P, c_int64, _P, c_int32, POINTER(SvmParams), c_int32,
                                              c_double, c_int32, POINTER(SvmResult), POINTER(c_int64)]),
     "svm_decomp_group_train_gram": (c_int32, [c_int32, _P, c_int64, _P, c_int64, _P, c_int32, POINTER(SvmParams),
@@ -415,6 +416,23 @@ def newton_step_probe(Kw, y, a, f, C=10.0, eps=1e-12, max_free=1024):
     check(core().svm_decomp_newton_step(ptr(Kw), Kw.shape[1], ptr(y), len(y), ptr(a), ptr(f), float(C), float(eps),
                                         int(max_free), code), "svm_decomp_newton_step")
     return a, f, int(code.value)
+
+
+def smo_plan(n, wss=1, ncu=256, int_rows=True, kq=832, nslots=16384):
+    """The pairwise SMO drivers' plans (csrc/include/smo_plan.h) for n points under the current environment.
+    Returns (smo, rc): smo = {path: single | persistent | graph, NT, E, G, xlocal, device_wide: (NT, E, G) or
+    None -- the shape the XCD fallback re-plans to}; rc = the row-cache solver's {E, G, rpl (records per
+    lane), nd (directory slots), lds} on ncu compute units, or None when it has no persistent shape."""
+    import numpy as np
+
+    s = np.zeros(9, dtype=np.int64)
+    q = np.zeros(6, dtype=np.int64)
+    check(core().svm_smo_plan(int(n), int(wss), int(ncu), int(bool(int_rows)), int(kq), int(nslots), ptr(s), ptr(q)),
+          "svm_smo_plan")
+    smo = {"path": ("single", "persistent", "graph")[s[0]], "NT": int(s[1]), "E": int(s[2]), "G": int(s[3]),
+           "xlocal": bool(s[4]), "device_wide": tuple(int(v) for v in s[6:9]) if s[5] else None}
+    rc = {"E": int(q[1]), "G": int(q[2]), "rpl": int(q[3]), "nd": int(q[4]), "lds": int(q[5])} if q[0] else None
+    return smo, rc
 
 
 def shrink_stats(st) -> dict:

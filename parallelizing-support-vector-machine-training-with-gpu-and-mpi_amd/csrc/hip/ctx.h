@@ -130,6 +130,30 @@ struct DeviceCtx {
   }
 };
 
+// A bump allocator over the context's workspace, 256-byte aligned: `layout` names every buffer once and
+// runs twice, first against no base for the total size, then against the (grown) workspace.
+struct WsCarver {
+  char* base;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t count, bool on = true) {
+    if (!on) return nullptr;
+    const size_t o = off;
+    off += (count * sizeof(T) + 255) & ~size_t(255);
+    return base ? reinterpret_cast<T*>(base + o) : nullptr;
+  }
+};
+template <class Layout>
+int carve_ws(DeviceCtx* ctx, Layout&& layout) {
+  WsCarver size{nullptr};
+  layout(size);
+  const int rc = ctx->ensure_ws(size.off);
+  if (rc) return rc;
+  WsCarver c{static_cast<char*>(ctx->ws)};
+  layout(c);
+  return SVM_OK;
+}
+
 #define SVMD_CTX(h)                                              \
   auto* ctx = static_cast<svm355::DeviceCtx*>(h);                 \
   if (!ctx) {                                                    \
@@ -221,12 +245,13 @@ int run_smo_rowcache(DeviceCtx* ctx, const double* X_d, const double* sqn_d, int
 int run_smo(DeviceCtx* ctx, const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha,
             int32_t warm, const svm_params& p, svm_result* r, int64_t* trace, int64_t trace_cap);
 // Persistent row-cache SMO (smo.hip): f / alpha initialised by the caller; kRcNotApplicable when no
-// persistent shape covers n (SVM355_RC_SMO=graph forces that answer).
+// persistent shape covers n (plan_rc, smo_plan.h; SVM355_RC_SMO=graph forces that answer).
 struct QRows;
+struct SmoKnobs;
 constexpr int kRcNotApplicable = -100;
 int run_smo_rc_persistent(DeviceCtx* ctx, const QRows& q, bool int_rows, double* cache, int64_t ldc, int64_t nslots,
                           const int32_t* y, double* alpha, double* f, int64_t n, const svm_params& p, svm_result* r,
-                          int64_t* trace, int64_t trace_cap);
+                          int64_t* trace, int64_t trace_cap, const SmoKnobs& k);
 // nclass cold-start solves on one Gram (Y, A: nclass x n, class-major): XCD teams (smo.hip).
 // exp self-test (igram.hip): device libm exp and the Gram epilogue's batched exp of x[0..n).
 int exp_selftest(hipStream_t s, const double* x, int64_t n, double* out_lib, double* out_batch);

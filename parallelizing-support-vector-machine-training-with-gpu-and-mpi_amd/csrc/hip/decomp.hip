@@ -941,30 +941,6 @@ int read_knobs(const DecompShape& sh, DecompKnobs* out) {
   return SVM_OK;
 }
 
-// A bump allocator over the context's workspace, 256-byte aligned: `layout` names every buffer once and
-// runs twice, first against no base for the total size, then against the (grown) workspace.
-struct WsCarver {
-  char* base;
-  size_t off = 0;
-  template <class T>
-  T* take(size_t count, bool on = true) {
-    if (!on) return nullptr;
-    const size_t o = off;
-    off += (count * sizeof(T) + 255) & ~size_t(255);
-    return base ? reinterpret_cast<T*>(base + o) : nullptr;
-  }
-};
-template <class Layout>
-int carve_ws(DeviceCtx* ctx, Layout&& layout) {
-  WsCarver size{nullptr};
-  layout(size);
-  const int rc = ctx->ensure_ws(size.off);
-  if (rc) return rc;
-  WsCarver c{static_cast<char*>(ctx->ws)};
-  layout(c);
-  return SVM_OK;
-}
-
 // A solve's buffers in the context's workspace (nullptr: not part of this solve).
 struct DecompWs {
   double* f = nullptr;                     // this GPU's rows

@@ -23,12 +23,12 @@
 // exp expressions), so the trajectory is bit-identical to the full-Gram solver.  Feature data that
 // are not integer-valued use the FP64 expression ||a||^2 + ||b||^2 - 2 a.b instead.
 #include <chrono>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "ctx.h"
 #include "qrows.h"
+#include "smo_host.h"
+#include "smo_plan.h"
 
 namespace svm355 {
 namespace {
@@ -349,53 +349,77 @@ __global__ __launch_bounds__(kNT) void kc_step_kernel(const KcPartial* __restric
 
 }  // namespace
 
-// SMO with the on-demand row cache.  X_d: preprocessed rows (n x ld); P: quantisation plan (P.ok ->
-// exact-integer rows, else FP64 rows with sqn_d).  cache_bytes: HBM budget for the row cache.
-int run_smo_rowcache(DeviceCtx* ctx, const double* X_d, const double* sqn_d, int64_t n, int64_t ld, int64_t d,
-                     const QuantPlan& P, const int32_t* y, double* alpha, int32_t warm, const svm_params& p,
-                     svm_result* r, size_t cache_bytes, int64_t* trace, int64_t trace_cap, int32_t* used_int) {
-  const auto t0 = std::chrono::steady_clock::now();
-  hipStream_t s = ctx->stream;
-  const int64_t ldc = (n + 1) / 2 * 2;
-  int64_t C = int64_t(cache_bytes / (size_t(ldc) * 8));
-  C = std::min<int64_t>(C, 2 * ((n + 1) / 2)) / 2 * 2;
-  if (C < 4) {
-    set_error("row cache: %zu bytes hold fewer than 4 rows of %lld doubles", cache_bytes, (long long)n);
-    return SVM_ERR_OOM;
-  }
-  const int nblk = int(std::min<int64_t>((n + kNT - 1) / kNT, 2048));
-  const int64_t tcap = trace ? std::max<int64_t>(trace_cap, 0) : 0;
+// ---- host driver -------------------------------------------------------------------------------------------
+namespace {
+
+// A fit's device buffers (allocated per fit): freed together, once the stream has drained, when the fit returns.
+struct DeviceBufs {
+  hipStream_t s;
   std::vector<void*> bufs;
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
-    bufs.push_back(q);
-    return q;
-  };
-  auto release = [&]() {
+  explicit DeviceBufs(hipStream_t stream) : s(stream) {}
+  ~DeviceBufs() {
     (void)hipStreamSynchronize(s);
     for (void* b : bufs) (void)hipFree(b);
-  };
+  }
+  DeviceBufs(const DeviceBufs&) = delete;
+  DeviceBufs& operator=(const DeviceBufs&) = delete;
+  template <class T>
+  T* alloc(size_t count) {  // nullptr when out of device memory
+    void* q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(count * sizeof(T), 256)) != hipSuccess) return nullptr;
+    bufs.push_back(q);
+    return static_cast<T*>(q);
+  }
+};
+
+struct CapturedGraph {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  CapturedGraph() = default;
+  ~CapturedGraph() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+  }
+  CapturedGraph(const CapturedGraph&) = delete;
+  CapturedGraph& operator=(const CapturedGraph&) = delete;
+};
+
+// One fit: the rows, the solver's vectors and the cache with its directory.
+struct RcFit {
   QRows q{};
-  bool int_ok = false;
+  bool int_ok = false;  // exact-integer rows (else FP64 rows)
+  int64_t n = 0;
+  const int32_t* y = nullptr;
+  double* alpha = nullptr;
+  double* f = nullptr;
+  KcPartial* part = nullptr;
+  int nblk = 0;
+  KcState* st = nullptr;
+  int64_t *tags = nullptr, *stamp = nullptr;  // the graph solver's directory: slots entries each
+  int64_t* idx = nullptr;                     // warm start: the nonzero alphas
+  int64_t* dtrace = nullptr;
+  int64_t tcap = 0;
+  double* cache = nullptr;  // slots x ldc doubles
+  int64_t slots = 0, ldc = 0;
+};
+
+// Stage 1: quantise the rows when the plan allows (exact-integer rows), else point at the FP64 rows.
+int upload_rows(hipStream_t s, DeviceBufs& bufs, const double* X_d, const double* sqn_d, int64_t n, int64_t ld,
+                int64_t d, const QuantPlan& P, RcFit* F) {
+  QRows& q = F->q;
   if (P.ok) {
-    auto* Q = static_cast<int8_t*>(dalloc(size_t(n) * size_t(P.kq)));
-    auto* N0 = static_cast<int32_t*>(dalloc(size_t(n) * 4));
-    auto* WN = static_cast<double*>(dalloc(size_t(n) * 8));
-    auto* stw = static_cast<double*>(dalloc(P.step_w.size() * 8));
-    void* aux = dalloc(quantize_aux_bytes(P));
+    auto* Q = bufs.alloc<int8_t>(size_t(n) * size_t(P.kq));
+    auto* N0 = bufs.alloc<int32_t>(size_t(n));
+    auto* WN = bufs.alloc<double>(size_t(n));
+    auto* stw = bufs.alloc<double>(P.step_w.size());
+    void* aux = bufs.alloc<char>(quantize_aux_bytes(P));
     if (!Q || !N0 || !WN || !stw || !aux) {
-      release();
       set_error("row cache: out of device memory for the quantised rows");
       return SVM_ERR_OOM;
     }
-    int rc = quantize_rows(s, X_d, n, ld, P, aux, Q, N0, WN, &int_ok);
-    if (rc) {
-      release();
-      return rc;
-    }
+    int rc = quantize_rows(s, X_d, n, ld, P, aux, Q, N0, WN, &F->int_ok);
+    if (rc) return rc;
     if (hipMemcpyAsync(stw, P.step_w.data(), P.step_w.size() * 8, hipMemcpyHostToDevice, s) != hipSuccess) {
-      release();
       set_error("row cache: H2D failed");
       return SVM_ERR_DEVICE;
     }
@@ -407,9 +431,8 @@ int run_smo_rowcache(DeviceCtx* ctx, const double* X_d, const double* sqn_d, int
     q.main_step0 = P.main0 / 32;
     q.w0 = P.w0;
   }
-  if (!int_ok) {
+  if (!F->int_ok) {
     if (!sqn_d) {
-      release();
       set_error("row cache: FP64 rows need the squared row norms");
       return SVM_ERR_ARG;
     }
@@ -418,167 +441,154 @@ int run_smo_rowcache(DeviceCtx* ctx, const double* X_d, const double* sqn_d, int
     q.ld = ld;
     q.d = d;
   }
-  if (used_int) *used_int = int_ok ? 1 : 0;
-  auto* f = static_cast<double*>(dalloc(size_t(n) * 8));
-  auto* part = static_cast<KcPartial*>(dalloc(size_t(nblk) * sizeof(KcPartial)));
-  auto* st = static_cast<KcState*>(dalloc(sizeof(KcState)));
-  auto* tags = static_cast<int64_t*>(dalloc(size_t(C) * 8));
-  auto* stamp = static_cast<int64_t*>(dalloc(size_t(C) * 8));
-  auto* idx = static_cast<int64_t*>(dalloc(size_t(n) * 8));
-  auto* dtrace = tcap ? static_cast<int64_t*>(dalloc(size_t(tcap) * 16)) : nullptr;
-  double* cache = ctx->ensure_rc_cache(size_t(C) * size_t(ldc) * 8);  // context-held slab
-  if (!f || !part || !st || !tags || !stamp || !idx || !cache || (tcap && !dtrace)) {
-    release();
-    set_error("row cache: out of device memory (cache of %lld rows x %lld)", (long long)C, (long long)n);
-    return SVM_ERR_OOM;
+  return SVM_OK;
+}
+
+// Stage 2: f of the start point (errors surface in the caller's hipGetLastError).
+void init_f_cold(hipStream_t s, const RcFit& F) {
+  hipLaunchKernelGGL(kc_init_cold_kernel, dim3(unsigned((F.n + 255) / 256)), dim3(256), 0, s, F.y, F.alpha, F.f, F.n,
+                     F.st);
+}
+
+void init_f_warm(hipStream_t s, const RcFit& F, double neg_gamma) {
+  // ascending list of nonzero alphas (host compaction: the warm set is small and this runs once)
+  const int64_t n = F.n;
+  std::vector<double> ah(static_cast<size_t>(n));
+  (void)hipMemcpyAsync(ah.data(), F.alpha, size_t(n) * 8, hipMemcpyDeviceToHost, s);
+  (void)hipStreamSynchronize(s);
+  std::vector<int64_t> nz;
+  for (int64_t i = 0; i < n; ++i)
+    if (ah[size_t(i)] != 0.0) nz.push_back(i);
+  if (!nz.empty()) (void)hipMemcpyAsync(F.idx, nz.data(), nz.size() * 8, hipMemcpyHostToDevice, s);
+  if (F.int_ok)
+    hipLaunchKernelGGL(kc_warm_f_kernel<true>, dim3(unsigned((n + kNT - 1) / kNT)), dim3(kNT), 0, s, F.q, F.y, F.alpha,
+                       F.idx, int64_t(nz.size()), F.f, n, neg_gamma, F.st);
+  else
+    hipLaunchKernelGGL(kc_warm_f_kernel<false>, dim3(unsigned((n + kNT - 1) / kNT)), dim3(kNT), 0, s, F.q, F.y, F.alpha,
+                       F.idx, int64_t(nz.size()), F.f, n, neg_gamma, F.st);
+  (void)hipStreamSynchronize(s);
+}
+
+// Stage 3: the persistent solver's misses walk each element's quantised row: give it the coalesced
+// interleaved copy (without it, e.g. out of memory, it reads the row-major rows).
+void interleave_rows(hipStream_t s, DeviceBufs& bufs, RcFit* F) {
+  QRows& q = F->q;
+  auto* Qt = bufs.alloc<int8_t>(size_t(F->n) * size_t(q.kq));
+  if (!Qt) return;
+  const int64_t work = F->n * (q.kq / 16);
+  hipLaunchKernelGGL(interleave_rows_kernel, dim3(unsigned((work + 255) / 256)), dim3(256), 0, s, q.Q, F->n, q.kq, Qt);
+  if (hipGetLastError() == hipSuccess) {
+    q.Qt = Qt;
+    q.n_rows = F->n;
   }
-  int rc = ctx->ensure_pinned(sizeof(KcState) * 3);
-  if (rc) {
-    release();
-    return rc;
-  }
+}
+
+// Stage 5, beyond the persistent solver's shapes: a graph of kKcChunk select / step iterations, replayed
+// until the state's stop flag is set.
+int solve_graph(DeviceCtx* ctx, const RcFit& F, const svm_params& p, svm_result* r, int64_t* trace,
+                std::chrono::steady_clock::time_point t0) {
+  hipStream_t s = ctx->stream;
   const double neg_gamma = -p.gamma;
-  // tags = -1 (empty), stamps = 0
-  (void)hipMemsetAsync(tags, 0xFF, size_t(C) * 8, s);
-  (void)hipMemsetAsync(stamp, 0, size_t(C) * 8, s);
-  if (!warm) {
-    hipLaunchKernelGGL(kc_init_cold_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, y, alpha, f, n, st);
-  } else {
-    // ascending list of nonzero alphas (host compaction: the warm set is small and this runs once)
-    std::vector<double> ah(static_cast<size_t>(n));
-    (void)hipMemcpyAsync(ah.data(), alpha, size_t(n) * 8, hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    std::vector<int64_t> nz;
-    for (int64_t i = 0; i < n; ++i)
-      if (ah[size_t(i)] != 0.0) nz.push_back(i);
-    if (!nz.empty()) (void)hipMemcpyAsync(idx, nz.data(), nz.size() * 8, hipMemcpyHostToDevice, s);
-    if (int_ok)
-      hipLaunchKernelGGL(kc_warm_f_kernel<true>, dim3(unsigned((n + kNT - 1) / kNT)), dim3(kNT), 0, s, q, y, alpha,
-                         idx, int64_t(nz.size()), f, n, neg_gamma, st);
-    else
-      hipLaunchKernelGGL(kc_warm_f_kernel<false>, dim3(unsigned((n + kNT - 1) / kNT)), dim3(kNT), 0, s, q, y, alpha,
-                         idx, int64_t(nz.size()), f, n, neg_gamma, st);
-    (void)hipStreamSynchronize(s);
-  }
-  if (hipGetLastError() != hipSuccess) {
-    release();
-    set_error("row cache: init launch failed");
-    return SVM_ERR_DEVICE;
-  }
-  // Default: the persistent solver (one launch, register-resident state, directory in LDS), whose
-  // misses walk each element's quantised row: give it the coalesced interleaved copy.
-  if (int_ok) {
-    auto* Qt = static_cast<int8_t*>(dalloc(size_t(n) * size_t(q.kq)));
-    if (Qt) {
-      const int64_t work = n * (q.kq / 16);
-      hipLaunchKernelGGL(interleave_rows_kernel, dim3(unsigned((work + 255) / 256)), dim3(256), 0, s, q.Q, n, q.kq,
-                         Qt);
-      if (hipGetLastError() == hipSuccess) {
-        q.Qt = Qt;
-        q.n_rows = n;
-      }
-    }
-  }
-  const char* vb = getenv("SVM355_RC_VERBOSE");
-  const bool verbose = vb && atoi(vb);
-  auto ms_since = [](std::chrono::steady_clock::time_point a) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-  };
-  if (verbose) (void)hipStreamSynchronize(s);
-  const double t_prep = ms_since(t0);
-  rc = run_smo_rc_persistent(ctx, q, int_ok, cache, ldc, C, y, alpha, f, n, p, r, trace, tcap);
-  if (rc == kRcNotApplicable && p.wss == 2) {
-    release();
-    set_error("row cache: second-order selection (wss = 2) needs the persistent row-cache solver (exact-integer "
-              "rows, n <= 1,048,576)");
-    return SVM_ERR_ARG;
-  }
-  if (rc != kRcNotApplicable) {
-    if (verbose)
-      fprintf(stderr, "[rowcache n=%lld] cache %lld slots (%.1f GB, slab %.1f GB) | prep (alloc, quantise, interleave) "
-              "%.1f ms | persistent solve %.1f ms, %lld iterations\n", (long long)n, (long long)C,
-              double(C) * double(ldc) * 8e-9, double(ctx->rc_cache_bytes) * 1e-9, t_prep, ms_since(t0) - t_prep,
-              (long long)(r ? r->iterations : -1));
-    release();
-    return rc;
-  }
-  const int64_t nsets = C / 2;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
+  const int64_t nsets = F.slots / 2, n = F.n;
+  CapturedGraph g;
   hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
   for (int it = 0; e == hipSuccess && it < kKcChunk; ++it) {
-    if (int_ok) {
-      hipLaunchKernelGGL(kc_select_kernel<true>, dim3(nblk), dim3(kNT), 0, s, q, cache, ldc, y, alpha, f, n, st,
-                         part, p.C, p.eps, neg_gamma);
-      hipLaunchKernelGGL(kc_step_kernel<true>, dim3(1), dim3(kNT), 0, s, part, nblk, q, y, alpha, n, st, tags, stamp,
-                         nsets, p.C, p.eps, p.tau, neg_gamma, p.max_iter, dtrace, tcap);
+    if (F.int_ok) {
+      hipLaunchKernelGGL(kc_select_kernel<true>, dim3(F.nblk), dim3(kNT), 0, s, F.q, F.cache, F.ldc, F.y, F.alpha, F.f, n,
+                         F.st, F.part, p.C, p.eps, neg_gamma);
+      hipLaunchKernelGGL(kc_step_kernel<true>, dim3(1), dim3(kNT), 0, s, F.part, F.nblk, F.q, F.y, F.alpha, n, F.st, F.tags,
+                         F.stamp, nsets, p.C, p.eps, p.tau, neg_gamma, p.max_iter, F.dtrace, F.tcap);
     } else {
-      hipLaunchKernelGGL(kc_select_kernel<false>, dim3(nblk), dim3(kNT), 0, s, q, cache, ldc, y, alpha, f, n, st,
-                         part, p.C, p.eps, neg_gamma);
-      hipLaunchKernelGGL(kc_step_kernel<false>, dim3(1), dim3(kNT), 0, s, part, nblk, q, y, alpha, n, st, tags,
-                         stamp, nsets, p.C, p.eps, p.tau, neg_gamma, p.max_iter, dtrace, tcap);
+      hipLaunchKernelGGL(kc_select_kernel<false>, dim3(F.nblk), dim3(kNT), 0, s, F.q, F.cache, F.ldc, F.y, F.alpha, F.f, n,
+                         F.st, F.part, p.C, p.eps, neg_gamma);
+      hipLaunchKernelGGL(kc_step_kernel<false>, dim3(1), dim3(kNT), 0, s, F.part, F.nblk, F.q, F.y, F.alpha, n, F.st,
+                         F.tags, F.stamp, nsets, p.C, p.eps, p.tau, neg_gamma, p.max_iter, F.dtrace, F.tcap);
     }
   }
-  hipError_t e2 = hipStreamEndCapture(s, &graph);
+  const hipError_t e2 = hipStreamEndCapture(s, &g.graph);
   if (e == hipSuccess) e = e2;
-  if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+  if (e == hipSuccess) e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
   if (e != hipSuccess) {
-    if (graph) (void)hipGraphDestroy(graph);
-    release();
     set_error("row cache: graph capture failed: %s", hipGetErrorString(e));
     return SVM_ERR_DEVICE;
   }
   KcState* hst = static_cast<KcState*>(ctx->pinned);
-  const int64_t max_replays = p.max_iter / kKcChunk + 4;
-  hipEvent_t ev[2];
-  (void)hipEventCreateWithFlags(&ev[0], hipEventDisableTiming);
-  (void)hipEventCreateWithFlags(&ev[1], hipEventDisableTiming);
-  hst[0].stop = hst[1].stop = 0;
-  auto enqueue = [&](int slot) {
-    hipError_t er = hipGraphLaunch(exec, s);
-    if (er == hipSuccess) er = hipMemcpyAsync(&hst[slot], st, sizeof(KcState), hipMemcpyDeviceToHost, s);
-    if (er == hipSuccess) er = hipEventRecord(ev[slot], s);
-    return er;
-  };
-  e = enqueue(0);
-  for (int64_t rep = 0; e == hipSuccess; ++rep) {
-    if (rep + 1 < max_replays) e = enqueue(int((rep + 1) & 1));
-    if (e != hipSuccess) break;
-    e = hipEventSynchronize(ev[rep & 1]);
-    if (e != hipSuccess || hst[rep & 1].stop || rep + 1 >= max_replays) break;
+  const int rc = replay_until_stop(s, g.exec, F.st, hst, p.max_iter / kKcChunk + 4, "row cache SMO");
+  if (rc) return rc;
+  return finish_smo(hst[kHstFinal], r, trace, F.dtrace, F.tcap, t0, "row cache SMO");
+}
+
+}  // namespace
+
+// SMO with the on-demand row cache.  X_d: preprocessed rows (n x ld); P: quantisation plan (P.ok ->
+// exact-integer rows, else FP64 rows with sqn_d).  cache_bytes: HBM budget for the row cache.
+int run_smo_rowcache(DeviceCtx* ctx, const double* X_d, const double* sqn_d, int64_t n, int64_t ld, int64_t d,
+                     const QuantPlan& P, const int32_t* y, double* alpha, int32_t warm, const svm_params& p,
+                     svm_result* r, size_t cache_bytes, int64_t* trace, int64_t trace_cap, int32_t* used_int) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const SmoKnobs k = read_smo_knobs();
+  hipStream_t s = ctx->stream;
+  RcFit F;
+  F.n = n;
+  F.y = y;
+  F.alpha = alpha;
+  F.ldc = (n + 1) / 2 * 2;
+  F.slots = std::min<int64_t>(int64_t(cache_bytes / (size_t(F.ldc) * 8)), 2 * ((n + 1) / 2)) / 2 * 2;
+  if (F.slots < 4) {
+    set_error("row cache: %zu bytes hold fewer than 4 rows of %lld doubles", cache_bytes, (long long)n);
+    return SVM_ERR_OOM;
   }
-  hipError_t es = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = es;
-  KcState fin{};
-  if (e == hipSuccess) e = hipMemcpy(&fin, st, sizeof(KcState), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && tcap) {
-    const int64_t nt = std::min<int64_t>(fin.num_iter - 1, tcap);
-    if (nt > 0) e = hipMemcpy(trace, dtrace, size_t(nt) * 16, hipMemcpyDeviceToHost);
+  F.nblk = int(std::min<int64_t>((n + kNT - 1) / kNT, 2048));
+  F.tcap = trace ? std::max<int64_t>(trace_cap, 0) : 0;
+  DeviceBufs bufs(s);
+  int rc = upload_rows(s, bufs, X_d, sqn_d, n, ld, d, P, &F);
+  if (rc) return rc;
+  if (used_int) *used_int = F.int_ok ? 1 : 0;
+  F.f = bufs.alloc<double>(size_t(n));
+  F.part = bufs.alloc<KcPartial>(size_t(F.nblk));
+  F.st = bufs.alloc<KcState>(1);
+  F.tags = bufs.alloc<int64_t>(size_t(F.slots));
+  F.stamp = bufs.alloc<int64_t>(size_t(F.slots));
+  F.idx = bufs.alloc<int64_t>(size_t(n));
+  F.dtrace = F.tcap ? bufs.alloc<int64_t>(size_t(F.tcap) * 2) : nullptr;
+  F.cache = ctx->ensure_rc_cache(size_t(F.slots) * size_t(F.ldc) * 8);  // context-held slab
+  if (!F.f || !F.part || !F.st || !F.tags || !F.stamp || !F.idx || !F.cache || (F.tcap && !F.dtrace)) {
+    set_error("row cache: out of device memory (cache of %lld rows x %lld)", (long long)F.slots, (long long)n);
+    return SVM_ERR_OOM;
   }
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  (void)hipGraphExecDestroy(exec);
-  (void)hipGraphDestroy(graph);
-  release();
-  if (e != hipSuccess) {
-    set_error("row cache SMO: %s", hipGetErrorString(e));
+  rc = ctx->ensure_pinned(sizeof(KcState) * kHstSlots);
+  if (rc) return rc;
+  // tags = -1 (empty), stamps = 0
+  (void)hipMemsetAsync(F.tags, 0xFF, size_t(F.slots) * 8, s);
+  (void)hipMemsetAsync(F.stamp, 0, size_t(F.slots) * 8, s);
+  if (warm)
+    init_f_warm(s, F, -p.gamma);
+  else
+    init_f_cold(s, F);
+  if (hipGetLastError() != hipSuccess) {
+    set_error("row cache: init launch failed");
     return SVM_ERR_DEVICE;
   }
-  if (!fin.stop) {
-    set_error("row cache SMO: solver did not stop within its budget");
-    return SVM_ERR_INTERNAL;
+  if (F.int_ok) interleave_rows(s, bufs, &F);
+  auto ms_since = [](std::chrono::steady_clock::time_point a) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+  };
+  if (k.rc_verbose) (void)hipStreamSynchronize(s);
+  const double t_prep = ms_since(t0);
+  // Stage 4, the default: the persistent solver (one launch, register-resident state, directory in LDS).
+  rc = run_smo_rc_persistent(ctx, F.q, F.int_ok, F.cache, F.ldc, F.slots, y, alpha, F.f, n, p, r, trace, F.tcap, k);
+  if (rc == kRcNotApplicable && p.wss == 2) {
+    set_error("row cache: second-order selection (wss = 2) needs the persistent row-cache solver (exact-integer "
+              "rows, n <= 1,048,576)");
+    return SVM_ERR_ARG;
   }
-  if (r) {
-    r->iterations = fin.num_iter;
-    r->b_high = fin.b_high;
-    r->b_low = fin.b_low;
-    r->b = (fin.b_high + fin.b_low) / 2;
-    r->stop_reason = fin.stop;
-    r->reserved = 0;
-    r->n_sv = -1;
-    r->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return SVM_OK;
+  if (rc == kRcNotApplicable) return solve_graph(ctx, F, p, r, trace, t0);
+  if (k.rc_verbose)
+    fprintf(stderr, "[rowcache n=%lld] cache %lld slots (%.1f GB, slab %.1f GB) | prep (alloc, quantise, interleave) "
+            "%.1f ms | persistent solve %.1f ms, %lld iterations\n", (long long)n, (long long)F.slots,
+            double(F.slots) * double(F.ldc) * 8e-9, double(ctx->rc_cache_bytes) * 1e-9, t_prep, ms_since(t0) - t_prep,
+            (long long)(r ? r->iterations : -1));
+  return rc;
 }
 
 }  // namespace svm355

@@ -21,13 +21,13 @@
 // trajectory is bit-identical to the CPU oracle.
 #include <atomic>
 #include <chrono>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "ctx.h"
 #include "persist.h"
 #include "qrows.h"
+#include "smo_host.h"
+#include "smo_plan.h"
 
 namespace svm355 {
 namespace {
@@ -622,482 +622,378 @@ __global__ __launch_bounds__(kSingleNT) void smo_single_kernel(
 
 }  // namespace
 
+// ---- host drivers ------------------------------------------------------------------------------------------
 namespace {
 
+static_assert(kPlanMaxG == kMaxG && kPlanSentinel == kSentinel, "smo_plan.h and persist.h disagree on a shape constant");
+
+// Polls a workgroup spends waiting for a record before the solve gives up (error word 1).
+constexpr int64_t kSpinXcdLocal = int64_t(1) << 22;
+constexpr int64_t kSpinDeviceWide = int64_t(1) << 24;
+
 // XCD-local registration window (SVM355_PSMO_REG_US overrides, microseconds).
-unsigned long long register_ticks() {
-  if (const char* v = getenv("SVM355_PSMO_REG_US")) return std::max(1ull, strtoull(v, nullptr, 10)) * 100ull;
-  return kRegisterTicks;
-}
+unsigned long long register_ticks(const SmoKnobs& k) { return k.reg_ticks ? k.reg_ticks : kRegisterTicks; }
 
 // Dynamic LDS reserved (unused) by the XCD-local launches so that at most one workgroup lands on a
 // CU: the team then spreads over the XCD's CUs instead of doubling up, e.g. 2.75 instead of 3.25
 // us/iter at n = 24k (SVM355_PSMO_LDS overrides; 0 = none).  1024-thread workgroups need none.
-size_t xcd_lds_pad(int NT) {
-  if (const char* v = getenv("SVM355_PSMO_LDS")) return size_t(std::max(0, atoi(v)));
+size_t xcd_lds_pad(int NT, const SmoKnobs& k) {
+  if (k.lds_pad >= 0) return size_t(k.lds_pad);
   return NT == 1024 ? 0 : size_t(96) << 10;
 }
 
-template <class Kern>
-void allow_lds(Kern k, size_t bytes) {
-  if (bytes > (size_t(64) << 10))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              int(bytes));
+// The exchange area of a persistent solve in the workspace: 2 x max_g records, 256 bytes of control words
+// and the exchange-skew stamps, zeroed as one piece before every launch.
+struct Exchange {
+  unsigned long long* rec = nullptr;         // candidate records, both epoch parities
+  unsigned* err = nullptr;                   // error word: 1 a record wait timed out, 2 no XCD-local team formed
+  unsigned* reg = nullptr;                   // XCD-local registration words (xcd_register)
+  unsigned long long* stamps = nullptr;      // 8 phase totals of the STAMP kernels
+  unsigned long long* stamp_from = nullptr;  // first stamped epoch (row cache; 0: kStampFrom)
+  unsigned long long* skew = nullptr;        // (kMaxG + 1) x kSkewEpochs publication / sweep-done times
+  size_t bytes = 0;
+  void carve(WsCarver& c, int max_g) {
+    const size_t rec_bytes = size_t(2) * max_g * kRecStride * 8;
+    bytes = rec_bytes + 256 + (size_t(kMaxG) + 1) * kSkewEpochs * 8;
+    char* base = c.take<char>(bytes);
+    if (!base) return;
+    rec = reinterpret_cast<unsigned long long*>(base);
+    err = reinterpret_cast<unsigned*>(base + rec_bytes);
+    reg = err + 2;
+    stamps = reinterpret_cast<unsigned long long*>(err) + 8;
+    stamp_from = stamps + 8;
+    skew = stamps + kSkewBase;
+  }
+};
+
+// What every resident-Gram solver works on: the Gram, the labels, alpha (in / out), f and the solver state in
+// the workspace, and the device trace (nullptr / 0: none).
+struct Resident {
+  const double* K;
+  int64_t ldk;
+  const int32_t* y;
+  double* alpha;
+  double* f;
+  int64_t n;
+  SmoState* st;
+  int64_t* dtrace;
+  int64_t tcap;
+};
+
+// One launch; more than 64 KB of dynamic LDS needs the kernel's limit raised first.
+template <class Kern, class... Args>
+void launch(Kern kern, hipStream_t s, int grid, int nt, size_t lds, Args... args) {
+  if (lds > (size_t(64) << 10))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              int(lds));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, s, args...);
 }
 
+// Compile-time shape lists: for_shape calls fn(Shape<A, B>{}) for the listed shape equal to (a, b) and
+// returns whether one was.  The lists are the kernels this file instantiates.
+template <int A, int B>
+struct Shape {
+  static constexpr int a = A, b = B;
+};
+template <class...>
+struct Shapes {};
+template <class Fn, int... A, int... B>
+bool for_shape(Shapes<Shape<A, B>...>, int a, int b, Fn&& fn) {
+  // a left fold: the compiler expands it first shape first, so the kernels keep the lists' order in the code object
+  return (... || (a == A && b == B && (fn(Shape<A, B>{}), true)));
+}
+// (threads per workgroup, points per thread)
+using PersistentShapes = Shapes<Shape<256, 1>, Shape<256, 2>, Shape<256, 4>, Shape<256, 8>, Shape<256, 16>, Shape<512, 1>,
+                                Shape<512, 2>, Shape<512, 4>, Shape<512, 8>, Shape<1024, 1>, Shape<1024, 2>, Shape<1024, 4>>;
+using SingleShapes = Shapes<Shape<256, 1>, Shape<256, 2>, Shape<256, 4>, Shape<256, 8>, Shape<256, 16>, Shape<256, 32>,
+                            Shape<512, 1>, Shape<512, 2>, Shape<512, 4>, Shape<512, 8>, Shape<512, 16>, Shape<1024, 1>,
+                            Shape<1024, 2>, Shape<1024, 4>, Shape<1024, 8>>;
+using MultiShapes = Shapes<Shape<256, 1>, Shape<256, 2>, Shape<512, 1>, Shape<512, 2>, Shape<512, 4>>;
+// (points per thread of a 512-thread workgroup, records per sweep lane)
+using RcShapes = Shapes<Shape<1, 1>, Shape<2, 1>, Shape<4, 1>, Shape<8, 1>, Shape<1, 2>, Shape<2, 2>, Shape<4, 2>,
+                        Shape<8, 2>, Shape<1, 4>, Shape<2, 4>, Shape<4, 4>, Shape<8, 4>>;
+
+// ---- diagnostics on stderr (SVM355_PSMO_STAMP, the XCD fallback) ---------------------------------------------
+int report_single_stamps(const SmoPlan& pl, const unsigned long long* stamps) {
+  unsigned long long hs[8];
+  SVMD_CHECK(hipMemcpy(hs, stamps, sizeof(hs), hipMemcpyDeviceToHost));
+  const double cnt = double(kStampCount);
+  fprintf(stderr, "[single stamps NT=%d E=%d] cycles/iter: scan+wavered %.0f | barrier %.0f | blockred %.0f | "
+          "loads %.0f | scalar %.0f | update %.0f | us/iter %.3f\n", pl.NT, pl.E, hs[0] / cnt, hs[1] / cnt, hs[2] / cnt,
+          hs[3] / cnt, hs[4] / cnt, hs[5] / cnt, double(hs[7]) / 100.0 / cnt);
+  return SVM_OK;
+}
+
+int report_psmo_stamps(const SmoPlan& pl, const Exchange& x) {
+  unsigned long long hs[8];
+  SVMD_CHECK(hipMemcpy(hs, x.stamps, sizeof(hs), hipMemcpyDeviceToHost));
+  const double cnt = double(kStampCount), mhz = hs[7] ? double(hs[0] + hs[1] + hs[2] + hs[3] + hs[4] + hs[5] + hs[6]) / (double(hs[7]) / 100.0) : 0.0;
+  fprintf(stderr, "[psmo stamps NT=%d G=%d E=%d] cycles/iter: scan+wavered %.0f | barrier1 %.0f | publish %.0f | sweep %.0f | "
+          "globalred+barrier2 %.0f | loads %.0f | update %.0f | clock %.0f MHz | us/iter %.3f\n", pl.NT, pl.G, pl.E,
+          hs[0] / cnt, hs[1] / cnt, hs[2] / cnt, hs[3] / cnt, hs[4] / cnt, hs[5] / cnt, hs[6] / cnt, mhz,
+          double(hs[7]) / 100.0 / cnt);
+  return SVM_OK;
+}
+
+// Exchange skew: spread of the record publications, and workgroup 0's wait past the last.
+int report_psmo_skew(int G, const Exchange& x) {
+  std::vector<unsigned long long> sk(size_t(kMaxG + 1) * kSkewEpochs);
+  SVMD_CHECK(hipMemcpy(sk.data(), x.skew, sk.size() * 8, hipMemcpyDeviceToHost));
+  double spread = 0.0, tail = 0.0;
+  std::vector<double> late(size_t(G), 0.0);  // mean lateness of each workgroup behind the first
+  int used = 0;
+  for (uint32_t e = 0; e < kSkewEpochs; ++e) {
+    unsigned long long lo = ~0ull, hi = 0;
+    for (int q = 0; q < G; ++q) {
+      const unsigned long long v = sk[size_t(q) * kSkewEpochs + e];
+      lo = std::min(lo, v);
+      hi = std::max(hi, v);
+    }
+    const unsigned long long done = sk[size_t(kMaxG) * kSkewEpochs + e];
+    if (!lo || !done || done < hi) continue;
+    ++used;
+    spread += double(hi - lo) * 10.0;
+    tail += double(done - hi) * 10.0;
+    for (int q = 0; q < G; ++q) late[size_t(q)] += double(sk[size_t(q) * kSkewEpochs + e] - lo) * 10.0;
+  }
+  if (used) {
+    fprintf(stderr, "[psmo skew G=%d, %d epochs] publication spread %.0f ns | last publication -> WG0 sweep done %.0f ns\n",
+            G, used, spread / used, tail / used);
+    fprintf(stderr, "[psmo skew] mean lateness per workgroup (ns):");
+    for (int q = 0; q < G; ++q) fprintf(stderr, " %.0f", late[size_t(q)] / used);
+    fprintf(stderr, "\n");
+  }
+  return SVM_OK;
+}
+
+int report_rc_stamps(const RcPlan& pl, const Exchange& x) {
+  unsigned long long hs[8];
+  SVMD_CHECK(hipMemcpy(hs, x.stamps, sizeof(hs), hipMemcpyDeviceToHost));
+  const double cnt = double(kStampCount);
+  fprintf(stderr, "[rc stamps G=%d E=%d RPL=%d] cycles/iter: scan+wavered %.0f | barrier1 %.0f | publish %.0f | sweep %.0f | "
+          "globalred+choose+barrier2 %.0f | rows (hit read / miss fill) %.0f | update %.0f | us/iter %.3f\n", pl.G, pl.E, pl.rpl,
+          hs[0] / cnt, hs[1] / cnt, hs[2] / cnt, hs[3] / cnt, hs[4] / cnt, hs[5] / cnt, hs[6] / cnt,
+          double(hs[7]) / 100.0 / cnt);
+  return SVM_OK;
+}
+
+void report_xcd_fallback(const SmoPlan& pl, unsigned landed, const SmoKnobs& k) {
+  static std::atomic<int> reported{0};
+  if (reported.fetch_add(1) == 0)
+    fprintf(stderr, "[svm355] XCD-local SMO: fewer than %d workgroups registered on XCD 0 within %.0f us "
+            "(%u landed there in all, grid %d; another XCD-local solve running concurrently?); running the "
+            "device-wide solver (reported once)\n", pl.G, double(register_ticks(k)) / 100.0, landed, 16 * pl.G);
+}
+
+// ---- resident Gram: the persistent solver.  (Every solve_* leaves the final state in the pinned slot
+// kHstFinal.) ------------------------------------------------------------------------------------------------
 // Launch the persistent solver for a (threads per workgroup NT, elements per thread E) shape.
 template <int NT, int E>
-int launch_persistent_e(hipStream_t s, int G, const double* K, int64_t ldk, const int32_t* y, double* alpha,
-                        double* f, int64_t n, unsigned long long* slots, SmoState* st, double C, double eps,
-                        double tau, int64_t max_iter, int64_t* trace, int64_t tcap, unsigned* err, bool xlocal,
-                        bool wss2) {
-  unsigned long long* stamps = reinterpret_cast<unsigned long long*>(err) + 8;
+void launch_persistent_e(hipStream_t s, const SmoPlan& pl, const Resident& P, const svm_params& p, const Exchange& x,
+                         const SmoKnobs& k) {
+  const bool wss2 = p.wss == 2;        // opt-in second-order selection
+  const bool stamp = !wss2 && k.stamp;  // (which has no stamp variant)
+  auto kern = wss2 ? (pl.xlocal ? smo_persistent_kernel<NT, E, false, true, true>
+                                : smo_persistent_kernel<NT, E, false, false, true>)
+              : pl.xlocal ? (stamp ? smo_persistent_kernel<NT, E, true, true> : smo_persistent_kernel<NT, E, false, true>)
+                          : (stamp ? smo_persistent_kernel<NT, E, true> : smo_persistent_kernel<NT, E, false>);
   const int64_t slice = int64_t(NT) * E;
-  if (wss2) {  // opt-in second-order selection (no stamp variant)
-    if (xlocal) {
-      const size_t lds = xcd_lds_pad(NT);
-      allow_lds(smo_persistent_kernel<NT, E, false, true, true>, lds);
-      hipLaunchKernelGGL((smo_persistent_kernel<NT, E, false, true, true>), dim3(16 * G), dim3(NT), lds, s, K, ldk, y,
-                         alpha, f, n, slice, slots, st, C, eps, tau, max_iter, trace, tcap, err, int64_t(1) << 22,
-                         stamps, G, register_ticks());
-    } else {
-      hipLaunchKernelGGL((smo_persistent_kernel<NT, E, false, false, true>), dim3(G), dim3(NT), 0, s, K, ldk, y, alpha,
-                         f, n, slice, slots, st, C, eps, tau, max_iter, trace, tcap, err, int64_t(1) << 24, stamps);
-    }
-    SVMD_LAUNCH_CHECK();
-    return SVM_OK;
-  }
-  const char* sv = getenv("SVM355_PSMO_STAMP");
-  if (xlocal) {
-    // Over-provisioned grid: ~2*G workgroups per XCD under round-robin dispatch; G of XCD 0's join.
-    const int grid = 16 * G;
-    const size_t lds = xcd_lds_pad(NT);
-    if (sv && atoi(sv)) {
-      allow_lds(smo_persistent_kernel<NT, E, true, true>, lds);
-      hipLaunchKernelGGL((smo_persistent_kernel<NT, E, true, true>), dim3(grid), dim3(NT), lds, s, K, ldk, y, alpha,
-                         f, n, slice, slots, st, C, eps, tau, max_iter, trace, tcap, err, int64_t(1) << 22, stamps, G,
-                         register_ticks());
-    } else {
-      allow_lds(smo_persistent_kernel<NT, E, false, true>, lds);
-      hipLaunchKernelGGL((smo_persistent_kernel<NT, E, false, true>), dim3(grid), dim3(NT), lds, s, K, ldk, y, alpha,
-                         f, n, slice, slots, st, C, eps, tau, max_iter, trace, tcap, err, int64_t(1) << 22, stamps, G,
-                         register_ticks());
-    }
-    SVMD_LAUNCH_CHECK();
-    return SVM_OK;
-  }
-  if (sv && atoi(sv))
-    hipLaunchKernelGGL((smo_persistent_kernel<NT, E, true>), dim3(G), dim3(NT), 0, s, K, ldk, y, alpha, f, n, slice,
-                       slots, st, C, eps, tau, max_iter, trace, tcap, err, int64_t(1) << 24, stamps);
+  if (pl.xlocal)  // over-provisioned grid: ~2*G workgroups per XCD under round-robin dispatch; G of XCD 0's join
+    launch(kern, s, 16 * pl.G, NT, xcd_lds_pad(NT, k), P.K, P.ldk, P.y, P.alpha, P.f, P.n, slice, x.rec, P.st, p.C, p.eps,
+           p.tau, p.max_iter, P.dtrace, P.tcap, x.err, kSpinXcdLocal, x.stamps, pl.G, register_ticks(k));
   else
-    hipLaunchKernelGGL((smo_persistent_kernel<NT, E, false>), dim3(G), dim3(NT), 0, s, K, ldk, y, alpha, f, n,
-                       slice, slots, st, C, eps, tau, max_iter, trace, tcap, err, int64_t(1) << 24, stamps);
+    launch(kern, s, pl.G, NT, 0, P.K, P.ldk, P.y, P.alpha, P.f, P.n, slice, x.rec, P.st, p.C, p.eps, p.tau, p.max_iter,
+           P.dtrace, P.tcap, x.err, kSpinDeviceWide, x.stamps, 0, kRegisterTicks);
+}
+
+int launch_persistent(hipStream_t s, const SmoPlan& pl, const Resident& P, const svm_params& p, const Exchange& x,
+                      const SmoKnobs& k) {
+  if (!for_shape(PersistentShapes{}, pl.NT, pl.E, [&](auto sh) {
+        launch_persistent_e<decltype(sh)::a, decltype(sh)::b>(s, pl, P, p, x, k);
+      })) {
+    set_error("persistent SMO: no kernel for NT=%d E=%d", pl.NT, pl.E);
+    return SVM_ERR_INTERNAL;
+  }
   SVMD_LAUNCH_CHECK();
   return SVM_OK;
 }
 
-// Grid shape: NT threads per workgroup (SVM355_PSMO_NT, default kDefaultNT), the smallest E in
-// {1, 2, 4, 8, 16} (capped per NT) with G = ceil(n / (NT*E)) <= target workgroups (SVM355_PSMO_WG,
-// default 64; all co-resident, one sweep pass).
-constexpr int kDefaultNT = 512;
-constexpr int kXcdMaxG = 32;              // workgroups of the XCD-local solver (one XCD has 32 CUs)
-constexpr int64_t kXcdDefaultMax = 65536;  // default n limit of the XCD-local solver (tuned on MI355X)
-constexpr int64_t kSingleDefaultMax = 2048;  // auto mode: single workgroup up to this n (tuned on MI355X)
-constexpr int kSingleDefaultNT = 512;
-int persistent_grid(int64_t n, int* G_out, int* E_out, int* NT_out, int gcap) {
-  int target = 64;
-  if (const char* v = getenv("SVM355_PSMO_WG")) target = std::max(1, std::min(kMaxG, atoi(v)));
-  if (gcap > 0) target = std::min(target, gcap);
-  // Measured on MI355X (profiles/r1_smo_launch_shape.txt): the XCD-local solver wants 256-thread
-  // workgroups up to ~16k points and 512-thread ones above, one per CU (xcd_lds_pad): 2.45-3.44
-  // us/iter from 10k to 60k, 4-17 % below the device-wide exchange.
-  int nt = kDefaultNT;
-  if (gcap > 0 && n <= 16000) nt = 256;
-  if (const char* v = getenv("SVM355_PSMO_NT")) nt = atoi(v);
-  if (nt != 256 && nt != 512 && nt != 1024) nt = kDefaultNT;
-  const int emax = nt == 256 ? 16 : nt == 512 ? 8 : 4;
-  for (int E = 1; E <= emax; E *= 2) {
-    const int64_t per_wg = int64_t(nt) * E;
-    const int64_t G = (n + per_wg - 1) / per_wg;
-    if (G <= target) {
-      *G_out = int(std::max<int64_t>(1, G));
-      *E_out = E;
-      *NT_out = nt;
-      return 1;
-    }
+// One launch; an XCD-local team that cannot form has touched nothing, and the solve runs device-wide instead.
+int solve_persistent(DeviceCtx* ctx, SmoPlan pl, const Resident& P, const svm_params& p, const Exchange& x,
+                     const SmoKnobs& k) {
+  hipStream_t s = ctx->stream;
+  SmoState* hst = static_cast<SmoState*>(ctx->pinned);
+  unsigned herr = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    SVMD_CHECK(hipMemsetAsync(x.rec, 0, x.bytes, s));  // epochs restart at 1 every launch
+    const int lrc = launch_persistent(s, pl, P, p, x, k);
+    if (lrc) return lrc;
+    SVMD_CHECK(hipMemcpyAsync(&hst[kHstFinal], P.st, sizeof(SmoState), hipMemcpyDeviceToHost, s));
+    SVMD_CHECK(hipMemcpyAsync(&herr, x.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    SVMD_CHECK(hipStreamSynchronize(s));
+    if (!(pl.xlocal && herr == 2)) break;
+    // XCD 0 did not receive enough workgroups: nothing was touched, run the device-wide kernel.
+    unsigned reg[2] = {0, 0};
+    SVMD_CHECK(hipMemcpy(reg, x.reg, sizeof(reg), hipMemcpyDeviceToHost));
+    report_xcd_fallback(pl, reg[0], k);
+    if (!replan_smo_device_wide(P.n, k, &pl)) break;
+    herr = 0;
   }
-  return 0;
-}
-
-int launch_persistent(hipStream_t s, int NT, int E, int G, const double* K, int64_t ldk, const int32_t* y,
-                      double* alpha, double* f, int64_t n, unsigned long long* slots, SmoState* st, double C,
-                      double eps, double tau, int64_t max_iter, int64_t* trace, int64_t tcap, unsigned* err,
-                      bool xlocal, bool wss2) {
-#define SVM_PSMO_CASE(nt, e)                                                                                 \
-  if (NT == nt && E == e)                                                                                    \
-    return launch_persistent_e<nt, e>(s, G, K, ldk, y, alpha, f, n, slots, st, C, eps, tau, max_iter, trace, \
-                                      tcap, err, xlocal, wss2);
-  SVM_PSMO_CASE(256, 1) SVM_PSMO_CASE(256, 2) SVM_PSMO_CASE(256, 4) SVM_PSMO_CASE(256, 8) SVM_PSMO_CASE(256, 16)
-  SVM_PSMO_CASE(512, 1) SVM_PSMO_CASE(512, 2) SVM_PSMO_CASE(512, 4) SVM_PSMO_CASE(512, 8)
-  SVM_PSMO_CASE(1024, 1) SVM_PSMO_CASE(1024, 2) SVM_PSMO_CASE(1024, 4)
-#undef SVM_PSMO_CASE
-  set_error("persistent SMO: no kernel for NT=%d E=%d", NT, E);
-  return SVM_ERR_INTERNAL;
-}
-
-int finish_smo(const SmoState& fin, svm_result* r, int64_t* trace, const int64_t* dtrace, int64_t tcap,
-               std::chrono::steady_clock::time_point t0) {
-  if (!fin.stop) {
-    set_error("svmd_smo: solver did not stop within its budget");
-    return SVM_ERR_INTERNAL;
+  if (herr) {
+    set_error("svmd_smo: persistent solver timed out waiting for a workgroup record (G=%d)", pl.G);
+    return SVM_ERR_DEVICE;
   }
-  if (tcap) {
-    const int64_t nt = std::min<int64_t>(fin.num_iter - 1, tcap);
-    if (nt > 0) SVMD_CHECK(hipMemcpy(trace, dtrace, size_t(nt) * 16, hipMemcpyDeviceToHost));
-  }
-  if (r) {
-    r->iterations = fin.num_iter;
-    r->b_high = fin.b_high;
-    r->b_low = fin.b_low;
-    r->b = (fin.b_high + fin.b_low) / 2;
-    r->stop_reason = fin.stop;
-    r->reserved = 0;
-    r->n_sv = -1;  // filled by the caller (needs alpha on the host or a device count)
-    r->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (k.stamp) {
+    const int rc = report_psmo_stamps(pl, x);
+    if (rc) return rc;
+    if (k.stamp == 2) return report_psmo_skew(pl.G, x);
   }
   return SVM_OK;
 }
 
 }  // namespace
 
+// ---- row cache ---------------------------------------------------------------------------------------------
 namespace {
-template <int E, bool INT, bool STAMP, int RPL, bool WSS2 = false>
-void launch_rc_e(hipStream_t s, int G, size_t lds, const QRows& q, double* cache, int64_t ldc, int64_t nslots,
-                 double neg_gamma, const int32_t* y, double* alpha, double* f, int64_t n, unsigned long long* slots,
-                 SmoState* st, const svm_params& p, int64_t* trace, int64_t tcap, unsigned* err) {
-  allow_lds(smo_rc_persistent_kernel<512, E, INT, STAMP, RPL, WSS2>, lds);
-  hipLaunchKernelGGL((smo_rc_persistent_kernel<512, E, INT, STAMP, RPL, WSS2>), dim3(G), dim3(512), lds, s, q, cache, ldc,
-                     nslots, neg_gamma, y, alpha, f, n, int64_t(512) * E, slots, st, p.C, p.eps, p.tau, p.max_iter,
-                     trace, tcap, err, int64_t(1) << 24, reinterpret_cast<unsigned long long*>(err) + 8);
-}
+// The row-cache solver's problem: rows, cache (nd directory slots) and the solver's vectors.
+struct RcProblem {
+  const QRows& q;
+  bool int_rows;
+  double* cache;
+  int64_t ldc;
+  const int32_t* y;
+  double* alpha;
+  double* f;
+  int64_t n;
+};
+
 template <int E, int RPL>
-void launch_rc_variant(bool int_rows, bool stamp, hipStream_t s, int G, size_t lds, const QRows& q, double* cache,
-                       int64_t ldc, int64_t nslots, double neg_gamma, const int32_t* y, double* alpha, double* f,
-                       int64_t n, unsigned long long* slots, SmoState* st, const svm_params& p, int64_t* trace,
-                       int64_t tcap, unsigned* err) {
-  if (int_rows && p.wss == 2)  // opt-in second-order selection (exact-integer rows)
-    launch_rc_e<E, true, false, RPL, true>(s, G, lds, q, cache, ldc, nslots, neg_gamma, y, alpha, f, n, slots, st, p,
-                                           trace, tcap, err);
-  else if (int_rows && stamp)
-    launch_rc_e<E, true, true, RPL>(s, G, lds, q, cache, ldc, nslots, neg_gamma, y, alpha, f, n, slots, st, p, trace,
-                                    tcap, err);
-  else if (int_rows)
-    launch_rc_e<E, true, false, RPL>(s, G, lds, q, cache, ldc, nslots, neg_gamma, y, alpha, f, n, slots, st, p, trace,
-                                     tcap, err);
-  else
-    launch_rc_e<E, false, false, RPL>(s, G, lds, q, cache, ldc, nslots, neg_gamma, y, alpha, f, n, slots, st, p, trace,
-                                      tcap, err);
+void launch_rc_e(hipStream_t s, const RcPlan& pl, const RcProblem& R, const svm_params& p, bool stamp, const Exchange& x,
+                 SmoState* st, int64_t* trace, int64_t tcap) {
+  auto kern = smo_rc_persistent_kernel<512, E, true, false, RPL, true>;  // opt-in second order (exact-integer rows)
+  if (R.int_rows && p.wss != 2)
+    kern = stamp ? smo_rc_persistent_kernel<512, E, true, true, RPL> : smo_rc_persistent_kernel<512, E, true, false, RPL>;
+  if (!R.int_rows) kern = smo_rc_persistent_kernel<512, E, false, false, RPL>;
+  launch(kern, s, pl.G, 512, pl.lds, R.q, R.cache, R.ldc, pl.nd, -p.gamma, R.y, R.alpha, R.f, R.n, int64_t(512) * E,
+         x.rec, st, p.C, p.eps, p.tau, p.max_iter, trace, tcap, x.err, kSpinDeviceWide, x.stamps);
 }
-constexpr int kRcMaxG = 256;  // records per epoch parity of the row-cache solver's slot array
 }  // namespace
 
 // Persistent row-cache solve (see smo_rc_persistent_kernel).  f / alpha hold the initial state (cold
 // or warm, set up by the caller); cache: nslots x ldc doubles.  Returns kRcNotApplicable when no
-// persistent shape covers n (the caller then replays its select/step graph).
+// persistent shape covers n (plan_rc; the caller then replays its select/step graph).
 int run_smo_rc_persistent(DeviceCtx* ctx, const QRows& q, bool int_rows, double* cache, int64_t ldc, int64_t nslots,
                           const int32_t* y, double* alpha, double* f, int64_t n, const svm_params& p, svm_result* r,
-                          int64_t* trace, int64_t trace_cap) {
-  if (const char* m = getenv("SVM355_RC_SMO"); m && !strcmp(m, "graph")) return kRcNotApplicable;
-  if (n <= 0 || n >= int64_t(kSentinel)) return kRcNotApplicable;
-  if (int_rows && q.kq > 32 * 128) return kRcNotApplicable;  // CachedRows::k12: two k-steps per lane
-  if (p.wss == 2 && !int_rows) return kRcNotApplicable;       // second order: exact-integer rows only
-  // Shape: up to 8 register-resident points per thread (E = 16 needs more than 256 VGPRs and
-  // spills) and one 512-thread workgroup per CU, all co-resident.  Teams of up to 64 workgroups
-  // (one record per sweep lane) with E <= 4, then 128 and 256 (two / four records per lane, capped
-  // by the CU count) with E <= 8: n <= 256 x 512 x 8 = 1,048,576.  Measured (profiles/
-  // r2_rowcache_persistent.txt): at 60k 59 x E=2 beats 118 x E=1 (98 vs 104 ms); at 250k 123 x E=4
-  // beats 62 x E=8 (465 vs 572 ms: half the miss fill per workgroup); 256-wide teams lose to 128
-  // wherever both fit.  SVM355_RC_MAXG=128|256 starts at a wider team.  Larger n keep the replayed
-  // select / step graph.
+                          int64_t* trace, int64_t trace_cap, const SmoKnobs& k) {
   int ncu = 0;
   SVMD_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-  int cap0 = 64;
-  if (const char* v = getenv("SVM355_RC_MAXG")) cap0 = std::max(64, std::min(kRcMaxG, atoi(v)));
-  int E = 0, G = 0;
-  for (int cap = cap0; cap <= kRcMaxG && !E; cap *= 2) {
-    const int maxg = std::min(cap, ncu);
-    for (int e = 1; e <= (cap == 64 ? 4 : 8) && !E; e *= 2)
-      if ((n + 512 * e - 1) / (512 * e) <= maxg) E = e;
-  }
-  if (!E) return kRcNotApplicable;
-  G = int((n + 512 * E - 1) / (512 * E));
-  const int rpl = G <= 64 ? 1 : G <= 128 ? 2 : 4;
-  // Directory in LDS: up to 16384 slots (64 KB of tags + 8 KB of MRU bits) next to PersistShared.
-  const int64_t nd = std::min<int64_t>(nslots, 16384) / 2 * 2;
-  if (nd < 4) return kRcNotApplicable;
-  const size_t lds = (size_t(nd) * 4 + size_t(nd) / 2 + 15) / 16 * 16;
+  const RcPlan pl = plan_rc(n, ncu, int_rows, q.kq, p.wss, nslots, k);
+  if (!pl.ok) return kRcNotApplicable;
   const auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = ctx->stream;
   const int64_t tcap = trace ? std::max<int64_t>(trace_cap, 0) : 0;
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  // records (both epoch parities), error word + phase stamps, exchange-skew stamps (RPL = 1)
-  const size_t rec_bytes = size_t(2) * kRcMaxG * kRecStride * 8;
-  const size_t off_slots = 0, slot_bytes = rec_bytes + 256 + (size_t(kMaxG) + 1) * kSkewEpochs * 8;
-  const size_t off_st = off_slots + al(slot_bytes);
-  const size_t off_trace = off_st + al(sizeof(SmoState));
-  int rc = ctx->ensure_ws(off_trace + al(size_t(tcap) * 16));
+  Exchange x;
+  SmoState* st = nullptr;
+  int64_t* dtrace = nullptr;
+  int rc = carve_ws(ctx, [&](WsCarver& c) {
+    x.carve(c, kRcMaxG);
+    st = c.take<SmoState>(1);
+    dtrace = c.take<int64_t>(size_t(tcap) * 2, tcap > 0);
+  });
   if (rc) return rc;
-  rc = ctx->ensure_pinned(sizeof(SmoState) * 3);
+  rc = ctx->ensure_pinned(sizeof(SmoState) * kHstSlots);
   if (rc) return rc;
-  char* ws = static_cast<char*>(ctx->ws);
-  auto* slots = reinterpret_cast<unsigned long long*>(ws + off_slots);
-  auto* err = reinterpret_cast<unsigned*>(ws + off_slots + rec_bytes);
-  auto* st = reinterpret_cast<SmoState*>(ws + off_st);
-  int64_t* dtrace = tcap ? reinterpret_cast<int64_t*>(ws + off_trace) : nullptr;
   SmoState* hst = static_cast<SmoState*>(ctx->pinned);
-  hst[0] = SmoState{0, 0, 0.0, 0.0, 0.0, 0.0, 1, 0, SVM_STOP_RUNNING};
-  SVMD_CHECK(hipMemsetAsync(slots, 0, slot_bytes, s));
-  SVMD_CHECK(hipMemcpyAsync(st, &hst[0], sizeof(SmoState), hipMemcpyHostToDevice, s));
-  const double ng = -p.gamma;
-  const char* stv = getenv("SVM355_PSMO_STAMP");
-  const bool stamp = stv && atoi(stv);
+  hst[kHstPoll] = SmoState{0, 0, 0.0, 0.0, 0.0, 0.0, 1, 0, SVM_STOP_RUNNING};  // staging of the fresh state
+  SVMD_CHECK(hipMemsetAsync(x.rec, 0, x.bytes, s));
+  SVMD_CHECK(hipMemcpyAsync(st, &hst[kHstPoll], sizeof(SmoState), hipMemcpyHostToDevice, s));
+  const bool stamp = k.stamp != 0;
   if (stamp) {
-    const char* fv = getenv("SVM355_PSMO_STAMP_FROM");
-    const unsigned long long from = fv ? std::max(1ll, atoll(fv)) : 0ull;
-    SVMD_CHECK(hipMemcpyAsync(reinterpret_cast<unsigned long long*>(err) + 16, &from, 8, hipMemcpyHostToDevice, s));
+    SVMD_CHECK(hipMemcpyAsync(x.stamp_from, &k.stamp_from, 8, hipMemcpyHostToDevice, s));
     SVMD_CHECK(hipStreamSynchronize(s));
   }
-#define SVM_RC_CASE(e, r)                                                                                           \
-  else if (E == e && rpl == r) launch_rc_variant<e, r>(int_rows, stamp, s, G, lds, q, cache, ldc, nd, ng, y, alpha, f, \
-                                                       n, slots, st, p, dtrace, tcap, err);
-  if (false) {
-  }
-  SVM_RC_CASE(1, 1) SVM_RC_CASE(2, 1) SVM_RC_CASE(4, 1) SVM_RC_CASE(8, 1)
-  SVM_RC_CASE(1, 2) SVM_RC_CASE(2, 2) SVM_RC_CASE(4, 2) SVM_RC_CASE(8, 2)
-  SVM_RC_CASE(1, 4) SVM_RC_CASE(2, 4) SVM_RC_CASE(4, 4) SVM_RC_CASE(8, 4)
-  else {
-    set_error("row-cache SMO: no kernel for E=%d, %d records per lane", E, rpl);
+  const RcProblem R{q, int_rows, cache, ldc, y, alpha, f, n};
+  if (!for_shape(RcShapes{}, pl.E, pl.rpl, [&](auto sh) {
+        launch_rc_e<decltype(sh)::a, decltype(sh)::b>(s, pl, R, p, stamp, x, st, dtrace, tcap);
+      })) {
+    set_error("row-cache SMO: no kernel for E=%d, %d records per lane", pl.E, pl.rpl);
     return SVM_ERR_INTERNAL;
   }
-#undef SVM_RC_CASE
   SVMD_LAUNCH_CHECK();
   unsigned herr = 0;
-  SVMD_CHECK(hipMemcpyAsync(&hst[2], st, sizeof(SmoState), hipMemcpyDeviceToHost, s));
-  SVMD_CHECK(hipMemcpyAsync(&herr, err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  SVMD_CHECK(hipMemcpyAsync(&hst[kHstFinal], st, sizeof(SmoState), hipMemcpyDeviceToHost, s));
+  SVMD_CHECK(hipMemcpyAsync(&herr, x.err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   SVMD_CHECK(hipStreamSynchronize(s));
   if (herr) {
-    set_error("row-cache SMO: persistent solver timed out waiting for a workgroup record (G=%d)", G);
+    set_error("row-cache SMO: persistent solver timed out waiting for a workgroup record (G=%d)", pl.G);
     return SVM_ERR_DEVICE;
   }
-  if (stamp && int_rows) {
-    unsigned long long hs[8];
-    SVMD_CHECK(hipMemcpy(hs, reinterpret_cast<unsigned long long*>(err) + 8, sizeof(hs), hipMemcpyDeviceToHost));
-    const double cnt = double(kStampCount);
-    fprintf(stderr, "[rc stamps G=%d E=%d RPL=%d] cycles/iter: scan+wavered %.0f | barrier1 %.0f | publish %.0f | sweep %.0f | "
-            "globalred+choose+barrier2 %.0f | rows (hit read / miss fill) %.0f | update %.0f | us/iter %.3f\n", G, E, rpl,
-            hs[0] / cnt, hs[1] / cnt, hs[2] / cnt, hs[3] / cnt, hs[4] / cnt, hs[5] / cnt, hs[6] / cnt,
-            double(hs[7]) / 100.0 / cnt);
-  }
-  return finish_smo(hst[2], r, trace, dtrace, tcap, t0);
+  if (stamp && int_rows && (rc = report_rc_stamps(pl, x))) return rc;
+  return finish_smo(hst[kHstFinal], r, trace, dtrace, tcap, t0);
 }
 
-int run_smo(DeviceCtx* ctx, const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha,
-            int32_t warm, const svm_params& p, svm_result* r, int64_t* trace, int64_t trace_cap) {
-  if (n <= 0) {
-    set_error("svmd_smo: empty problem");
-    return SVM_ERR_EMPTY;
-  }
-  const auto t0 = std::chrono::steady_clock::now();
+// ---- resident Gram: f of the start point, the single-workgroup and graph solvers, the driver ----------------
+// (Kernel templates are emitted in the order this file first names them: keep persistent, row cache, warm
+// start, single, batched, or the code object's layout changes.)
+namespace {
+int init_f_cold(hipStream_t s, const Resident& P) {
+  hipLaunchKernelGGL(smo_init_cold_kernel, dim3(unsigned((P.n + 255) / 256)), dim3(256), 0, s, P.y, P.alpha, P.f, P.n,
+                     P.st);
+  SVMD_LAUNCH_CHECK();
+  return SVM_OK;
+}
+
+// f = sum of alpha_j y_j K_j - y over the nonzero alphas, compacted into idx / coef / cnt first.
+int init_f_warm(hipStream_t s, const Resident& P, int64_t* idx, double* coef, int64_t* cnt, const SmoKnobs& k) {
+  hipLaunchKernelGGL(nonzero_compact_kernel, dim3(1), dim3(1024), 0, s, P.alpha, P.y, P.n, idx, coef, cnt, P.st);
+  SVMD_LAUNCH_CHECK();
+  // SVM355_WARM_U = 8 (one group of 8 in flight) | 16 | 32 (two groups in flight, pipelined)
+  const dim3 wg(unsigned((P.n + 63) / 64));
+  if (k.warm_u == 8)
+    hipLaunchKernelGGL((warm_f_kernel<8, false>), wg, dim3(64), 0, s, P.K, P.ldk, P.y, idx, coef, cnt, P.f, P.n);
+  else if (k.warm_u == 32)
+    hipLaunchKernelGGL((warm_f_kernel<32, true>), wg, dim3(64), 0, s, P.K, P.ldk, P.y, idx, coef, cnt, P.f, P.n);
+  else
+    hipLaunchKernelGGL((warm_f_kernel<16, true>), wg, dim3(64), 0, s, P.K, P.ldk, P.y, idx, coef, cnt, P.f, P.n);
+  SVMD_LAUNCH_CHECK();
+  return SVM_OK;
+}
+
+template <int NT, int E>
+void launch_single_e(hipStream_t s, const Resident& P, const svm_params& p, bool stamp, unsigned long long* stamps) {
+  auto kern = stamp ? smo_single_kernel<NT, E, true> : smo_single_kernel<NT, E, false>;
+  launch(kern, s, 1, NT, 0, P.K, P.ldk, P.y, P.alpha, P.f, P.n, P.st, p.C, p.eps, p.tau, p.max_iter, P.dtrace, P.tcap,
+         stamps);
+}
+
+// Single workgroup, no exchange: its phase totals go to the head of the (otherwise unused) exchange area.
+int solve_single(DeviceCtx* ctx, const SmoPlan& pl, const Resident& P, const svm_params& p, const Exchange& x,
+                 const SmoKnobs& k) {
   hipStream_t s = ctx->stream;
-  const int nblk = int(std::min<int64_t>((n + kSelectThreads - 1) / kSelectThreads, 2048));
-  if (trace_cap < 0) trace_cap = 0;
-  const int64_t tcap = trace ? trace_cap : 0;
-  // Workspace layout (256-byte aligned pieces).
-  auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t off_f = 0;
-  const size_t off_part = off_f + al(size_t(n) * 8);
-  const size_t off_state = off_part + al(size_t(nblk) * sizeof(Partial));
-  const size_t off_idx = off_state + al(sizeof(SmoState));
-  const size_t off_coef = off_idx + al(size_t(n) * 8);
-  const size_t off_cnt = off_coef + al(size_t(n) * 8);
-  const size_t off_trace = off_cnt + al(8);
-  const size_t off_slots = off_trace + al(size_t(tcap) * 16);
-  // records + error word + phase stamps + exchange-skew stamps
-  const size_t slot_bytes = size_t(2) * kMaxG * kRecStride * 8 + 256 + (size_t(kMaxG) + 1) * kSkewEpochs * 8;
-  const size_t total = off_slots + al(slot_bytes);
-  int rc = ctx->ensure_ws(total);
-  if (rc) return rc;
-  rc = ctx->ensure_pinned(sizeof(SmoState) * 3);
-  if (rc) return rc;
-  char* ws = static_cast<char*>(ctx->ws);
-  double* f = reinterpret_cast<double*>(ws + off_f);
-  Partial* part = reinterpret_cast<Partial*>(ws + off_part);
-  SmoState* st = reinterpret_cast<SmoState*>(ws + off_state);
-  int64_t* idx = reinterpret_cast<int64_t*>(ws + off_idx);
-  double* coef = reinterpret_cast<double*>(ws + off_coef);
-  int64_t* cnt = reinterpret_cast<int64_t*>(ws + off_cnt);
-  int64_t* dtrace = tcap ? reinterpret_cast<int64_t*>(ws + off_trace) : nullptr;
+  const bool stamp = k.stamp != 0;
+  unsigned long long* stamps = x.rec;
+  if (!for_shape(SingleShapes{}, pl.NT, pl.E, [&](auto sh) {
+        launch_single_e<decltype(sh)::a, decltype(sh)::b>(s, P, p, stamp, stamps);
+      })) {
+    set_error("single-workgroup SMO: n = %lld too large for %d threads", (long long)P.n, pl.NT);
+    return SVM_ERR_INTERNAL;
+  }
+  SVMD_LAUNCH_CHECK();
+  SmoState* hst = static_cast<SmoState*>(ctx->pinned);
+  SVMD_CHECK(hipMemcpyAsync(&hst[kHstFinal], P.st, sizeof(SmoState), hipMemcpyDeviceToHost, s));
+  SVMD_CHECK(hipStreamSynchronize(s));
+  return stamp ? report_single_stamps(pl, stamps) : SVM_OK;
+}
 
-  if (!warm) {
-    hipLaunchKernelGGL(smo_init_cold_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, y, alpha, f,
-                       n, st);
-    SVMD_LAUNCH_CHECK();
-  } else {
-    hipLaunchKernelGGL(nonzero_compact_kernel, dim3(1), dim3(1024), 0, s, alpha, y, n, idx, coef, cnt, st);
-    SVMD_LAUNCH_CHECK();
-    // SVM355_WARM_U = 8 (one group of 8 in flight) | 16 | 32 (two groups in flight, pipelined)
-    int wu = 16;
-    if (const char* v = getenv("SVM355_WARM_U")) wu = atoi(v);
-    const dim3 wg(unsigned((n + 63) / 64));
-    if (wu == 8)
-      hipLaunchKernelGGL((warm_f_kernel<8, false>), wg, dim3(64), 0, s, K, ldk, y, idx, coef, cnt, f, n);
-    else if (wu == 32)
-      hipLaunchKernelGGL((warm_f_kernel<32, true>), wg, dim3(64), 0, s, K, ldk, y, idx, coef, cnt, f, n);
-    else
-      hipLaunchKernelGGL((warm_f_kernel<16, true>), wg, dim3(64), 0, s, K, ldk, y, idx, coef, cnt, f, n);
-    SVMD_LAUNCH_CHECK();
-  }
-
-  // ---- persistent single-launch solver (default when the slices fit in registers)
-  int G = 0, E = 0, NT = 0;
-  const char* mode = getenv("SVM355_SMO");
-  // ---- single-workgroup solver for small problems (no cross-workgroup exchange)
-  const bool force_single = mode && strcmp(mode, "single") == 0;
-  int64_t single_max = kSingleDefaultMax;
-  if (const char* v = getenv("SVM355_SMO_SINGLE_MAX")) single_max = atoll(v);
-  // Second-order selection (p.wss == 2, opt-in) exists in the persistent solver only.
-  const bool wss2 = p.wss == 2;
-  if (!wss2 && (force_single || !mode || strcmp(mode, "auto") == 0) && (force_single || n <= single_max) &&
-      n <= 8192) {
-    int snt = kSingleDefaultNT;
-    if (const char* v = getenv("SVM355_SMO_SINGLE_NT")) snt = atoi(v);
-    if (snt != 256 && snt != 512 && snt != 1024) snt = kSingleDefaultNT;
-    int e = 1;
-    while (int64_t(snt) * e < n) e *= 2;
-    const char* stv = getenv("SVM355_PSMO_STAMP");
-    const bool stamp = stv && atoi(stv);
-    auto* sstamps = reinterpret_cast<unsigned long long*>(ws + off_slots);
-#define SVM_SINGLE_CASE(nt, ee)                                                                                     \
-  else if (snt == nt && e == ee) {                                                                                  \
-    if (stamp)                                                                                                      \
-      hipLaunchKernelGGL((smo_single_kernel<nt, ee, true>), dim3(1), dim3(nt), 0, s, K, ldk, y, alpha, f, n, st,    \
-                         p.C, p.eps, p.tau, p.max_iter, dtrace, tcap, sstamps);                                     \
-    else                                                                                                            \
-      hipLaunchKernelGGL((smo_single_kernel<nt, ee, false>), dim3(1), dim3(nt), 0, s, K, ldk, y, alpha, f, n, st,   \
-                         p.C, p.eps, p.tau, p.max_iter, dtrace, tcap, sstamps);                                     \
-  }
-    if (false) {
-    }
-    SVM_SINGLE_CASE(256, 1) SVM_SINGLE_CASE(256, 2) SVM_SINGLE_CASE(256, 4) SVM_SINGLE_CASE(256, 8)
-    SVM_SINGLE_CASE(256, 16) SVM_SINGLE_CASE(256, 32)
-    SVM_SINGLE_CASE(512, 1) SVM_SINGLE_CASE(512, 2) SVM_SINGLE_CASE(512, 4) SVM_SINGLE_CASE(512, 8) SVM_SINGLE_CASE(512, 16)
-    SVM_SINGLE_CASE(1024, 1) SVM_SINGLE_CASE(1024, 2) SVM_SINGLE_CASE(1024, 4) SVM_SINGLE_CASE(1024, 8)
-    else {
-      set_error("single-workgroup SMO: n = %lld too large for %d threads", (long long)n, snt);
-      return SVM_ERR_INTERNAL;
-    }
-#undef SVM_SINGLE_CASE
-    SVMD_LAUNCH_CHECK();
-    SmoState* hst = static_cast<SmoState*>(ctx->pinned);
-    SVMD_CHECK(hipMemcpyAsync(&hst[2], st, sizeof(SmoState), hipMemcpyDeviceToHost, s));
-    SVMD_CHECK(hipStreamSynchronize(s));
-    if (stamp) {
-      unsigned long long hs[8];
-      SVMD_CHECK(hipMemcpy(hs, sstamps, sizeof(hs), hipMemcpyDeviceToHost));
-      const double cnt = double(kStampCount);
-      fprintf(stderr, "[single stamps NT=%d E=%d] cycles/iter: scan+wavered %.0f | barrier %.0f | blockred %.0f | "
-              "loads %.0f | scalar %.0f | update %.0f | us/iter %.3f\n", snt, e, hs[0] / cnt, hs[1] / cnt, hs[2] / cnt,
-              hs[3] / cnt, hs[4] / cnt, hs[5] / cnt, double(hs[7]) / 100.0 / cnt);
-    }
-    return finish_smo(hst[2], r, trace, dtrace, tcap, t0);
-  }
-  const bool want_persistent = wss2 || !(mode && strcmp(mode, "graph") == 0);
-  // XCD-local exchange (all workgroups on one XCD, records through its L2): SVM355_PSMO_XCD=1/0
-  // forces it on/off; the default enables it up to kXcdDefaultMax points.
-  bool xlocal = n <= kXcdDefaultMax;
-  if (const char* v = getenv("SVM355_PSMO_XCD")) xlocal = atoi(v) != 0;
-  if (want_persistent && n < int64_t(kSentinel) && persistent_grid(n, &G, &E, &NT, xlocal ? kXcdMaxG : 0)) {
-    auto* slots = reinterpret_cast<unsigned long long*>(ws + off_slots);
-    auto* err = reinterpret_cast<unsigned*>(ws + off_slots + size_t(2) * kMaxG * kRecStride * 8);
-    SmoState* hst = static_cast<SmoState*>(ctx->pinned);
-    unsigned herr = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      SVMD_CHECK(hipMemsetAsync(slots, 0, slot_bytes, s));  // epochs restart at 1 every launch
-      const int lrc = launch_persistent(s, NT, E, G, K, ldk, y, alpha, f, n, slots, st, p.C, p.eps, p.tau,
-                                        p.max_iter, dtrace, tcap, err, xlocal, wss2);
-      if (lrc) return lrc;
-      SVMD_CHECK(hipMemcpyAsync(&hst[2], st, sizeof(SmoState), hipMemcpyDeviceToHost, s));
-      SVMD_CHECK(hipMemcpyAsync(&herr, err, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-      SVMD_CHECK(hipStreamSynchronize(s));
-      if (!(xlocal && herr == 2)) break;
-      // XCD 0 did not receive enough workgroups: nothing was touched, run the device-wide kernel.
-      unsigned reg[2] = {0, 0};
-      SVMD_CHECK(hipMemcpy(reg, err + 2, sizeof(reg), hipMemcpyDeviceToHost));
-      static std::atomic<int> reported{0};
-      if (reported.fetch_add(1) == 0)
-        fprintf(stderr, "[svm355] XCD-local SMO: fewer than %d workgroups registered on XCD 0 within %.0f us "
-                "(%u landed there in all, grid %d; another XCD-local solve running concurrently?); running the "
-                "device-wide solver (reported once)\n", G, double(register_ticks()) / 100.0, reg[0], 16 * G);
-      xlocal = false;
-      if (!persistent_grid(n, &G, &E, &NT, 0)) break;
-      herr = 0;
-    }
-    if (herr) {
-      set_error("svmd_smo: persistent solver timed out waiting for a workgroup record (G=%d)", G);
-      return SVM_ERR_DEVICE;
-    }
-    if (const char* sv = getenv("SVM355_PSMO_STAMP"); sv && atoi(sv)) {
-      unsigned long long hs[8];
-      SVMD_CHECK(hipMemcpy(hs, reinterpret_cast<unsigned long long*>(err) + 8, sizeof(hs), hipMemcpyDeviceToHost));
-      const double cnt = double(kStampCount), mhz = hs[7] ? double(hs[0] + hs[1] + hs[2] + hs[3] + hs[4] + hs[5] + hs[6]) / (double(hs[7]) / 100.0) : 0.0;
-      fprintf(stderr, "[psmo stamps NT=%d G=%d E=%d] cycles/iter: scan+wavered %.0f | barrier1 %.0f | publish %.0f | sweep %.0f | "
-              "globalred+barrier2 %.0f | loads %.0f | update %.0f | clock %.0f MHz | us/iter %.3f\n", NT, G, E,
-              hs[0] / cnt, hs[1] / cnt, hs[2] / cnt, hs[3] / cnt, hs[4] / cnt, hs[5] / cnt, hs[6] / cnt, mhz,
-              double(hs[7]) / 100.0 / cnt);
-      if (atoi(sv) == 2) {  // exchange skew: spread of the record publications, and WG 0's wait past the last
-        std::vector<unsigned long long> sk(size_t(kMaxG + 1) * kSkewEpochs);
-        SVMD_CHECK(hipMemcpy(sk.data(), reinterpret_cast<unsigned long long*>(err) + 8 + kSkewBase,
-                             sk.size() * 8, hipMemcpyDeviceToHost));
-        double spread = 0.0, tail = 0.0;
-        std::vector<double> late(size_t(G), 0.0);  // mean lateness of each workgroup behind the first
-        int used = 0;
-        for (uint32_t e = 0; e < kSkewEpochs; ++e) {
-          unsigned long long lo = ~0ull, hi = 0;
-          for (int q = 0; q < G; ++q) {
-            const unsigned long long v = sk[size_t(q) * kSkewEpochs + e];
-            lo = std::min(lo, v);
-            hi = std::max(hi, v);
-          }
-          const unsigned long long done = sk[size_t(kMaxG) * kSkewEpochs + e];
-          if (!lo || !done || done < hi) continue;
-          ++used;
-          spread += double(hi - lo) * 10.0;
-          tail += double(done - hi) * 10.0;
-          for (int q = 0; q < G; ++q) late[size_t(q)] += double(sk[size_t(q) * kSkewEpochs + e] - lo) * 10.0;
-        }
-        if (used) {
-          fprintf(stderr, "[psmo skew G=%d, %d epochs] publication spread %.0f ns | last publication -> WG0 sweep done %.0f ns\n",
-                  G, used, spread / used, tail / used);
-          fprintf(stderr, "[psmo skew] mean lateness per workgroup (ns):");
-          for (int q = 0; q < G; ++q) fprintf(stderr, " %.0f", late[size_t(q)] / used);
-          fprintf(stderr, "\n");
-        }
-      }
-    }
-    return finish_smo(hst[2], r, trace, dtrace, tcap, t0);
-  }
-  if (wss2) {
-    set_error("svmd_smo: second-order selection (wss = 2) needs the persistent solver (n = %lld has no shape)",
-              (long long)n);
-    return SVM_ERR_ARG;
-  }
-
-  // Graph of kChunk iterations, cached per context for identical arguments.
+// A graph of kChunk select / step iterations, cached per context for identical arguments, replayed until
+// the state's stop flag is set.
+int solve_graph(DeviceCtx* ctx, const Resident& P, const svm_params& p, Partial* part, int nblk) {
+  hipStream_t s = ctx->stream;
   const double C = p.C, eps = p.eps, tau = p.tau;
   const int64_t max_iter = p.max_iter;
-  std::vector<uint64_t> key = {uint64_t(uintptr_t(K)), uint64_t(ldk), uint64_t(uintptr_t(y)),
-                               uint64_t(n), uint64_t(uintptr_t(alpha)), uint64_t(uintptr_t(ws)),
-                               uint64_t(tcap), uint64_t(uintptr_t(s)), uint64_t(nblk)};
+  std::vector<uint64_t> key = {uint64_t(uintptr_t(P.K)), uint64_t(P.ldk), uint64_t(uintptr_t(P.y)),
+                               uint64_t(P.n), uint64_t(uintptr_t(P.alpha)), uint64_t(uintptr_t(ctx->ws)),
+                               uint64_t(P.tcap), uint64_t(uintptr_t(s)), uint64_t(nblk)};
   for (double v : {C, eps, tau}) {
     key.push_back(__builtin_bit_cast(uint64_t, v));
   }
@@ -1106,10 +1002,10 @@ int run_smo(DeviceCtx* ctx, const double* K, int64_t ldk, const int32_t* y, int6
     ctx->release_graph();
     SVMD_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     for (int it = 0; it < kChunk; ++it) {
-      hipLaunchKernelGGL(smo_select_kernel, dim3(nblk), dim3(kSelectThreads), 0, s, K, ldk, y, alpha, f, n,
-                         st, part, C, eps);
-      hipLaunchKernelGGL(smo_step_kernel, dim3(1), dim3(256), 0, s, part, nblk, K, ldk, y, alpha, n, st, C,
-                         eps, tau, max_iter, dtrace, tcap);
+      hipLaunchKernelGGL(smo_select_kernel, dim3(nblk), dim3(kSelectThreads), 0, s, P.K, P.ldk, P.y, P.alpha, P.f, P.n,
+                         P.st, part, C, eps);
+      hipLaunchKernelGGL(smo_step_kernel, dim3(1), dim3(256), 0, s, part, nblk, P.K, P.ldk, P.y, P.alpha, P.n, P.st, C,
+                         eps, tau, max_iter, P.dtrace, P.tcap);
     }
     hipGraph_t graph;
     SVMD_CHECK(hipStreamEndCapture(s, &graph));
@@ -1119,61 +1015,118 @@ int run_smo(DeviceCtx* ctx, const double* K, int64_t ldk, const int32_t* y, int6
     ctx->smo_graph = graph;
     ctx->smo_key = key;
   }
+  return replay_until_stop(s, ctx->smo_exec, P.st, static_cast<SmoState*>(ctx->pinned), max_iter / kChunk + 4,
+                           "svmd_smo");
+}
+}  // namespace
 
-  // Replay with two chunks in flight; poll the stop flag of the older one.
-  SmoState* hst = static_cast<SmoState*>(ctx->pinned);  // [0], [1] poll slots, [2] final
-  hst[0].stop = hst[1].stop = 0;
-  hipEvent_t ev[2];
-  SVMD_CHECK(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-  SVMD_CHECK(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-  const int64_t max_replays = max_iter / kChunk + 4;
-  int rc_loop = SVM_OK;
-  auto enqueue = [&](int slot) -> int {
-    SVMD_CHECK(hipGraphLaunch(ctx->smo_exec, s));
-    SVMD_CHECK(hipMemcpyAsync(&hst[slot], st, sizeof(SmoState), hipMemcpyDeviceToHost, s));
-    SVMD_CHECK(hipEventRecord(ev[slot], s));
-    return SVM_OK;
-  };
-  rc_loop = enqueue(0);
-  for (int64_t rep = 0; rc_loop == SVM_OK; ++rep) {
-    if (rep + 1 < max_replays) rc_loop = enqueue(int((rep + 1) & 1));
-    if (rc_loop) break;
-    hipError_t e = hipEventSynchronize(ev[rep & 1]);
-    if (e != hipSuccess) {
-      set_error("svmd_smo: %s", hipGetErrorString(e));
-      rc_loop = SVM_ERR_DEVICE;
-      break;
-    }
-    if (hst[rep & 1].stop || rep + 1 >= max_replays) break;
+int run_smo(DeviceCtx* ctx, const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha,
+            int32_t warm, const svm_params& p, svm_result* r, int64_t* trace, int64_t trace_cap) {
+  if (n <= 0) {
+    set_error("svmd_smo: empty problem");
+    return SVM_ERR_EMPTY;
   }
-  hipError_t e = hipStreamSynchronize(s);
-  (void)hipEventDestroy(ev[0]);
-  (void)hipEventDestroy(ev[1]);
-  if (rc_loop) return rc_loop;
-  if (e != hipSuccess) {
-    set_error("svmd_smo: %s", hipGetErrorString(e));
-    return SVM_ERR_DEVICE;
+  const auto t0 = std::chrono::steady_clock::now();
+  const SmoKnobs k = read_smo_knobs();
+  hipStream_t s = ctx->stream;
+  const int nblk = int(std::min<int64_t>((n + kSelectThreads - 1) / kSelectThreads, 2048));
+  const int64_t tcap = trace ? std::max<int64_t>(trace_cap, 0) : 0;
+  Resident P{K, ldk, y, alpha, nullptr, n, nullptr, nullptr, tcap};
+  Partial* part = nullptr;  // the graph solver's block partials
+  int64_t *idx = nullptr, *cnt = nullptr;  // the warm start's nonzero alphas
+  double* coef = nullptr;
+  Exchange x;
+  int rc = carve_ws(ctx, [&](WsCarver& c) {
+    P.f = c.take<double>(size_t(n));
+    part = c.take<Partial>(size_t(nblk));
+    P.st = c.take<SmoState>(1);
+    idx = c.take<int64_t>(size_t(n));
+    coef = c.take<double>(size_t(n));
+    cnt = c.take<int64_t>(1);
+    P.dtrace = c.take<int64_t>(size_t(tcap) * 2, tcap > 0);
+    x.carve(c, kMaxG);
+  });
+  if (rc) return rc;
+  rc = ctx->ensure_pinned(sizeof(SmoState) * kHstSlots);
+  if (rc) return rc;
+  rc = warm ? init_f_warm(s, P, idx, coef, cnt, k) : init_f_cold(s, P);
+  if (rc) return rc;
+
+  const SmoPlan pl = plan_smo(n, p.wss, k);
+  if (p.wss == 2 && pl.path != SmoPlan::kPersistent) {
+    set_error("svmd_smo: second-order selection (wss = 2) needs the persistent solver (n = %lld has no shape)",
+              (long long)n);
+    return SVM_ERR_ARG;
   }
-  SVMD_CHECK(hipMemcpy(&hst[2], st, sizeof(SmoState), hipMemcpyDeviceToHost));
-  return finish_smo(hst[2], r, trace, dtrace, tcap, t0);
+  switch (pl.path) {
+    case SmoPlan::kSingle: rc = solve_single(ctx, pl, P, p, x, k); break;
+    case SmoPlan::kPersistent: rc = solve_persistent(ctx, pl, P, p, x, k); break;
+    case SmoPlan::kGraph: rc = solve_graph(ctx, P, p, part, nblk); break;
+  }
+  if (rc) return rc;
+  return finish_smo(static_cast<SmoState*>(ctx->pinned)[kHstFinal], r, trace, P.dtrace, tcap, t0);
 }
 
+// ---- batched one-vs-rest -----------------------------------------------------------------------------------
 namespace {
 template <int NT, int E>
-void launch_multi_e(hipStream_t s, int grid, const double* K, int64_t ldk, const int32_t* Y, double* A, double* F,
-                    int64_t n, unsigned long long* slots, SmoState* st, int nclass, const svm_params& p, unsigned* ctl,
-                    int G) {
-  const size_t lds = xcd_lds_pad(NT);
-  if (p.wss == 2) {  // opt-in second-order selection: the same persist_solve as the single-class solver
-    allow_lds(smo_multi_kernel<NT, E, true>, lds);
-    hipLaunchKernelGGL((smo_multi_kernel<NT, E, true>), dim3(grid), dim3(NT), lds, s, K, ldk, Y, A, F, n,
-                       int64_t(NT) * E, slots, st, nclass, p.C, p.eps, p.tau, p.max_iter, ctl, int64_t(1) << 22, G,
-                       register_ticks());
-    return;
+void launch_multi_e(hipStream_t s, const SmoPlan& pl, const double* K, int64_t ldk, const int32_t* Y, double* A,
+                    double* F, int64_t n, unsigned long long* slots, SmoState* st, int nclass, const svm_params& p,
+                    unsigned* ctl, const SmoKnobs& k) {
+  // opt-in second-order selection: the same persist_solve as the single-class solver
+  auto kern = p.wss == 2 ? smo_multi_kernel<NT, E, true> : smo_multi_kernel<NT, E>;
+  // Over-provisioned grid as for the single XCD-local solve: ~2*G workgroups per XCD.
+  launch(kern, s, 16 * pl.G, NT, xcd_lds_pad(NT, k), K, ldk, Y, A, F, n, int64_t(NT) * E, slots, st, nclass, p.C, p.eps,
+         p.tau, p.max_iter, ctl, kSpinXcdLocal, pl.G, register_ticks(k));
+}
+
+// All classes in one launch of XCD teams; fin[k].stop stays RUNNING for a class no team took.
+int solve_multi_batched(DeviceCtx* ctx, const SmoPlan& pl, const double* K, int64_t ldk, const int32_t* Y, int64_t n,
+                        int nclass, double* A, const svm_params& p, SmoState* fin, const SmoKnobs& k) {
+  hipStream_t s = ctx->stream;
+  const size_t total = size_t(nclass) * size_t(n);
+  double* F = nullptr;
+  SmoState* st = nullptr;
+  unsigned long long* slots = nullptr;
+  unsigned* ctl = nullptr;
+  size_t zero_bytes = 0;  // the teams' records and the control words, adjacent
+  int rc = carve_ws(ctx, [&](WsCarver& c) {
+    F = c.take<double>(total);
+    st = c.take<SmoState>(size_t(nclass));
+    const size_t z0 = c.off;
+    slots = c.take<unsigned long long>(size_t(kMultiTeams) * 2 * kMaxG * kRecStride);
+    ctl = c.take<unsigned>(kMultiCtlWords);
+    zero_bytes = c.off - z0;
+  });
+  if (rc) return rc;
+  const int64_t init_n = std::max<int64_t>(int64_t(total), nclass);
+  hipLaunchKernelGGL(smo_multi_init_kernel, dim3(unsigned((init_n + 255) / 256)), dim3(256), 0, s, Y, A, F,
+                     int64_t(total), st, nclass);
+  SVMD_LAUNCH_CHECK();
+  SVMD_CHECK(hipMemsetAsync(slots, 0, zero_bytes, s));
+  if (!for_shape(MultiShapes{}, pl.NT, pl.E, [&](auto sh) {
+        launch_multi_e<decltype(sh)::a, decltype(sh)::b>(s, pl, K, ldk, Y, A, F, n, slots, st, nclass, p, ctl, k);
+      })) {
+    set_error("svmd_smo_multi: no kernel for NT=%d E=%d", pl.NT, pl.E);
+    return SVM_ERR_INTERNAL;
   }
-  allow_lds(smo_multi_kernel<NT, E>, lds);
-  hipLaunchKernelGGL((smo_multi_kernel<NT, E>), dim3(grid), dim3(NT), lds, s, K, ldk, Y, A, F, n, int64_t(NT) * E,
-                     slots, st, nclass, p.C, p.eps, p.tau, p.max_iter, ctl, int64_t(1) << 22, G, register_ticks());
+  SVMD_LAUNCH_CHECK();
+  unsigned herr = 0;
+  SVMD_CHECK(hipMemcpyAsync(fin, st, size_t(nclass) * sizeof(SmoState), hipMemcpyDeviceToHost, s));
+  SVMD_CHECK(hipMemcpyAsync(&herr, ctl + kMultiErr, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  SVMD_CHECK(hipStreamSynchronize(s));
+  if (k.multi_debug) {
+    unsigned hc[kMultiCtlWords];
+    SVMD_CHECK(hipMemcpy(hc, ctl, sizeof(hc), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[smo_multi G=%d NT=%d E=%d] per XCD landed/decision:", pl.G, pl.NT, pl.E);
+    for (int t = 0; t < kMultiTeams; ++t) fprintf(stderr, " %u/%u", hc[4 * t], hc[4 * t + 1]);
+    fprintf(stderr, " | queue %u err %u\n", hc[kMultiQueue], hc[kMultiErr]);
+  }
+  if (herr == 1) {
+    set_error("svmd_smo_multi: a team timed out waiting for a workgroup record or its mailbox");
+    return SVM_ERR_DEVICE;
+  }
+  return SVM_OK;
 }
 }  // namespace
 
@@ -1184,68 +1137,25 @@ int run_smo_multi(DeviceCtx* ctx, const double* K, int64_t ldk, const int32_t* Y
     return SVM_ERR_EMPTY;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  hipStream_t s = ctx->stream;
+  const SmoKnobs k = read_smo_knobs();
   std::vector<SmoState> fin(static_cast<size_t>(nclass));
-  int G = 0, E = 0, NT = 0;
-  bool ok = nclass < 1000 && n < int64_t(kSentinel) && persistent_grid(n, &G, &E, &NT, kXcdMaxG);
-  ok = ok && ((NT == 256 && E <= 2) || (NT == 512 && E <= 4));
-  if (const char* v = getenv("SVM355_SMO_MULTI"); v && atoi(v) == 0) ok = false;
+  SmoPlan pl;
+  bool ok = nclass < 1000 && n < int64_t(kSentinel) && plan_smo_grid(n, kXcdMaxG, k, &pl);
+  ok = ok && ((pl.NT == 256 && pl.E <= 2) || (pl.NT == 512 && pl.E <= 4)) && k.multi;
   if (batched) *batched = 0;
   if (ok) {
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t total = size_t(nclass) * size_t(n);
-    const size_t off_f = 0;
-    const size_t off_st = off_f + al(total * 8);
-    const size_t off_slots = off_st + al(size_t(nclass) * sizeof(SmoState));
-    const size_t slot_bytes = size_t(kMultiTeams) * 2 * kMaxG * kRecStride * 8;
-    const size_t off_ctl = off_slots + al(slot_bytes);
-    int rc = ctx->ensure_ws(off_ctl + al(kMultiCtlWords * 4));
+    const int rc = solve_multi_batched(ctx, pl, K, ldk, Y, n, nclass, A, p, fin.data(), k);
     if (rc) return rc;
-    char* ws = static_cast<char*>(ctx->ws);
-    double* F = reinterpret_cast<double*>(ws + off_f);
-    SmoState* st = reinterpret_cast<SmoState*>(ws + off_st);
-    auto* slots = reinterpret_cast<unsigned long long*>(ws + off_slots);
-    auto* ctl = reinterpret_cast<unsigned*>(ws + off_ctl);
-    const int64_t init_n = std::max<int64_t>(int64_t(total), nclass);
-    hipLaunchKernelGGL(smo_multi_init_kernel, dim3(unsigned((init_n + 255) / 256)), dim3(256), 0, s, Y, A, F,
-                       int64_t(total), st, nclass);
-    SVMD_LAUNCH_CHECK();
-    SVMD_CHECK(hipMemsetAsync(ws + off_slots, 0, al(slot_bytes) + al(kMultiCtlWords * 4), s));
-    // Over-provisioned grid as for the single XCD-local solve: ~2*G workgroups per XCD.
-    const int grid = 16 * G;
-#define SVM_MULTI_CASE(nt, e) \
-  else if (NT == nt && E == e) launch_multi_e<nt, e>(s, grid, K, ldk, Y, A, F, n, slots, st, nclass, p, ctl, G);
-    if (false) {
-    }
-    SVM_MULTI_CASE(256, 1) SVM_MULTI_CASE(256, 2) SVM_MULTI_CASE(512, 1) SVM_MULTI_CASE(512, 2)
-    SVM_MULTI_CASE(512, 4)
-#undef SVM_MULTI_CASE
-    SVMD_LAUNCH_CHECK();
-    unsigned herr = 0;
-    SVMD_CHECK(hipMemcpyAsync(fin.data(), st, size_t(nclass) * sizeof(SmoState), hipMemcpyDeviceToHost, s));
-    SVMD_CHECK(hipMemcpyAsync(&herr, ctl + kMultiErr, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    SVMD_CHECK(hipStreamSynchronize(s));
-    if (const char* v = getenv("SVM355_SMO_MULTI_DEBUG"); v && atoi(v)) {
-      unsigned hc[kMultiCtlWords];
-      SVMD_CHECK(hipMemcpy(hc, ctl, sizeof(hc), hipMemcpyDeviceToHost));
-      fprintf(stderr, "[smo_multi G=%d NT=%d E=%d] per XCD landed/decision:", G, NT, E);
-      for (int x = 0; x < kMultiTeams; ++x) fprintf(stderr, " %u/%u", hc[4 * x], hc[4 * x + 1]);
-      fprintf(stderr, " | queue %u err %u\n", hc[kMultiQueue], hc[kMultiErr]);
-    }
-    if (herr == 1) {
-      set_error("svmd_smo_multi: a team timed out waiting for a workgroup record or its mailbox");
-      return SVM_ERR_DEVICE;
-    }
     if (batched) *batched = 1;
   }
   // Classes no team solved (batched path off or unavailable, or teams that could not form): one by one.
-  for (int k = 0; k < nclass; ++k) {
-    if (ok && fin[size_t(k)].stop != SVM_STOP_RUNNING) {
-      const int rc = finish_smo(fin[size_t(k)], r ? &r[k] : nullptr, nullptr, nullptr, 0, t0);
+  for (int c = 0; c < nclass; ++c) {
+    if (ok && fin[size_t(c)].stop != SVM_STOP_RUNNING) {
+      const int rc = finish_smo(fin[size_t(c)], r ? &r[c] : nullptr, nullptr, nullptr, 0, t0);
       if (rc) return rc;
       continue;
     }
-    const int rc = run_smo(ctx, K, ldk, Y + int64_t(k) * n, n, A + int64_t(k) * n, 0, p, r ? &r[k] : nullptr,
+    const int rc = run_smo(ctx, K, ldk, Y + int64_t(c) * n, n, A + int64_t(c) * n, 0, p, r ? &r[c] : nullptr,
                            nullptr, 0);
     if (rc) return rc;
   }

@@ -1,6 +1,7 @@
 """A/B of a row-cache solver switch read from the environment at each solve, e.g.
-    python scripts/rc_env_ab.py SVM355_RC_LAYOUT rows,sliced 60000,250000 2
-Same process, the variants alternate, best of REPS per variant after one warm-up round; every
+    python scripts/rc_env_ab.py SVM355_RC_MAXG 64,128 60000,250000 2
+(docs/KNOBS.md lists the switches; SVM355_RC_LAYOUT, which profiles/r2_rowcache_layout_ab.txt measured with
+this script, was an experimental variant that no source reads any more.)  Same process, the variants alternate, best of REPS per variant after one warm-up round; every
 fit must follow the same trajectory (iterations, b, alphas)."""
 import os
 import sys

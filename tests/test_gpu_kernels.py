@@ -160,7 +160,8 @@ def test_device_wss2_bit_identical_to_oracle_on_same_gram(dev, D, monkeypatch, n
 
 
 def test_persistent_vs_graph_many_workgroups(dev, D, monkeypatch):
-    """Many workgroups (G = 40 at n = 20000): both device paths bit-identical."""
+    """Many workgroups (n = 20000: 20 x 512 threads x 2 points with the default XCD-local exchange; G = 40
+    only device-wide, tests/test_smo_plan_cpu.py): both device paths bit-identical."""
     tr = synthetic_mnist(20000, seed=9)
     Xd = D.upload_rows(tr.X, dev)
     _, _, sqn = D.minmax_scale_(Xd, 784)
@@ -181,7 +182,8 @@ def test_persistent_vs_graph_many_workgroups(dev, D, monkeypatch):
 
 @pytest.mark.parametrize("n", [3000, 7000])
 def test_single_workgroup_smo_matches_persistent(dev, D, monkeypatch, n):
-    """The single-workgroup solver (E = 4 and 8 register elements) follows the persistent trajectory."""
+    """The single-workgroup solver (512 threads with E = 8 and 16 register elements at n = 3000 and 7000,
+    tests/test_smo_plan_cpu.py) follows the persistent trajectory."""
     tr = synthetic_mnist(n, seed=11)
     Xd = D.upload_rows(tr.X, dev)
     mn, mx, sqn = D.minmax_scale_(Xd, 784)
