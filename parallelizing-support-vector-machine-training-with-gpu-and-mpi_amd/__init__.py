@@ -8,6 +8,9 @@ re-designed for gfx950:
                                      arithmetic): on the GPU the SMO-type working-set decomposition
                                      solver by default (``solver="smo"``: the reference's pairwise
                                      trajectory, bit for bit the CPU oracle's); on the CPU the oracle
+* ``svm355.SVR``                     epsilon-SVR on the same solvers: the 2n-variable problem whose twins a_k / a*_k
+                                     share a kernel row, so on the GPU the decomposition solver's kernel work
+                                     runs over n rows, not 2n (the CPU oracle is the pairwise solver)
 * ``svm355.OneVsRestSVC``            all classes one-vs-rest: the decomposition solver per class on the
                                      shared device rows (default), or one resident Gram with every
                                      pairwise class solve in one launch (``solver="batched"``)
@@ -37,9 +40,10 @@ from .utils.config import SVMParams  # noqa: E402
 from .utils.data import Dataset, MinMaxScaler, load_csv, one_vs_rest, synthetic_mnist, write_csv
 from .models.multiclass import OneVsRestSVC
 from .models.svc import SVC
+from .models.svr import SVR
 
 __all__ = ["SVMParams", "Dataset", "MinMaxScaler", "load_csv", "one_vs_rest", "synthetic_mnist", "write_csv",
-           "SVC", "OneVsRestSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
+           "SVC", "SVR", "OneVsRestSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
 __version__ = "0.1.0"
 
 

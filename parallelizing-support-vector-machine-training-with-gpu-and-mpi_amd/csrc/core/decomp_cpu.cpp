@@ -22,6 +22,11 @@
 //   * class weights (svm_params.weight_pos / weight_neg): per-class boxes in the set membership of every
 //     selection and in the clip of both pairs (smo_cpu.cpp has the expressions); shrinking and the Newton
 //     polish are unweighted and refuse them.
+//   * twin mode (epsilon-SVR, svm_decomp_train_gram_svr): 2n virtual points over the n rows of K -- point k
+//     is a_k with sign +1, point k + n its twin a*_k with sign -1, both reading kernel row k (id mod n); the
+//     start is f_k = epsilon - z_k, f_{k+n} = -epsilon - z_k; the moved list is folded to one entry per row
+//     (fold_twins) and every row's sum is added to both twins' f.  Cold start, one rank, no shrinking, no
+//     Newton polish, no class weights.
 // The kernel values themselves come from the caller (the device Gram on the exact-integer path).
 #include <chrono>
 #include <climits>
@@ -82,8 +87,9 @@ struct Cand {
 static_assert(sizeof(Cand) == 16, "candidate records are exchanged as 16-byte records");
 
 // One device GEMV + half-sum pass: f[i] += sum over halves c of half(c, i) (see the header comment).
+// f2 (twin mode): the twins' f, which takes the same row sum.
 void gemv_update(const double* K, int64_t ldk, int64_t n, const int32_t* cols, const double* coef, int64_t cnt,
-                 double* f, WorkerTeam& team) {
+                 double* f, WorkerTeam& team, double* f2) {
   if (cnt <= 0) return;
   const int64_t halves = (cnt + 63) / 64;
   team.parallel_for(n, [&](int64_t lo, int64_t hi) {
@@ -108,8 +114,55 @@ void gemv_update(const double* K, int64_t ldk, int64_t n, const int32_t* cols, c
         s += v[0];
       }
       f[i] += s;
+      if (f2) f2[i] += s;
     }
   });
+}
+
+// The FP64-row path's f update (ws_rowsum_f64_kernel on the FP64-MFMA block K(rows, moved columns)): per row one
+// wave, lane l's terms k = l, l + 64, ... summed from 0 in that order, then the 64-lane xor butterfly (32, 16, 8,
+// 4, 2, 1) as lane 0 sees it, and one add into f (and into the twin's f).
+void rowsum_update_f64(const double* K, int64_t ldk, int64_t n, const int32_t* cols, const double* coef, int64_t cnt,
+                       double* f, WorkerTeam& team, double* f2) {
+  if (cnt <= 0) return;
+  team.parallel_for(n, [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const double* Ki = K + i * ldk;
+      double v[64], w[64];
+      for (int l = 0; l < 64; ++l) {
+        double acc = 0.0;
+        for (int64_t k = l; k < cnt; k += 64) acc += coef[k] * Ki[cols[k]];
+        v[l] = acc;
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        for (int l = 0; l < 64; ++l) w[l] = v[l] + v[l ^ off];
+        for (int l = 0; l < 64; ++l) v[l] = w[l];
+      }
+      f[i] += v[0];
+      if (f2) f2[i] += v[0];
+    }
+  });
+}
+
+// Twin mode's moved-column fold (ws_twin_fold_kernel): the moved list of virtual ids (k: a_k, k + n: a*_k)
+// and their coefficients becomes one entry per kernel row, at the position of the row's first occurrence;
+// when both twins moved their coefficients are added, coef_k + coef_{k+n}.
+void fold_twins(const int32_t* cols, const double* coef, int64_t cnt, int64_t n, std::vector<int32_t>& fcols,
+                std::vector<double>& fcoef) {
+  fcols.clear();
+  fcoef.clear();
+  for (int64_t j = 0; j < cnt; ++j) {
+    const int32_t row = int32_t(cols[j] % n);
+    size_t at = fcols.size();
+    for (size_t q = 0; q < fcols.size(); ++q)
+      if (fcols[q] == row) at = q;
+    if (at == fcols.size()) {
+      fcols.push_back(row);
+      fcoef.push_back(coef[j]);
+    } else {
+      fcoef[at] = cols[j] < n ? coef[j] + fcoef[at] : fcoef[at] + coef[j];
+    }
+  }
 }
 
 // The solve of one rank (t == nullptr: one rank).  Distributed (decomp.hip run_decomp, world > 1):
@@ -120,13 +173,46 @@ void gemv_update(const double* K, int64_t ldk, int64_t n, const int32_t* cols, c
 // updates f for its own rows.  The block partition is the one-rank partition for world | 8, so the
 // trajectory is the one-rank trajectory bit for bit.  Returns SVM_OK or an error code (set_error);
 // transport failures throw (TransportError / CascadeAborted).
+// Twin mode (twin_z: the n regression targets, twin_eps: the tube's half width): y is not read, alpha holds
+// the 2n virtual points' values and the trace's snapshots are 2n long; f64_rows: the f update sums in the
+// FP64-row path's order (rowsum_update_f64) instead of the exact-integer GEMV's.
 int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha, int32_t warm,
                  const svm_params& p, int32_t qws, double tau_frac, int32_t inner_wss, svm_result* res,
-                 int64_t* stats, svm_decomp_trace* tr, Transport* t) {
+                 int64_t* stats, svm_decomp_trace* tr, Transport* t, const double* twin_z = nullptr,
+                 double twin_eps = 0.0, bool f64_rows = false) {
   const int world = t ? t->world() : 1, rank = t ? t->rank() : 0;
-  if (!K || !y || !alpha || n < 2 || ldk < n) {
+  const bool twin = twin_z != nullptr;
+  if (!K || (!y && !twin) || !alpha || n < 2 || ldk < n) {
     set_error("svm_decomp_train_gram: bad arguments");
     return SVM_ERR_ARG;
+  }
+  const int64_t nr = n;  // kernel rows: point id's row is id mod nr (twin mode), id itself otherwise
+  std::vector<int32_t> sgn;
+  if (twin) {
+    const char* what = world != 1                               ? "the distributed solve (world > 1)"
+                       : warm                                   ? "a warm start"
+                       : shrink_cfg(p).on                       ? "shrinking"
+                       : newton_cfg(p).on                       ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                       : (p.weight_pos != 0.0 && p.weight_pos != 1.0) || (p.weight_neg != 0.0 && p.weight_neg != 1.0)
+                           ? "class weights"
+                           : nullptr;
+    if (what) {
+      set_error("svm_decomp_train_gram_svr: the regression (twin) solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+    if (!(twin_eps >= 0.0) || !std::isfinite(twin_eps) || 2 * nr > int64_t(INT32_MAX)) {
+      set_error("svm_decomp_train_gram_svr: epsilon must be finite and >= 0, and 2 n <= 2^31 - 1");
+      return SVM_ERR_ARG;
+    }
+    for (int64_t i = 0; i < nr; ++i)
+      if (!std::isfinite(twin_z[i])) {
+        set_error("svm_decomp_train_gram_svr: target %lld is not finite", (long long)i);
+        return SVM_ERR_ARG;
+      }
+    n = 2 * nr;
+    sgn.resize(size_t(n));
+    for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = i < nr ? 1 : -1;
+    y = sgn.data();
   }
   if (!(tau_frac >= 0.0 && tau_frac < 0.5)) {
     set_error("svm_decomp_train_gram: tau_frac must be in [0, 0.5)");
@@ -183,10 +269,16 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       }
     for (size_t c0 = 0; c0 < nzc.size(); c0 += kMaxWS)
       gemv_update(K + lo * ldk, ldk, nloc, nzc.data() + c0, nzv.data() + c0,
-                  int64_t(std::min<size_t>(kMaxWS, nzc.size() - c0)), f.data(), team);
+                  int64_t(std::min<size_t>(kMaxWS, nzc.size() - c0)), f.data(), team, nullptr);
     return int64_t(nzc.size());
   };
-  if (!warm) {
+  if (twin) {  // ws_twin_init_kernel
+    for (int64_t k = 0; k < nr; ++k) {
+      f[size_t(k)] = twin_eps - twin_z[k];
+      f[size_t(k + nr)] = -twin_eps - twin_z[k];
+    }
+    for (int64_t i = 0; i < n; ++i) alpha[i] = 0.0;
+  } else if (!warm) {
     for (int64_t i = lo; i < hi; ++i) f[size_t(i - lo)] = -static_cast<double>(y[i]);
     for (int64_t i = 0; i < n; ++i) alpha[i] = 0.0;
   } else {
@@ -207,10 +299,10 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   int32_t last_reason = SVM_STOP_CONVERGED, stop = SVM_STOP_RUNNING;
   double bh = inf, bl = -inf;
   std::vector<Cand> cown(size_t(std::max<int64_t>(Lr, 1))), call(size_t(sh.L));
-  std::vector<int32_t> W;
+  std::vector<int32_t> W, Wr;  // the working set's point ids and their kernel rows (id mod nr)
   std::vector<double> a, a0, ft, kh, kl;
-  std::vector<int32_t> yw, cols;
-  std::vector<double> coef;
+  std::vector<int32_t> yw, cols, fcols;
+  std::vector<double> coef, fcoef;
   if (tr) tr->count = 0;
   for (;;) {
     if (outer == fail_outer) {
@@ -276,6 +368,9 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         Wf.push_back(ids[q].second);
       }
     const int m = int(W.size());
+    Wr.assign(W.begin(), W.end());
+    if (twin)
+      for (int32_t& id : Wr) id = int32_t(id % nr);
     if (outer > 0 && last_inner_it == 0)
       stop = last_reason == SVM_STOP_CONVERGED ? SVM_STOP_NO_CANDIDATE : last_reason;
     else if (!(bh < inf) || !(bl > -inf))
@@ -350,7 +445,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         int code = 0, steps = 0;
         while (steps < nwc.repeat &&
                (code = newton_step_ref(m, a.data(), ft.data(), yw.data(),
-                                       [&](int q, int k) { return K[int64_t(W[size_t(q)]) * ldk + W[size_t(k)]]; },
+                                       [&](int q, int k) { return K[int64_t(Wr[size_t(q)]) * ldk + Wr[size_t(k)]]; },
                                        C, eps, nwc.max_free)) != 0) {
           ++steps;
           if (code == 1) break;
@@ -379,13 +474,13 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       if (inner_wss == 4) {
         j2 = -1;
         if (i2 >= 0) {
-          const double* K2 = K + int64_t(W[size_t(i2)]) * ldk;
+          const double* K2 = K + int64_t(Wr[size_t(i2)]) * ldk;
           const double h2 = ft[size_t(i2)];
           double gv2 = inf;
           for (int k = 0; k < m; ++k) {
             if (!in_low(yw[size_t(k)], a[size_t(k)]) || !(ft[size_t(k)] > h2)) continue;
             const double bb = ft[size_t(k)] - h2;
-            double at = 2.0 - 2.0 * K2[W[size_t(k)]];
+            double at = 2.0 - 2.0 * K2[Wr[size_t(k)]];
             at = at <= 0.0 ? eps : at;
             const double gain = -(bb * bb) / at;
             if (gain < gv2) {
@@ -395,8 +490,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
           }
         }
       }
-      const double* Ki = K + int64_t(W[size_t(ih)]) * ldk;
-      for (int k = 0; k < m; ++k) kh[size_t(k)] = Ki[W[size_t(k)]];
+      const double* Ki = K + int64_t(Wr[size_t(ih)]) * ldk;
+      for (int k = 0; k < m; ++k) kh[size_t(k)] = Ki[Wr[size_t(k)]];
       double bl_upd = lv;
       if (inner_wss != 1) {
         double gv = inf;
@@ -420,8 +515,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         bl_upd = ft[size_t(il)];
       }
       const double K12 = kh[size_t(il)];
-      const double* Kj = K + int64_t(W[size_t(il)]) * ldk;
-      for (int k = 0; k < m; ++k) kl[size_t(k)] = Kj[W[size_t(k)]];
+      const double* Kj = K + int64_t(Wr[size_t(il)]) * ldk;
+      for (int k = 0; k < m; ++k) kl[size_t(k)] = Kj[Wr[size_t(k)]];
       const double ah = a[size_t(ih)], al = a[size_t(il)];
       const int32_t yh = yw[size_t(ih)], yl = yw[size_t(il)];
       const int s = yh * yl;
@@ -460,7 +555,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         const double a2h = a[size_t(i2)], a2l = a[size_t(j2)];
         const int32_t yh2 = yw[size_t(i2)], yl2 = yw[size_t(j2)];
         const int s2 = yh2 * yl2;
-        const double eta2 = 1.0 + 1.0 - 2.0 * K[int64_t(W[size_t(i2)]) * ldk + W[size_t(j2)]];
+        const double eta2 = 1.0 + 1.0 - 2.0 * K[int64_t(Wr[size_t(i2)]) * ldk + Wr[size_t(j2)]];
         const double Ch2 = yh2 == 1 ? Cp : Cn, Cl2 = yl2 == 1 ? Cp : Cn;
         double U2, V2;
         if (s2 == -1) {
@@ -477,9 +572,9 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
           const double ah2 = a2h + double(s2) * (a2l - al2);
           const double ch2 = (ah2 - a2h) * double(yh2);
           const double cl2 = (al2 - a2l) * double(yl2);
-          const double* Ki2 = K + int64_t(W[size_t(i2)]) * ldk;
-          const double* Kj2 = K + int64_t(W[size_t(j2)]) * ldk;
-          for (int k = 0; k < m; ++k) ft[size_t(k)] += ch2 * Ki2[W[size_t(k)]] + cl2 * Kj2[W[size_t(k)]];
+          const double* Ki2 = K + int64_t(Wr[size_t(i2)]) * ldk;
+          const double* Kj2 = K + int64_t(Wr[size_t(j2)]) * ldk;
+          for (int k = 0; k < m; ++k) ft[size_t(k)] += ch2 * Ki2[Wr[size_t(k)]] + cl2 * Kj2[Wr[size_t(k)]];
           moved_status = moved_status || bound_status(ah2, Ch2, eps) != bound_status(a2h, Ch2, eps) ||
                          bound_status(al2, Cl2, eps) != bound_status(a2l, Cl2, eps);
           a[size_t(i2)] = ah2;
@@ -505,7 +600,13 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     last_inner_it = it;
     last_m = m;
     last_reason = reason;
-    gemv_update(K + lo * ldk, ldk, nloc, cols.data(), coef.data(), int64_t(cols.size()), f.data(), team);
+    if (twin) {  // one entry per kernel row, every row's sum to both twins
+      fold_twins(cols.data(), coef.data(), int64_t(cols.size()), nr, fcols, fcoef);
+      (f64_rows ? rowsum_update_f64 : gemv_update)(K, ldk, nr, fcols.data(), fcoef.data(), int64_t(fcols.size()),
+                                                   f.data(), team, f.data() + nr);
+    } else {
+      gemv_update(K + lo * ldk, ldk, nloc, cols.data(), coef.data(), int64_t(cols.size()), f.data(), team, nullptr);
+    }
     if (shc.pass_after(outer, origin)) {  // shrink pass with this outer iteration's bounds
       int64_t drop = 0;
       double hc, lc;
@@ -593,6 +694,43 @@ extern "C" SVM_API int svm_decomp_train_gram(const double* K, int64_t ldk, const
                       nullptr);
 }
 
+// The regression (epsilon-SVR) form of svm_decomp_train_gram: twin mode over the n x n kernel matrix K and
+// the n targets z; alpha (2n, out) holds a (first n) and a* (last n), the trace's snapshots are 2n long.
+// f64_rows: the f update sums as the device's FP64-row path does (real-valued rows), else as its GEMV.
+extern "C" SVM_API int svm_decomp_train_gram_svr(const double* K, int64_t ldk, const double* z, int64_t n,
+                                                 double epsilon, double* alpha, const svm_params* pp, int32_t qws,
+                                                 double tau_frac, int32_t inner_wss, int32_t f64_rows, svm_result* res,
+                                                 int64_t* stats, svm_decomp_trace* tr) {
+  if (!z) {
+    set_error("svm_decomp_train_gram_svr: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  return decomp_solve(K, ldk, nullptr, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
+                      nullptr, z, epsilon, f64_rows != 0);
+}
+
+// Twin mode's moved-column fold alone (tests): cnt <= 1024 virtual ids in [0, 2n) and their coefficients to one
+// entry per kernel row (out_cols / out_coef: cnt entries of room), *out_cnt of them.
+extern "C" SVM_API int svm_decomp_twin_fold(const int32_t* cols, const double* coef, int32_t cnt, int64_t n,
+                                            int32_t* out_cols, double* out_coef, int32_t* out_cnt) {
+  if (cnt < 0 || cnt > kMaxWS || n < 1 || (cnt > 0 && (!cols || !coef || !out_cols || !out_coef)) || !out_cnt) {
+    set_error("svm_decomp_twin_fold: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  for (int k = 0; k < cnt; ++k)
+    if (cols[k] < 0 || cols[k] >= 2 * n) {
+      set_error("svm_decomp_twin_fold: id %d outside [0, 2 n)", cols[k]);
+      return SVM_ERR_ARG;
+    }
+  std::vector<int32_t> fc;
+  std::vector<double> fv;
+  fold_twins(cols, coef, cnt, n, fc, fv);
+  std::copy(fc.begin(), fc.end(), out_cols);
+  std::copy(fv.begin(), fv.end(), out_coef);
+  *out_cnt = int32_t(fc.size());
+  return SVM_OK;
+}
+
 // This process's rank of the distributed form over caller-supplied host collectives (a gloo group
 // under torchrun: the CPU twin of the per-process device rank, svmd_cascade_rank_decomp).
 extern "C" SVM_API int svm_decomp_rank_train_gram(const svm_host_comm* comm, const double* K, int64_t ldk,
@@ -674,6 +812,6 @@ extern "C" SVM_API int svm_decomp_gemv_ref(const double* K, int64_t ldk, int64_t
     return SVM_ERR_ARG;
   }
   WorkerTeam team(std::max<int32_t>(1, std::min<int32_t>(resolve_threads(0), int32_t(n / 256) + 1)));
-  gemv_update(K, ldk, n, cols, coef, cnt, f, team);
+  gemv_update(K, ldk, n, cols, coef, cnt, f, team, nullptr);
   return SVM_OK;
 }

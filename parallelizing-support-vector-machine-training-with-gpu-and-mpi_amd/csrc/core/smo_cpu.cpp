@@ -20,9 +20,11 @@
 // With n_threads > 1 the O(n) loops are split into static chunks; each element is computed by the
 // same expression, and the argmin/argmax merge keeps the serial lowest-index rule, so the result is
 // bit-identical to the serial run.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <limits>
+#include <vector>
 
 #include "internal.h"
 
@@ -62,7 +64,8 @@ struct GramRows {
 
 template <class Rows>
 int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int32_t warm,
-              const svm_params* pp, svm_result* res, int64_t* trace, int64_t trace_cap) {
+              const svm_params* pp, svm_result* res, int64_t* trace, int64_t trace_cap,
+              const double* f0 = nullptr) {  // f0: a cold start's f instead of -y (a linear term: epsilon-SVR)
   svm_params p;
   if (pp)
     p = *pp;
@@ -86,7 +89,7 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
 
   if (!warm) {
     for (int64_t i = 0; i < n; ++i) alpha[i] = 0.0;
-    for (int64_t i = 0; i < n; ++i) f[size_t(i)] = -static_cast<double>(y[i]);
+    for (int64_t i = 0; i < n; ++i) f[size_t(i)] = f0 ? f0[i] : -static_cast<double>(y[i]);
   } else {
     // f_i = sum_{alpha_j != 0} alpha_j y_j K(x_j, x_i) - y_i, j ascending (mpi_svm_main3.cpp:169-186)
     std::vector<int64_t> nz;
@@ -278,6 +281,37 @@ SVM_API int svm_smo_train_gram(const double* K, int64_t ldk, const int32_t* y, i
   }
   GramRows rows{K, ldk};
   return smo_solve(rows, y, n, alpha, warm, p, r, trace, trace_cap);
+}
+
+// epsilon-SVR on the pairwise solver (the small-n oracle): the 2n-variable problem on duplicated rows -- row k
+// with sign +1 is a_k, its copy k + n with sign -1 is a*_k -- started from f_k = epsilon - z_k, f_{k+n} =
+// -epsilon - z_k.  alpha (2n, out): a, then a*.  The model is beta = a - a*, prediction sum beta_k K(x_k, x) - b.
+SVM_API int svm_smo_train_svr(const double* X, const double* z, int64_t n, int64_t d, double epsilon, double* alpha,
+                              const svm_params* p, svm_result* r) {
+  if (!X || !z || !alpha || d <= 0 || n < 1 || !(epsilon >= 0.0) || !std::isfinite(epsilon)) {
+    set_error("svm_smo_train_svr: bad X / z / d, or epsilon not finite and >= 0");
+    return SVM_ERR_ARG;
+  }
+  if (p && ((p->weight_pos != 0.0 && p->weight_pos != 1.0) || (p->weight_neg != 0.0 && p->weight_neg != 1.0))) {
+    set_error("svm_smo_train_svr: the regression solve does not support class weights");
+    return SVM_ERR_ARG;
+  }
+  std::vector<double> X2(size_t(2 * n * d)), f0(size_t(2 * n));
+  std::vector<int32_t> y2(size_t(2 * n));
+  for (int64_t k = 0; k < n; ++k) {
+    if (!std::isfinite(z[k])) {
+      set_error("svm_smo_train_svr: target %lld is not finite", (long long)k);
+      return SVM_ERR_ARG;
+    }
+    std::copy(X + k * d, X + (k + 1) * d, X2.begin() + k * d);
+    std::copy(X + k * d, X + (k + 1) * d, X2.begin() + (k + n) * d);
+    y2[size_t(k)] = 1;
+    y2[size_t(k + n)] = -1;
+    f0[size_t(k)] = epsilon - z[k];
+    f0[size_t(k + n)] = -epsilon - z[k];
+  }
+  XRows rows{X2.data(), d, p ? p->gamma : 0.00125};
+  return smo_solve(rows, y2.data(), 2 * n, alpha, 0, p, r, nullptr, 0, f0.data());
 }
 
 }  // extern "C"

@@ -51,6 +51,14 @@ struct DecompOpts {
   svm_decomp_trace* trace = nullptr;
   DecompSolo* solo = nullptr;  // world > 1 rehearsal on one GPU: per-rank solo timing (above)
   double* host_wait_ms = nullptr;  // out: host time blocked in the per-batch waits (all outer iterations)
+  // Twin mode (epsilon-SVR): twin_z = the n targets on the device, twin_eps = the tube's half width.  The
+  // solve then runs over 2n virtual points that share the n kernel rows -- point k is a_k with sign +1, point
+  // k + n its twin a*_k with sign -1, both on row k -- from f_k = eps - z_k, f_{k+n} = -eps - z_k.  run_decomp
+  // takes n rows as always, reads no y (it keeps the signs itself), and alpha holds 2n values: a, then a*.
+  // One GPU, cold start, no shrinking, no Newton polish, no class weights: anything else is SVM_ERR_ARG.
+  const double* twin_z = nullptr;
+  double twin_eps = 0.0;
+  bool twin() const { return twin_z != nullptr; }
 };
 
 // The rows a solve reads its kernel values from: the exact-integer plan's quantised rows (Q; int8

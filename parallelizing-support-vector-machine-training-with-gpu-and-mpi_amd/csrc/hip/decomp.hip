@@ -354,9 +354,81 @@ __global__ __launch_bounds__(64) void ws_gather_f64_kernel(const double* __restr
   if (threadIdx.x == 0) no[k] = nrm[src];
 }
 
+// Twin mode (epsilon-SVR, DecompOpts): a point id in [0, 2 nrow) reads kernel row id mod nrow.  The two
+// gathers above for a working set of such points (kernels of their own: the classifier's keep their arguments).
+__device__ __forceinline__ int64_t twin_row(int32_t id, int64_t nrow) { return id >= nrow ? id - nrow : id; }
+
+__global__ __launch_bounds__(64) void ws_gather_twin_kernel(const int8_t* __restrict__ Q,
+                                                            const int32_t* __restrict__ N0,
+                                                            const double* __restrict__ WN, int kq,
+                                                            const int32_t* __restrict__ W,
+                                                            const DecompCtl* __restrict__ ctl, int8_t* __restrict__ Qw,
+                                                            int32_t* __restrict__ N0w, double* __restrict__ WNw,
+                                                            int64_t nrow) {
+  const int k = blockIdx.x;
+  if (ctl->stop != SVM_STOP_RUNNING || k >= ctl->m) return;
+  const int64_t src = twin_row(W[k], nrow);
+  const int4* s = reinterpret_cast<const int4*>(Q + src * int64_t(kq));
+  int4* d = reinterpret_cast<int4*>(Qw + int64_t(k) * kq);
+  for (int c = threadIdx.x; c < kq / 16; c += 64) d[c] = s[c];
+  if (threadIdx.x == 0) {
+    N0w[k] = N0[src];
+    WNw[k] = WN[src];
+  }
+}
+
+__global__ __launch_bounds__(64) void ws_gather_f64_twin_kernel(const double* __restrict__ X,
+                                                                const double* __restrict__ nrm, int64_t ld,
+                                                                const int32_t* __restrict__ ids,
+                                                                const int32_t* __restrict__ count,
+                                                                const int32_t* __restrict__ gate,
+                                                                double* __restrict__ Xo, double* __restrict__ no,
+                                                                int64_t nrow) {
+  const int k = blockIdx.x;
+  if ((gate && *gate != 0) || k >= *count) return;
+  const int64_t src = twin_row(ids[k], nrow);
+  const double2* s = reinterpret_cast<const double2*>(X + src * ld);
+  double2* d = reinterpret_cast<double2*>(Xo + int64_t(k) * ld);
+  for (int64_t c = threadIdx.x; c < ld / 2; c += 64) d[c] = s[c];
+  if (threadIdx.x == 0) no[k] = nrm[src];
+}
+
+// Twin mode: two twins in one working set (W is ascending, so k sits before k + nrow) are the same kernel
+// row, and K(W, W) between their positions is the diagonal's 1 -- as the f update has it for that row -- not
+// the off-diagonal arithmetic's value for a zero distance.  One workgroup after the K(W, W) build: every
+// position holding a point k + nrow looks k up by bisection and sets both mirrored entries.
+__global__ __launch_bounds__(kMaxWS) void ws_twin_kww_kernel(const int32_t* __restrict__ W,
+                                                             const DecompCtl* __restrict__ ctl, int64_t nrow,
+                                                             double* __restrict__ Kw, int64_t ldw) {
+  if (ctl->stop != SVM_STOP_RUNNING) return;
+  __shared__ int32_t s[kMaxWS];
+  const int k = threadIdx.x, m = min(ctl->m, kMaxWS);
+  const int32_t id = k < m ? W[k] : -1;
+  s[k] = id;
+  __syncthreads();
+  if (id < nrow) return;  // a point of the first half (or none): its twin, if present, does the work
+  const int32_t want = int32_t(id - nrow);
+  int a = 0, b = m;  // the first position whose id is >= want
+  while (a < b) {
+    const int mid = (a + b) >> 1;
+    if (s[mid] < want)
+      a = mid + 1;
+    else
+      b = mid;
+  }
+  if (a < m && s[a] == want) {
+    Kw[int64_t(k) * ldw + a] = 1.0;
+    Kw[int64_t(a) * ldw + k] = 1.0;
+  }
+}
+
 // ---- cache plan and sums --------------------------------------------------------------------------------
 // FP64 rows: f[i] += sum_{k < *count} coef[k] Kc[i][k] (the block K(rows, moved columns)), one wave
 // per row, lane-strided then a fixed butterfly (deterministic).
+// TWIN (twin mode; also ws_cache_fsum_kernel and ws_fsum_count_kernel below): a row's sum is computed once,
+// exactly as otherwise, and added to both of the row's points, f[row] and f[row + nloc] (nloc = the kernel
+// rows, all on this GPU; no packed rows in twin mode).
+template <bool TWIN>
 __global__ __launch_bounds__(256) void ws_rowsum_f64_kernel(const double* __restrict__ Kc, int64_t ldc,
                                                             const double* __restrict__ coef,
                                                             const int32_t* __restrict__ count, double* __restrict__ f,
@@ -370,6 +442,7 @@ __global__ __launch_bounds__(256) void ws_rowsum_f64_kernel(const double* __rest
   for (int k = lane; k < cnt; k += 64) acc += coef[k] * kr[k];
   acc = wave_sum(acc);
   if (lane == 0) f[row] += acc;
+  if (TWIN && lane == 0) f[row + nloc] += acc;
 }
 
 // Column cache bookkeeping of one f update (one 1024-thread workgroup): the moved columns cols[0..*count)
@@ -507,7 +580,7 @@ __global__ __launch_bounds__(1024) void ws_cache_plan_kernel(const int32_t* __re
 // rolled groups of 8 (8 column pairs of loads in flight per group; unrolled, the compiler hoisted all
 // 64 and ran at 3 waves / SIMD: 4.3 against 5.9 TB/s), the level of a group's last leaf depending on g.
 // Packed rows (a shrunk solve): row i of the cache is f[act[i]], i < *nrows.
-template <int RPT>
+template <int RPT, bool TWIN>
 __global__ __launch_bounds__(256) void ws_cache_fsum_kernel(const double* __restrict__ cache, int64_t ldc,
                                                              const int32_t* __restrict__ rd_slot,
                                                              const double* __restrict__ coef,
@@ -583,10 +656,16 @@ __global__ __launch_bounds__(256) void ws_cache_fsum_kernel(const double* __rest
 #pragma unroll
   for (int r = 0; r < RPT; ++r)
     if (i + r < nloc) f[act ? int64_t(act[i + r]) : i + r] += s[r];
+  if (TWIN) {
+#pragma unroll
+    for (int r = 0; r < RPT; ++r)
+      if (i + r < nloc) f[nloc + i + r] += s[r];
+  }
 }
 
 // f[i] += the first ceil(*mcount / 64) column halves of part (the ones the GEMV wrote).  Packed rows
 // (a shrunk solve): part row i is f[act[i]], i < *nrows.
+template <bool TWIN>
 __global__ __launch_bounds__(256) void ws_fsum_count_kernel(const double* __restrict__ part, int64_t ldp,
                                                             const int32_t* __restrict__ mcount,
                                                             double* __restrict__ f, int64_t n,
@@ -600,6 +679,39 @@ __global__ __launch_bounds__(256) void ws_fsum_count_kernel(const double* __rest
   double s = 0.0;
   for (int c = 0; c < npart; ++c) s += p[c];
   f[act ? int64_t(act[i]) : i] += s;
+  if (TWIN) f[n + i] += s;
+}
+
+// Twin mode's moved-column fold, between the inner solve and the f update (one workgroup): the moved list
+// (cols: virtual ids k / k + nrow, coef: the change of alpha times the sign, *mcount <= kMaxWS of them) becomes
+// one entry per kernel row -- fcols: the row, at the position order of the rows' first occurrences; fcoef:
+// the point's coefficient, or coef_k + coef_{k+nrow} when both twins moved; *fcount: the rows.  The column
+// cache and the column store key on the column id and must never see one twice, so the merge is not optional.
+__global__ __launch_bounds__(kMaxWS) void ws_twin_fold_kernel(const int32_t* __restrict__ cols,
+                                                              const double* __restrict__ coef,
+                                                              const int32_t* __restrict__ mcount, int64_t nrow,
+                                                              int32_t* __restrict__ fcols, double* __restrict__ fcoef,
+                                                              int32_t* __restrict__ fcount) {
+  __shared__ int32_t s[kMaxWS];
+  __shared__ int32_t wsum[16];
+  const int k = threadIdx.x, cnt = max(0, min(*mcount, kMaxWS));
+  const int32_t id = k < cnt ? cols[k] : -1;
+  s[k] = id;
+  __syncthreads();
+  const int32_t twin = id < 0 ? -2 : (id < nrow ? int32_t(id + nrow) : int32_t(id - nrow));
+  int at = -1;  // the twin's position in the list (a point is listed once)
+  for (int q = 0; q < cnt; ++q)
+    if (s[q] == twin) at = q;
+  const bool keep = id >= 0 && (at < 0 || at > k);
+  int tot = 0;
+  const int r = block_excl_scan_1024(keep, wsum, tot);
+  if (keep) {
+    double c = coef[k];
+    if (at >= 0) c = id < nrow ? c + coef[at] : coef[at] + c;
+    fcols[r] = int32_t(twin_row(id, nrow));
+    fcoef[r] = c;
+  }
+  if (k == 0) *fcount = tot;
 }
 
 // ---- init and warm start --------------------------------------------------------------------------------
@@ -615,6 +727,23 @@ __global__ void ws_init_kernel(const int32_t* __restrict__ y, double* __restrict
   if (i < n && !warm) alpha[i] = 0.0;
   if (i < nloc) f[i] = -static_cast<double>(y[lo + i]);  // main3.cpp:165-172
   if (i == 0 && ctl) ctl->n_active = nloc;
+}
+
+// Twin mode's (cold) start over the nrow targets z: f_k = eps - z_k, f_{k+nrow} = -eps - z_k, alpha = 0, and the
+// 2 nrow points' signs (the solve's y): +1 for a_k, -1 for its twin a*_k.
+__global__ void ws_twin_init_kernel(const double* __restrict__ z, double eps, int64_t nrow, int32_t* __restrict__ sgn,
+                                    double* __restrict__ alpha, double* __restrict__ f, DecompCtl* __restrict__ ctl) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < nrow) {
+    const double zi = z[i];
+    f[i] = eps - zi;
+    f[i + nrow] = -eps - zi;
+    alpha[i] = 0.0;
+    alpha[i + nrow] = 0.0;
+    sgn[i] = 1;
+    sgn[i + nrow] = -1;
+  }
+  if (i == 0) ctl->n_active = 2 * nrow;
 }
 
 // Warm start: the ascending ids j with alpha_j != 0 into cols, alpha_j y_j into coef, their number to
@@ -974,6 +1103,9 @@ struct DecompWs {
   int32_t *bcnt = nullptr, *pos_of = nullptr, *nrows = nullptr, *cdiag = nullptr, *mdiag = nullptr, *N0a = nullptr;
   int8_t* Qa = nullptr;
   double* WNa = nullptr;
+  // twin mode (epsilon-SVR): the 2n points' signs (the solve's y) and the folded moved list (one entry per row)
+  int32_t *sgn = nullptr, *fcols = nullptr, *fcount = nullptr;
+  double* fcoef = nullptr;
 };
 
 // The f update's kernel columns K(this GPU's rows, j) kept in HBM (size_col_cache); slab null: no cache.
@@ -1000,6 +1132,13 @@ struct Solve {
   int64_t n = 0, NBr = 0, lo = 0, nloc = 0, Lr = 0, nchunks = 0;
   DecompKnobs k;
   bool wide_select = false, kww_narrow = false, pack_on = false;
+  // twin mode (DecompOpts): n, lo, nloc and the selection shape are those of the 2 nrow virtual points; the
+  // kernel rows -- what the GEMV, the column store and the column cache run over -- are the nrow rows
+  bool twin = false;
+  int64_t nrow = 0;
+  const double* twin_z = nullptr;
+  double twin_eps = 0.0;
+  int64_t rows() const { return twin ? nrow : nloc; }  // this GPU's kernel rows
   ShrinkCfg shc;
   InnerVariant inner;
   NwDev nwd{};
@@ -1038,7 +1177,7 @@ struct PackState {
 int size_col_cache(const Solve& S, bool warm, ColCache* out) {
   DeviceCtx* ctx = S.ctx;
   const DecompKnobs& k = S.k;
-  const int64_t n = S.n, nloc = S.nloc;
+  const int64_t n = S.twin ? S.nrow : S.n, nloc = S.rows();  // slots per kernel row
   *out = ColCache{};
   if (S.f64 || nloc <= 0) return SVM_OK;
   if (!(k.ccache >= 0 ? k.ccache != 0 : nloc * int64_t(S.kq) > (int64_t(192) << 20))) return SVM_OK;
@@ -1091,6 +1230,7 @@ int size_col_cache(const Solve& S, bool warm, ColCache* out) {
 void layout_ws(Solve& S, bool warm, WsCarver& c) {
   DecompWs& w = S.w;
   const size_t nl1 = size_t(std::max<int64_t>(S.nloc, 1)), n = size_t(S.n), kq = size_t(S.kq), ld = size_t(S.R.ld);
+  const size_t nr1 = size_t(std::max<int64_t>(S.rows(), 1)), ncol = S.twin ? size_t(S.nrow) : n;  // kernel rows / columns
   const bool f64 = S.f64, q8 = !f64, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
   w.f = c.take<double>(nl1);
   w.own = c.take<CandRec>(size_t(S.Lr));
@@ -1105,13 +1245,13 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.Qw = c.take<int8_t>(size_t(kMaxWS) * kq, q8);
   w.N0w = c.take<int32_t>(kMaxWS, q8);
   w.WNw = c.take<double>(kMaxWS, q8);
-  w.part = c.take<double>(nl1 * kLdp, q8);
+  w.part = c.take<double>(nr1 * kLdp, q8);
   w.Xw = c.take<double>(size_t(kMaxWS) * ld, f64);
   w.nw = c.take<double>(kMaxWS, f64);
   w.Xc = c.take<double>(size_t(kMaxWS) * ld, f64);
   w.nc = c.take<double>(kMaxWS, f64);
-  w.Kc = c.take<double>(nl1 * kMaxWS, f64);
-  w.cslot = c.take<int32_t>(n, cache);
+  w.Kc = c.take<double>(nr1 * kMaxWS, f64);
+  w.cslot = c.take<int32_t>(ncol, cache);
   w.crd = c.take<int32_t>(kMaxWS, cache);
   w.cmid = c.take<int32_t>(kMaxWS, cache);
   w.cmsl = c.take<int32_t>(kMaxWS, cache);
@@ -1136,12 +1276,37 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.Qa = c.take<int8_t>(nl1 * kq, pack);
   w.N0a = c.take<int32_t>(nl1, pack);
   w.WNa = c.take<double>(nl1, pack);
+  w.sgn = c.take<int32_t>(n, S.twin);
+  w.fcols = c.take<int32_t>(kMaxWS, S.twin);
+  w.fcoef = c.take<double>(kMaxWS, S.twin);
+  w.fcount = c.take<int32_t>(64, S.twin);
 }
 
 // The checks, the shape and this GPU's slice of it, the knobs and what follows from them.
 int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n,
                 const svm_params& p, int qws, const DecompOpts& o) {
   const int world = o.world, rank = o.rank;
+  const int64_t nrow = n;  // the kernel rows; n below counts the points the solve selects among
+  if (o.twin()) {  // everything twin mode does not cover is refused here, before any device work
+    double cp = 0.0, cn = 0.0;
+    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
+    const char* what = world != 1                 ? "the distributed solve (world > 1)"
+                       : o.warm                   ? "a warm start"
+                       : shrink_cfg(p).on         ? "shrinking"
+                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                       : (cp != p.C || cn != p.C) ? "class weights"
+                                                  : nullptr;
+    if (what) {
+      set_error("decomposition SMO: the regression (twin) solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+    if (!(o.twin_eps >= 0.0) || !std::isfinite(o.twin_eps) || nrow < 2 || 2 * nrow > int64_t(INT32_MAX)) {
+      set_error("decomposition SMO: the regression (twin) solve needs a finite epsilon >= 0 and 2 <= n with "
+                "2 n <= 2^31 - 1 (n = %lld)", (long long)nrow);
+      return SVM_ERR_ARG;
+    }
+    n = 2 * nrow;
+  }
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !o.allgather)) {
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
@@ -1170,8 +1335,12 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.R = R;
   S.f64 = f64;
   S.kq = f64 ? 0 : R.P->kq;
-  S.y = y;
+  S.y = y;  // twin mode: the signs, in the workspace (alloc_solve)
   S.alpha = alpha;
+  S.twin = o.twin();
+  S.nrow = nrow;
+  S.twin_z = o.twin_z;
+  S.twin_eps = o.twin_eps;
   S.n = n;
   S.p = p;
   S.sh = sh;
@@ -1221,6 +1390,7 @@ int alloc_solve(Solve& S, bool warm) {
   int rc = size_col_cache(S, warm, &S.cc);
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
+  if (S.twin) S.y = S.w.sgn;
   if ((rc = S.ctx->ensure_pinned(sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl) + 64))) return rc;
   char* pin = static_cast<char*>(S.ctx->pinned);
   S.hs = reinterpret_cast<DecompHost*>(pin);
@@ -1243,7 +1413,11 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
   const DecompWs& w = S.w;
   const DecompRows& R = S.R;
   hipStream_t s = S.s;
-  const int64_t lo = S.lo, nloc = S.nloc;
+  // twin mode: cl / cf / cnt are the folded list (rows, one entry each), the kernel work runs over the nrow
+  // rows exactly as a classification of them would, and the sums' TWIN instantiations add each row's sum to
+  // both of its points
+  const bool twin = S.twin;
+  const int64_t lo = S.lo, nloc = S.rows();
   if (nloc <= 0) return SVM_OK;
   if (S.f64) {
     hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, cl, cnt,
@@ -1252,8 +1426,8 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
     const int rc = launch_rbf_block_dev(s, R.X + lo * R.ld, R.nrm + lo, nloc, R.ld, w.Xc, w.nc, kMaxWS, R.ld, R.ld,
                                         S.p.gamma, w.Kc, kMaxWS, false, nullptr, cnt, cl, lo);
     if (rc) return rc;
-    hipLaunchKernelGGL(ws_rowsum_f64_kernel, dim3(unsigned((nloc + 3) / 4)), dim3(256), 0, s, w.Kc, int64_t(kMaxWS), cf,
-                       cnt, w.f, nloc);
+    hipLaunchKernelGGL(twin ? ws_rowsum_f64_kernel<true> : ws_rowsum_f64_kernel<false>, dim3(unsigned((nloc + 3) / 4)),
+                       dim3(256), 0, s, w.Kc, int64_t(kMaxWS), cf, cnt, w.f, nloc);
     SVMD_LAUNCH_CHECK();
     return SVM_OK;
   }
@@ -1274,16 +1448,17 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
                                          kMaxWS, P, S.p.gamma, S.cc.slab, S.cc.ld, w.cst + 2, tiled,
                                          packed ? w.mdiag : nullptr);
     if (rc) return rc;
-    hipLaunchKernelGGL((ws_cache_fsum_kernel<2>), dim3(unsigned((nr + 511) / 512)), dim3(256), 0, s, S.cc.slab, S.cc.ld,
-                       w.crd, cf, cnt, w.f, nr, pa, pn);
+    hipLaunchKernelGGL((twin ? ws_cache_fsum_kernel<2, true> : ws_cache_fsum_kernel<2, false>),
+                       dim3(unsigned((nr + 511) / 512)), dim3(256), 0, s, S.cc.slab, S.cc.ld, w.crd, cf, cnt, w.f, nr, pa,
+                       pn);
     SVMD_LAUNCH_CHECK();
     return SVM_OK;
   }
   const int rc = launch_igram_gemv(s, Qr, N0r, WNr, R.stw, nr, roff, R.Q, R.N0, R.WN, cl, cf, cnt, kMaxWS, P, S.p.gamma,
                                    w.part, kLdp, packed ? w.cdiag : nullptr);
   if (rc) return rc;
-  hipLaunchKernelGGL(ws_fsum_count_kernel, dim3(unsigned((nr + 255) / 256)), dim3(256), 0, s, w.part, kLdp, cnt, w.f, nr,
-                     pa, pn);
+  hipLaunchKernelGGL(twin ? ws_fsum_count_kernel<true> : ws_fsum_count_kernel<false>, dim3(unsigned((nr + 255) / 256)),
+                     dim3(256), 0, s, w.part, kLdp, cnt, w.f, nr, pa, pn);
   SVMD_LAUNCH_CHECK();
   return SVM_OK;
 }
@@ -1291,7 +1466,7 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
 int cache_reset(const Solve& S) {  // no point has a slot, the first free slot is 0
   if (!S.cc.slab) return SVM_OK;
   const DecompWs& w = S.w;
-  SVMD_CHECK(hipMemsetAsync(w.cslot, 0xFF, size_t(S.n) * 4, S.s));
+  SVMD_CHECK(hipMemsetAsync(w.cslot, 0xFF, size_t(S.twin ? S.nrow : S.n) * 4, S.s));
   SVMD_CHECK(hipMemsetAsync(w.cst, 0, 64, S.s));
   if (w.cmeta) {  // owners and stamps -1, CLOCK bits clear
     SVMD_CHECK(hipMemsetAsync(w.cmeta, 0xFF, size_t(S.cc.cap) * 8, S.s));
@@ -1350,8 +1525,12 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
   int rc = cache_reset(S);  // a fresh cache per fit
   if (rc) return rc;
   if (w.shr) SVMD_CHECK(hipMemsetAsync(w.shr, 0, size_t(std::max<int64_t>(S.nloc, 1)), s));
-  hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo, S.nloc,
-                     S.n, int(warm), w.ctl);
+  if (S.twin)
+    hipLaunchKernelGGL(ws_twin_init_kernel, dim3(unsigned((S.nrow + 255) / 256)), dim3(256), 0, s, S.twin_z, S.twin_eps,
+                       S.nrow, w.sgn, S.alpha, w.f, w.ctl);
+  else
+    hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo,
+                       S.nloc, S.n, int(warm), w.ctl);
   SVMD_LAUNCH_CHECK();
   if (warm && (rc = nz_update(S, ps, warm_cols))) return rc;
   return SVM_OK;
@@ -1454,17 +1633,33 @@ int enqueue_kww(const Solve& S) {
   const DecompRows& R = S.R;
   hipStream_t s = S.s;
   int32_t* gate = &w.ctl->stop;
+  // twin mode: a point's row is its id mod nrow, and two twins in W get the diagonal's 1 between them
+  auto twin_diag = [&]() -> int {
+    if (!S.twin) return SVM_OK;
+    hipLaunchKernelGGL(ws_twin_kww_kernel, dim3(1), dim3(kMaxWS), 0, s, w.W, w.ctl, S.nrow, w.Kw, kLdw);
+    SVMD_LAUNCH_CHECK();
+    return SVM_OK;
+  };
   if (S.f64) {
-    hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W, &w.ctl->m,
-                       gate, w.Xw, w.nw);
+    if (S.twin)
+      hipLaunchKernelGGL(ws_gather_f64_twin_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W,
+                         &w.ctl->m, gate, w.Xw, w.nw, S.nrow);
+    else
+      hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W, &w.ctl->m,
+                         gate, w.Xw, w.nw);
     SVMD_LAUNCH_CHECK();
     // K(W, W) on FP64 MFMA, columns bounded by m, unit diagonal; skipped once stopped
-    return launch_rbf_block_dev(s, w.Xw, w.nw, kMaxWS, R.ld, w.Xw, w.nw, kMaxWS, R.ld, R.ld, S.p.gamma, w.Kw, kLdw, true,
-                                gate, &w.ctl->m, nullptr, 0);
+    const int rc = launch_rbf_block_dev(s, w.Xw, w.nw, kMaxWS, R.ld, w.Xw, w.nw, kMaxWS, R.ld, R.ld, S.p.gamma, w.Kw,
+                                        kLdw, true, gate, &w.ctl->m, nullptr, 0);
+    return rc ? rc : twin_diag();
   }
   const QuantPlan& P = *R.P;
-  hipLaunchKernelGGL(ws_gather_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.Q, R.N0, R.WN, P.kq, w.W, w.ctl, w.Qw,
-                     w.N0w, w.WNw);
+  if (S.twin)
+    hipLaunchKernelGGL(ws_gather_twin_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.Q, R.N0, R.WN, P.kq, w.W, w.ctl,
+                       w.Qw, w.N0w, w.WNw, S.nrow);
+  else
+    hipLaunchKernelGGL(ws_gather_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.Q, R.N0, R.WN, P.kq, w.W, w.ctl,
+                       w.Qw, w.N0w, w.WNw);
   SVMD_LAUNCH_CHECK();
   // K(W, W) over the full capacity (rows beyond m are never read); skipped once stopped
   bool ww = false;
@@ -1475,7 +1670,7 @@ int enqueue_kww(const Solve& S) {
   if (!ww)
     rc = launch_igram_sym(s, w.Qw, w.N0w, w.WNw, const_cast<double*>(R.stw), kMaxWS, P, S.p.gamma, w.Kw, kLdw, false,
                           gate);
-  return rc;
+  return rc ? rc : twin_diag();
 }
 
 // One outer iteration on the stream, the `index`-th enqueued: (repack,) select, all-gather, build, gather,
@@ -1518,7 +1713,15 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
                                       w.gAw, w.Wf, w.nAmat, S.nwd, S.Cn})))
     return rc;
   SVMD_LAUNCH_CHECK();
-  if ((rc = f_update(S, ps, w.cols, w.coef, w.mcount, index < 4))) return rc;
+  if (S.twin) {  // the moved points folded to one entry per kernel row
+    hipLaunchKernelGGL(ws_twin_fold_kernel, dim3(1), dim3(kMaxWS), 0, s, w.cols, w.coef, w.mcount, S.nrow, w.fcols,
+                       w.fcoef, w.fcount);
+    SVMD_LAUNCH_CHECK();
+    rc = f_update(S, ps, w.fcols, w.fcoef, w.fcount, index < 4);
+  } else {
+    rc = f_update(S, ps, w.cols, w.coef, w.mcount, index < 4);
+  }
+  if (rc) return rc;
   ++ps.o_dev;  // this outer iteration's count once it has run
   if (S.shc.pass_after(ps.o_dev, ps.origin) && nloc > 0) {  // the shrink pass, with this outer iteration's bounds
     const int64_t np = packed ? ps.pk_bound : nloc;
@@ -1714,9 +1917,9 @@ int decomp_solve(DeviceCtx* ctx, const DecompRows& R, const int32_t* y_d, double
     const int rc = run_decomp(ctx, R, y_d, alpha_d, n, p, q > 0 ? q : 1024, r, stats, o);
     if (rc) return rc;
   }
-  if (r) {
+  if (r) {  // twin mode: the points with a_k or a*_k above the tolerance (never both of a row at a solution)
     int64_t c = 0;
-    const int rc = count_sv(ctx, alpha_d, n, 1, p.sv_tol, &c);
+    const int rc = count_sv(ctx, alpha_d, o.twin() ? 2 * n : n, 1, p.sv_tol, &c);
     if (rc) return rc;
     r->n_sv = c;
   }
@@ -1777,7 +1980,7 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
                     int64_t* stats, bool* used, double* prep_ms, const DecompOpts& o) {
   const auto t0 = std::chrono::steady_clock::now();
   *used = false;
-  if (!decomp_shape(n, q, o.world).ok) return SVM_OK;  // beyond the solver's shapes: the caller's fallback
+  if (!decomp_shape(o.twin() ? 2 * n : n, q, o.world).ok) return SVM_OK;  // beyond the solver's shapes: the caller's fallback
   const char* fe = getenv("SVM355_DECOMP_F64");
   const bool force_f64 = fe && atoi(fe) == 1;
   QuantPlan P;
@@ -1835,7 +2038,7 @@ int decomp_fit_u8(DeviceCtx* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, con
   *used = false;
   // outside the solver's shapes (n < 2 or n >= 2^31 - 1, decomp_shape): nothing runs, the caller takes
   // the pairwise solver (SVC(solver="auto"))
-  if (!decomp_shape(n, q, o.world).ok) return SVM_OK;
+  if (!decomp_shape(o.twin() ? 2 * n : n, q, o.world).ok) return SVM_OK;
   QuantPlan P;
   if (!plan_quant(mn_h, mx_h, d, &P) || P.kq > 32 * 128) return SVM_OK;  // igram's LDS table bound
   QuantBufs b;
@@ -1946,27 +2149,84 @@ SVM_API int svmd_train_decomp(void* h, const void* X_d, int32_t is_u8, int64_t n
   return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, o, r, timing, stats, used_out);
 }
 
+// The regression (epsilon-SVR) form of svmd_train_decomp: twin mode (DecompOpts) over the n rows and the n
+// targets z_d (device FP64).  alpha_d: 2n doubles, out -- a (first n), then a* (last n); the model is beta =
+// a - a*, a prediction sum_k beta_k K(x_k, x) - r->b.  r->n_sv counts the points of either half above sv_tol.
+// A trace's W / cols / coef hold virtual ids (k and k + n) and its snapshots are 2n long (trace->n = 2n).  Cold
+// start, one GPU; shrinking, the Newton polish and class weights in *pp are SVM_ERR_ARG, as is 2n > 2^31 - 1.
+SVM_API int svmd_train_decomp_svr(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                  const double* mn_h, const double* mx_h, const double* z_d, double epsilon,
+                                  double* alpha_d, const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
+                                  int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
+  SVMD_CTX(h);
+  if (used_out) *used_out = 0;
+  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !z_d || !alpha_d) {
+    set_error("svmd_train_decomp_svr: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) {
+    set_error("svmd_train_decomp_svr: epsilon must be finite and >= 0, got %g", epsilon);
+    return SVM_ERR_ARG;
+  }
+  if (2 * n > int64_t(INT32_MAX)) {
+    set_error("svmd_train_decomp_svr: n = %lld rows are 2 n > 2^31 - 1 points", (long long)n);
+    return SVM_ERR_ARG;
+  }
+  {  // what twin mode refuses, before any device work (setup_solve checks the same)
+    svm_params p;
+    if (pp)
+      p = *pp;
+    else
+      svm_default_params(&p);
+    double cp = 0.0, cn = 0.0;
+    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
+    const char* what = shrink_cfg(p).on           ? "shrinking"
+                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                       : (cp != p.C || cn != p.C) ? "class weights"
+                                                  : nullptr;
+    if (what) {
+      set_error("svmd_train_decomp_svr: the regression (twin) solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+  }
+  DecompOpts o;
+  o.trace = trace;
+  o.twin_z = z_d;
+  o.twin_eps = epsilon;
+  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, nullptr, alpha_d, pp, q, o, r, timing, stats, used_out);
+}
+
 // The decomposition solver's f update alone (tests): the uint8 rows quantised as a solve would, then
 // f_out[i] = sum_k coef[k] K(lo + i, cols[k]) over k < m for the rows [lo, lo + nloc) -- the solver's own
 // f_update from f = 0 with the device-side count m, on the GEMV (its partial halves summed in order) or,
 // with SVM355_GEMV_VIA_CACHE set, on a fresh column cache of m persistent slots (every column a miss: the
 // narrow store up to 64 columns, the tiled one beyond; then the reader).  cols / coef / f_out are host
 // arrays; m <= 1024.  *used = 0 without an exact plan.
-SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
-                                const double* mx_h, double gamma, int64_t lo, int64_t nloc, const int32_t* cols_h,
-                                const double* coef_h, int32_t m, double* f_out, int32_t* used_out) {
-  SVMD_CTX(h);
+// Twin mode (twin: svmd_decomp_twin_step_u8): lo = 0 and nloc = n, cols_h holds virtual ids in [0, 2n), f_out
+// is 2n long and holds the start on entry; the list is folded on the device (ws_twin_fold_kernel) and the
+// update adds every row's sum to both of its points.
+static int gemv_probe_u8(DeviceCtx* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
+                         const double* mx_h, double gamma, int64_t lo, int64_t nloc, const int32_t* cols_h,
+                         const double* coef_h, int32_t m, double* f_out, int32_t* used_out, bool twin) {
+  const char* who = twin ? "svmd_decomp_twin_step_u8" : "svmd_decomp_gemv_u8";
   if (used_out) *used_out = 0;
   if (!Xu_d || n < 1 || d <= 0 || lo < 0 || nloc < 1 || lo + nloc > n || m < 1 || m > kMaxWS || !cols_h || !coef_h ||
-      !f_out) {
-    set_error("svmd_decomp_gemv_u8: bad arguments");
+      !f_out || (twin && (lo != 0 || nloc != n || 2 * n > int64_t(INT32_MAX)))) {
+    set_error("%s: bad arguments", who);
     return SVM_ERR_ARG;
   }
   for (int k = 0; k < m; ++k)
-    if (cols_h[k] < 0 || cols_h[k] >= n) {
-      set_error("svmd_decomp_gemv_u8: column %d out of range", cols_h[k]);
+    if (cols_h[k] < 0 || cols_h[k] >= (twin ? 2 * n : n)) {
+      set_error("%s: column %d out of range", who, cols_h[k]);
       return SVM_ERR_ARG;
     }
+  if (twin)  // a point is listed once (the inner solve's moved list): the fold pairs k with k + n only
+    for (int k = 0; k < m; ++k)
+      for (int q = 0; q < k; ++q)
+        if (cols_h[q] == cols_h[k]) {
+          set_error("%s: point %d listed twice", who, cols_h[k]);
+          return SVM_ERR_ARG;
+        }
   int rc = ctx->begin();
   if (rc) return rc;
   hipStream_t s = ctx->stream;
@@ -1985,9 +2245,11 @@ SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t
   S.s = s;
   S.R = b.rows(P);
   S.kq = P.kq;
-  S.n = n;
+  S.n = twin ? 2 * n : n;
   S.lo = lo;
-  S.nloc = nloc;
+  S.nloc = twin ? 2 * n : nloc;
+  S.twin = twin;
+  S.nrow = n;
   S.p.gamma = gamma;
   const char* vc = getenv("SVM355_GEMV_VIA_CACHE");
   const bool via_cache = vc && atoi(vc) != 0;
@@ -1996,7 +2258,7 @@ SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t
     S.cc.ld = (nloc + 3) & ~int64_t(3);
     S.cc.slab = ctx->ensure_rc_cache(size_t(m + kMaxWS) * S.cc.ld * 8);
     if (!S.cc.slab) {
-      set_error("svmd_decomp_gemv_u8: no memory for the column cache");
+      set_error("%s: no memory for the column cache", who);
       return SVM_ERR_DEVICE;
     }
   }
@@ -2005,25 +2267,57 @@ SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t
     w.cols = c.take<int32_t>(kMaxWS);
     w.coef = c.take<double>(kMaxWS);
     w.mcount = c.take<int32_t>(64);
-    w.f = c.take<double>(size_t(nloc));
+    w.f = c.take<double>(size_t(S.nloc));
     w.part = c.take<double>(size_t(nloc) * kLdp, !via_cache);
     w.cslot = c.take<int32_t>(size_t(n), via_cache);
     w.crd = c.take<int32_t>(kMaxWS, via_cache);
     w.cmid = c.take<int32_t>(kMaxWS, via_cache);
     w.cmsl = c.take<int32_t>(kMaxWS, via_cache);
     w.cst = c.take<int32_t>(64, via_cache);
+    w.fcols = c.take<int32_t>(kMaxWS, twin);
+    w.fcoef = c.take<double>(kMaxWS, twin);
+    w.fcount = c.take<int32_t>(64, twin);
   });
   if (rc) return rc;
   SVMD_CHECK(hipMemcpyAsync(w.cols, cols_h, size_t(m) * 4, hipMemcpyHostToDevice, s));
   SVMD_CHECK(hipMemcpyAsync(w.coef, coef_h, size_t(m) * 8, hipMemcpyHostToDevice, s));
   SVMD_CHECK(hipMemcpyAsync(w.mcount, &m, 4, hipMemcpyHostToDevice, s));
-  SVMD_CHECK(hipMemsetAsync(w.f, 0, size_t(nloc) * 8, s));
+  if (twin)
+    SVMD_CHECK(hipMemcpyAsync(w.f, f_out, size_t(S.nloc) * 8, hipMemcpyHostToDevice, s));
+  else
+    SVMD_CHECK(hipMemsetAsync(w.f, 0, size_t(nloc) * 8, s));
   if ((rc = cache_reset(S))) return rc;
-  if ((rc = f_update(S, PackState(nloc), w.cols, w.coef, w.mcount))) return rc;
-  SVMD_CHECK(hipMemcpyAsync(f_out, w.f, size_t(nloc) * 8, hipMemcpyDeviceToHost, s));
+  if (twin) {
+    hipLaunchKernelGGL(ws_twin_fold_kernel, dim3(1), dim3(kMaxWS), 0, s, w.cols, w.coef, w.mcount, n, w.fcols, w.fcoef,
+                       w.fcount);
+    SVMD_LAUNCH_CHECK();
+    rc = f_update(S, PackState(nloc), w.fcols, w.fcoef, w.fcount);
+  } else {
+    rc = f_update(S, PackState(nloc), w.cols, w.coef, w.mcount);
+  }
+  if (rc) return rc;
+  SVMD_CHECK(hipMemcpyAsync(f_out, w.f, size_t(S.nloc) * 8, hipMemcpyDeviceToHost, s));
   SVMD_CHECK(hipStreamSynchronize(s));
   if (used_out) *used_out = 1;
   return ctx->end();
+}
+
+SVM_API int svmd_decomp_gemv_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
+                                const double* mx_h, double gamma, int64_t lo, int64_t nloc, const int32_t* cols_h,
+                                const double* coef_h, int32_t m, double* f_out, int32_t* used_out) {
+  SVMD_CTX(h);
+  return gemv_probe_u8(ctx, Xu_d, n, d, mn_h, mx_h, gamma, lo, nloc, cols_h, coef_h, m, f_out, used_out, false);
+}
+
+// The twin mode's fold and f update alone (tests): cols_h / coef_h = a moved list of m <= 1024 distinct virtual
+// ids in [0, 2n) (k: a_k, k + n: a*_k), f_io = the 2n points' f (host, in and out).  The list is folded on the
+// device to one entry per kernel row and f_io[k] and f_io[k + n] both take row k's sum, computed once over the
+// n rows by the solver's own f_update (the GEMV, or the column cache with SVM355_GEMV_VIA_CACHE).
+SVM_API int svmd_decomp_twin_step_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
+                                     const double* mx_h, double gamma, const int32_t* cols_h, const double* coef_h,
+                                     int32_t m, double* f_io, int32_t* used_out) {
+  SVMD_CTX(h);
+  return gemv_probe_u8(ctx, Xu_d, n, d, mn_h, mx_h, gamma, 0, n, cols_h, coef_h, m, f_io, used_out, true);
 }
 
 // One Newton polish step (decomp_newton.h) on the device for a host working set (tests / timing): Kw_h

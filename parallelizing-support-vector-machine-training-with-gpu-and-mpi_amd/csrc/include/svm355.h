@@ -155,6 +155,30 @@ SVM_API int svm_decomp_train_gram(const double* K, int64_t ldk, const int32_t* y
 SVM_API int svm_decomp_gemv_ref(const double* K, int64_t ldk, int64_t n, const int32_t* cols, const double* coef,
                                 int64_t cnt, double* f);
 
+// ---------------------------------------------------------------- epsilon-SVR (L3)
+// epsilon-SVR is the same box-constrained problem over 2n variables in pairs ("twins") that share a kernel
+// row: variable k is a_k with sign +1, variable k + n is a*_k with sign -1, Q_ij = s_i s_j K(i mod n, j mod n),
+// and the start is f_k = epsilon - z_k, f_{k+n} = -epsilon - z_k.  alpha (2n, out): a, then a*.  The model is
+// beta = a - a*; a prediction is sum_k beta_k K(x_k, x) - b.  Cold start only; class weights are refused.
+// The pairwise oracle (small n: it solves on duplicated rows).
+SVM_API int svm_smo_train_svr(const double* X, const double* z, int64_t n, int64_t d, double epsilon, double* alpha,
+                              const svm_params* p, svm_result* r);
+// The decomposition oracle's twin mode on the n x n kernel matrix K (the device's own kernel values for a
+// bit-for-bit comparison with svmd_train_decomp_svr): selection and the working set over the 2n virtual
+// points, kernel rows by id mod n, the moved list folded to one entry per row, every row's sum added to both
+// twins' f.  The trace's W / cols / coef hold virtual ids, its snapshots 2n values (trace->n = 2n).
+// f64_rows: 0 = the f update sums in the exact-integer GEMV's order (svm_decomp_gemv_ref), 1 = in the FP64-row
+// path's (real-valued rows: one wave per row, lane-strided terms, a 64-lane butterfly).
+SVM_API int svm_decomp_train_gram_svr(const double* K, int64_t ldk, const double* z, int64_t n, double epsilon,
+                                      double* alpha, const svm_params* p, int32_t q, double tau_frac,
+                                      int32_t inner_wss, int32_t f64_rows, svm_result* r, int64_t* stats,
+                                      svm_decomp_trace* trace);
+// The twin mode's moved-column fold alone (tests): cnt <= 1024 virtual ids in [0, 2n) with their coefficients
+// become one entry per kernel row, at the position of the row's first occurrence; where both twins are listed
+// the coefficient is coef_k + coef_{k+n}.  out_cols / out_coef: room for cnt entries; *out_cnt: entries written.
+SVM_API int svm_decomp_twin_fold(const int32_t* cols, const double* coef, int32_t cnt, int64_t n, int32_t* out_cols,
+                                 double* out_coef, int32_t* out_cnt);
+
 // ---------------------------------------------------------------- evaluation (L4)
 // out[i] = sum_k alphas[k]*ys[k]*K(Xq_i, Xs_k) - b, summed in SV order from -b (main3.cpp:391-402).
 SVM_API int svm_decision(const double* Xs, const int32_t* ys, const double* alphas, int64_t nsv,

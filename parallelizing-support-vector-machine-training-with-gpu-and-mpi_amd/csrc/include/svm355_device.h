@@ -69,6 +69,22 @@ SVM_API int svmd_train_decomp_rows(void* ctx, const double* X_d, int64_t n, int6
                                    const double* mn_h, const double* mx_h, const int32_t* y_d, double* alpha_d,
                                    const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
                                    int64_t* stats, int32_t* used);
+// epsilon-SVR on the decomposition solver (svm355.h has the twin mapping): uint8 pixel rows (is_u8, X_d n x d)
+// or min-max scaled FP64 rows (X_d n x ld), the n targets z_d on the device.  alpha_d: 2n doubles, out -- a,
+// then a*; the model is beta = a - a*.  The exact-integer plan when the rows' statistics admit it, FP64-MFMA
+// kernel values otherwise (FP64 rows; *used = 0 and nothing done for uint8 rows without a plan).  The GEMV, the
+// column store and the column cache run over the n rows, as a classification of them.  Cold start, one GPU;
+// shrinking, the Newton polish, class weights and 2n > 2^31 - 1 are SVM_ERR_ARG.  trace (tests, may be NULL):
+// virtual ids k / k + n, snapshots of 2n values.
+SVM_API int svmd_train_decomp_svr(void* ctx, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                  const double* mn_h, const double* mx_h, const double* z_d, double epsilon,
+                                  double* alpha_d, const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
+                                  int64_t* stats, int32_t* used, svm_decomp_trace* trace);
+// The twin mode's moved-column fold and f update alone (tests): a moved list of m <= 1024 distinct virtual ids
+// (host), f_io = the 2n points' f (host, in and out).
+SVM_API int svmd_decomp_twin_step_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
+                                     const double* mx_h, double gamma, const int32_t* cols_h, const double* coef_h,
+                                     int32_t m, double* f_io, int32_t* used);
 SVM_API int svmd_minmax_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, double* mn_d, double* mx_d);
 SVM_API int svmd_rbf_gram_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
                              const double* mx_h, double gamma, double* K_d, int64_t ldk, int32_t* used);

@@ -6,7 +6,9 @@ The reference's (commented-out) model dump writes four text files, one value per
 Those are written natively (svm_model_save) with %.17g so they round-trip bit-exactly.  Because
 IDs alone cannot reproduce a prediction without the training set, a loadable model additionally
 stores the scaled SV rows (``sv_rows.npy``) and the scaler (``scaler.npz``) in numpy's
-pickle-free formats, plus ``model.json`` with the hyper-parameters.
+pickle-free formats, plus ``model.json`` with the hyper-parameters and the model's kind: "svc" (a
+classifier; also what a file without the marker is) or "svr" (an epsilon-SVR, stored with labels = sign(beta)
+and alphas = |beta|).  Each class loads its own kind only.
 """
 from __future__ import annotations
 
@@ -23,7 +25,7 @@ from ..utils.data import MinMaxScaler
 
 
 def save_model(directory, ids, labels, alphas, b, sv_rows=None, scaler: Optional[MinMaxScaler] = None,
-               params: Optional[SVMParams] = None, meta: Optional[dict] = None) -> None:
+               params: Optional[SVMParams] = None, meta: Optional[dict] = None, kind: str = "svc") -> None:
     d = Path(directory)
     d.mkdir(parents=True, exist_ok=True)
     ids = np.ascontiguousarray(ids, dtype=np.int64)
@@ -35,7 +37,7 @@ def save_model(directory, ids, labels, alphas, b, sv_rows=None, scaler: Optional
         np.save(d / "sv_rows.npy", np.ascontiguousarray(sv_rows, dtype=np.float64), allow_pickle=False)
     if scaler is not None:
         np.savez(d / "scaler.npz", min=scaler.min_, max=scaler.max_)
-    info = {"format": "svm355-model-v1", "n_sv": int(ids.shape[0]), "b": float(b),
+    info = {"format": "svm355-model-v1", "kind": kind, "n_sv": int(ids.shape[0]), "b": float(b),
             "params": (params or SVMParams()).as_dict(), "meta": meta or {}}
     (d / "model.json").write_text(json.dumps(info, indent=2))
 
@@ -57,8 +59,10 @@ def load_model(directory) -> dict:
         z = np.load(d / "scaler.npz", allow_pickle=False)
         scaler = MinMaxScaler(z["min"], z["max"])
     params = SVMParams()
+    kind, meta = "svc", {}
     if (d / "model.json").exists():
         info = json.loads((d / "model.json").read_text())
         params = SVMParams(**info.get("params", {}))
+        kind, meta = info.get("kind", "svc"), info.get("meta", {})
     return {"ids": ids, "labels": labels, "alphas": alphas, "b": b, "sv_rows": sv_rows, "scaler": scaler,
-            "params": params}
+            "params": params, "kind": kind, "meta": meta}

@@ -356,6 +356,8 @@ class SVC:
         from ..models.model_io import load_model
 
         m = load_model(directory)
+        if m["kind"] != "svc":
+            raise ValueError(f"{directory} holds a {m['kind']!r} model, not a classifier (load it with its own class)")
         p = m["params"]
         svc = cls(C=p.C, gamma=p.gamma, tol=p.tau, eps=p.eps, sv_tol=p.sv_tol, max_iter=p.max_iter, device=device,
                   scale=m["scaler"] is not None,

@@ -100,6 +100,67 @@ def decomp_train_gram(K: np.ndarray, y: np.ndarray, params: SVMParams, alpha: Op
     return a, SMOResult.from_struct(r), _decomp_stats(st), tr
 
 
+def _targets(z, n: int) -> np.ndarray:
+    z = _c64(z)
+    if z.shape != (n,):
+        raise ValueError(f"z must have shape ({n},), got {z.shape}")
+    return z
+
+
+def smo_train_svr(X: np.ndarray, z: np.ndarray, params: SVMParams, epsilon: float = 0.1
+                  ) -> Tuple[np.ndarray, SMOResult]:
+    """epsilon-SVR on the pairwise oracle (svm_smo_train_svr: the 2n-variable problem on duplicated rows, for
+    small n).  Returns (alpha of 2n entries: a, then a*; result); the model is beta = a - a*."""
+    X = _c64(X)
+    n, d = X.shape
+    z = _targets(z, n)
+    a = np.zeros(2 * n)
+    r = N.SvmResult()
+    p = params.to_struct()
+    N.check(N.core().svm_smo_train_svr(N.ptr(X), N.ptr(z), n, d, float(epsilon), N.ptr(a), ctypes.byref(p),
+                                       ctypes.byref(r)), "svm_smo_train_svr")
+    return a, SMOResult.from_struct(r)
+
+
+def decomp_train_gram_svr(K: np.ndarray, z: np.ndarray, params: SVMParams, epsilon: float = 0.1, q: int = 1024,
+                          tau_frac: float = 0.1, inner_wss: int = 3, trace_cap: int = 0, snapshots: bool = False,
+                          fp64_rows: bool = False):
+    """The decomposition oracle's twin mode (epsilon-SVR, svm_decomp_train_gram_svr) on the n x n kernel matrix
+    K and the n targets z.  Returns (alpha of 2n entries: a, then a*; SMOResult; stats dict; N.DecompTrace or
+    None -- its ids are virtual, k and k + n, and its snapshots 2n long).  fp64_rows: the f update sums in the
+    order of the device's FP64-row path (real-valued rows) instead of its exact-integer GEMV's."""
+    K = _c64(K)
+    n = np.shape(z)[0]
+    z = _targets(z, n)
+    _gram_shape(K, n)
+    a = np.zeros(2 * n)
+    r = N.SvmResult()
+    st = (ctypes.c_int64 * 16)()
+    tr = N.DecompTrace(trace_cap, 2 * n if snapshots else 0) if trace_cap > 0 else None
+    p = params.to_struct()
+    N.check(N.core().svm_decomp_train_gram_svr(N.ptr(K), K.shape[1], N.ptr(z), n, float(epsilon), N.ptr(a),
+                                               ctypes.byref(p), int(q), float(tau_frac), int(inner_wss),
+                                               int(bool(fp64_rows)), ctypes.byref(r), st,
+                                               ctypes.byref(tr.struct) if tr is not None else None),
+            "svm_decomp_train_gram_svr")
+    return a, SMOResult.from_struct(r), _decomp_stats(st), tr
+
+
+def twin_fold(cols: np.ndarray, coef: np.ndarray, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The twin mode's moved-column fold (svm_decomp_twin_fold): virtual ids in [0, 2n) and their coefficients
+    to one entry per kernel row.  Returns (rows, coefficients)."""
+    cols = _c32(cols)
+    coef = _c64(coef)
+    if cols.shape != coef.shape or cols.ndim != 1:
+        raise ValueError("cols and coef must be 1-D arrays of one length")
+    oc = np.zeros(max(1, cols.size), dtype=np.int32)
+    ov = np.zeros(max(1, cols.size))
+    cnt = ctypes.c_int32(0)
+    N.check(N.core().svm_decomp_twin_fold(N.ptr(cols), N.ptr(coef), int(cols.size), int(n), N.ptr(oc), N.ptr(ov),
+                                          ctypes.byref(cnt)), "svm_decomp_twin_fold")
+    return oc[: cnt.value].copy(), ov[: cnt.value].copy()
+
+
 def _decomp_stats(st) -> dict:
     return {"outer_iterations": int(st[0]), "inner_iterations": int(st[1]), "working_set": int(st[2]),
             "solve_us": int(st[3]), "update_columns": int(st[4]), "chain_iterations": int(st[13]),

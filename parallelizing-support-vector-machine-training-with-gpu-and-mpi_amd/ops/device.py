@@ -469,6 +469,65 @@ def train_decomp_rows(X: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, par
     return train_decomp(X, y, alpha, params, mn, mx, working_set, warm)
 
 
+def train_decomp_svr(X: torch.Tensor, z: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
+                     epsilon: float = 0.1, working_set: int = 1024,
+                     trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:
+    """epsilon-SVR on the decomposition solver (svmd_train_decomp_svr): twin mode over the n rows of X (device
+    uint8 pixel rows (n, d), or min-max scaled FP64 rows (n, ld), as ``train_decomp``) and the n float64 targets
+    z on the device.  alpha (2n float64, out): a, then a*; the model is beta = a - a*.  The kernel work of the f
+    update runs over the n rows, as a classification of them.  Cold start only; shrinking, the Newton polish and
+    class weights raise.  trace: an ``N.DecompTrace`` of 2n-long snapshots (tests).  None when nothing ran
+    (uint8 rows without an exact-integer plan; FP64 rows whose workspace does not fit)."""
+    u8 = X.dtype == torch.uint8
+    if not u8:
+        _check_rows(X)
+    n, ld = X.shape
+    if z.dtype != torch.float64 or z.shape != (n,) or not z.is_contiguous():
+        raise ValueError(f"z must be a contiguous float64 tensor of shape ({n},)")
+    if alpha.dtype != torch.float64 or alpha.shape != (2 * n,) or not alpha.is_contiguous():
+        raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({2 * n},): a, then a*")
+    ctx = _ctx_for(X)
+    a, b, dd = _host_stats(mn, mx)
+    d = ld if u8 else dd
+    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
+    st = (ctypes.c_int64 * 16)()
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_train_decomp_svr(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), N.ptr(z),
+                                          float(epsilon), N.ptr(alpha), ctypes.byref(p), int(working_set),
+                                          ctypes.byref(r), ctypes.byref(tm), st, ctypes.byref(used),
+                                          ctypes.byref(trace.struct) if trace is not None else None),
+            "svmd_train_decomp_svr")
+    if not used.value:
+        return None
+    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
+                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
+                                      "rows": "uint8" if u8 else "fp64", "solver": "decomp-svr",
+                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
+                                      "working_set": int(st[2]), "update_columns": int(st[4]),
+                                      "inner_threads": int(st[5])}
+
+
+def decomp_twin_step_u8(Xu: torch.Tensor, mn, mx, gamma: float, cols: np.ndarray, coef: np.ndarray,
+                        f: np.ndarray) -> Optional[np.ndarray]:
+    """The twin mode's fold and f update alone (svmd_decomp_twin_step_u8): the moved list ``cols`` (distinct
+    virtual ids in [0, 2n): k is a_k, k + n its twin) with ``coef`` is folded on the device to one entry per
+    row, and the returned copy of ``f`` (2n) has every row's sum added to both of its points.  None when no
+    exact-integer plan applies."""
+    n, d = Xu.shape
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    out = np.array(f, dtype=np.float64, copy=True)
+    if out.shape != (2 * n,) or cols.shape != coef.shape:
+        raise ValueError(f"f must have shape ({2 * n},) and cols / coef one length")
+    a, b, _ = _host_stats(mn, mx)
+    used = ctypes.c_int32(0)
+    ctx = _ctx_for(Xu)
+    N.check(ctx.lib.svmd_decomp_twin_step_u8(ctx.bind(), N.ptr(Xu), n, d, N.ptr(a), N.ptr(b), float(gamma), N.ptr(cols),
+                                             N.ptr(coef), int(cols.size), N.ptr(out), ctypes.byref(used)),
+            "svmd_decomp_twin_step_u8")
+    return out if used.value else None
+
+
 def decomp_gemv_u8(Xu: torch.Tensor, mn, mx, gamma: float, cols: np.ndarray, coef: np.ndarray, lo: int = 0,
                    nloc: Optional[int] = None) -> Optional[np.ndarray]:
     """The decomposition solver's f-update GEMV alone (svmd_decomp_gemv_u8): sum_k coef[k] K(i, cols[k])
