@@ -206,6 +206,9 @@ _CORE_SIGS = {
                                      POINTER(SvmResult), _P, c_int64]),
     "svm_decomp_train_gram": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int32, POINTER(SvmParams), c_int32, c_double,
                                         c_int32, POINTER(SvmResult), POINTER(c_int64), POINTER(SvmDecompTrace)]),
+    "svm_decomp_train_gram_rows": (c_int32, [_P, c_int64, _P, c_int64, _P, POINTER(SvmParams), c_int32, c_double,
+                                             c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
+                                             POINTER(SvmDecompTrace)]),
     "svm_smo_train_svr": (c_int32, [_P, _P, c_int64, c_int64, c_double, _P, POINTER(SvmParams), POINTER(SvmResult)]),
     "svm_decomp_train_gram_svr": (c_int32, [_P, c_int64, _P, c_int64, c_double, _P, POINTER(SvmParams), c_int32,
                                             c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),

@@ -11,7 +11,8 @@
 //   * inner solve (ws_inner_kernel): i = argmin f over I_high, j second order (Fan, Chen & Lin gain
 //     -(f_t - b_high)^2 / (2 - 2 K(i, t)), exact division as on the device) or first order, the
 //     reference's clip / eta / update arithmetic (main3.cpp:235-275) with the same operation order
-//     (both sides build with -ffp-contract=off), W's own stop max(tau, tau_frac * gap);
+//     (both sides build with -ffp-contract=off), W's own stop max(tau, tau_frac * gap); one departure from the
+//     reference: a first pair with eta <= eps (identical rows) is not a stop, eta is floored at eps (LIBSVM);
 //   * f update (igram GEMV epilogue + ws_fsum_count_kernel): per row, per 64-column half, lane l's
 //     two terms (columns l and 32 + l) summed from 0, a 32-lane xor butterfly (16, 8, 4, 2, 1), and
 //     the halves added in index order before the one add into f.
@@ -292,6 +293,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
 
   int64_t outer = 0, inner_total = 0, changed_total = 0, last_inner_it = 0, newton_steps = 0;
   int64_t chain_it = 0;  // inner-solve loop iterations (each one or more pair updates)
+  int64_t eta_floored = 0;  // first-pair updates whose eta was floored at eps (the device does not count them)
   int last_m = 0;
   const int inner_threads = inner_nt();
   NewtonCfg nwc = newton_cfg(p);
@@ -520,7 +522,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       const double ah = a[size_t(ih)], al = a[size_t(il)];
       const int32_t yh = yw[size_t(ih)], yl = yw[size_t(il)];
       const int s = yh * yl;
-      const double eta = 1.0 + 1.0 - 2.0 * K12;
+      double eta = 1.0 + 1.0 - 2.0 * K12;
       const double Ch = yh == 1 ? Cp : Cn, Cl = yl == 1 ? Cp : Cn;
       double U, V;
       if (s == -1) {
@@ -534,9 +536,14 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         reason = SVM_STOP_INFEASIBLE;
         break;
       }
+      // Identical rows (K12 = 1, or 1 - ulp from the FP64 Gram) with conflicting labels or targets: a
+      // violating pair without curvature.  LIBSVM's rule, not the reference's stop: eta is floored at eps and
+      // the box clips the step.  high is in I_high and low in I_low, so the step has room of more than eps in
+      // its direction; with eta = eps it lands on U or V, which are finite.  (The pairwise solvers keep the
+      // reference's stop; the second pair below still skips.)
       if (eta <= eps) {
-        reason = SVM_STOP_NONPOS_ETA;
-        break;
+        eta = eps;
+        ++eta_floored;
       }
       double al_new = al + double(yl) * (hv - bl_upd) / eta;
       if (al_new > V) al_new = V;
@@ -605,7 +612,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       (f64_rows ? rowsum_update_f64 : gemv_update)(K, ldk, nr, fcols.data(), fcoef.data(), int64_t(fcols.size()),
                                                    f.data(), team, f.data() + nr);
     } else {
-      gemv_update(K + lo * ldk, ldk, nloc, cols.data(), coef.data(), int64_t(cols.size()), f.data(), team, nullptr);
+      (f64_rows ? rowsum_update_f64 : gemv_update)(K + lo * ldk, ldk, nloc, cols.data(), coef.data(),
+                                                   int64_t(cols.size()), f.data(), team, nullptr);
     }
     if (shc.pass_after(outer, origin)) {  // shrink pass with this outer iteration's bounds
       int64_t drop = 0;
@@ -661,6 +669,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     stats[11] = 0;
     stats[12] = newton_steps;
     stats[13] = chain_it;
+    stats[14] = eta_floored;
   }
   if (res) {
     res->iterations = inner_total + 1;
@@ -692,6 +701,16 @@ extern "C" SVM_API int svm_decomp_train_gram(const double* K, int64_t ldk, const
                                              svm_decomp_trace* tr) {
   return decomp_solve(K, ldk, y, n, alpha, warm, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
                       nullptr);
+}
+
+// svm_decomp_train_gram on a cold start with the f update's summation order chosen: f64_rows = 1 sums as the
+// device's FP64-row path does (real-valued rows, ws_rowsum_f64_kernel), 0 as its exact-integer GEMV.
+extern "C" SVM_API int svm_decomp_train_gram_rows(const double* K, int64_t ldk, const int32_t* y, int64_t n,
+                                                  double* alpha, const svm_params* pp, int32_t qws, double tau_frac,
+                                                  int32_t inner_wss, int32_t f64_rows, svm_result* res,
+                                                  int64_t* stats, svm_decomp_trace* tr) {
+  return decomp_solve(K, ldk, y, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
+                      nullptr, nullptr, 0.0, f64_rows != 0);
 }
 
 // The regression (epsilon-SVR) form of svm_decomp_train_gram: twin mode over the n x n kernel matrix K and

@@ -858,7 +858,7 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
     }
     const double K11 = 1.0, K22 = 1.0;  // the Gram's unit diagonal
     const int s = yh * yl;
-    const double eta = K11 + K22 - 2.0 * K12;
+    double eta = K11 + K22 - 2.0 * K12;
     const double Ch = box(yh), Cl = box(yl);
     double U, V;
     if (s == -1) {
@@ -872,10 +872,12 @@ __global__ __launch_bounds__(NT) void ws_inner_kernel(const double* __restrict__
       reason = SVM_STOP_INFEASIBLE;
       break;
     }
-    if (eta <= eps) {
-      reason = SVM_STOP_NONPOS_ETA;
-      break;
-    }
+    // Identical rows (K12 = 1, or 1 - ulp from the FP64 Gram) with conflicting labels or targets: a violating
+    // pair without curvature.  LIBSVM's rule, not the reference's stop: eta is floored at eps and the box clips
+    // the step.  high is in I_high and low in I_low, so the step has room of more than eps in its direction;
+    // with eta = eps it lands on U or V, which are finite.  (The second pair below still skips: the next
+    // selection picks it up as a first pair.)
+    eta = eta <= eps ? eps : eta;
     double al_new = al + double(yl) * (bh - bl_upd) / eta;
     if (al_new > V) al_new = V;
     if (al_new < U) al_new = U;

@@ -37,7 +37,9 @@ enum svm_stop {
   SVM_STOP_CONVERGED = 1,     // b_low <= b_high + 2*tau
   SVM_STOP_NO_CANDIDATE = 2,  // "i_high or i_low not found; iteration stops"
   SVM_STOP_INFEASIBLE = 3,    // "warning: infeasible U and V; iteration stops"
-  SVM_STOP_NONPOS_ETA = 4,    // "warning: non positive eta; iteration stops"
+  SVM_STOP_NONPOS_ETA = 4,    // "warning: non positive eta; iteration stops": the pairwise solvers only (smo.hip,
+                              // persist.h, rowcache.hip, smo_cpu.cpp: the reference's stop); the decomposition
+                              // solver and its oracle floor eta at eps instead and never report it
   SVM_STOP_MAX_ITER = 5,      // "Too many iterations; stopping"
 };
 
@@ -120,7 +122,8 @@ SVM_API int svm_smo_train_gram(const double* K, int64_t ldk, const int32_t* y, i
 #define SVM_DECOMP_MAX_WS 1024
 // int64 entries of a decomposition solve's stats array: outer / inner iterations, working-set capacity,
 // solve us, moved columns, inner threads, kernel-value path, warm columns, unshrinks, shrink passes,
-// the least active rows seen, repacks, Newton steps (decomp_shrink.h / decomp_newton.h), 3 reserved
+// the least active rows seen, repacks, Newton steps (decomp_shrink.h / decomp_newton.h), the oracle's chain
+// iterations and its first-pair updates with eta floored at eps (0 from the device, which does not count), 1 reserved
 #define SVM_DECOMP_STATS 16
 typedef struct svm_decomp_trace {
   int64_t cap;     // capacity in outer iterations
@@ -149,6 +152,12 @@ typedef struct svm_decomp_trace {
 SVM_API int svm_decomp_train_gram(const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha,
                                   int32_t warm, const svm_params* p, int32_t q, double tau_frac, int32_t inner_wss,
                                   svm_result* r, int64_t* stats, svm_decomp_trace* trace);
+
+// The same on a cold start with the f update's summation order chosen (tests): f64_rows = 1 sums as the device's
+// FP64-row path does (real-valued rows: one wave per row, lane-strided terms, a 64-lane butterfly), 0 as the GEMV.
+SVM_API int svm_decomp_train_gram_rows(const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha,
+                                       const svm_params* p, int32_t q, double tau_frac, int32_t inner_wss,
+                                       int32_t f64_rows, svm_result* r, int64_t* stats, svm_decomp_trace* trace);
 
 // The device f-update GEMV's arithmetic alone: f[i] += sum_{k < cnt} coef[k] K(i, cols[k]) for the n
 // rows of K, in the device's summation order (bit-for-bit tests of the GEMV kernel).

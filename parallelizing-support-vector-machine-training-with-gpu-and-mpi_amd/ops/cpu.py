@@ -81,9 +81,11 @@ def smo_train_gram(K: np.ndarray, y: np.ndarray, params: SVMParams, alpha: Optio
 
 def decomp_train_gram(K: np.ndarray, y: np.ndarray, params: SVMParams, alpha: Optional[np.ndarray] = None,
                       q: int = 1024, tau_frac: float = 0.1, inner_wss: int = 3, trace_cap: int = 0,
-                      snapshots: bool = False):
+                      snapshots: bool = False, fp64_rows: bool = False):
     """CPU oracle of the device decomposition solver (csrc/core/decomp_cpu.cpp) on a kernel matrix K.
-    alpha given = warm start.  Returns (alpha, SMOResult, stats dict, N.DecompTrace or None)."""
+    alpha given = warm start.  Returns (alpha, SMOResult, stats dict, N.DecompTrace or None).  fp64_rows (cold
+    start only): the f update sums in the order of the device's FP64-row path (real-valued rows) instead of its
+    exact-integer GEMV's."""
     K = _c64(K)
     y = _c32(y)
     n = y.shape[0]
@@ -93,10 +95,17 @@ def decomp_train_gram(K: np.ndarray, y: np.ndarray, params: SVMParams, alpha: Op
     st = (ctypes.c_int64 * 16)()
     tr = N.DecompTrace(trace_cap, n if snapshots else 0) if trace_cap > 0 else None
     p = params.to_struct()
-    N.check(N.core().svm_decomp_train_gram(N.ptr(K), K.shape[1], N.ptr(y), n, N.ptr(a), int(alpha is not None),
-                                           ctypes.byref(p), int(q), float(tau_frac), int(inner_wss), ctypes.byref(r),
-                                           st, ctypes.byref(tr.struct) if tr is not None else None),
-            "svm_decomp_train_gram")
+    trp = ctypes.byref(tr.struct) if tr is not None else None
+    if alpha is None:  # cold: the entry that takes the f update's summation order
+        N.check(N.core().svm_decomp_train_gram_rows(N.ptr(K), K.shape[1], N.ptr(y), n, N.ptr(a), ctypes.byref(p),
+                                                    int(q), float(tau_frac), int(inner_wss), int(bool(fp64_rows)),
+                                                    ctypes.byref(r), st, trp), "svm_decomp_train_gram_rows")
+    elif fp64_rows:
+        raise ValueError("fp64_rows: cold start only")
+    else:
+        N.check(N.core().svm_decomp_train_gram(N.ptr(K), K.shape[1], N.ptr(y), n, N.ptr(a), 1, ctypes.byref(p),
+                                               int(q), float(tau_frac), int(inner_wss), ctypes.byref(r), st, trp),
+                "svm_decomp_train_gram")
     return a, SMOResult.from_struct(r), _decomp_stats(st), tr
 
 
@@ -164,6 +173,7 @@ def twin_fold(cols: np.ndarray, coef: np.ndarray, n: int) -> Tuple[np.ndarray, n
 def _decomp_stats(st) -> dict:
     return {"outer_iterations": int(st[0]), "inner_iterations": int(st[1]), "working_set": int(st[2]),
             "solve_us": int(st[3]), "update_columns": int(st[4]), "chain_iterations": int(st[13]),
+            "eta_floor_updates": int(st[14]),  # first-pair updates on a pair with eta <= eps (identical rows)
             **N.shrink_stats(st)}
 
 

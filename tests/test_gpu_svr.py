@@ -5,7 +5,9 @@
   (virtual ids k / k + n), moved list, coefficients, inner iterations, bounds, the 2n alphas and the 2n f; on
   FP64 real rows (n = 300; n = 1,537 with working_set = 256: several selection blocks, several outer
   iterations, 2n not a multiple of 64), on uint8 pixel rows with a float target (the exact-integer plan), and
-  on the same pixel rows with the column cache forced (SVM355_DECOMP_CCACHE=1: slots per row).
+  on the same pixel rows with the column cache forced (SVM355_DECOMP_CCACHE=1: slots per row); an odd n; the
+  cache under eviction, the streamed selection, the symmetric K(W, W), the inner solve's shapes and rules; twins
+  of one row in different selection blocks (n = 1,537, working_set = 64).
 * The fold + twin accumulate step alone, against the oracle's fold and its GEMV order applied to both halves.
 * The KKT conditions of a GPU fit from a torch FP64 RBF (not the library's kernels), the scikit-learn
   fixture's predictions, and inference / persistence of device models (zero support vectors included).
@@ -42,16 +44,16 @@ def _compare(dt, ot):
     return len(dr)
 
 
-def _trajectory(Xdev, mn, mx, K, z, p, eps, q, fp64_rows=False):
+def _trajectory(Xdev, mn, mx, K, z, p, eps, q, fp64_rows=False, inner_wss=3, cap=400):
     n = z.shape[0]
     zd = torch.from_numpy(z).to(DEV)
     alpha = torch.empty(2 * n, dtype=torch.float64, device=DEV)
-    dt = N.DecompTrace(400, 2 * n)
+    dt = N.DecompTrace(cap, 2 * n)
     out = D.train_decomp_svr(Xdev, zd, alpha, p, mn, mx, epsilon=eps, working_set=q, trace=dt)
     assert out is not None
     res, tm = out
-    a_o, r_o, st_o, ot = C.decomp_train_gram_svr(K, z, p.replace(n_threads=8), epsilon=eps, q=q, trace_cap=400,
-                                                 snapshots=True, fp64_rows=fp64_rows)
+    a_o, r_o, st_o, ot = C.decomp_train_gram_svr(K, z, p.replace(n_threads=8), epsilon=eps, q=q, trace_cap=cap,
+                                                 snapshots=True, fp64_rows=fp64_rows, inner_wss=inner_wss)
     outers = _compare(dt, ot)
     assert res.stop_reason == r_o.stop_reason == "converged"
     assert res.iterations == r_o.iterations and res.b == r_o.b
@@ -92,6 +94,77 @@ def test_pixel_rows_trajectory_equals_the_twin_oracle(cache, monkeypatch):
     D.release_gram_buffers()
     tm = _trajectory(Xu, mn, mx, K, z, SVMParams(), 0.05, 1024)
     assert tm["gram_path"] == "int8-exact" and tm["outer_iterations"] >= 3
+
+
+def _pixel_rows(n):
+    """n uint8 pixel rows on the device, their column bounds, the float target (the row's mean intensity / 16) and
+    the device's own exact-integer Gram on the host."""
+    tr = synthetic_mnist(n, seed=91).compact()
+    z = np.ascontiguousarray(tr.X.astype(np.float64).mean(axis=1) / 16.0)
+    Xu = D.upload_u8(tr.X, DEV)
+    mmd = torch.empty(2 * tr.d, dtype=torch.float64, device=DEV)
+    D.minmax_u8(Xu, out=mmd)
+    mm = mmd.cpu().numpy()
+    mn, mx = mm[: tr.d].copy(), mm[tr.d:].copy()
+    Kd = D.rbf_gram_u8(Xu, 0.00125, mn, mx)
+    assert Kd is not None
+    K = np.ascontiguousarray(Kd[:n, :n].cpu().numpy())
+    del Kd
+    D.release_gram_buffers()
+    return Xu, mn, mx, K, z
+
+
+@pytest.fixture(scope="module")
+def pixel2000():
+    return _pixel_rows(2000)
+
+
+def test_odd_number_of_pixel_rows():
+    """n = 1999: the twins' f update pairs rows (ws_cache_fsum_kernel<2, true>), and the last row has no partner."""
+    Xu, mn, mx, K, z = _pixel_rows(1999)
+    tm = _trajectory(Xu, mn, mx, K, z, SVMParams(), 0.05, 1024)
+    assert tm["gram_path"] == "int8-exact" and tm["outer_iterations"] >= 3
+
+
+# The decomposition solver's other paths in twin mode (the classifier's tests run them in test_gpu_decomp_oracle.py):
+# the column cache under eviction (300 slots: the cache fills and the CLOCK sweep evicts; 8: the hand wraps, most
+# misses take scratch slots), the streamed selection, K(W, W) from the triangular Gram launch, the inner solve's
+# workgroup shapes and selection rules (the oracle reads SVM355_DECOMP_NT and takes inner_wss).
+@pytest.mark.parametrize("env,inner_wss", [({"SVM355_DECOMP_CCACHE": "1", "SVM355_DECOMP_CCACHE_SLOTS": "300"}, 3),
+                                           ({"SVM355_DECOMP_CCACHE": "1", "SVM355_DECOMP_CCACHE_SLOTS": "8"}, 3),
+                                           ({"SVM355_DECOMP_WIDE_SELECT": "1"}, 3),
+                                           ({"SVM355_DECOMP_KWW": "sym"}, 3),
+                                           ({"SVM355_DECOMP_NT": "64"}, 3),
+                                           ({"SVM355_DECOMP_NT": "128"}, 3),
+                                           ({"SVM355_DECOMP_NT": "512"}, 3),
+                                           ({"SVM355_DECOMP_WSS": "1"}, 1),
+                                           ({"SVM355_DECOMP_WSS": "2"}, 2),
+                                           ({"SVM355_DECOMP_WSS": "4"}, 4)],
+                         ids=lambda v: "-".join(f"{k[14:]}{x}" for k, x in v.items()) if isinstance(v, dict) else None)
+def test_twin_mode_paths_equal_the_twin_oracle(pixel2000, env, inner_wss, monkeypatch):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    Xu, mn, mx, K, z = pixel2000
+    tm = _trajectory(Xu, mn, mx, K, z, SVMParams(), 0.05, 1024, inner_wss=inner_wss)
+    assert tm["gram_path"] == "int8-exact" and tm["outer_iterations"] >= 3
+    if "SVM355_DECOMP_NT" in env:
+        assert tm["inner_threads"] == int(env["SVM355_DECOMP_NT"])
+
+
+def test_twins_of_one_row_in_different_selection_blocks():
+    """n = 1,537 real rows, q = 64: the 2n = 3,074 virtual points fall into 56 selection blocks of 55, one
+    candidate pair per block and working set (112 slots), so a row's twins (k and k + 1,537) lie in different
+    blocks and the solve takes hundreds of outer iterations."""
+    n = 1537
+    X, z = real_rows(n, seed=n)
+    p = SVMParams(C=10.0, gamma=0.5, tau=1e-5)
+    Xd = D.upload_rows(X, DEV)
+    mn, mx, sqn = D.minmax_scale_(Xd, X.shape[1])
+    nrm = D.row_norms(Xd, X.shape[1])
+    K = D.rbf_gram(Xd, nrm, Xd, nrm, p.gamma, symmetric=True)[:n, :n].cpu().numpy()
+    tm = _trajectory(Xd, mn.cpu().numpy(), mx.cpu().numpy(), np.ascontiguousarray(K), z, p, 0.1, 64, fp64_rows=True,
+                     cap=800)
+    assert tm["gram_path"] == "fp64" and tm["working_set"] == 112 and tm["outer_iterations"] >= 100
 
 
 @pytest.mark.parametrize("via", ["gemv", "cache"])

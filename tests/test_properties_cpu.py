@@ -61,6 +61,8 @@ def test_both_oracles_meet_the_stop_test_at_the_same_optimum(prob, q):
     for a, r in ((a1, r1), (a2, r2)):
         # a hard draw (large C, tiny gamma) may end on the iteration cap: a reported reason, never silent
         assert r.stop_reason in ("converged", "max_iter", "nonpositive_eta", "infeasible"), r.stop_reason
+        # the decomposition oracle floors eta at eps: the reference's eta stop is the pairwise oracle's alone
+        assert r is r1 or r.stop_reason != "nonpositive_eta"
         assert np.all((a >= -1e-9) & (a <= Cb + 1e-9))
         assert abs(float(a @ y)) <= 1e-9 * max(1.0, float(a.sum()))
     if r1.stop_reason == r2.stop_reason == "converged":

@@ -81,6 +81,7 @@ def test_kkt_from_an_independent_rbf(oracle, epsilon):
 #                   determined.  The twin pair is still never violating (f_k = f_{k+n}), and the solve must end
 #                   converged like every other.
 # No solve ended in SVM_STOP_NONPOS_ETA, and every solve converged.
+# (Identical ROWS with different targets are the other source of eta = 0: test_decomp_degenerate_cpu.py.)
 _SEEDS = {50: 20, 300: 20, 1537: 2}
 
 
