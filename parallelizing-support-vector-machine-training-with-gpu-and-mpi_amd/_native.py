@@ -217,6 +217,7 @@ _CORE_SIGS = {
     "svm_crash_handler_install": (c_int32, [c_char_p]),
     "svm_decomp_gemv_ref": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int64, _P]),
     "svm_decomp_newton_step": (c_int32, [_P, c_int64, _P, c_int32, _P, _P, c_double, c_double, c_int32, POINTER(c_int32)]),
+    "svm_tile_map_ref": (c_int32, [c_int32, c_int64, c_int64, c_int64, c_int64, _P, _P]),
     "svm_smo_plan": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int64, _P, _P]),
     "svm_decomp_rank_train_gram": (c_int32, [_P, _P, c_int64, _P, c_int64, _P, c_int32, POINTER(SvmParams), c_int32,
                                              c_double, c_int32, POINTER(SvmResult), POINTER(c_int64)]),
@@ -446,6 +447,20 @@ def smo_plan(n, wss=1, ncu=256, int_rows=True, kq=832, nslots=16384):
            "xlocal": bool(s[4]), "device_wide": tuple(int(v) for v in s[6:9]) if s[5] else None}
     rc = {"E": int(q[1]), "G": int(q[2]), "rpl": int(q[3]), "nd": int(q[4]), "lds": int(q[5])} if q[0] else None
     return smo, rc
+
+
+def tile_map(kind, tiles_m, tiles_n=1):
+    """The FP64 Gram kernel's workgroup -> tile map (csrc/hip/tile_map.h, compiled for the host): kind "rect"
+    for the tiles_m x tiles_n launch, "tri" for the upper-triangle launch of tiles_m (tiles_m + 1) / 2
+    workgroups.  Returns (tm, tn), one int64 entry per workgroup id."""
+    import numpy as np
+
+    k = {"rect": 0, "tri": 1}[kind]
+    nwg = tiles_m * (tiles_m + 1) // 2 if k else tiles_m * tiles_n
+    tm = np.empty(nwg, dtype=np.int64)
+    tn = np.empty(nwg, dtype=np.int64)
+    check(core().svm_tile_map_ref(k, 0, nwg, int(tiles_m), int(tiles_n), ptr(tm), ptr(tn)), "svm_tile_map_ref")
+    return tm, tn
 
 
 def shrink_stats(st) -> dict:

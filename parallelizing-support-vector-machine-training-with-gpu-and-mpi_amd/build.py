@@ -30,7 +30,8 @@ ARCH = os.environ.get("SVM355_ARCH", "gfx950")
 ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 
 CXXFLAGS = ["-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra",
-            "-Wno-unused-parameter", f"-I{CSRC / 'include'}", f"-I{CSRC / 'cascade'}"]
+            "-Wno-unused-parameter", f"-I{CSRC / 'include'}", f"-I{CSRC / 'cascade'}",
+            f"-I{CSRC / 'hip'}"]  # hip/tile_map.h: the Gram kernels' tile maps, also plain C++ (core/tile_map_ref.cpp)
 HIPFLAGS = ["-std=c++17", "-O3", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=off", f"-I{ROCM / 'include'}",
             f'-DSVM355_RCCL_PATH="{ROCM / "lib" / "librccl.so.1"}"',  # rccl_api.h: the RCCL of these headers
             "-Wall", "-Wno-unused-parameter", "-Wno-unused-result", f"-I{CSRC / 'include'}",
@@ -45,7 +46,7 @@ HIP_SRCS = sorted((CSRC / "hip").glob("*.hip"))
 HIP_HDRS = (sorted((CSRC / "hip").glob("*.h")) + sorted((CSRC / "include").glob("*.h"))
             + sorted((CSRC / "cascade").glob("*.h")))
 CORE_HDRS = (sorted((CSRC / "core").glob("*.h")) + sorted((CSRC / "include").glob("*.h"))
-             + sorted((CSRC / "cascade").glob("*.h")))
+             + sorted((CSRC / "cascade").glob("*.h")) + [CSRC / "hip" / "tile_map.h"])
 
 
 def _stale(out: Path, deps) -> bool:

@@ -712,6 +712,7 @@ SVM_API int svmd_decision(void* h, const double* Xs_d, const double* ns_d, const
   TraceRange tr("svm355:decision");
   // Cross-kernel block K(Xq, Xs) in row chunks of <= 512 MB scratch, then a deterministic GEMV.
   const int64_t ldk = (nsv + 1) / 2 * 2;
+  // tests/test_gpu_predict_kernels.py (test_decision_chunk_size_still_makes_this_two_chunks) recomputes this.
   int64_t rows = std::max<int64_t>(128, (int64_t(512) << 20) / (ldk * 8) / 128 * 128);
   rows = std::min<int64_t>(rows, (m + 127) / 128 * 128);
   rc = ctx->ensure_ws(size_t(rows) * size_t(ldk) * 8);

@@ -25,7 +25,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 128, BK = 16;
 constexpr int LS = 18;  // padded LDS row stride (doubles)
-constexpr int GROUP_M = 8;
 
 // SYM: force K_ii = 1.  TRI: A == B, compute only tiles tn >= tm and also store each off-diagonal
 // tile transposed (staged through LDS so the mirror rows are written as coalesced 32-B runs) —
@@ -51,12 +50,7 @@ __global__ __launch_bounds__(256, 2) void rbf_gram_kernel(
     tri_tile(xcd_remap(blockIdx.x, nwg), tiles_m, tm, tn);
   } else {
     const int64_t nwg = tiles_m * tiles_n;
-    const int64_t wg = xcd_remap(blockIdx.x, nwg);
-    const int64_t band = GROUP_M * tiles_n;
-    const int64_t first_m = (wg / band) * GROUP_M;
-    const int64_t gsz = std::min<int64_t>(tiles_m - first_m, GROUP_M);
-    tm = first_m + (wg % band) % gsz;
-    tn = (wg % band) / gsz;
+    band_tile(xcd_remap(blockIdx.x, nwg), tiles_m, tiles_n, GROUP_M, tm, tn);
   }
   const int64_t bm = tm * BM, bn = tn * BN;
   if (ncount && bn >= n) return;

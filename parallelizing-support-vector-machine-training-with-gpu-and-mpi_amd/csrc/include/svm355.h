@@ -164,6 +164,12 @@ SVM_API int svm_decomp_train_gram_rows(const double* K, int64_t ldk, const int32
 SVM_API int svm_decomp_gemv_ref(const double* K, int64_t ldk, int64_t n, const int32_t* cols, const double* coef,
                                 int64_t cnt, double* f);
 
+// The FP64 MFMA Gram kernel's workgroup -> output-tile maps (csrc/hip/tile_map.h, the functions the kernel
+// calls) for the CPU tests: tm[k], tn[k] = the tile of workgroup id0 + k, k < count.  kind 0: the rectangular
+// launch of tiles_m x tiles_n workgroups; kind 1: the triangular launch of tiles_m (tiles_m + 1) / 2.
+SVM_API int svm_tile_map_ref(int32_t kind, int64_t id0, int64_t count, int64_t tiles_m, int64_t tiles_n, int64_t* tm,
+                             int64_t* tn);
+
 // ---------------------------------------------------------------- epsilon-SVR (L3)
 // epsilon-SVR is the same box-constrained problem over 2n variables in pairs ("twins") that share a kernel
 // row: variable k is a_k with sign +1, variable k + n is a*_k with sign -1, Q_ij = s_i s_j K(i mod n, j mod n),

@@ -581,14 +581,18 @@ def rbf_gram_u8(Xu: torch.Tensor, gamma: float, mn, mx, out: Optional[torch.Tens
     return out if used.value else None
 
 
-def sv_rows_u8(Xu: torch.Tensor, idx: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor,
-               ld: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Scaled FP64 rows idx (zero padded to ld) and their squared norms from device uint8 rows."""
+def sv_rows_u8(Xu: torch.Tensor, idx: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor, ld: Optional[int] = None,
+               out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Scaled FP64 rows idx (zero padded to ld) and their squared norms from device uint8 rows.  ``out``: a
+    contiguous (len(idx), ld) float64 tensor to write the rows into (every element of it is written)."""
     d = Xu.shape[1]
     ld = padded_dim(d) if ld is None else ld
     idx = idx.to(torch.int64).contiguous()
     k = idx.numel()
-    out = torch.empty((k, ld), dtype=torch.float64, device=Xu.device)
+    if out is None:
+        out = torch.empty((k, ld), dtype=torch.float64, device=Xu.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (k, ld) or not out.is_contiguous() or out.device != Xu.device:
+        raise ValueError(f"out must be a contiguous float64 tensor of shape ({k}, {ld}) on {Xu.device}")
     sqn = torch.empty(k, dtype=torch.float64, device=Xu.device)
     ctx = _ctx_for(Xu)
     N.check(ctx.lib.svmd_sv_rows_u8(ctx.bind(), N.ptr(Xu), d, N.ptr(idx) if k else None, k, N.ptr(mn), N.ptr(mx),
