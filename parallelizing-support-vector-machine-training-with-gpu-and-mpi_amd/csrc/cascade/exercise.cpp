@@ -2,7 +2,7 @@
 // every received byte is checked.  Two uses:
 //   * tests: svm_loopback_exercise drives a (strict) LoopbackGroup of CPU-backend ranks through any
 //     call sequence -- including deliberately wrong ones, which must fail naming the ranks;
-//   * preflight: the device groups / ranks (cascade_dev.hip) run preflight_script(P) -- every op the
+//   * preflight: the device groups / ranks (cascade_ranks.hip) run preflight_script(P) -- every op the
 //     cascade driver issues, the tree's send / recv pairs per level included -- on the real RCCL
 //     communicators right after creating them, before any timed region, with a short deadline.
 //

@@ -3,7 +3,7 @@
 // (svm355.parallel.hostcomm).  Two uses:
 //   * the CPU oracle backend (svm_cascade_rank_fit_cpu, svm_decomp_rank_train_gram): buffers are host
 //     memory and go to the callbacks as they are -- the CPU twin of the per-process RCCL rank;
-//   * a GPU rank without RCCL (svmd_cascade_rank_create_hostcomm, cascade_dev.hip): buffers are device
+//   * a GPU rank without RCCL (svmd_cascade_rank_create_hostcomm, cascade_ranks.hip): buffers are device
 //     memory, staged through host vectors with the backend's synchronous copies.  This is how one GPU
 //     rehearses the per-process launch of the N-GPU run (torchrun, several processes on one device:
 //     RCCL refuses two ranks on one GPU) with the same driver code, so the torchrun path of the

@@ -13,23 +13,6 @@
 
 using namespace svm355;
 
-namespace {
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-svm_params resolve(const svm_params* p) {
-  svm_params q;
-  if (p)
-    q = *p;
-  else
-    svm_default_params(&q);
-  return q;
-}
-
-}  // namespace
-
 namespace svm355 {
 // The solvers without per-class boxes (the pairwise device solvers, the distributed and cascade trainers)
 // refuse class weights that differ from 1 -- none solves the unweighted problem in their place.  SVM_OK
@@ -370,7 +353,7 @@ SVM_API int svmd_smo(void* h, const double* K_d, int64_t ldk, const int32_t* y_d
                      int64_t* trace_host, int64_t trace_cap) {
   SVMD_CTX(h);
   TraceRange tr("svm355:smo");
-  const svm_params q = resolve(p);
+  const svm_params q = params_or_default(p);
   int rc = refuse_class_weights(q, "svmd_smo");
   if (rc) return rc;
   if ((rc = ctx->begin())) return rc;
@@ -389,7 +372,7 @@ SVM_API int svmd_smo_multi(void* h, const double* K_d, int64_t ldk, const int32_
                            double* A_d, const svm_params* p, svm_result* r, int32_t* batched) {
   SVMD_CTX(h);
   TraceRange tr("svm355:smo_multi");
-  const svm_params q = resolve(p);
+  const svm_params q = params_or_default(p);
   int rc = refuse_class_weights(q, "svmd_smo_multi");
   if (rc) return rc;
   if ((rc = ctx->begin())) return rc;
@@ -521,8 +504,8 @@ SVM_API int svmd_train(void* h, const double* X_d, const double* sqn_d, int64_t 
                        const int32_t* y_d, double* alpha_d, int32_t warm, const svm_params* p,
                        svm_result* r, double* K_d, int64_t ldk, svmd_timing* timing) {
   SVMD_CTX(h);
-  if (const int rc = refuse_class_weights(resolve(p), "svmd_train")) return rc;
-  return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, resolve(p), r, K_d, ldk, timing, nullptr,
+  if (const int rc = refuse_class_weights(params_or_default(p), "svmd_train")) return rc;
+  return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, params_or_default(p), r, K_d, ldk, timing, nullptr,
                     nullptr, 0, 1, nullptr);
 }
 
@@ -531,8 +514,8 @@ SVM_API int svmd_train_q(void* h, const double* X_d, const double* sqn_d, int64_
                          double* K_d, int64_t ldk, svmd_timing* timing, const double* mn_h, const double* mx_h,
                          int64_t d, int32_t gram_mode, int32_t* gram_used) {
   SVMD_CTX(h);
-  if (const int rc = refuse_class_weights(resolve(p), "svmd_train_q")) return rc;
-  return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, resolve(p), r, K_d, ldk, timing, mn_h, mx_h,
+  if (const int rc = refuse_class_weights(params_or_default(p), "svmd_train_q")) return rc;
+  return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, params_or_default(p), r, K_d, ldk, timing, mn_h, mx_h,
                     d, gram_mode, gram_used);
 }
 
@@ -550,7 +533,7 @@ SVM_API int svmd_train_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, co
     set_error("svmd_train_u8: bad arguments");
     return SVM_ERR_ARG;
   }
-  const svm_params q = resolve(p);
+  const svm_params q = params_or_default(p);
   int rc = refuse_class_weights(q, "svmd_train_u8");
   if (rc) return rc;
   const auto t0 = std::chrono::steady_clock::now();
@@ -648,7 +631,7 @@ SVM_API int svmd_train_rows(void* h, const double* X_d, const double* sqn_d, int
                             const double* mn_h, const double* mx_h, int32_t gram_mode, int64_t cache_bytes,
                             int32_t* gram_used, int64_t* trace_host, int64_t trace_cap) {
   SVMD_CTX(h);
-  const svm_params q = resolve(p);
+  const svm_params q = params_or_default(p);
   int rc = refuse_class_weights(q, "svmd_train_rows");
   if (rc) return rc;
   if ((rc = ctx->begin())) return rc;

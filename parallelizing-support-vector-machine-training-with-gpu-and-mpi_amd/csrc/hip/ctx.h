@@ -161,6 +161,16 @@ int carve_ws(DeviceCtx* ctx, Layout&& layout) {
     return SVM_ERR_ARG;                                          \
   }
 
+// *p, or the library's defaults when p is null: the optional parameter block of every training entry.
+inline svm_params params_or_default(const svm_params* p) {
+  svm_params q;
+  if (p)
+    q = *p;
+  else
+    svm_default_params(&q);
+  return q;
+}
+
 // SVM_ERR_ARG (with the error set) when p's class weights differ from 1: the check of every solver
 // without per-class boxes (capi.hip).
 int refuse_class_weights(const svm_params& p, const char* who);

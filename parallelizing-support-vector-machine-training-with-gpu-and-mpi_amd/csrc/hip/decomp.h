@@ -1,6 +1,6 @@
 // Working-set decomposition SMO (decomp.hip; the inner solve: decomp_inner.hip): shapes and the host driver,
 // shared by the one-GPU C ABI (svmd_train_decomp_u8) and the distributed solve over a cascade group or process rank
-// (cascade_dev.hip: svmd_cascade_group_decomp / svmd_cascade_rank_decomp).
+// (cascade_ranks.hip: svmd_cascade_group_decomp / svmd_cascade_rank_decomp).
 #pragma once
 #include <cstdint>
 #include <functional>

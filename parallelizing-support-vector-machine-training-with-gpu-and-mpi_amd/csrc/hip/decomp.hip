@@ -954,10 +954,6 @@ __global__ void ws_unshrink_ctl_kernel(DecompCtl* __restrict__ ctl, int64_t nloc
   }
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 DecompShape decomp_shape(int64_t n, int qws, int world) {
@@ -2065,11 +2061,7 @@ namespace {
 int train_decomp(DeviceCtx* ctx, const void* X_d, bool is_u8, int64_t n, int64_t ld, int64_t d, const double* mn_h,
                  const double* mx_h, const int32_t* y_d, double* alpha_d, const svm_params* pp, int32_t q,
                  const DecompOpts& o, svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used_out) {
-  svm_params p;
-  if (pp)
-    p = *pp;
-  else
-    svm_default_params(&p);
+  const svm_params p = params_or_default(pp);
   double cp, cn;  // the class weights' range check, before anything runs
   int rc = svm_class_boxes(&p, &cp, &cn);
   if (rc) return rc;
@@ -2173,11 +2165,7 @@ SVM_API int svmd_train_decomp_svr(void* h, const void* X_d, int32_t is_u8, int64
     return SVM_ERR_ARG;
   }
   {  // what twin mode refuses, before any device work (setup_solve checks the same)
-    svm_params p;
-    if (pp)
-      p = *pp;
-    else
-      svm_default_params(&p);
+    const svm_params p = params_or_default(pp);
     double cp = 0.0, cn = 0.0;
     if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
     const char* what = shrink_cfg(p).on           ? "shrinking"

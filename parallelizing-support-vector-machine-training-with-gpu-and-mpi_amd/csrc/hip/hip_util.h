@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 
@@ -43,6 +44,11 @@ void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 namespace svm355 {
 
 constexpr int kWave = 64;  // CDNA wavefront width (hard-coded per the gfx950 guide)
+
+// Host wall time since t0, in milliseconds.
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // Rows of device feature matrices are padded to a multiple of kKPad doubles (zero-filled) so the
 // MFMA Gram kernel needs no k-tail handling and every row start is 16-byte aligned.

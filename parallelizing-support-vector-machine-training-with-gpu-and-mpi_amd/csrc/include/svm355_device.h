@@ -188,7 +188,7 @@ SVM_API int svmd_count_correct(void* ctx, const double* dec_d, const int32_t* y_
 SVM_API int svmd_gather_rows(void* ctx, const double* src_d, int64_t ld, const int64_t* idx_d,
                              int64_t k, double* dst_d);
 
-// ---- Cascade SVM on MI355X GPUs (csrc/hip/cascade_dev.hip; round logic in csrc/cascade).
+// ---- Cascade SVM on MI355X GPUs (entries: csrc/hip/cascade_ranks.hip; backend: cascade_dev.hip; round logic in csrc/cascade).
 // Thread-rank group of this process: world ranks on GPUs 0..world-1 with one RCCL communicator each
 // (ncclCommInitAll over xGMI, transport "rccl"), or world ranks sharing the visible GPUs with
 // host-staged exchanges ("loopback", a rehearsal of any P on one GPU); "auto" = rccl when world

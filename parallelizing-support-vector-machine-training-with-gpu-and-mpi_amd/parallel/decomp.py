@@ -1,5 +1,5 @@
 """Distributed working-set decomposition SMO over the GPUs of one node (``--parallel decomp``;
-csrc/hip/decomp.hip + the group / rank entry points of csrc/hip/cascade_dev.hip).
+csrc/hip/decomp.hip + the group / rank entry points of csrc/hip/cascade_ranks.hip).
 
 The one-GPU decomposition solver (``SVC(solver="decomp")``) spends its outer iterations on three
 kinds of work: choosing the working set (top violators per block of points), solving it (one

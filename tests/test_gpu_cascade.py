@@ -1,4 +1,5 @@
-"""Cascade SVM on the gfx950 backend (csrc/hip/cascade_dev.hip) driven by the one native driver.
+"""Cascade SVM on the gfx950 backend (csrc/hip/cascade_dev.hip; its groups and ranks: cascade_ranks.hip)
+driven by the one native driver.
 
 * HIP backend vs the CPU-oracle backend on the same partitions (kernel values differ in the last
   ulps between the MFMA norm form and the direct sum, so tolerances);
@@ -18,6 +19,7 @@ import pytest
 from svm355 import SVC, SVMParams
 from svm355._native import NativeError
 from svm355.parallel.cascade import CascadeSVM, preflight_script
+from svm355.parallel.decomp import DistributedDecompSVC
 from svm355.parallel.rccl import DeviceGroup, RcclRank, rccl_info
 from svm355.utils.data import synthetic_mnist
 
@@ -197,6 +199,11 @@ def test_rccl_failure_aborts_the_communicator(data):
             CascadeSVM(SVMParams(), fail_rank=0, fail_round=0).fit(X, tr.y, world=1, device="cuda", group=g)
         with pytest.raises(NativeError, match="aborted"):
             CascadeSVM(SVMParams()).fit(X, tr.y, world=1, device="cuda", group=g)
+        # the group's three entries share one failure guard: the other two refuse the broken group too
+        with pytest.raises(NativeError, match="aborted by an earlier failure"):
+            g.exercise(preflight_script(1, 1 << 20))
+        with pytest.raises(NativeError, match="aborted by an earlier failure"):
+            DistributedDecompSVC(1, group=g).fit(X, tr.y)
     finally:
         g.close()
 
