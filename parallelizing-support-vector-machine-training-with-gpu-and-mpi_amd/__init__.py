@@ -11,6 +11,9 @@ re-designed for gfx950:
 * ``svm355.SVR``                     epsilon-SVR on the same solvers: the 2n-variable problem whose twins a_k / a*_k
                                      share a kernel row, so on the GPU the decomposition solver's kernel work
                                      runs over n rows, not 2n (the CPU oracle is the pairwise solver)
+* ``svm355.OneClassSVM``             one-class SVM (novelty detection on unlabelled rows, LIBSVM's -s 2): the
+                                     classifier's dual with every sign +1, box 1 and no linear term, solved by
+                                     the decomposition solver's one-class mode from LIBSVM's feasible start
 * ``svm355.OneVsRestSVC``            all classes one-vs-rest: the decomposition solver per class on the
                                      shared device rows (default), or one resident Gram with every
                                      pairwise class solve in one launch (``solver="batched"``)
@@ -41,9 +44,10 @@ from .utils.data import Dataset, MinMaxScaler, load_csv, one_vs_rest, synthetic_
 from .models.multiclass import OneVsRestSVC
 from .models.svc import SVC
 from .models.svr import SVR
+from .models.oneclass import OneClassSVM
 
 __all__ = ["SVMParams", "Dataset", "MinMaxScaler", "load_csv", "one_vs_rest", "synthetic_mnist", "write_csv",
-           "SVC", "SVR", "OneVsRestSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
+           "SVC", "SVR", "OneClassSVM", "OneVsRestSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
 __version__ = "0.1.0"
 
 

@@ -213,6 +213,11 @@ _CORE_SIGS = {
     "svm_decomp_train_gram_svr": (c_int32, [_P, c_int64, _P, c_int64, c_double, _P, POINTER(SvmParams), c_int32,
                                             c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
                                             POINTER(SvmDecompTrace)]),
+    "svm_oneclass_start": (c_int32, [c_double, c_int64, POINTER(c_int64), POINTER(c_double)]),
+    "svm_smo_train_oneclass": (c_int32, [_P, c_int64, c_int64, c_double, _P, POINTER(SvmParams), POINTER(SvmResult)]),
+    "svm_decomp_train_gram_oneclass": (c_int32, [_P, c_int64, c_int64, c_double, _P, POINTER(SvmParams), c_int32,
+                                                 c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
+                                                 POINTER(SvmDecompTrace)]),
     "svm_decomp_twin_fold": (c_int32, [_P, _P, c_int32, c_int64, _P, _P, POINTER(c_int32)]),
     "svm_crash_handler_install": (c_int32, [c_char_p]),
     "svm_decomp_gemv_ref": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int64, _P]),
@@ -292,6 +297,9 @@ _HIP_SIGS = {
     "svmd_train_decomp_svr": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, c_double, _P,
                                         POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                         POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
+    "svmd_train_decomp_oneclass": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, c_double, _P,
+                                             POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
+                                             POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
     "svmd_decomp_twin_step_u8": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, c_double, _P, _P, c_int32, _P,
                                            POINTER(c_int32)]),
     "svmd_decomp_newton_probe": (c_int32, [c_void_p, _P, _P, c_int32, _P, _P, c_double, c_double, c_int32, c_int32,

@@ -124,6 +124,17 @@ SVM_API int svm_class_boxes(const svm_params* p, double* c_pos, double* c_neg) {
   return SVM_OK;
 }
 
+SVM_API int svm_oneclass_start(double nu, int64_t n, int64_t* full, double* frac) {
+  if (!full || !frac || n < 2 || !(nu > 0.0 && nu < 1.0)) {
+    set_error("one-class SVM: nu must be in (0, 1) and n >= 2 (nu = %g, n = %lld)", nu, (long long)n);
+    return SVM_ERR_ARG;
+  }
+  const double total = nu * double(n);
+  *full = std::min<int64_t>(int64_t(total), n);
+  *frac = *full < n ? total - double(*full) : 0.0;
+  return SVM_OK;
+}
+
 SVM_API const char* svm_stop_message(int32_t reason) {
   switch (reason) {
     case SVM_STOP_CONVERGED: return "converged";

@@ -28,6 +28,9 @@
 //     start is f_k = epsilon - z_k, f_{k+n} = -epsilon - z_k; the moved list is folded to one entry per row
 //     (fold_twins) and every row's sum is added to both twins' f.  Cold start, one rank, no shrinking, no
 //     Newton polish, no class weights.
+//   * one-class mode (svm_decomp_train_gram_oneclass): every sign +1, box 1, no linear term; the start is
+//     LIBSVM's feasible alpha (svm_oneclass_start) and f = K[:, nz] alpha_nz in chunks of kMaxWS columns
+//     (ws_oneclass_init_kernel, then decomp.hip's nz_update).  One rank, no shrinking, no Newton polish.
 // The kernel values themselves come from the caller (the device Gram on the exact-integer path).
 #include <chrono>
 #include <climits>
@@ -180,10 +183,10 @@ void fold_twins(const int32_t* cols, const double* coef, int64_t cnt, int64_t n,
 int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha, int32_t warm,
                  const svm_params& p, int32_t qws, double tau_frac, int32_t inner_wss, svm_result* res,
                  int64_t* stats, svm_decomp_trace* tr, Transport* t, const double* twin_z = nullptr,
-                 double twin_eps = 0.0, bool f64_rows = false) {
+                 double twin_eps = 0.0, bool f64_rows = false, double oneclass_nu = 0.0) {
   const int world = t ? t->world() : 1, rank = t ? t->rank() : 0;
-  const bool twin = twin_z != nullptr;
-  if (!K || (!y && !twin) || !alpha || n < 2 || ldk < n) {
+  const bool twin = twin_z != nullptr, oneclass = oneclass_nu > 0.0;
+  if (!K || (!y && !twin && !oneclass) || !alpha || n < 2 || ldk < n) {
     set_error("svm_decomp_train_gram: bad arguments");
     return SVM_ERR_ARG;
   }
@@ -213,6 +216,23 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     n = 2 * nr;
     sgn.resize(size_t(n));
     for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = i < nr ? 1 : -1;
+    y = sgn.data();
+  }
+  int64_t oc_full = 0;
+  double oc_frac = 0.0;
+  if (oneclass) {  // the caller (svm_decomp_train_gram_oneclass) has set C = 1 and cleared the weights
+    const char* what = world != 1           ? "the distributed solve (world > 1)"
+                       : twin               ? "the regression (twin) solve"
+                       : warm               ? "a warm start"
+                       : shrink_cfg(p).on   ? "shrinking"
+                       : newton_cfg(p).on   ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                            : nullptr;
+    if (what) {
+      set_error("svm_decomp_train_gram_oneclass: the one-class solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+    if (const int rc = svm_oneclass_start(oneclass_nu, n, &oc_full, &oc_frac)) return rc;
+    sgn.assign(size_t(n), 1);
     y = sgn.data();
   }
   if (!(tau_frac >= 0.0 && tau_frac < 0.5)) {
@@ -260,7 +280,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   // f = -y + K (alpha y) over the nonzero alphas (ascending ids, chunks of kMaxWS columns): the warm
   // start, and the recomputation when the solve unshrinks
   auto f_from_alpha = [&]() -> int64_t {
-    for (int64_t i = lo; i < hi; ++i) f[size_t(i - lo)] = -static_cast<double>(y[i]);
+    for (int64_t i = lo; i < hi; ++i) f[size_t(i - lo)] = oneclass ? 0.0 : -static_cast<double>(y[i]);
     std::vector<int32_t> nzc;
     std::vector<double> nzv;
     for (int64_t j = 0; j < n; ++j)
@@ -269,8 +289,9 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         nzv.push_back(alpha[j] * double(y[j]));
       }
     for (size_t c0 = 0; c0 < nzc.size(); c0 += kMaxWS)
-      gemv_update(K + lo * ldk, ldk, nloc, nzc.data() + c0, nzv.data() + c0,
-                  int64_t(std::min<size_t>(kMaxWS, nzc.size() - c0)), f.data(), team, nullptr);
+      (f64_rows ? rowsum_update_f64 : gemv_update)(
+          K + lo * ldk, ldk, nloc, nzc.data() + c0, nzv.data() + c0,
+          int64_t(std::min<size_t>(kMaxWS, nzc.size() - c0)), f.data(), team, nullptr);
     return int64_t(nzc.size());
   };
   if (twin) {  // ws_twin_init_kernel
@@ -279,6 +300,9 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       f[size_t(k + nr)] = -twin_eps - twin_z[k];
     }
     for (int64_t i = 0; i < n; ++i) alpha[i] = 0.0;
+  } else if (oneclass) {  // ws_oneclass_init_kernel, then nz_update
+    for (int64_t i = 0; i < n; ++i) alpha[i] = i < oc_full ? 1.0 : i == oc_full ? oc_frac : 0.0;
+    warm_cols = f_from_alpha();
   } else if (!warm) {
     for (int64_t i = lo; i < hi; ++i) f[size_t(i - lo)] = -static_cast<double>(y[i]);
     for (int64_t i = 0; i < n; ++i) alpha[i] = 0.0;
@@ -726,6 +750,22 @@ extern "C" SVM_API int svm_decomp_train_gram_svr(const double* K, int64_t ldk, c
   }
   return decomp_solve(K, ldk, nullptr, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
                       nullptr, z, epsilon, f64_rows != 0);
+}
+
+// The one-class form of svm_decomp_train_gram (svm355.h): y = +1, C = 1, no linear term, LIBSVM's start.
+extern "C" SVM_API int svm_decomp_train_gram_oneclass(const double* K, int64_t ldk, int64_t n, double nu,
+                                                      double* alpha, const svm_params* pp, int32_t qws,
+                                                      double tau_frac, int32_t inner_wss, int32_t f64_rows,
+                                                      svm_result* res, int64_t* stats, svm_decomp_trace* tr) {
+  if (!(nu > 0.0 && nu < 1.0)) {
+    set_error("svm_decomp_train_gram_oneclass: nu must be in (0, 1), got %g", nu);
+    return SVM_ERR_ARG;
+  }
+  svm_params p = params_or_default(pp);
+  p.C = 1.0;
+  p.weight_pos = p.weight_neg = 0.0;
+  return decomp_solve(K, ldk, nullptr, n, alpha, 0, p, qws, tau_frac, inner_wss, res, stats, tr, nullptr, nullptr, 0.0,
+                      f64_rows != 0, nu);
 }
 
 // Twin mode's moved-column fold alone (tests): cnt <= 1024 virtual ids in [0, 2n) and their coefficients to one

@@ -65,7 +65,8 @@ struct GramRows {
 template <class Rows>
 int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int32_t warm,
               const svm_params* pp, svm_result* res, int64_t* trace, int64_t trace_cap,
-              const double* f0 = nullptr) {  // f0: a cold start's f instead of -y (a linear term: epsilon-SVR)
+              const double* f0 = nullptr,  // f0: a cold start's f instead of -y (a linear term: epsilon-SVR)
+              bool no_linear = false) {    // a warm start's f without the -y term (p = 0: one-class)
   svm_params p;
   if (pp)
     p = *pp;
@@ -99,7 +100,7 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
       for (int64_t i = lo; i < hi; ++i) {
         double sum = 0.0;
         for (int64_t j : nz) sum += alpha[j] * y[j] * rows.k(j, i);
-        f[size_t(i)] = sum - static_cast<double>(y[i]);
+        f[size_t(i)] = no_linear ? sum : sum - static_cast<double>(y[i]);
       }
     });
   }
@@ -312,6 +313,33 @@ SVM_API int svm_smo_train_svr(const double* X, const double* z, int64_t n, int64
   }
   XRows rows{X2.data(), d, p ? p->gamma : 0.00125};
   return smo_solve(rows, y2.data(), 2 * n, alpha, 0, p, r, nullptr, 0, f0.data());
+}
+
+// One-class SVM (LIBSVM's -s 2) on the pairwise solver: minimise 1/2 a' K a over 0 <= a_i <= 1 with sum a = nu n.
+// Every sign is +1, there is no linear term, and the equality is carried by LIBSVM's feasible start: a_i = 1 for
+// i < floor(nu n), a_floor(nu n) = nu n - floor(nu n), 0 beyond.  f_i = sum_j a_j K_ij, summed over the nonzero
+// start ids in ascending order (the warm branch above without its -y); r->b is rho, and the decision value of x is
+// sum_k a_k K(x_k, x) - rho.  p->C and the class weights are not read (the box is 1).
+SVM_API int svm_smo_train_oneclass(const double* X, int64_t n, int64_t d, double nu, double* alpha,
+                                   const svm_params* p, svm_result* r) {
+  if (!X || !alpha || d <= 0) {
+    set_error("svm_smo_train_oneclass: bad X / d");
+    return SVM_ERR_ARG;
+  }
+  int64_t full = 0;
+  double frac = 0.0;
+  if (const int rc = svm_oneclass_start(nu, n, &full, &frac)) return rc;
+  svm_params p1;
+  if (p)
+    p1 = *p;
+  else
+    svm_default_params(&p1);
+  p1.C = 1.0;
+  p1.weight_pos = p1.weight_neg = 0.0;
+  for (int64_t i = 0; i < n; ++i) alpha[i] = i < full ? 1.0 : i == full ? frac : 0.0;
+  const std::vector<int32_t> y(size_t(n), 1);
+  XRows rows{X, d, p1.gamma};
+  return smo_solve(rows, y.data(), n, alpha, 1, &p1, r, nullptr, 0, nullptr, true);
 }
 
 }  // extern "C"

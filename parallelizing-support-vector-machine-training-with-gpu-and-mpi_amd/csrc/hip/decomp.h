@@ -59,6 +59,13 @@ struct DecompOpts {
   const double* twin_z = nullptr;
   double twin_eps = 0.0;
   bool twin() const { return twin_z != nullptr; }
+  // One-class mode (LIBSVM's -s 2; svm355.h has the problem): oneclass_nu > 0 selects it.  Every sign is +1, the
+  // box is 1 (p.C is not read), there is no linear term, and the solve starts from LIBSVM's feasible alpha with
+  // f = K[:, nz] alpha_nz summed by the chunked start.  run_decomp takes n rows, reads no y (it keeps the signs
+  // itself), and alpha holds n values (out).  One GPU, no caller's warm start, no shrinking, no Newton polish,
+  // no class weights, not together with twin mode, 0 < nu < 1: anything else is SVM_ERR_ARG.
+  double oneclass_nu = 0.0;
+  bool oneclass() const { return oneclass_nu > 0.0; }
 };
 
 // The rows a solve reads its kernel values from: the exact-integer plan's quantised rows (Q; int8

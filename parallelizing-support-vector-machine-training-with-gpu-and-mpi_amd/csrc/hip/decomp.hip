@@ -746,6 +746,21 @@ __global__ void ws_twin_init_kernel(const double* __restrict__ z, double eps, in
   if (i == 0) ctl->n_active = 2 * nrow;
 }
 
+// One-class mode's start over the n points: LIBSVM's feasible alpha (full ones, then frac at point `full`, zeros
+// beyond; svm_oneclass_start), f = 0 (no linear term: nz_update adds K[:, nz] alpha_nz), and the signs (the
+// solve's y), all +1.
+__global__ void ws_oneclass_init_kernel(int64_t full, double frac, int64_t n, int32_t* __restrict__ sgn,
+                                        double* __restrict__ alpha, double* __restrict__ f,
+                                        DecompCtl* __restrict__ ctl) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) {
+    alpha[i] = i < full ? 1.0 : (i == full ? frac : 0.0);
+    f[i] = 0.0;
+    sgn[i] = 1;
+  }
+  if (i == 0) ctl->n_active = n;
+}
+
 // Warm start: the ascending ids j with alpha_j != 0 into cols, alpha_j y_j into coef, their number to
 // *count (device) and *count_h (pinned host).  One 1024-thread workgroup; each thread takes 8
 // consecutive points of a 8192-point chunk, a workgroup exclusive scan of the per-thread counts
@@ -1135,6 +1150,11 @@ struct Solve {
   const double* twin_z = nullptr;
   double twin_eps = 0.0;
   int64_t rows() const { return twin ? nrow : nloc; }  // this GPU's kernel rows
+  // one-class mode (DecompOpts): y is the workspace's signs (all +1), the boxes are 1, and the start is
+  // (oc_full, oc_frac) followed by the chunked start (nz_update), so the workspace is a warm solve's
+  bool oneclass = false;
+  int64_t oc_full = 0;
+  double oc_frac = 0.0;
   ShrinkCfg shc;
   InnerVariant inner;
   NwDev nwd{};
@@ -1272,7 +1292,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.Qa = c.take<int8_t>(nl1 * kq, pack);
   w.N0a = c.take<int32_t>(nl1, pack);
   w.WNa = c.take<double>(nl1, pack);
-  w.sgn = c.take<int32_t>(n, S.twin);
+  w.sgn = c.take<int32_t>(n, S.twin || S.oneclass);
   w.fcols = c.take<int32_t>(kMaxWS, S.twin);
   w.fcoef = c.take<double>(kMaxWS, S.twin);
   w.fcount = c.take<int32_t>(64, S.twin);
@@ -1303,6 +1323,28 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     }
     n = 2 * nrow;
   }
+  svm_params p1 = p;  // the solve's parameters (one-class mode: the box is 1 whatever p.C says)
+  int64_t oc_full = 0;
+  double oc_frac = 0.0;
+  if (o.oneclass()) {  // everything one-class mode does not cover is refused here, before any device work
+    double cp = 0.0, cn = 0.0;
+    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
+    // shrinking: its unshrink rebuilds f from -y
+    const char* what = world != 1                 ? "the distributed solve (world > 1)"
+                       : o.twin()                 ? "the regression (twin) solve"
+                       : o.warm                   ? "a warm start"
+                       : shrink_cfg(p).on         ? "shrinking"
+                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                       : (cp != p.C || cn != p.C) ? "class weights"
+                                                  : nullptr;
+    if (what) {
+      set_error("decomposition SMO: the one-class solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+    if (const int rc = svm_oneclass_start(o.oneclass_nu, n, &oc_full, &oc_frac)) return rc;
+    p1.C = 1.0;
+    p1.weight_pos = p1.weight_neg = 0.0;
+  }
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !o.allgather)) {
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
@@ -1325,7 +1367,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   }
   int rc = read_knobs(sh, &S.k);
   if (rc) return rc;
-  if ((rc = svm_class_boxes(&p, &S.Cp, &S.Cn))) return rc;
+  if ((rc = svm_class_boxes(&p1, &S.Cp, &S.Cn))) return rc;
   S.ctx = ctx;
   S.s = ctx->stream;
   S.R = R;
@@ -1337,8 +1379,11 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.nrow = nrow;
   S.twin_z = o.twin_z;
   S.twin_eps = o.twin_eps;
+  S.oneclass = o.oneclass();
+  S.oc_full = oc_full;
+  S.oc_frac = oc_frac;
   S.n = n;
-  S.p = p;
+  S.p = p1;
   S.sh = sh;
   S.world = world;
   S.rank = rank;
@@ -1386,7 +1431,7 @@ int alloc_solve(Solve& S, bool warm) {
   int rc = size_col_cache(S, warm, &S.cc);
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
-  if (S.twin) S.y = S.w.sgn;
+  if (S.twin || S.oneclass) S.y = S.w.sgn;
   if ((rc = S.ctx->ensure_pinned(sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl) + 64))) return rc;
   char* pin = static_cast<char*>(S.ctx->pinned);
   S.hs = reinterpret_cast<DecompHost*>(pin);
@@ -1502,7 +1547,8 @@ int nz_update(const Solve& S, const PackState& ps, int64_t* nz_out) {
 }
 
 // The start of a solve on the stream: the control block running with its counters 0, a fresh cache,
-// alpha (cold start) and f = -y, and a warm start's f (*warm_cols = its columns).
+// alpha (cold start) and f = -y, and a warm start's f (*warm_cols = its columns).  One-class mode: its own
+// alpha, f = 0, and always the chunked start (*warm_cols = the start's columns).
 int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_cols) {
   const DecompWs& w = S.w;
   hipStream_t s = S.s;
@@ -1524,11 +1570,14 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
   if (S.twin)
     hipLaunchKernelGGL(ws_twin_init_kernel, dim3(unsigned((S.nrow + 255) / 256)), dim3(256), 0, s, S.twin_z, S.twin_eps,
                        S.nrow, w.sgn, S.alpha, w.f, w.ctl);
+  else if (S.oneclass)
+    hipLaunchKernelGGL(ws_oneclass_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.oc_full,
+                       S.oc_frac, S.n, w.sgn, S.alpha, w.f, w.ctl);
   else
     hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo,
                        S.nloc, S.n, int(warm), w.ctl);
   SVMD_LAUNCH_CHECK();
-  if (warm && (rc = nz_update(S, ps, warm_cols))) return rc;
+  if ((warm || S.oneclass) && (rc = nz_update(S, ps, warm_cols))) return rc;
   return SVM_OK;
 }
 
@@ -1835,7 +1884,7 @@ int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* al
   S.t0 = std::chrono::steady_clock::now();
   int rc = setup_solve(S, ctx, R, y, alpha, n, p, qws, o);
   if (rc) return rc;
-  if ((rc = alloc_solve(S, o.warm))) return rc;
+  if ((rc = alloc_solve(S, o.warm || S.oneclass))) return rc;  // one-class: sized as a warm solve (its start's columns)
   hipStream_t s = S.s;
   svm_decomp_trace* tr = S.tr;
   PackState ps(S.nloc);
@@ -2181,6 +2230,44 @@ SVM_API int svmd_train_decomp_svr(void* h, const void* X_d, int32_t is_u8, int64
   o.trace = trace;
   o.twin_z = z_d;
   o.twin_eps = epsilon;
+  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, nullptr, alpha_d, pp, q, o, r, timing, stats, used_out);
+}
+
+// The one-class form of svmd_train_decomp (LIBSVM's -s 2; svm355.h has the problem): one-class mode (DecompOpts)
+// over the n rows.  alpha_d: n doubles, out; r->b is rho, and a decision value is sum_k alpha_k K(x_k, x) - rho.
+// The same row paths and *used contract as svmd_train_decomp_svr.  pp->C is not read (the box is 1).  stats[7]:
+// the start's columns.  One GPU; shrinking, the Newton polish and class weights in *pp are SVM_ERR_ARG, as is
+// nu outside (0, 1).
+SVM_API int svmd_train_decomp_oneclass(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                       const double* mn_h, const double* mx_h, double nu, double* alpha_d,
+                                       const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
+                                       int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
+  SVMD_CTX(h);
+  if (used_out) *used_out = 0;
+  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !alpha_d) {
+    set_error("svmd_train_decomp_oneclass: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  if (!(nu > 0.0 && nu < 1.0)) {
+    set_error("svmd_train_decomp_oneclass: nu must be in (0, 1), got %g", nu);
+    return SVM_ERR_ARG;
+  }
+  {  // what one-class mode refuses, before any device work (setup_solve checks the same)
+    const svm_params p = params_or_default(pp);
+    double cp = 0.0, cn = 0.0;
+    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
+    const char* what = shrink_cfg(p).on           ? "shrinking"
+                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                       : (cp != p.C || cn != p.C) ? "class weights"
+                                                  : nullptr;
+    if (what) {
+      set_error("svmd_train_decomp_oneclass: the one-class solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+  }
+  DecompOpts o;
+  o.trace = trace;
+  o.oneclass_nu = nu;
   return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, nullptr, alpha_d, pp, q, o, r, timing, stats, used_out);
 }
 

@@ -194,6 +194,27 @@ SVM_API int svm_decomp_train_gram_svr(const double* K, int64_t ldk, const double
 SVM_API int svm_decomp_twin_fold(const int32_t* cols, const double* coef, int32_t cnt, int64_t n, int32_t* out_cols,
                                  double* out_coef, int32_t* out_cnt);
 
+// ---------------------------------------------------------------- one-class SVM (L3)
+// LIBSVM's -s 2: minimise 1/2 a' K a over 0 <= a_i <= 1 with sum a_i = nu n, 0 < nu < 1.  It is the classifier's
+// dual with every sign +1, box 1 and no linear term: f_i = sum_j a_j K_ij (no -y_i), I_high = {a_i < 1 - eps},
+// I_low = {a_i > eps}, the stop test b_low <= b_high + 2 tau, rho = b = (b_high + b_low) / 2, and the decision
+// value of x is sum_k a_k K(x_k, x) - rho.  The equality is carried by LIBSVM's feasible start: a_i = 1 for
+// i < full = floor(nu n), a_full = frac = nu n - full (if full < n), 0 beyond; f starts as K[:, nz] a_nz over
+// the start's nonzero ids in ascending order.  p->C and the class weights are not read.
+// The start's two numbers (SVM_ERR_ARG unless 0 < nu < 1 and n >= 2).
+SVM_API int svm_oneclass_start(double nu, int64_t n, int64_t* full, double* frac);
+// The pairwise oracle from that start.  alpha (n, out); r->b is rho.
+SVM_API int svm_smo_train_oneclass(const double* X, int64_t n, int64_t d, double nu, double* alpha,
+                                   const svm_params* p, svm_result* r);
+// The decomposition oracle's one-class mode on the n x n kernel matrix K (the device's own kernel values for a
+// bit-for-bit comparison with svmd_train_decomp_oneclass): the start's f is summed in chunks of 1024 columns, each
+// in the f update's order (f64_rows: 0 = the exact-integer GEMV's, 1 = the FP64-row path's); everything after the
+// start is the classifier's solve with y = +1 and C = 1.  stats[7]: the start's columns.  Shrinking and the
+// Newton polish are SVM_ERR_ARG.
+SVM_API int svm_decomp_train_gram_oneclass(const double* K, int64_t ldk, int64_t n, double nu, double* alpha,
+                                           const svm_params* p, int32_t q, double tau_frac, int32_t inner_wss,
+                                           int32_t f64_rows, svm_result* r, int64_t* stats, svm_decomp_trace* trace);
+
 // ---------------------------------------------------------------- evaluation (L4)
 // out[i] = sum_k alphas[k]*ys[k]*K(Xq_i, Xs_k) - b, summed in SV order from -b (main3.cpp:391-402).
 SVM_API int svm_decision(const double* Xs, const int32_t* ys, const double* alphas, int64_t nsv,

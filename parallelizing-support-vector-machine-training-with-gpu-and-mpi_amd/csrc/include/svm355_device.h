@@ -80,6 +80,15 @@ SVM_API int svmd_train_decomp_svr(void* ctx, const void* X_d, int32_t is_u8, int
                                   const double* mn_h, const double* mx_h, const double* z_d, double epsilon,
                                   double* alpha_d, const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
                                   int64_t* stats, int32_t* used, svm_decomp_trace* trace);
+// One-class SVM (LIBSVM's -s 2, svm355.h) on the decomposition solver: uint8 pixel rows or min-max scaled FP64
+// rows as above.  alpha_d: n doubles, out; r->b is rho.  The solver's one-class mode: y = +1, box 1 (p->C is not
+// read), no linear term, LIBSVM's feasible start written on the device and its f summed by the chunked start
+// (1,024 columns per f update); stats[7] = the start's columns.  One GPU; shrinking, the Newton polish, class
+// weights and nu outside (0, 1) are SVM_ERR_ARG.  *used as svmd_train_decomp_svr.
+SVM_API int svmd_train_decomp_oneclass(void* ctx, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                       const double* mn_h, const double* mx_h, double nu, double* alpha_d,
+                                       const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
+                                       int64_t* stats, int32_t* used, svm_decomp_trace* trace);
 // The twin mode's moved-column fold and f update alone (tests): a moved list of m <= 1024 distinct virtual ids
 // (host), f_io = the 2n points' f (host, in and out).
 SVM_API int svmd_decomp_twin_step_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,

@@ -7,8 +7,9 @@ Those are written natively (svm_model_save) with %.17g so they round-trip bit-ex
 IDs alone cannot reproduce a prediction without the training set, a loadable model additionally
 stores the scaled SV rows (``sv_rows.npy``) and the scaler (``scaler.npz``) in numpy's
 pickle-free formats, plus ``model.json`` with the hyper-parameters and the model's kind: "svc" (a
-classifier; also what a file without the marker is) or "svr" (an epsilon-SVR, stored with labels = sign(beta)
-and alphas = |beta|).  Each class loads its own kind only.
+classifier; also what a file without the marker is), "svr" (an epsilon-SVR, stored with labels = sign(beta)
+and alphas = |beta|) or "oneclass" (a one-class SVM: labels all +1, alphas = alpha, b = rho, ``meta["nu"]``).
+Each class loads its own kind only.
 """
 from __future__ import annotations
 

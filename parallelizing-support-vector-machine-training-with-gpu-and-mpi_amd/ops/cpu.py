@@ -170,6 +170,42 @@ def twin_fold(cols: np.ndarray, coef: np.ndarray, n: int) -> Tuple[np.ndarray, n
     return oc[: cnt.value].copy(), ov[: cnt.value].copy()
 
 
+def smo_train_oneclass(X: np.ndarray, params: SVMParams, nu: float = 0.5) -> Tuple[np.ndarray, SMOResult]:
+    """One-class SVM on the pairwise oracle (svm_smo_train_oneclass: y = +1, box 1, no linear term, LIBSVM's
+    feasible start).  Returns (alpha of n entries, result); result.b is rho.  params.C is not read."""
+    X = _c64(X)
+    n, d = X.shape
+    a = np.zeros(n)
+    r = N.SvmResult()
+    p = params.to_struct()
+    N.check(N.core().svm_smo_train_oneclass(N.ptr(X), n, d, float(nu), N.ptr(a), ctypes.byref(p), ctypes.byref(r)),
+            "svm_smo_train_oneclass")
+    return a, SMOResult.from_struct(r)
+
+
+def decomp_train_gram_oneclass(K: np.ndarray, params: SVMParams, nu: float = 0.5, q: int = 1024,
+                               tau_frac: float = 0.1, inner_wss: int = 3, trace_cap: int = 0,
+                               snapshots: bool = False, fp64_rows: bool = False):
+    """The decomposition oracle's one-class mode (svm_decomp_train_gram_oneclass) on the n x n kernel matrix K.
+    Returns (alpha of n entries; SMOResult, b = rho; stats dict, "start_columns" = the start's columns;
+    N.DecompTrace or None).  fp64_rows: the start and the f update sum in the order of the device's FP64-row
+    path (real-valued rows) instead of its exact-integer GEMV's."""
+    K = _c64(K)
+    n = K.shape[0]
+    _gram_shape(K, n)
+    a = np.zeros(n)
+    r = N.SvmResult()
+    st = (ctypes.c_int64 * 16)()
+    tr = N.DecompTrace(trace_cap, n if snapshots else 0) if trace_cap > 0 else None
+    p = params.to_struct()
+    N.check(N.core().svm_decomp_train_gram_oneclass(N.ptr(K), K.shape[1], n, float(nu), N.ptr(a), ctypes.byref(p),
+                                                    int(q), float(tau_frac), int(inner_wss), int(bool(fp64_rows)),
+                                                    ctypes.byref(r), st,
+                                                    ctypes.byref(tr.struct) if tr is not None else None),
+            "svm_decomp_train_gram_oneclass")
+    return a, SMOResult.from_struct(r), {**_decomp_stats(st), "start_columns": int(st[7])}, tr
+
+
 def _decomp_stats(st) -> dict:
     return {"outer_iterations": int(st[0]), "inner_iterations": int(st[1]), "working_set": int(st[2]),
             "solve_us": int(st[3]), "update_columns": int(st[4]), "chain_iterations": int(st[13]),

@@ -507,6 +507,43 @@ def train_decomp_svr(X: torch.Tensor, z: torch.Tensor, alpha: torch.Tensor, para
                                       "inner_threads": int(st[5])}
 
 
+def train_decomp_oneclass(X: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx, nu: float = 0.5,
+                          working_set: int = 1024,
+                          trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:
+    """One-class SVM on the decomposition solver (svmd_train_decomp_oneclass): the solver's one-class mode over
+    the n rows of X (device uint8 pixel rows (n, d), or min-max scaled FP64 rows (n, ld), as ``train_decomp``).
+    alpha (n float64, out); the result's b is rho and a decision value is sum_k alpha_k K(x_k, x) - rho.
+    params.C is not read (the box is 1).  Shrinking, the Newton polish, class weights and nu outside (0, 1)
+    raise.  The timing dict's "start_columns" counts the start's nonzero alphas (one f update per 1,024 of
+    them before the first selection).  None when nothing ran (uint8 rows without an exact-integer plan; FP64
+    rows whose workspace does not fit)."""
+    u8 = X.dtype == torch.uint8
+    if not u8:
+        _check_rows(X)
+    n, ld = X.shape
+    if alpha.dtype != torch.float64 or alpha.shape != (n,) or not alpha.is_contiguous():
+        raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({n},)")
+    ctx = _ctx_for(X)
+    a, b, dd = _host_stats(mn, mx)
+    d = ld if u8 else dd
+    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
+    st = (ctypes.c_int64 * 16)()
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_train_decomp_oneclass(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), float(nu),
+                                               N.ptr(alpha), ctypes.byref(p), int(working_set), ctypes.byref(r),
+                                               ctypes.byref(tm), st, ctypes.byref(used),
+                                               ctypes.byref(trace.struct) if trace is not None else None),
+            "svmd_train_decomp_oneclass")
+    if not used.value:
+        return None
+    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
+                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
+                                      "rows": "uint8" if u8 else "fp64", "solver": "decomp-oneclass",
+                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
+                                      "working_set": int(st[2]), "update_columns": int(st[4]),
+                                      "inner_threads": int(st[5]), "start_columns": int(st[7])}
+
+
 def decomp_twin_step_u8(Xu: torch.Tensor, mn, mx, gamma: float, cols: np.ndarray, coef: np.ndarray,
                         f: np.ndarray) -> Optional[np.ndarray]:
     """The twin mode's fold and f update alone (svmd_decomp_twin_step_u8): the moved list ``cols`` (distinct
