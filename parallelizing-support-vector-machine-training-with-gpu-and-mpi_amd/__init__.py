@@ -8,6 +8,9 @@ re-designed for gfx950:
                                      arithmetic): on the GPU the SMO-type working-set decomposition
                                      solver by default (``solver="smo"``: the reference's pairwise
                                      trajectory, bit for bit the CPU oracle's); on the CPU the oracle
+* ``SVC(probability=True)``          Platt probabilities (LIBSVM's -b 1) and ``SVC.cross_val_decision`` / ``cross_val_score``
+                                     (-v k): a fold is the decomposition solve with its labels masked to 0, the
+                                     folds run beside the final model, the sigmoid is fitted in one workgroup
 * ``svm355.SVR``                     epsilon-SVR on the same solvers: the 2n-variable problem whose twins a_k / a*_k
                                      share a kernel row, so on the GPU the decomposition solver's kernel work
                                      runs over n rows, not 2n (the CPU oracle is the pairwise solver)

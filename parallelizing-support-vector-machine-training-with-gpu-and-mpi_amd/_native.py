@@ -64,6 +64,13 @@ class SvmResult(ctypes.Structure):
     ]
 
 
+class SvmPlatt(ctypes.Structure):
+    _fields_ = [("A", c_double), ("B", c_double), ("iterations", c_int32), ("status", c_int32)]
+
+
+PLATT_STATUS = {0: "converged", 1: "max_iter", 2: "line_search_failed", 3: "degenerate"}
+
+
 class SvmdTiming(ctypes.Structure):
     _fields_ = [
         ("h2d_ms", c_double),
@@ -218,6 +225,10 @@ _CORE_SIGS = {
     "svm_decomp_train_gram_oneclass": (c_int32, [_P, c_int64, c_int64, c_double, _P, POINTER(SvmParams), c_int32,
                                                  c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
                                                  POINTER(SvmDecompTrace)]),
+    "svm_decomp_train_gram_heldout": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, POINTER(SvmParams), c_int32,
+                                                c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64), _P,
+                                                POINTER(SvmDecompTrace)]),
+    "svm_platt_fit": (c_int32, [_P, _P, _P, c_int64, POINTER(SvmPlatt)]),
     "svm_decomp_twin_fold": (c_int32, [_P, _P, c_int32, c_int64, _P, _P, POINTER(c_int32)]),
     "svm_crash_handler_install": (c_int32, [c_char_p]),
     "svm_decomp_gemv_ref": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int64, _P]),
@@ -300,6 +311,10 @@ _HIP_SIGS = {
     "svmd_train_decomp_oneclass": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, c_double, _P,
                                              POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                              POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
+    "svmd_train_decomp_heldout": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P,
+                                            POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
+                                            POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
+    "svmd_platt_fit": (c_int32, [c_void_p, _P, _P, _P, c_int64, POINTER(SvmPlatt)]),
     "svmd_decomp_twin_step_u8": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, c_double, _P, _P, c_int32, _P,
                                            POINTER(c_int32)]),
     "svmd_decomp_newton_probe": (c_int32, [c_void_p, _P, _P, c_int32, _P, _P, c_double, c_double, c_int32, c_int32,

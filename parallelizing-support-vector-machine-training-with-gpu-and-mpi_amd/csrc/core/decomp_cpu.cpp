@@ -31,6 +31,10 @@
 //   * one-class mode (svm_decomp_train_gram_oneclass): every sign +1, box 1, no linear term; the start is
 //     LIBSVM's feasible alpha (svm_oneclass_start) and f = K[:, nz] alpha_nz in chunks of kMaxWS columns
 //     (ws_oneclass_init_kernel, then decomp.hip's nz_update).  One rank, no shrinking, no Newton polish.
+//   * held-out mode (svm_decomp_train_gram_heldout): the masked points run with label 0, which no selection
+//     takes (in_high / in_low below are false for it), so their alpha stays 0 and their f collects every update:
+//     f - b is their held-out decision value (ws_heldout_init_kernel, ws_heldout_dec_kernel).  Cold start, one
+//     rank, no shrinking, no Newton polish; class weights are allowed.
 // The kernel values themselves come from the caller (the device Gram on the exact-integer path).
 #include <chrono>
 #include <climits>
@@ -183,7 +187,8 @@ void fold_twins(const int32_t* cols, const double* coef, int64_t cnt, int64_t n,
 int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha, int32_t warm,
                  const svm_params& p, int32_t qws, double tau_frac, int32_t inner_wss, svm_result* res,
                  int64_t* stats, svm_decomp_trace* tr, Transport* t, const double* twin_z = nullptr,
-                 double twin_eps = 0.0, bool f64_rows = false, double oneclass_nu = 0.0) {
+                 double twin_eps = 0.0, bool f64_rows = false, double oneclass_nu = 0.0,
+                 const uint8_t* heldout = nullptr, double* f_out = nullptr) {
   const int world = t ? t->world() : 1, rank = t ? t->rank() : 0;
   const bool twin = twin_z != nullptr, oneclass = oneclass_nu > 0.0;
   if (!K || (!y && !twin && !oneclass) || !alpha || n < 2 || ldk < n) {
@@ -233,6 +238,22 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     }
     if (const int rc = svm_oneclass_start(oneclass_nu, n, &oc_full, &oc_frac)) return rc;
     sgn.assign(size_t(n), 1);
+    y = sgn.data();
+  }
+  if (heldout) {  // label 0: held out, never selected
+    const char* what = world != 1           ? "the distributed solve (world > 1)"
+                       : twin               ? "the regression (twin) solve"
+                       : oneclass           ? "the one-class solve"
+                       : warm               ? "a warm start"
+                       : shrink_cfg(p).on   ? "shrinking"
+                       : newton_cfg(p).on   ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                            : nullptr;
+    if (what) {
+      set_error("svm_decomp_train_gram_heldout: the held-out solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+    sgn.resize(size_t(n));
+    for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = heldout[i] ? 0 : y[i];
     y = sgn.data();
   }
   if (!(tau_frac >= 0.0 && tau_frac < 0.5)) {
@@ -695,6 +716,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     stats[13] = chain_it;
     stats[14] = eta_floored;
   }
+  if (f_out) std::copy(f.begin(), f.begin() + nloc, f_out + lo);
   if (res) {
     res->iterations = inner_total + 1;
     res->b_high = bh;
@@ -766,6 +788,20 @@ extern "C" SVM_API int svm_decomp_train_gram_oneclass(const double* K, int64_t l
   p.weight_pos = p.weight_neg = 0.0;
   return decomp_solve(K, ldk, nullptr, n, alpha, 0, p, qws, tau_frac, inner_wss, res, stats, tr, nullptr, nullptr, 0.0,
                       f64_rows != 0, nu);
+}
+
+// The held-out form of svm_decomp_train_gram_rows (svm355.h): label 0 on the masked points, the final f out.
+extern "C" SVM_API int svm_decomp_train_gram_heldout(const double* K, int64_t ldk, const int32_t* y,
+                                                     const uint8_t* heldout, int64_t n, double* alpha,
+                                                     const svm_params* pp, int32_t qws, double tau_frac,
+                                                     int32_t inner_wss, int32_t f64_rows, svm_result* res,
+                                                     int64_t* stats, double* f_out, svm_decomp_trace* tr) {
+  if (!heldout || !y) {
+    set_error("svm_decomp_train_gram_heldout: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  return decomp_solve(K, ldk, y, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr, nullptr,
+                      nullptr, 0.0, f64_rows != 0, 0.0, heldout, f_out);
 }
 
 // Twin mode's moved-column fold alone (tests): cnt <= 1024 virtual ids in [0, 2n) and their coefficients to one

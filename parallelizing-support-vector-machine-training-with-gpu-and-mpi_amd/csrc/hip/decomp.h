@@ -66,6 +66,14 @@ struct DecompOpts {
   // no class weights, not together with twin mode, 0 < nu < 1: anything else is SVM_ERR_ARG.
   double oneclass_nu = 0.0;
   bool oneclass() const { return oneclass_nu > 0.0; }
+  // Held-out mode (svm355.h): heldout = device uint8[n], 1 = point i is out of the fit, and heldout_dec = n
+  // doubles on the device, out.  The solve keeps its own signs (0 on the held-out points: never selected, alpha
+  // exactly 0, f collecting every update) and does not read the caller's y after the start; after the last
+  // outer iteration heldout_dec_i = f_i - b for the held-out points and 0.0 for the others.  One GPU, cold
+  // start, no shrinking, no Newton polish, not with twin or one-class mode: anything else is SVM_ERR_ARG.
+  // Class weights are allowed.  The training part must hold both classes (the caller checks).
+  const uint8_t* heldout = nullptr;
+  double* heldout_dec = nullptr;
 };
 
 // The rows a solve reads its kernel values from: the exact-integer plan's quantised rows (Q; int8

@@ -761,6 +761,31 @@ __global__ void ws_oneclass_init_kernel(int64_t full, double frac, int64_t n, in
   if (i == 0) ctl->n_active = n;
 }
 
+// Held-out mode's start over the n points: the solve's own signs -- 0 for a held-out point, which no selection
+// takes (ws_select_kernel, ws_select_wide_kernel and ws_inner_kernel test y == 1 / y == -1), so its alpha stays 0
+// -- alpha = 0 and f = -sgn.
+__global__ void ws_heldout_init_kernel(const int32_t* __restrict__ y, const uint8_t* __restrict__ mask, int64_t n,
+                                       int32_t* __restrict__ sgn, double* __restrict__ alpha,
+                                       double* __restrict__ f, DecompCtl* __restrict__ ctl) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const int32_t sg = mask[i] ? 0 : y[i];
+    sgn[i] = sg;
+    alpha[i] = 0.0;
+    f[i] = -static_cast<double>(sg);
+  }
+  if (i == 0) ctl->n_active = n;
+}
+
+// Held-out mode's result after the last outer iteration: a held-out point's f has received every f update from
+// -0, so it is sum_j alpha_j y_j K_ij, and f - b (b as finish_solve computes it from the same two bounds, so the
+// same bits) is its decision value under a model that never saw it.  0.0 for the training part.
+__global__ void ws_heldout_dec_kernel(const double* __restrict__ f, const uint8_t* __restrict__ mask, int64_t n,
+                                      const DecompCtl* __restrict__ ctl, double* __restrict__ dec) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i < n) dec[i] = mask[i] ? f[i] - (ctl->b_high + ctl->b_low) / 2 : 0.0;
+}
+
 // Warm start: the ascending ids j with alpha_j != 0 into cols, alpha_j y_j into coef, their number to
 // *count (device) and *count_h (pinned host).  One 1024-thread workgroup; each thread takes 8
 // consecutive points of a 8192-point chunk, a workgroup exclusive scan of the per-thread counts
@@ -1155,6 +1180,10 @@ struct Solve {
   bool oneclass = false;
   int64_t oc_full = 0;
   double oc_frac = 0.0;
+  // held-out mode (DecompOpts): y is the workspace's signs (0 on the masked points), y_in the caller's labels
+  const uint8_t* heldout = nullptr;
+  double* heldout_dec = nullptr;
+  const int32_t* y_in = nullptr;
   ShrinkCfg shc;
   InnerVariant inner;
   NwDev nwd{};
@@ -1292,7 +1321,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.Qa = c.take<int8_t>(nl1 * kq, pack);
   w.N0a = c.take<int32_t>(nl1, pack);
   w.WNa = c.take<double>(nl1, pack);
-  w.sgn = c.take<int32_t>(n, S.twin || S.oneclass);
+  w.sgn = c.take<int32_t>(n, S.twin || S.oneclass || S.heldout);
   w.fcols = c.take<int32_t>(kMaxWS, S.twin);
   w.fcoef = c.take<double>(kMaxWS, S.twin);
   w.fcount = c.take<int32_t>(64, S.twin);
@@ -1345,6 +1374,24 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     p1.C = 1.0;
     p1.weight_pos = p1.weight_neg = 0.0;
   }
+  if (o.heldout) {  // everything held-out mode does not cover is refused here, before any device work
+    // shrinking: its unshrink rebuilds f from the nonzero alphas, the polish: untested on label 0
+    const char* what = world != 1                 ? "the distributed solve (world > 1)"
+                       : o.twin()                 ? "the regression (twin) solve"
+                       : o.oneclass()             ? "the one-class solve"
+                       : o.warm                   ? "a warm start"
+                       : shrink_cfg(p).on         ? "shrinking"
+                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                                  : nullptr;
+    if (what) {
+      set_error("decomposition SMO: the held-out solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+    if (!o.heldout_dec || !y) {
+      set_error("decomposition SMO: the held-out solve needs labels and a buffer for the held-out decisions");
+      return SVM_ERR_ARG;
+    }
+  }
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !o.allgather)) {
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
@@ -1382,6 +1429,9 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.oneclass = o.oneclass();
   S.oc_full = oc_full;
   S.oc_frac = oc_frac;
+  S.heldout = o.heldout;
+  S.heldout_dec = o.heldout_dec;
+  S.y_in = y;
   S.n = n;
   S.p = p1;
   S.sh = sh;
@@ -1431,7 +1481,7 @@ int alloc_solve(Solve& S, bool warm) {
   int rc = size_col_cache(S, warm, &S.cc);
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
-  if (S.twin || S.oneclass) S.y = S.w.sgn;
+  if (S.twin || S.oneclass || S.heldout) S.y = S.w.sgn;
   if ((rc = S.ctx->ensure_pinned(sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl) + 64))) return rc;
   char* pin = static_cast<char*>(S.ctx->pinned);
   S.hs = reinterpret_cast<DecompHost*>(pin);
@@ -1573,6 +1623,9 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
   else if (S.oneclass)
     hipLaunchKernelGGL(ws_oneclass_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.oc_full,
                        S.oc_frac, S.n, w.sgn, S.alpha, w.f, w.ctl);
+  else if (S.heldout)
+    hipLaunchKernelGGL(ws_heldout_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y_in, S.heldout,
+                       S.n, w.sgn, S.alpha, w.f, w.ctl);
   else
     hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo,
                        S.nloc, S.n, int(warm), w.ctl);
@@ -1948,6 +2001,11 @@ int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* al
       return SVM_ERR_INTERNAL;
     }
   }
+  if (S.heldout) {  // behind the queued no-op batch on the stream: the control block and f are final
+    hipLaunchKernelGGL(ws_heldout_dec_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.w.f, S.heldout, S.n,
+                       S.w.ctl, S.heldout_dec);
+    SVMD_LAUNCH_CHECK();
+  }
   return finish_solve(S, ps, *fin, warm_cols, r, stats);
 }
 
@@ -2269,6 +2327,35 @@ SVM_API int svmd_train_decomp_oneclass(void* h, const void* X_d, int32_t is_u8, 
   o.trace = trace;
   o.oneclass_nu = nu;
   return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, nullptr, alpha_d, pp, q, o, r, timing, stats, used_out);
+}
+
+// The held-out form of svmd_train_decomp (svm355_device.h): held-out mode (DecompOpts) over the n rows.
+SVM_API int svmd_train_decomp_heldout(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                      const double* mn_h, const double* mx_h, const int32_t* y_d,
+                                      const uint8_t* heldout_d, double* alpha_d, double* dec_out_d,
+                                      const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
+                                      int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
+  SVMD_CTX(h);
+  if (used_out) *used_out = 0;
+  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !y_d || !heldout_d || !alpha_d || !dec_out_d) {
+    set_error("svmd_train_decomp_heldout: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  {  // what held-out mode refuses, before any device work (setup_solve checks the same)
+    const svm_params p = params_or_default(pp);
+    const char* what = shrink_cfg(p).on   ? "shrinking"
+                       : newton_cfg(p).on ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                          : nullptr;
+    if (what) {
+      set_error("svmd_train_decomp_heldout: the held-out solve does not support %s", what);
+      return SVM_ERR_ARG;
+    }
+  }
+  DecompOpts o;
+  o.trace = trace;
+  o.heldout = heldout_d;
+  o.heldout_dec = dec_out_d;
+  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, o, r, timing, stats, used_out);
 }
 
 // The decomposition solver's f update alone (tests): the uint8 rows quantised as a solve would, then

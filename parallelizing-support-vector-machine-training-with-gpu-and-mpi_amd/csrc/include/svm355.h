@@ -215,6 +215,37 @@ SVM_API int svm_decomp_train_gram_oneclass(const double* K, int64_t ldk, int64_t
                                            const svm_params* p, int32_t q, double tau_frac, int32_t inner_wss,
                                            int32_t f64_rows, svm_result* r, int64_t* stats, svm_decomp_trace* trace);
 
+// ---------------------------------------------------------------- held-out points and Platt scaling (L3)
+// The held-out form of svm_decomp_train_gram_rows (cold start): heldout[i] != 0 takes point i out of the fit.  In
+// THIS entry (and the device's svmd_train_decomp_heldout) only, such a point runs with label 0, which means "held
+// out, never selected": it is in neither I_high nor I_low of any selection, so its alpha stays exactly 0, while
+// its f starts from -0 and receives every f update.  At the end f_i = sum_j alpha_j y_j K_ij, and f_i - r->b is
+// the decision value of a model that never saw point i.  f_out (n, optional): the final f of every point.  The
+// training part must hold both classes (the caller checks).  One rank; a warm start, shrinking and the Newton
+// polish are SVM_ERR_ARG; class weights are allowed.
+SVM_API int svm_decomp_train_gram_heldout(const double* K, int64_t ldk, const int32_t* y, const uint8_t* heldout,
+                                          int64_t n, double* alpha, const svm_params* p, int32_t q, double tau_frac,
+                                          int32_t inner_wss, int32_t f64_rows, svm_result* r, int64_t* stats,
+                                          double* f_out, svm_decomp_trace* trace);
+
+// Platt scaling: P(y = +1 | f) = 1 / (1 + exp(A f + B)) fitted to (decision value, label) pairs by Lin, Lin and
+// Weng's Newton method with backtracking, as LIBSVM's -b 1: targets (N+ + 1) / (N+ + 2) and 1 / (N- + 2), start
+// A = 0, B = log((N- + 1) / (N+ + 1)), at most 100 iterations, stop when both gradient components are below 1e-5,
+// Hessian ridge 1e-12, sufficient decrease 1e-4, step floor 1e-10.
+enum svm_platt_status {
+  SVM_PLATT_CONVERGED = 0,    // both gradient components below 1e-5
+  SVM_PLATT_MAX_ITER = 1,     // 100 Newton iterations without that
+  SVM_PLATT_LINE_SEARCH = 2,  // no step down to 1e-10 decreased the objective enough
+  SVM_PLATT_DEGENERATE = 3,   // one class only, or all decision values equal: nothing to fit, (A, B) = the start
+};
+typedef struct svm_platt {
+  double A, B;
+  int32_t iterations, status;
+} svm_platt;
+// The host fit, every sum in ascending order.  y: labels, > 0 is the positive class; use: optional n bytes,
+// nonzero = the pair counts (null: all of them).
+SVM_API int svm_platt_fit(const double* dec, const int32_t* y, const uint8_t* use, int64_t n, svm_platt* out);
+
 // ---------------------------------------------------------------- evaluation (L4)
 // out[i] = sum_k alphas[k]*ys[k]*K(Xq_i, Xs_k) - b, summed in SV order from -b (main3.cpp:391-402).
 SVM_API int svm_decision(const double* Xs, const int32_t* ys, const double* alphas, int64_t nsv,

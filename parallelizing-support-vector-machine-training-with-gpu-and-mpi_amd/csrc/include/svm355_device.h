@@ -89,6 +89,22 @@ SVM_API int svmd_train_decomp_oneclass(void* ctx, const void* X_d, int32_t is_u8
                                        const double* mn_h, const double* mx_h, double nu, double* alpha_d,
                                        const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
                                        int64_t* stats, int32_t* used, svm_decomp_trace* trace);
+// The held-out form of svmd_train_decomp (svm355.h: label 0 means "held out, never selected" in this entry only):
+// heldout_d uint8[n], 1 = out of the fit; dec_out_d n doubles, out: f_i - r->b for the held-out points (the decision
+// value of a model that never saw them, from the training's own kernel values), 0.0 for the others.  The solve keeps
+// its own signs (ws_heldout_init_kernel) and does not read y_d after the start; alpha_d is exactly 0 on the held-out
+// points.  Class weights are allowed.  One GPU, cold start; shrinking and the Newton polish in *p are SVM_ERR_ARG.
+// The training part must hold both classes (the caller checks it on the host).  *used as svmd_train_decomp.
+SVM_API int svmd_train_decomp_heldout(void* ctx, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                      const double* mn_h, const double* mx_h, const int32_t* y_d,
+                                      const uint8_t* heldout_d, double* alpha_d, double* dec_out_d,
+                                      const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
+                                      int64_t* stats, int32_t* used, svm_decomp_trace* trace);
+// Platt scaling on the device (platt.hip; svm355.h has the method): one launch of one 1,024-thread workgroup runs
+// the whole Newton iteration with deterministic sums.  dec_d n doubles, y_d n labels, use_d optional uint8[n]
+// (nonzero = the pair counts); *out (host) holds A, B, the iterations and the status on return.
+SVM_API int svmd_platt_fit(void* ctx, const double* dec_d, const int32_t* y_d, const uint8_t* use_d, int64_t n,
+                           svm_platt* out);
 // The twin mode's moved-column fold and f update alone (tests): a moved list of m <= 1024 distinct virtual ids
 // (host), f_io = the 2n points' f (host, in and out).
 SVM_API int svmd_decomp_twin_step_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,

@@ -25,7 +25,8 @@ from typing import Optional
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
-from ..utils.data import MinMaxScaler, check_finite_bounds, check_warm_start, resolve_class_weight
+from ..utils.data import (MinMaxScaler, check_finite_bounds, check_folds, check_warm_start, resolve_class_weight,
+                          stratified_folds)
 
 
 def _resolve_device(device: str) -> str:
@@ -45,7 +46,7 @@ class SVC:
                  sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
                  scale: bool = True, zero_is_positive: bool = False, gram: str = "auto", kcache: str = "auto",
                  wss: str = "first", solver: str = "auto", working_set: int = 1024, shrinking=False,
-                 class_weight=None):
+                 class_weight=None, probability: bool = False, cv: int = 5, cv_seed: int = 0):
         if wss not in ("first", "second"):
             raise ValueError("wss must be 'first' (the reference's selection) or 'second'")
         if solver not in ("auto", "smo", "decomp"):
@@ -78,9 +79,22 @@ class SVC:
         # profiles/shrinking.md), or a pass every k outer iterations.
         self.solver = solver
         self.working_set = int(working_set)
+        # probability (LIBSVM's -b 1, scikit-learn's probability=True): fit also runs cv-fold cross-validation
+        # and fits Platt's sigmoid P(y = +1 | f) = 1 / (1 + exp(A f + B)) to the held-out decision values
+        # (probA_, probB_, cv_decision_, cv_folds_; predict_proba).  On a GPU the folds are the decomposition
+        # solver's held-out mode -- the ordinary solve on the shared device rows with the fold's labels masked
+        # to 0 -- run side by side with the final model; predict stays the sign of the decision value.
+        self.probability = bool(probability)
+        self.cv = int(cv)
+        self.cv_seed = int(cv_seed)
+        if self.probability and self.cv < 2:
+            raise ValueError(f"probability=True needs cv >= 2 folds, got cv={cv}")
+        self.probA_ = self.probB_ = None
 
     # ------------------------------------------------------------------ fit
-    def fit(self, X: np.ndarray, y: np.ndarray, alpha0: Optional[np.ndarray] = None) -> "SVC":
+    def fit(self, X: np.ndarray, y: np.ndarray, alpha0: Optional[np.ndarray] = None,
+            folds: Optional[np.ndarray] = None) -> "SVC":
+        """folds (probability=True only): an explicit fold id per row instead of stratified_folds(y, cv, cv_seed)."""
         dev = _resolve_device(self.device)
         # uint8 pixel rows stay compact up to the device (8x less H2D; widened to FP64 there)
         X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
@@ -96,13 +110,249 @@ class SVC:
             self._check_weighted(dev)
         if alpha0 is not None:
             alpha0 = check_warm_start(alpha0, y, self.params.box(y) if self.params.weighted else self.params.C)
+        if folds is not None and not self.probability:
+            raise ValueError("folds= is the cross-validation of probability=True (or use cross_val_decision)")
+        self.probA_ = self.probB_ = self.cv_decision_ = self.cv_folds_ = self.platt_ = None
+        self.classes_ = np.array([-1, 1], dtype=np.int32)
         t0 = time.perf_counter()
-        if dev == "cpu":
+        if self.probability:
+            self._check_cv(dev, alpha0)
+            folds = self._folds(y, self.cv, self.cv_seed, folds)
+            if dev == "cpu":
+                self._fit_cpu(X, y, None)
+                self._fit_probability_cpu(X, y, folds)
+            else:
+                self._fit_cuda_probability(X, y, folds, dev)
+        elif dev == "cpu":
             self._fit_cpu(X, y, alpha0)
         else:
             self._fit_cuda(X, y, alpha0, dev)
         self.fit_time_ = time.perf_counter() - t0
         return self
+
+    # ------------------------------------------------------------------ cross-validation and probabilities
+    def _check_cv(self, dev: str, alpha0=None) -> None:
+        """What cross-validation (and so probability=True) does not cover raises here, before any device work."""
+        what = "probability=True / cross-validation"
+        if alpha0 is not None:
+            raise ValueError(f"{what} does not take a warm start (alpha0): every fold is a cold solve")
+        if self.params._shrink_code() > 0:
+            raise ValueError(f"{what} is not supported with shrinking (the held-out solve has none)")
+        if dev == "cpu":
+            return
+        if self.solver == "smo":
+            raise ValueError(f"{what} on a GPU runs on the decomposition solver's held-out mode, not solver='smo'")
+        if not self.scale:
+            raise ValueError(f"{what} on a GPU needs scale=True (the decomposition solver's min-max scaled rows)")
+        for name, on in (("wss='second'", self.params.wss == 2), (f"gram={self.gram!r}", self.gram != "auto"),
+                         (f"kcache={self.kcache!r}", self.kcache != "auto")):
+            if on:
+                raise ValueError(f"{what} on a GPU runs on the decomposition solver, which {name} (the pairwise "
+                                 "solver) rules out")
+
+    @staticmethod
+    def _folds(y: np.ndarray, cv: int, seed: int, folds) -> np.ndarray:
+        if folds is None:
+            if int(cv) < 2:
+                raise ValueError(f"cross-validation needs cv >= 2 folds, got cv={cv}")
+            folds = stratified_folds(y, int(cv), int(seed))
+        return check_folds(folds, y)
+
+    def _cv_cpu(self, Xs: np.ndarray, y: np.ndarray, folds: np.ndarray):
+        """Held-out decision values on the CPU: the pairwise oracle fits each fold's training rows (already
+        scaled with all rows' bounds) and svm_decision scores the fold.  Returns (n values, per-fold ms)."""
+        from ..ops import cpu as C
+
+        dec = np.zeros(y.shape[0])
+        fold_ms = []
+        for j in range(int(folds.max()) + 1):
+            t0 = time.perf_counter()
+            te = folds == j
+            Xtr, ytr = np.ascontiguousarray(Xs[~te]), np.ascontiguousarray(y[~te])
+            a, res, _ = C.smo_train(Xtr, ytr, self.params)
+            sv = a > self.params.sv_tol
+            dec[te] = C.decision(Xtr[sv], ytr[sv], a[sv], np.ascontiguousarray(Xs[te]), self.params.gamma, res.b,
+                                 self.params.n_threads)
+            fold_ms.append((time.perf_counter() - t0) * 1e3)
+        return dec, fold_ms
+
+    def _scaled_cpu(self, X: np.ndarray) -> np.ndarray:
+        if self.scale:
+            sc = MinMaxScaler().fit(X)
+            check_finite_bounds(sc.min_, sc.max_)
+            return sc.transform(X)
+        if not np.all(np.isfinite(X)):
+            raise ValueError("X holds NaN or infinite values")
+        return X
+
+    def _fit_probability_cpu(self, X, y, folds) -> None:
+        from ..ops import cpu as C
+
+        t0 = time.perf_counter()
+        dec, fold_ms = self._cv_cpu(self._scaled_cpu(X), y, folds)
+        t1 = time.perf_counter()
+        self._set_platt(C.platt_fit(dec, y), dec, folds)
+        self.timings_.update({"cv_ms": (t1 - t0) * 1e3, "platt_ms": (time.perf_counter() - t1) * 1e3,
+                              "fold_ms": fold_ms})
+
+    def _set_platt(self, pl, dec: np.ndarray, folds: np.ndarray) -> None:
+        self.platt_ = pl
+        self.probA_, self.probB_ = pl.A, pl.B
+        self.cv_decision_ = dec
+        self.cv_folds_ = folds
+
+    def _cv_device(self, X, y, folds, device, final: bool, concurrent_solves: Optional[int] = None):
+        """The fold solves on the GPU, and with ``final`` the model's own solve beside them: the rows go to the
+        device once, and every solve is the decomposition solver on them -- a fold's with its rows' labels masked
+        to 0 (held-out mode: their f - b is their held-out decision value, no prediction pass) -- one per host
+        thread and stream through the one-vs-rest pool.  Returns a dict: the rows and their statistics, "dec"
+        (device, n: the folds' disjoint held-out vectors summed), "final" ((alpha, result, timing) or None),
+        "fold_timings", "cv_ms"."""
+        import torch
+
+        from .. import _native as N
+        from ..ops import device as D
+        from .multiclass import _pool, _thread_stream
+
+        n, d = X.shape
+        k = int(folds.max()) + 1
+        masks_h = np.stack([(folds == j).astype(np.uint8) for j in range(k)], 0)
+
+        def rows_of(Xh):
+            if Xh.dtype == np.uint8:
+                Xu = D.upload_u8(Xh, device)
+                mn, mx = D.minmax_u8(Xu)
+                return Xu, mn, mx, None
+            Xd = D.upload_rows(Xh, device)
+            mn, mx, sqn = D.minmax_scale_(Xd, d)
+            return Xd, mn, mx, sqn
+
+        def attempt(Xh):
+            t0 = time.perf_counter()
+            rows, mn, mx, sqn = rows_of(Xh)
+            mm = torch.cat([mn, mx]).cpu().numpy()
+            mn_h, mx_h = mm[:d].copy(), mm[d:].copy()
+            check_finite_bounds(mn_h, mx_h)
+            yd = torch.from_numpy(y).to(device)
+            masks = torch.from_numpy(masks_h).to(device)
+            alphas = torch.zeros((k + 1, n), dtype=torch.float64, device=device)
+            decs = torch.zeros((k, n), dtype=torch.float64, device=device)
+            torch.cuda.synchronize(device)
+            t1 = time.perf_counter()
+            tasks = ([-1] if final else []) + list(range(k))
+            # side by side while the rows sit in the last-level cache, two at a time beyond it (the one-vs-rest
+            # pool's rule and its column-cache share, models/multiclass.py)
+            big = n * d > (192 << 20)
+            width = max(1, min(concurrent_solves or (2 if big else len(tasks)), len(tasks)))
+            frac = min(0.25, 0.5 / width)
+
+            def solve(j):
+                s = _thread_stream(device)
+                ctx = D.DeviceContext.get(device)
+                N.check(ctx.lib.svmd_set_ccache_frac(ctx.handle, frac), "svmd_set_ccache_frac")
+                with torch.cuda.stream(s):
+                    if j < 0:
+                        out = D.train_decomp(rows, yd, alphas[k], self.params, mn_h, mx_h, working_set=self.working_set)
+                    else:
+                        out = D.train_decomp_heldout(rows, yd, masks[j], alphas[j], decs[j], self.params, mn_h, mx_h,
+                                                     working_set=self.working_set)
+                s.synchronize()
+                return out
+
+            outs = dict(zip(tasks, _pool(width).map(solve, tasks)))
+            torch.cuda.synchronize(device)
+            if any(o is None for o in outs.values()):
+                return None
+            dec = decs.sum(0)  # disjoint and zero elsewhere: exact in any order
+            torch.cuda.synchronize(device)
+            t2 = time.perf_counter()
+            return {"rows": rows, "mn": mn, "mx": mx, "sqn": sqn, "mn_h": mn_h, "mx_h": mx_h, "yd": yd, "dec": dec,
+                    "final": (alphas[k],) + outs[-1] if final else None,
+                    "fold_timings": [outs[j][1] for j in range(k)],
+                    "upload_preprocess_ms": (t1 - t0) * 1e3, "cv_ms": (t2 - t1) * 1e3, "width": width}
+
+        out = attempt(X)
+        if out is None and X.dtype == np.uint8:  # no exact-integer plan for these bytes: the FP64 rows
+            out = attempt(np.ascontiguousarray(X, dtype=np.float64))
+        if out is None:
+            raise ValueError("the decomposition solver does not cover these rows (n beyond its shapes, or the "
+                             "FP64-row solve's workspace does not fit the device); cross-validation on a GPU "
+                             "needs it")
+        return out
+
+    def _fit_cuda_probability(self, X, y, folds, dev) -> None:
+        import torch
+
+        from ..ops import device as D
+
+        device = torch.device(dev)
+        cv = self._cv_device(X, y, folds, device, final=True)
+        alpha, res, tm = cv["final"]
+        t0 = time.perf_counter()
+        pl = D.platt_fit(cv["dec"], cv["yd"])
+        platt_ms = (time.perf_counter() - t0) * 1e3
+        self._finish(alpha.cpu().numpy(), y, res)
+        idx = torch.from_numpy(self.support_).to(device)
+        rows, mn, mx, d = cv["rows"], cv["mn"], cv["mx"], X.shape[1]
+        if rows.dtype == torch.uint8:
+            Xs, ns = D.sv_rows_u8(rows, idx, mn, mx)
+        else:
+            Xs, ns = D.gather_rows(rows, idx), cv["sqn"][idx].contiguous()
+        self._dev = {"Xs": Xs, "ns": ns, "coef": torch.from_numpy(self.dual_coef_).to(device), "mn": mn, "mx": mx,
+                     "d": d, "device": device}
+        self.scaler_ = MinMaxScaler(cv["mn_h"], cv["mx_h"])
+        self._sv_host = None
+        self._set_platt(pl, cv["dec"].cpu().numpy(), folds)
+        self.timings_ = {"upload_preprocess_ms": cv["upload_preprocess_ms"], **tm, "cv_ms": cv["cv_ms"],
+                         "platt_ms": platt_ms, "fold_ms": [t["total_ms"] for t in cv["fold_timings"]],
+                         "concurrent_solves": cv["width"]}
+
+    def cross_val_decision(self, X: np.ndarray, y: np.ndarray, cv: int = 5, seed: int = 0,
+                           folds: Optional[np.ndarray] = None, concurrent_solves: Optional[int] = None) -> np.ndarray:
+        """The n held-out decision values of k-fold cross-validation with this estimator's options: row i's value
+        comes from the model fitted without row i's fold.  folds: an explicit fold id per row instead of
+        ``stratified_folds(y, cv, seed)``.  Min-max scaling is that of all rows, and class_weight="balanced"
+        resolves on all labels.  Fits no sigmoid and leaves the estimator's own model alone.  On a GPU the folds
+        run ``concurrent_solves`` at a time (default: all of them while the rows fit the last-level cache)."""
+        dev = _resolve_device(self.device)
+        X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if X.ndim != 2 or y.shape != (X.shape[0],):
+            raise ValueError("X must be (n, d) and y (n,)")
+        if not np.all(np.abs(y) == 1):
+            raise ValueError("labels must be +1/-1 (use svm355.utils.data.one_vs_rest)")
+        wp, wn = resolve_class_weight(self.class_weight, y)
+        self.params = self.params.replace(weight_pos=wp, weight_neg=wn)
+        if self.params.weighted:
+            self._check_weighted(dev)
+        self._check_cv(dev)
+        folds = self._folds(y, cv, seed, folds)
+        if dev == "cpu":
+            return self._cv_cpu(self._scaled_cpu(X), y, folds)[0]
+        import torch
+
+        out = self._cv_device(X, y, folds, torch.device(dev), final=False, concurrent_solves=concurrent_solves)
+        self.cv_timings_ = {"cv_ms": out["cv_ms"], "fold_ms": [t["total_ms"] for t in out["fold_timings"]],
+                            "concurrent_solves": out["width"]}
+        return out["dec"].cpu().numpy()
+
+    def cross_val_score(self, X: np.ndarray, y: np.ndarray, cv: int = 5, seed: int = 0,
+                        folds: Optional[np.ndarray] = None) -> float:
+        """The held-out accuracy of k-fold cross-validation (LIBSVM's -v k): the share of rows whose held-out
+        decision value has their label's sign (``zero_is_positive`` as in predict)."""
+        dec = self.cross_val_decision(X, y, cv, seed, folds)
+        pos = dec >= 0 if self.zero_is_positive else dec > 0
+        return float(np.mean(np.where(pos, 1, -1) == np.asarray(y)))
+
+    def predict_proba(self, X: np.ndarray) -> np.ndarray:
+        """(m, 2) probabilities in the order of classes_ = [-1, 1]: Platt's sigmoid of decision_function(X), in
+        its overflow-safe form, on the host."""
+        if self.probA_ is None:
+            raise ValueError("predict_proba needs a model fitted with probability=True")
+        z = self.probA_ * self.decision_function(X) + self.probB_
+        e = np.exp(-np.abs(z))
+        big, small = 1.0 / (1.0 + e), e / (1.0 + e)
+        return np.stack([np.where(z >= 0, big, small), np.where(z >= 0, small, big)], 1)
 
     def _check_weighted(self, dev: str) -> None:
         """Class weights run on the CPU oracle and on the GPU decomposition solver (no shrinking); everything
@@ -348,8 +598,9 @@ class SVC:
 
         save_model(directory, ids=self.support_ if ids is None else ids, labels=self.support_labels_,
                    alphas=self.alpha_[self.support_], b=self.b_, sv_rows=self.support_vectors_,
-                   scaler=self.scaler_, params=self.params, meta={"n_iter": self.n_iter_,
-                                                                  "stop_reason": self.stop_reason_})
+                   scaler=self.scaler_, params=self.params,
+                   meta={"n_iter": self.n_iter_, "stop_reason": self.stop_reason_,
+                         **({"probA": self.probA_, "probB": self.probB_} if self.probA_ is not None else {})})
 
     @classmethod
     def load(cls, directory: str | os.PathLike, device: str = "cpu") -> "SVC":
@@ -375,6 +626,10 @@ class SVC:
         svc.alpha_ = np.zeros(int(svc.support_.max()) + 1 if len(svc.support_) else 0)
         svc.alpha_[svc.support_] = alphas
         svc.dual_coef_ = alphas * svc.support_labels_
+        svc.classes_ = np.array([-1, 1], dtype=np.int32)
+        if "probA" in m["meta"] and "probB" in m["meta"]:
+            svc.probability = True
+            svc.probA_, svc.probB_ = float(m["meta"]["probA"]), float(m["meta"]["probB"])
         if _resolve_device(device) != "cpu":
             svc._upload_model(_resolve_device(device))
         return svc

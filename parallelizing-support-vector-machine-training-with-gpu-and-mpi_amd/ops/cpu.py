@@ -13,7 +13,7 @@ import numpy as np
 
 from .. import _native as N
 from ..utils.config import SVMParams
-from .device import SMOResult
+from .device import PlattResult, SMOResult
 
 
 def _c64(a) -> np.ndarray:
@@ -204,6 +204,50 @@ def decomp_train_gram_oneclass(K: np.ndarray, params: SVMParams, nu: float = 0.5
                                                     ctypes.byref(tr.struct) if tr is not None else None),
             "svm_decomp_train_gram_oneclass")
     return a, SMOResult.from_struct(r), {**_decomp_stats(st), "start_columns": int(st[7])}, tr
+
+
+def decomp_train_gram_heldout(K: np.ndarray, y: np.ndarray, heldout: np.ndarray, params: SVMParams, q: int = 1024,
+                              tau_frac: float = 0.1, inner_wss: int = 3, trace_cap: int = 0,
+                              snapshots: bool = False, fp64_rows: bool = False):
+    """The decomposition oracle's held-out mode (svm_decomp_train_gram_heldout) on the n x n kernel matrix K:
+    the points with ``heldout[i]`` true run with label 0, which no selection takes, so their alpha stays exactly
+    0 while their f collects every update.  Returns (alpha; SMOResult; stats dict; the final f of all n points;
+    N.DecompTrace or None): ``f[heldout] - result.b`` are the held-out decision values."""
+    K = _c64(K)
+    y = _c32(y)
+    n = y.shape[0]
+    _gram_shape(K, n)
+    m = np.ascontiguousarray(np.asarray(heldout).astype(bool), dtype=np.uint8)
+    if m.shape != (n,):
+        raise ValueError(f"heldout must have shape ({n},), got {m.shape}")
+    a = np.zeros(n)
+    f = np.zeros(n)
+    r = N.SvmResult()
+    st = (ctypes.c_int64 * 16)()
+    tr = N.DecompTrace(trace_cap, n if snapshots else 0) if trace_cap > 0 else None
+    p = params.to_struct()
+    N.check(N.core().svm_decomp_train_gram_heldout(N.ptr(K), K.shape[1], N.ptr(y), N.ptr(m), n, N.ptr(a),
+                                                   ctypes.byref(p), int(q), float(tau_frac), int(inner_wss),
+                                                   int(bool(fp64_rows)), ctypes.byref(r), st, N.ptr(f),
+                                                   ctypes.byref(tr.struct) if tr is not None else None),
+            "svm_decomp_train_gram_heldout")
+    return a, SMOResult.from_struct(r), _decomp_stats(st), f, tr
+
+
+def platt_fit(dec: np.ndarray, y: np.ndarray, use: Optional[np.ndarray] = None) -> PlattResult:
+    """Platt scaling on the host (svm_platt_fit): P(y = +1 | f) = 1 / (1 + exp(A f + B)) fitted to the pairs
+    (dec_i, y_i) by Lin, Lin and Weng's Newton method, as LIBSVM's -b 1.  use: optional boolean mask of the pairs
+    that count."""
+    dec = _c64(dec)
+    y = _c32(y)
+    if dec.ndim != 1 or y.shape != dec.shape:
+        raise ValueError("dec and y must be 1-D arrays of one length")
+    u = None if use is None else np.ascontiguousarray(np.asarray(use).astype(bool), dtype=np.uint8)
+    if u is not None and u.shape != dec.shape:
+        raise ValueError("use must have the shape of dec")
+    o = N.SvmPlatt()
+    N.check(N.core().svm_platt_fit(N.ptr(dec), N.ptr(y), N.ptr(u), dec.shape[0], ctypes.byref(o)), "svm_platt_fit")
+    return PlattResult.from_struct(o)
 
 
 def _decomp_stats(st) -> dict:

@@ -40,6 +40,18 @@ class SMOResult:
                    N.STOP_NAMES.get(int(r.stop_reason), str(r.stop_reason)), int(r.n_sv), float(r.seconds))
 
 
+@dataclass
+class PlattResult:
+    A: float
+    B: float
+    iterations: int
+    status: str  # "converged", "max_iter", "line_search_failed" or "degenerate" (svm355.h)
+
+    @classmethod
+    def from_struct(cls, o: N.SvmPlatt) -> "PlattResult":
+        return cls(float(o.A), float(o.B), int(o.iterations), N.PLATT_STATUS.get(int(o.status), str(o.status)))
+
+
 class DeviceContext:
     """One native device context (private HIP stream + workspace) per GPU per host thread
     (thread-ranks sharing a GPU must not share a workspace).  Contexts live in thread-local storage:
@@ -542,6 +554,61 @@ def train_decomp_oneclass(X: torch.Tensor, alpha: torch.Tensor, params: SVMParam
                                       "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
                                       "working_set": int(st[2]), "update_columns": int(st[4]),
                                       "inner_threads": int(st[5]), "start_columns": int(st[7])}
+
+
+def train_decomp_heldout(X: torch.Tensor, y: torch.Tensor, heldout: torch.Tensor, alpha: torch.Tensor,
+                         dec: torch.Tensor, params: SVMParams, mn, mx, working_set: int = 1024,
+                         trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:
+    """The decomposition solver's held-out mode (svmd_train_decomp_heldout): the ordinary cold-start solve on the
+    rows of X (as ``train_decomp``) with the points of ``heldout`` (device uint8 (n,), 1 = held out) taken out of
+    the fit: they run with label 0, which no selection takes, so their alpha stays exactly 0 while their f
+    collects every update.  alpha (n float64, out); dec (n float64, out): f - b on the held-out points -- their
+    decision values under a model that never saw them, from the training's own kernel values -- and 0.0 on the
+    others.  Class weights are allowed; shrinking and the Newton polish raise.  The training part must hold both
+    classes (check it on the host).  None when nothing ran, as ``train_decomp``."""
+    u8 = X.dtype == torch.uint8
+    if not u8:
+        _check_rows(X)
+    n, ld = X.shape
+    for name, t, dt in (("y", y, torch.int32), ("heldout", heldout, torch.uint8), ("alpha", alpha, torch.float64),
+                        ("dec", dec, torch.float64)):
+        if t.dtype != dt or t.shape != (n,) or not t.is_contiguous() or t.device != X.device:
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({n},) on the rows' device")
+    ctx = _ctx_for(X)
+    a, b, dd = _host_stats(mn, mx)
+    d = ld if u8 else dd
+    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
+    st = (ctypes.c_int64 * 16)()
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_train_decomp_heldout(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), N.ptr(y),
+                                              N.ptr(heldout), N.ptr(alpha), N.ptr(dec), ctypes.byref(p),
+                                              int(working_set), ctypes.byref(r), ctypes.byref(tm), st,
+                                              ctypes.byref(used),
+                                              ctypes.byref(trace.struct) if trace is not None else None),
+            "svmd_train_decomp_heldout")
+    if not used.value:
+        return None
+    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
+                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
+                                      "rows": "uint8" if u8 else "fp64", "solver": "decomp-heldout",
+                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
+                                      "working_set": int(st[2]), "update_columns": int(st[4]),
+                                      "inner_threads": int(st[5])}
+
+
+def platt_fit(dec: torch.Tensor, y: torch.Tensor, use: Optional[torch.Tensor] = None) -> PlattResult:
+    """Platt scaling on the device (svmd_platt_fit, platt.hip): P(y = +1 | f) = 1 / (1 + exp(A f + B)) fitted to
+    the pairs (dec_i, y_i) by Lin, Lin and Weng's Newton method (LIBSVM's -b 1) in one launch of one workgroup,
+    with deterministic sums.  dec (n float64), y (n int32 labels), use: optional (n uint8), nonzero = the pair
+    counts.  Synchronises (the result is four numbers on the host)."""
+    n = dec.shape[0]
+    for name, t, dt in (("dec", dec, torch.float64), ("y", y, torch.int32), ("use", use, torch.uint8)):
+        if t is not None and (t.dtype != dt or t.shape != (n,) or not t.is_contiguous() or t.device != dec.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({n},) on one device")
+    ctx = _ctx_for(dec)
+    o = N.SvmPlatt()
+    N.check(ctx.lib.svmd_platt_fit(ctx.bind(), N.ptr(dec), N.ptr(y), N.ptr(use), n, ctypes.byref(o)), "svmd_platt_fit")
+    return PlattResult.from_struct(o)
 
 
 def decomp_twin_step_u8(Xu: torch.Tensor, mn, mx, gamma: float, cols: np.ndarray, coef: np.ndarray,

@@ -142,6 +142,50 @@ def pixel_rows(X, what: str) -> np.ndarray:
     return np.ascontiguousarray(Xc)
 
 
+def stratified_folds(y, k: int, seed: int = 0) -> np.ndarray:
+    """Fold ids in [0, k) for k-fold cross-validation, stratified per class: each class's rows are permuted by
+    one seeded ``numpy.random.Generator`` (the classes in ascending label order) and dealt round-robin, class
+    after class without restarting the deal, so every class's fold sizes differ by at most 1 and so do the folds'.
+    Deterministic for (y, k, seed); host only."""
+    y = np.asarray(y)
+    k = int(k)
+    if y.ndim != 1:
+        raise ValueError("y must be 1-D")
+    if k < 2:
+        raise ValueError(f"cross-validation needs k >= 2 folds, got {k}")
+    if k > y.shape[0]:
+        raise ValueError(f"{k} folds for {y.shape[0]} rows")
+    rng = np.random.default_rng(int(seed))
+    folds = np.empty(y.shape[0], dtype=np.int32)
+    dealt = 0
+    for c in np.unique(y):
+        idx = np.flatnonzero(y == c)
+        idx = idx[rng.permutation(idx.size)]
+        folds[idx] = (dealt + np.arange(idx.size)) % k
+        dealt += idx.size
+    return folds
+
+
+def check_folds(folds, y: np.ndarray) -> np.ndarray:
+    """A fold array for y as int32 (n,): ids 0 .. k - 1 with k >= 2, every id used, and both classes present in
+    every fold's training part (all rows outside the fold).  ValueError otherwise."""
+    f = np.ascontiguousarray(folds)
+    n = y.shape[0]
+    if f.shape != (n,) or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"folds must be an integer array of shape ({n},)")
+    k = int(f.max()) + 1 if n else 0
+    if k < 2 or f.min() < 0:
+        raise ValueError(f"cross-validation needs fold ids 0 .. k - 1 with k >= 2, got ids {int(f.min())} .. {k - 1}")
+    for j in range(k):
+        out = f == j
+        if not out.any():
+            raise ValueError(f"fold {j} of {k} is empty")
+        tr = y[~out]
+        if not (np.any(tr == 1) and np.any(tr == -1)):
+            raise ValueError(f"fold {j}: its training part (the rows outside it) lacks a class")
+    return f.astype(np.int32, copy=False)
+
+
 def one_vs_rest(labels: np.ndarray, positive_label: int = 1) -> np.ndarray:
     """label == positive_label -> +1, else -1 (main3.cpp:49-52 with positive_label = 1)."""
     return np.where(np.asarray(labels) == positive_label, 1, -1).astype(np.int32)
