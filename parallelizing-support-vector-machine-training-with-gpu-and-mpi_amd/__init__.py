@@ -20,6 +20,9 @@ re-designed for gfx950:
 * ``svm355.OneVsRestSVC``            all classes one-vs-rest: the decomposition solver per class on the
                                      shared device rows (default), or one resident Gram with every
                                      pairwise class solve in one launch (``solver="batched"``)
+* ``svm355.OneVsOneSVC``             all class pairs one-vs-one (LIBSVM's and scikit-learn's multi-class scheme, their
+                                     ``dual_coef_`` / ``n_support_`` layout): the decomposition solver per pair on
+                                     the pair's gathered rows, prediction by a segmented vote kernel
 * ``svm355.CascadeSVM``              classical tree and modified two-layer star Cascade SVM: one native
                                      driver over RCCL (a thread per GPU, or one rank per process under
                                      torchrun), over gloo (host-staged process ranks), or the loopback
@@ -45,12 +48,13 @@ _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 from .utils.config import SVMParams  # noqa: E402
 from .utils.data import Dataset, MinMaxScaler, load_csv, one_vs_rest, synthetic_mnist, write_csv
 from .models.multiclass import OneVsRestSVC
+from .models.ovo import OneVsOneSVC
 from .models.svc import SVC
 from .models.svr import SVR
 from .models.oneclass import OneClassSVM
 
 __all__ = ["SVMParams", "Dataset", "MinMaxScaler", "load_csv", "one_vs_rest", "synthetic_mnist", "write_csv",
-           "SVC", "SVR", "OneClassSVM", "OneVsRestSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
+           "SVC", "SVR", "OneClassSVM", "OneVsRestSVC", "OneVsOneSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
 __version__ = "0.1.0"
 
 

@@ -21,6 +21,7 @@ scale    the rank-count sweep of code/mpi_svm2.sh / mpi_svm3.sh (``mpirun -np P`
 
 multiclass  all-digit one-vs-rest (models/multiclass.py): one shared Gram per GPU, class solves
          concurrent on streams; ``--gpus P`` deals the classes over P ranks (torchrun, RCCL).
+         ``--scheme ovo``: one-vs-one (models/ovo.py), a decomposition solve per pair of classes on one GPU.
 
 The native CLIs take the options listed in ``csrc/apps/cli_common.h`` (``--dataset``,
 ``--synthetic N[,M]``, ``--C``, ``--gamma``, ``--tau``, ``--model-dir``, ``--json`` ...).
@@ -397,11 +398,20 @@ def _multiclass(argv) -> int:
     ap.add_argument("--solver", choices=["auto", "batched", "streams", "decomp"], default="auto",
                     help="GPU class solves: one batched pairwise launch over a shared Gram (auto), or the "
                          "decomposition solver per class with no Gram (decomp)")
+    ap.add_argument("--scheme", choices=["ovr", "ovo"], default="ovr",
+                    help="one-vs-rest (a solve per class) or one-vs-one (a solve per pair of classes, LIBSVM's and "
+                         "scikit-learn's scheme; one GPU or --cpu)")
     ap.add_argument("--gpus", type=int, default=0, help="launch torchrun with this many ranks (classes dealt over them)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--model-dir", default=None, help="save the model (one directory of reference model files per class)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args(argv)
+    if a.scheme == "ovo":
+        if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("--scheme ovo runs on one GPU (or --cpu): --gpus > 1 is not supported")
+        if a.solver not in ("auto", "decomp"):
+            raise ValueError(f"--scheme ovo solves every pair with the decomposition solver, not --solver {a.solver}")
+        return _multiclass_ovo(a)
     if "RANK" not in os.environ and a.gpus > 1:
         return _launch_self("multiclass", argv, a.gpus)
 
@@ -459,6 +469,47 @@ def _multiclass(argv) -> int:
                 "training_ms": (t1 - t0) * 1e3, "prediction_ms": (t2 - t1) * 1e3}) + "\n")
     if world > 1:
         dist.destroy_process_group()
+    return 0
+
+
+def _multiclass_ovo(a) -> int:
+    """``multiclass --scheme ovo``: one-vs-one over all pairs of classes (models/ovo.py)."""
+    import torch
+
+    from .models.ovo import OneVsOneSVC
+    from .utils.data import load_csv, synthetic_mnist
+
+    use_gpu = not a.cpu and torch.cuda.is_available()
+    dev = f"cuda:{torch.cuda.current_device()}" if use_gpu else "cpu"
+    if a.synthetic:
+        parts = a.synthetic.split(",")
+        n, m = int(parts[0]), int(parts[1]) if len(parts) > 1 else 10000
+        tr, te = synthetic_mnist(n, seed=a.seed), synthetic_mnist(m, seed=a.seed, offset=n)
+    else:
+        tr = load_csv(a.train or f"{a.dataset}_train_data.csv")
+        te = load_csv(a.test or f"{a.dataset}_test_data.csv")
+    model = OneVsOneSVC(C=a.C, gamma=a.gamma, tol=a.tau, device=dev)
+    t0 = time.perf_counter()
+    model.fit(tr.X, tr.labels)
+    if use_gpu:
+        torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    acc = model.score(te.X, te.labels) if te.n else None
+    t2 = time.perf_counter()
+    print(f"[rank 0] one-vs-one over {len(model.classes_)} classes ({len(model.rho_)} pairs) on 1 rank(s), n = {tr.n}")
+    print(f"[rank 0] union SV count = {len(model.support_)}, support vectors per class = {model.n_support_.tolist()}")
+    print(f"[rank 0] Test accuracy = {acc}")
+    print(f"[rank 0] training time = {int((t1 - t0) * 1e3)} ms, prediction time = {int((t2 - t1) * 1e3)} ms")
+    if a.model_dir:
+        model.save(a.model_dir)
+    if a.json:
+        Path(a.json).write_text(json.dumps({
+            "program": "svm355 multiclass", "scheme": "ovo", "world": 1, "n": tr.n, "classes": model.classes_.tolist(),
+            "pairs": [[int(model.classes_[x]), int(model.classes_[y])] for x, y in model._pairs],
+            "n_sv_union": int(len(model.support_)), "n_support": model.n_support_.tolist(),
+            "n_iter": model.n_iter_.tolist(), "rho": model.rho_.tolist(), "stop_reasons": model.stop_reasons_,
+            "accuracy": acc, "solver": model.timings_["solver"], "training_ms": (t1 - t0) * 1e3,
+            "prediction_ms": (t2 - t1) * 1e3}) + "\n")
     return 0
 
 

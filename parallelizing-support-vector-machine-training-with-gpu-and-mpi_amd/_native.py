@@ -294,6 +294,9 @@ _HIP_SIGS = {
     "svmd_decision_int": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, _P, _P, _P, c_int64, c_double, _P,
                                     POINTER(c_int32)]),
     "svmd_gather_rows": (c_int32, [c_void_p, _P, c_int64, _P, c_int64, _P]),
+    "svmd_ovo_votes": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P]),
+    "svmd_ovo_predict": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, c_double,
+                                   c_int64, _P, _P, c_int64, _P, c_int64, _P, _P]),
     "svmd_train_u8": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, _P, _P, c_int32, POINTER(SvmParams),
                                 POINTER(SvmResult), _P, c_int64, POINTER(SvmdTiming), POINTER(c_int32)]),
     "svmd_train_decomp_u8": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, _P, _P, POINTER(SvmParams), c_int32,

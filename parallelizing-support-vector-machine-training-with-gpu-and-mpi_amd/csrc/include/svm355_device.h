@@ -209,6 +209,25 @@ SVM_API int svmd_decision_int(void* ctx, const double* X_d, int64_t k, int64_t l
 SVM_API int svmd_count_correct(void* ctx, const double* dec_d, const int32_t* y_d, int64_t m,
                                int32_t zero_positive, int64_t* correct);
 
+// One-vs-one multi-class prediction (csrc/hip/ovo.hip).  The nsv support vectors lie grouped by class, class c
+// in [start_d[c], start_d[c + 1]) (int32[k + 1], 2 <= k <= 64); coef_d is LIBSVM's (k - 1) x ldc coefficient
+// matrix (for a support vector of class c, row j is its alpha * y in the pair (c, o), o = j for j < c, else
+// j + 1); rho_d the P = k (k - 1) / 2 pair offsets in the order (0,1), (0,2), ..., (k-2,k-1).  For the m rows of
+// the cross-kernel block K_d (m x ldk, K[i][s] = K(x_i, sv_s)):
+//   dec_d[i][p] = sum_{s in a} coef[b-1][s] K[i][s] + sum_{s in b} coef[a][s] K[i][s] - rho[p],  p = (a, b), a < b
+// (m x P; may be NULL) and label_d[i] (int32) the class INDEX with the most votes, dec > 0 voting for a and
+// anything else for b, ties to the lowest index.  Fixed summation order: the same bits on every run.
+SVM_API int svmd_ovo_votes(void* ctx, const double* K_d, int64_t ldk, int64_t m, int64_t nsv, int64_t k,
+                           const int32_t* start_d, const double* coef_d, int64_t ldc, const double* rho_d,
+                           double* dec_d, int32_t* label_d);
+// The same from rows: K(Xq, Xs) in row chunks of at most 512 MB (as svmd_decision), svmd_ovo_votes' kernel on
+// every chunk.  max_rows > 0 caps a chunk at max_rows rounded up to 128 rows (0: the 512 MB rule alone).
+// nsv = 0: dec = -rho and the votes that follow from it.
+SVM_API int svmd_ovo_predict(void* ctx, const double* Xs_d, const double* ns_d, int64_t nsv, int64_t lds,
+                             const double* Xq_d, const double* nq_d, int64_t m, int64_t ldq, int64_t kdim,
+                             double gamma, int64_t k, const int32_t* start_d, const double* coef_d, int64_t ldc,
+                             const double* rho_d, int64_t max_rows, double* dec_d, int32_t* label_d);
+
 // dst[k] = src[idx[k]] rows (device gather), for SV compaction and cascade training-set assembly.
 SVM_API int svmd_gather_rows(void* ctx, const double* src_d, int64_t ld, const int64_t* idx_d,
                              int64_t k, double* dst_d);

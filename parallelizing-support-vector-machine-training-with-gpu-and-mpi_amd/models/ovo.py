@@ -1,0 +1,357 @@
+"""Multi-class RBF SVM, one-vs-one: what LIBSVM and ``sklearn.svm.SVC`` train for more than two labels.
+
+For k classes there are P = k (k - 1) / 2 pairs (a, b), a < b, in LIBSVM's order (0,1), (0,2), ..., (k-2,k-1);
+class a is the pair's +1 side.  A pair is an ordinary two-class fit on the rows of its two classes, 2n/k rows
+in place of n: all pairs together do (k - 1) n rows of kernel work against k n for one-vs-rest.  A decision
+value > 0 votes for a, anything else (exactly 0 included) for b; the label is the class with the most votes,
+the lowest class index on a tie.
+
+One min/max over ALL training rows scales every pair (each solve is passed that ``mn`` / ``mx``), so the union
+of support vectors has one scaling and a query row is scaled once.
+
+On the GPU the rows are uploaded once and gathered once into a class-grouped copy (a stable sort by class
+index: ids ascend within a class); a pair's rows are two contiguous slices of it packed into one small buffer,
+and every pair is ``ops.device.train_decomp`` -- the decomposition solver, unchanged -- on its packed rows, the
+pairs side by side on the persistent pool of ``OneVsRestSVC(solver="decomp")``.  (The rows are gathered, not
+masked: a label of 0 on the shared rows would make every pair's f update run over all n rows, k/2 times the
+kernel work, and produce decision values nobody wants.)  Prediction is one cross-kernel block against the
+union of support vectors and the segmented vote kernel (csrc/hip/ovo.hip).
+
+On the CPU (``device="cpu"``) a pair is the pairwise oracle ``ops.cpu.smo_train_gram`` on its block of one
+``rbf_matrix`` over the scaled rows.  A pair's decision is the oracle's own (``svm_decision``: from -rho over the
+pair's support vectors in ascending training-row order), so for k = 2 model and decisions are
+``SVC(device="cpu")``'s bit for bit; the vote is ``ops.cpu.ovo_labels``, the rule of ``ops.cpu.ovo_votes`` (numpy,
+the vote kernel's host twin, which sums class segment by class segment as the kernel does).
+
+The fitted attributes are in scikit-learn's / LIBSVM's layout, so a model can be compared with
+``sklearn.svm.SVC(decision_function_shape="ovo")``: ``support_`` (grouped by class, ascending within a class),
+``n_support_``, ``dual_coef_`` ((k - 1, S): for a support vector of class c, row j holds its alpha * y in the
+pair (c, o), o = j for j < c, else j + 1), ``rho_`` and ``intercept_ = -rho_``.
+"""
+from __future__ import annotations
+
+import time
+from typing import List, Optional
+
+import numpy as np
+
+from ..utils.config import SVMParams, default_threads
+from ..utils.data import MinMaxScaler, check_finite_bounds
+from ..utils.trace import trace_range
+
+MAX_CLASSES = 64  # the vote kernel keeps the k (k - 1) segment sums of a query row in LDS (32 KB at 64)
+FORMAT = "svm355-ovo-v1"
+
+_UNSUPPORTED = {
+    "class_weight": "class weights", "probability": "pairwise-coupling probabilities", "alpha0": "warm starts",
+    "warm_start": "warm starts", "shrinking": "shrinking", "newton": "the Newton polish", "polish": "the Newton polish",
+    "transport": "multi-GPU transports", "solver": "a solver other than the decomposition ('decomp')",
+}
+
+
+def _refuse(name: str, value) -> None:
+    if value is None or value is False:
+        return
+    if name == "solver" and value in ("auto", "decomp"):
+        return
+    what = _UNSUPPORTED.get(name)
+    if what is None:
+        raise TypeError(f"OneVsOneSVC got an unexpected argument {name!r}")
+    raise ValueError(f"OneVsOneSVC does not support {what} ({name}={value!r}): every pair is the plain cold-start "
+                     "decomposition solve on one GPU (or the pairwise oracle on the CPU)")
+
+
+class OneVsOneSVC:
+    def __init__(self, C: float = 10.0, gamma: float = 0.00125, tol: float = 1e-5, eps: float = 1e-12,
+                 sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
+                 concurrent_solves: Optional[int] = None, working_set: int = 1024, **unsupported):
+        """``concurrent_solves`` (GPU): how many pair solves run side by side (default: all, at most 10).
+        ``working_set``: the decomposition solver's working-set size.  Class weights, probabilities, warm starts,
+        shrinking, the Newton polish, ``solver="smo"`` and transports are refused with a ``ValueError``."""
+        for name, value in unsupported.items():
+            _refuse(name, value)
+        if concurrent_solves is not None and int(concurrent_solves) < 1:
+            raise ValueError("concurrent_solves must be at least 1")
+        self.params = SVMParams(C=C, gamma=gamma, tau=tol, eps=eps, sv_tol=sv_tol, max_iter=max_iter,
+                                n_threads=n_threads if n_threads > 0 else default_threads())
+        self.device = device
+        self.concurrent_solves = concurrent_solves
+        self.working_set = int(working_set)
+        self._dev_model = None
+
+    def _dev(self) -> str:
+        if self.device == "auto":
+            import torch
+
+            return "cuda" if torch.cuda.is_available() else "cpu"
+        return self.device
+
+    # ------------------------------------------------------------------ fit
+    def fit(self, X: np.ndarray, labels: np.ndarray, classes: Optional[List[int]] = None,
+            transport=None) -> "OneVsOneSVC":
+        _refuse("transport", transport)
+        cuda = self._dev() != "cpu"
+        X = np.ascontiguousarray(X, dtype=np.uint8 if (cuda and X.dtype == np.uint8) else np.float64)
+        labels = np.asarray(labels)
+        if X.ndim != 2 or labels.shape != (X.shape[0],):
+            raise ValueError("X must be (n, d) and labels (n,)")
+        self.classes_ = np.array(sorted(set(labels.tolist()) if classes is None else set(classes)))
+        k = len(self.classes_)
+        if k < 2:
+            raise ValueError(f"one-vs-one needs at least 2 classes, got {k}")
+        if k > MAX_CLASSES:
+            raise ValueError(f"{k} classes: one-vs-one supports at most {MAX_CLASSES} classes")
+        cls = np.searchsorted(self.classes_, labels)
+        if np.any(self.classes_[np.minimum(cls, k - 1)] != labels):
+            raise ValueError("labels holds a value that `classes` does not list")
+        counts = np.bincount(cls, minlength=k)
+        if np.any(counts == 0):
+            empty = [int(c) for c in self.classes_[counts == 0]]
+            raise ValueError(f"classes {empty} have no rows: every one-vs-one pair needs rows of both classes")
+        from ..ops.cpu import ovo_pairs
+
+        self._pairs = ovo_pairs(k)
+        order = np.argsort(cls, kind="stable").astype(np.int64)  # class-grouped, ids ascending within a class
+        cstart = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        t0 = time.perf_counter()
+        if cuda:
+            self._fit_cuda(X, order, cstart)
+        else:
+            self._fit_cpu(X, order, cstart)
+        self.fit_time_ = time.perf_counter() - t0
+        return self
+
+    def _pair_label(self, p: int):
+        a, b = self._pairs[p]
+        return int(self.classes_[a]), int(self.classes_[b])
+
+    def _fit_cpu(self, X, order, cstart):
+        from ..ops import cpu as C
+
+        self.scaler_ = MinMaxScaler().fit(X)
+        check_finite_bounds(self.scaler_.min_, self.scaler_.max_)
+        Xg = self.scaler_.transform(X)[order]  # scaled, class-grouped
+        K = C.rbf_matrix(Xg, Xg, self.params.gamma, self.params.n_threads)
+        alphas, results, timings = [], [], {}
+        for p, (a, b) in enumerate(self._pairs):
+            idx = np.concatenate([np.arange(cstart[a], cstart[a + 1]), np.arange(cstart[b], cstart[b + 1])])
+            y = np.where(np.arange(len(idx)) < cstart[a + 1] - cstart[a], 1, -1).astype(np.int32)
+            al, r, _ = C.smo_train_gram(np.ascontiguousarray(K[np.ix_(idx, idx)]), y, self.params)
+            alphas.append(al)
+            results.append(r)
+            timings[self._pair_label(p)] = {"smo_ms": r.seconds * 1e3, "gram_path": "host"}
+        keep = self._finish(alphas, results, order, cstart)
+        self.support_vectors_ = np.ascontiguousarray(Xg[keep])
+        self.pair_timings_ = timings
+        self.timings_ = {"gram_path": "host", "solver": "smo (cpu oracle)", "pairs": len(self._pairs)}
+        self._dev_model = None
+
+    def _fit_cuda(self, X, order, cstart):
+        import torch
+
+        from .. import _native as N
+        from ..ops import device as D
+        from .multiclass import _pool, _thread_stream
+
+        device = torch.device(self._dev())
+        t0 = time.perf_counter()
+        d = X.shape[1]
+        order_d = torch.from_numpy(order).to(device)
+        Xu = Xd = sqn = None
+        if X.dtype == np.uint8:
+            Xu = D.upload_u8(X, device)
+            mn, mx = D.minmax_u8(Xu)
+            grouped = Xu[order_d].contiguous()  # the one row gather
+        else:
+            Xd = D.upload_rows(X, device)
+            mn, mx, sqn = D.minmax_scale_(Xd, d)
+            grouped = D.gather_rows(Xd, order_d)
+        mm = torch.cat([mn, mx]).cpu().numpy()
+        mn_h, mx_h = mm[:d].copy(), mm[d:].copy()
+        check_finite_bounds(mn_h, mx_h)
+        torch.cuda.synchronize(device)
+        t1 = time.perf_counter()
+        P = len(self._pairs)
+        width = max(1, min(int(self.concurrent_solves or 10), P))
+        frac = min(0.25, 0.5 / width)
+
+        def solve(p):
+            a, b = self._pairs[p]
+            s = _thread_stream(device)
+            ctx = D.DeviceContext.get(device)
+            N.check(ctx.lib.svmd_set_ccache_frac(ctx.handle, frac), "svmd_set_ccache_frac")
+            na, nb = int(cstart[a + 1] - cstart[a]), int(cstart[b + 1] - cstart[b])
+            with torch.cuda.stream(s):
+                rows = torch.cat([grouped[cstart[a]:cstart[a + 1]], grouped[cstart[b]:cstart[b + 1]]]).contiguous()
+                y = torch.ones(na + nb, dtype=torch.int32, device=device)
+                y[na:] = -1
+                alpha = torch.zeros(na + nb, dtype=torch.float64, device=device)
+                out = D.train_decomp(rows, y, alpha, self.params, mn_h, mx_h, working_set=self.working_set)
+                al = alpha.cpu().numpy() if out is not None else None
+            s.synchronize()
+            if out is None:
+                raise N.NativeError(f"pair {self._pair_label(p)}: the decomposition solver declined these rows (no "
+                                    "exact-integer plan for uint8 rows, or beyond its shapes); pass the rows as "
+                                    "float64")
+            return al, out[0], out[1]
+
+        with trace_range(f"svm355.ovo.decomp pairs={P}"):
+            outs = list(_pool(width).map(solve, range(P)))
+            torch.cuda.synchronize(device)
+        t2 = time.perf_counter()
+        keep = self._finish([o[0] for o in outs], [o[1] for o in outs], order, cstart)
+        idx = torch.from_numpy(self.support_).to(device)
+        Xs, ns = D.sv_rows_u8(Xu, idx, mn, mx) if Xu is not None else (D.gather_rows(Xd, idx), sqn[idx].contiguous())
+        self.scaler_ = MinMaxScaler(mn_h, mx_h)
+        self._set_dev_model(Xs, ns, mn, mx, d, device)
+        self.pair_timings_ = {self._pair_label(p): outs[p][2] for p in range(P)}
+        paths = sorted({o[2]["gram_path"] for o in outs})
+        self.timings_ = {"upload_preprocess_ms": (t1 - t0) * 1e3, "smo_ms_all_pairs": (t2 - t1) * 1e3,
+                         "gram_path": paths[0] if len(paths) == 1 else "mixed", "solver": "decomp", "pairs": P,
+                         "concurrent_solves": width}
+
+    def _finish(self, alphas, results, order, cstart) -> np.ndarray:
+        """The per-pair alphas (a's rows, then b's) to LIBSVM's layout.  Returns the positions of the support
+        vectors in the class-grouped order."""
+        k = len(self.classes_)
+        per_class = [np.zeros((k - 1, int(cstart[c + 1] - cstart[c]))) for c in range(k)]
+        for (a, b), al in zip(self._pairs, alphas):
+            na = int(cstart[a + 1] - cstart[a])
+            per_class[a][b - 1] = al[:na]     # y = +1
+            per_class[b][a] = -al[na:]        # y = -1
+        masks = [(np.abs(pc) > self.params.sv_tol).any(0) for pc in per_class]
+        keep = np.concatenate([cstart[c] + np.flatnonzero(masks[c]) for c in range(k)]).astype(np.int64)
+        self.support_ = order[keep]
+        self.n_support_ = np.array([int(mk.sum()) for mk in masks], dtype=np.int64)
+        self.dual_coef_ = np.ascontiguousarray(np.concatenate([per_class[c][:, masks[c]] for c in range(k)], axis=1))
+        self.rho_ = np.array([r.b for r in results], dtype=np.float64)
+        self.intercept_ = -self.rho_
+        self.n_iter_ = np.array([r.iterations for r in results])
+        self.stop_reasons_ = [r.stop_reason for r in results]
+        return keep
+
+    def _start(self) -> np.ndarray:
+        return np.concatenate([[0], np.cumsum(self.n_support_)]).astype(np.int32)
+
+    def _set_dev_model(self, Xs, ns, mn, mx, d, device) -> None:
+        import torch
+
+        self._dev_model = {"Xs": Xs, "ns": ns, "mn": mn, "mx": mx, "d": d, "device": device,
+                           "start": torch.from_numpy(self._start()).to(device),
+                           "coef": torch.from_numpy(np.ascontiguousarray(self.dual_coef_)).to(device),
+                           "rho": torch.from_numpy(np.ascontiguousarray(self.rho_)).to(device)}
+
+    # ------------------------------------------------------------------ persistence
+    def _host_sv_rows(self) -> np.ndarray:
+        if self._dev_model is not None:
+            dm = self._dev_model
+            return np.ascontiguousarray(dm["Xs"][:, : dm["d"]].cpu().numpy())
+        return np.ascontiguousarray(self.support_vectors_)
+
+    def save(self, directory) -> None:
+        """``dual_coef.npy``, ``rho.npy``, ``support.npy``, ``n_support.npy``, the support vectors' scaled rows
+        (``sv_rows.npy``), the scaler (``scaler.npz``) and ``ovo.json`` -- pickle-free throughout."""
+        import json
+        from pathlib import Path
+
+        d = Path(directory)
+        d.mkdir(parents=True, exist_ok=True)
+        np.save(d / "sv_rows.npy", self._host_sv_rows(), allow_pickle=False)
+        np.save(d / "dual_coef.npy", np.ascontiguousarray(self.dual_coef_, dtype=np.float64), allow_pickle=False)
+        np.save(d / "rho.npy", np.ascontiguousarray(self.rho_, dtype=np.float64), allow_pickle=False)
+        np.save(d / "support.npy", np.ascontiguousarray(self.support_, dtype=np.int64), allow_pickle=False)
+        np.save(d / "n_support.npy", np.ascontiguousarray(self.n_support_, dtype=np.int64), allow_pickle=False)
+        np.savez(d / "scaler.npz", min=self.scaler_.min_, max=self.scaler_.max_)
+        (d / "ovo.json").write_text(json.dumps({
+            "format": FORMAT, "classes": [int(x) for x in self.classes_], "n_sv_union": int(len(self.support_)),
+            "n_iter": [int(x) for x in self.n_iter_], "stop_reasons": list(self.stop_reasons_),
+            "params": self.params.as_dict()}, indent=2))
+
+    @classmethod
+    def load(cls, directory, device: str = "cpu") -> "OneVsOneSVC":
+        """The model ``save`` wrote; ``device`` "cuda[:k]" keeps the support vectors on that GPU for prediction."""
+        import json
+        from pathlib import Path
+
+        d = Path(directory)
+        info = json.loads((d / "ovo.json").read_text())
+        if info.get("format") != FORMAT:
+            raise ValueError(f"{d / 'ovo.json'}: format {info.get('format')!r}, expected {FORMAT!r}")
+        p = SVMParams(**info["params"])
+        m = cls(C=p.C, gamma=p.gamma, tol=p.tau, eps=p.eps, sv_tol=p.sv_tol, max_iter=p.max_iter, device=device)
+        m.classes_ = np.array(info["classes"])
+        k = len(m.classes_)
+        from ..ops.cpu import ovo_pairs
+
+        m._pairs = ovo_pairs(k)
+        m.dual_coef_ = np.load(d / "dual_coef.npy", allow_pickle=False)
+        m.rho_ = np.load(d / "rho.npy", allow_pickle=False)
+        m.intercept_ = -m.rho_
+        m.support_ = np.load(d / "support.npy", allow_pickle=False)
+        m.n_support_ = np.load(d / "n_support.npy", allow_pickle=False)
+        m.support_vectors_ = np.load(d / "sv_rows.npy", allow_pickle=False)
+        S = len(m.support_)
+        if (m.dual_coef_.shape != (k - 1, S) or m.rho_.shape != (len(m._pairs),) or m.n_support_.shape != (k,)
+                or int(m.n_support_.sum()) != S or m.support_vectors_.shape[0] != S or np.any(m.n_support_ < 0)):
+            raise ValueError(f"{d}: the saved arrays do not fit {k} classes and {S} support vectors")
+        z = np.load(d / "scaler.npz", allow_pickle=False)
+        m.scaler_ = MinMaxScaler(z["min"], z["max"])
+        m.n_iter_ = np.asarray(info.get("n_iter", [0] * len(m._pairs)))
+        m.stop_reasons_ = list(info.get("stop_reasons", [""] * len(m._pairs)))
+        m._dev_model = None
+        if m._dev() != "cpu":
+            import torch
+
+            from ..ops import device as D
+
+            dev = torch.device(m._dev())
+            dd = int(np.size(m.scaler_.min_))
+            Xs = D.upload_rows(m.support_vectors_.reshape(S, dd), dev)
+            mmd = torch.from_numpy(np.concatenate([m.scaler_.min_, m.scaler_.max_]).astype(np.float64)).to(dev)
+            m._set_dev_model(Xs, D.row_norms(Xs, dd), mmd[:dd], mmd[dd:], dd, dev)
+        return m
+
+    # ------------------------------------------------------------------ inference
+    def _decide(self, X: np.ndarray, want_dec: bool):
+        d = int(np.size(self.scaler_.min_))
+        if np.ndim(X) != 2 or np.shape(X)[1] != d:
+            raise ValueError(f"X must be (m, {d}) like the training rows, got shape {np.shape(X)}")
+        X = np.ascontiguousarray(X, dtype=np.uint8 if (self._dev_model is not None and X.dtype == np.uint8)
+                                 else np.float64)
+        if self._dev_model is not None:
+            from ..ops import device as D
+
+            dm = self._dev_model
+            Xq = D.upload_rows(X, dm["device"])
+            _, _, nq = D.minmax_scale_(Xq, dm["d"], dm["mn"], dm["mx"])
+            dec, lab = D.ovo_predict(dm["Xs"], dm["ns"], Xq, nq, self.params.gamma, dm["start"], dm["coef"],
+                                     dm["rho"], want_dec=want_dec)
+            return (dec.cpu().numpy() if want_dec else None), lab.cpu().numpy()
+        from ..ops import cpu as C
+
+        # the CPU oracle's arithmetic, pair by pair: from -rho over the pair's support vectors in ascending
+        # training-row order (svm_decision), so that k = 2 is SVC(device="cpu") bit for bit; the vote is
+        # ovo_votes' rule
+        Xq = self.scaler_.transform(X)
+        sv = self.support_vectors_.reshape(len(self.support_), d)
+        start = self._start()
+        dec = np.empty((Xq.shape[0], len(self._pairs)))
+        for p, (a, b) in enumerate(self._pairs):
+            seg = np.concatenate([np.arange(start[a], start[a + 1]), np.arange(start[b], start[b + 1])])
+            coef = np.concatenate([self.dual_coef_[b - 1, start[a]:start[a + 1]],
+                                   self.dual_coef_[a, start[b]:start[b + 1]]])
+            by_row = np.argsort(self.support_[seg], kind="stable")
+            seg, coef = seg[by_row], coef[by_row]
+            dec[:, p] = C.decision(sv[seg], np.where(np.signbit(coef), -1, 1), np.abs(coef), Xq, self.params.gamma,
+                                   self.rho_[p], self.params.n_threads)
+        return dec, C.ovo_labels(dec, len(self.classes_))
+
+    def decision_function(self, X: np.ndarray) -> np.ndarray:
+        """(m, P) pair decisions in LIBSVM's pair order; > 0 is a vote for the pair's first class."""
+        return self._decide(X, True)[0]
+
+    def predict(self, X: np.ndarray) -> np.ndarray:
+        return self.classes_[self._decide(X, False)[1]]
+
+    def score(self, X: np.ndarray, labels: np.ndarray) -> float:
+        return float(np.mean(self.predict(X) == np.asarray(labels)))

@@ -311,6 +311,56 @@ def decision(Xs: np.ndarray, ys: np.ndarray, alphas: np.ndarray, Xq: np.ndarray,
     return out
 
 
+def ovo_pairs(k: int) -> np.ndarray:
+    """The k (k - 1) / 2 one-vs-one pairs (a, b), a < b, in LIBSVM's order (0,1), (0,2), ..., (k-2,k-1)."""
+    return np.array([(a, b) for a in range(k) for b in range(a + 1, k)], dtype=np.int64).reshape(-1, 2)
+
+
+def ovo_votes(K: np.ndarray, start: np.ndarray, coef: np.ndarray, rho: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """One-vs-one pair decisions and votes on the host, by the rule of the device kernel (csrc/hip/ovo.hip).
+    K (m, >= S): K[i, s] = K(x_i, sv_s) over the class-grouped support vectors; start (k + 1,): class c is
+    [start[c], start[c + 1]); coef (k - 1, >= S): LIBSVM's layout (for a support vector of class c, row j is
+    its alpha * y in the pair (c, o), o = j for j < c, else j + 1); rho (P,).  For the pair p = (a, b):
+    dec[:, p] = (sum over a's segment of coef[b - 1] K) + (sum over b's segment of coef[a] K) - rho[p].
+    dec > 0 votes for a, anything else for b; the label index is the first class with the most votes.
+    Returns (dec (m, P), label index (m,) int32)."""
+    K = np.asarray(K, dtype=np.float64)
+    start = np.asarray(start, dtype=np.int64)
+    coef = np.asarray(coef, dtype=np.float64)
+    rho = np.asarray(rho, dtype=np.float64)
+    k = start.shape[0] - 1
+    pairs = ovo_pairs(k)
+    if k < 2 or rho.shape != (len(pairs),) or coef.ndim != 2 or coef.shape[0] != k - 1 or K.ndim != 2:
+        raise ValueError(f"ovo_votes: k = {k} classes need coef ({k - 1}, S) and rho ({len(pairs)},)")
+    if start[0] != 0 or np.any(np.diff(start) < 0) or start[-1] > min(K.shape[1], coef.shape[1]):
+        raise ValueError("ovo_votes: start must ascend from 0 to at most the columns of K and coef")
+    m = K.shape[0]
+    part = np.zeros((k, k - 1, m))
+    for c in range(k):
+        seg = slice(int(start[c]), int(start[c + 1]))
+        if seg.stop > seg.start:
+            part[c] = coef[:, seg] @ K[:, seg].T
+    dec = np.empty((m, len(pairs)))
+    for p, (a, b) in enumerate(pairs):
+        dec[:, p] = part[a, b - 1] + part[b, a] - rho[p]
+    return dec, ovo_labels(dec, k)
+
+
+def ovo_labels(dec: np.ndarray, k: int) -> np.ndarray:
+    """The one-vs-one vote over (m, P) pair decisions in LIBSVM's pair order: dec > 0 votes for the pair's first
+    class, anything else (exactly 0 included) for its second; the label index (int32) is the first class with the
+    most votes."""
+    dec = np.asarray(dec, dtype=np.float64)
+    pairs = ovo_pairs(k)
+    if dec.ndim != 2 or dec.shape[1] != len(pairs):
+        raise ValueError(f"ovo_labels: {k} classes need (m, {len(pairs)}) decisions, got {dec.shape}")
+    votes = np.zeros((dec.shape[0], k), dtype=np.int64)
+    rows = np.arange(dec.shape[0])
+    for p, (a, b) in enumerate(pairs):
+        votes[rows, np.where(dec[:, p] > 0.0, a, b)] += 1
+    return np.argmax(votes, axis=1).astype(np.int32)
+
+
 def sv_indices(alpha: np.ndarray, tol: float = 1e-8) -> np.ndarray:
     alpha = _c64(alpha)
     out = np.empty(alpha.shape[0], dtype=np.int64)

@@ -769,6 +769,71 @@ def count_correct(dec: torch.Tensor, y, zero_is_positive: bool = False) -> int:
     return int(out.value)
 
 
+def _ovo_args(start: torch.Tensor, coef: torch.Tensor, rho: torch.Tensor, nsv: int, device) -> int:
+    """Check the one-vs-one model tensors (device int32 start (k + 1,), float64 coef (k - 1, >= nsv) and
+    rho (k (k - 1) / 2,)); returns k."""
+    k = start.numel() - 1
+    if k < 2 or k > 64:
+        raise ValueError(f"one-vs-one prediction takes 2 to 64 classes, got {k}")
+    for name, t, dt in (("start", start, torch.int32), ("coef", coef, torch.float64), ("rho", rho, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{name} must be a contiguous {dt} tensor on {device}")
+    if start.dim() != 1 or coef.dim() != 2 or coef.shape[0] != k - 1 or coef.shape[1] < nsv:
+        raise ValueError(f"coef must be ({k - 1}, >= {nsv}) for {k} classes, got {tuple(coef.shape)}")
+    if rho.shape != (k * (k - 1) // 2,):
+        raise ValueError(f"rho must have shape ({k * (k - 1) // 2},), got {tuple(rho.shape)}")
+    return k
+
+
+def ovo_votes(K: torch.Tensor, start: torch.Tensor, coef: torch.Tensor, rho: torch.Tensor, want_dec: bool = True,
+              nsv: Optional[int] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """One-vs-one pair decisions and votes from a cross-kernel block (svmd_ovo_votes, ovo.hip): K (m, ldk)
+    float64 with K[i, s] = K(x_i, sv_s) over the nsv class-grouped support vectors (nsv: default start[-1], read
+    back from the device), start int32 (k + 1,) the class segments, coef (k - 1, ldc) LIBSVM's coefficient
+    layout, rho (P,).  Returns (dec (m, P) or None without ``want_dec``, label index (m,) int32): a decision
+    > 0 votes for the pair's first class, anything else for its second; ties go to the lowest index.  The
+    summation order is fixed (``ops.cpu.ovo_votes`` is the host twin)."""
+    if K.dtype != torch.float64 or K.dim() != 2 or K.stride(1) != 1:
+        raise ValueError("K must be a 2-D float64 tensor with unit column stride")
+    nsv = int(start[-1].item()) if nsv is None else int(nsv)
+    if nsv < 0 or nsv > K.shape[1]:
+        raise ValueError(f"{nsv} support vectors but K has {K.shape[1]} columns")
+    k = _ovo_args(start, coef, rho, nsv, K.device)
+    m, P = K.shape[0], k * (k - 1) // 2
+    dec = torch.empty((m, P), dtype=torch.float64, device=K.device) if want_dec else None
+    label = torch.empty(m, dtype=torch.int32, device=K.device)
+    ctx = _ctx_for(K)
+    N.check(ctx.lib.svmd_ovo_votes(ctx.bind(), N.ptr(K), K.stride(0) if m > 1 else max(K.shape[1], 1), m, nsv, k,
+                                   N.ptr(start), N.ptr(coef), coef.stride(0), N.ptr(rho), N.ptr(dec), N.ptr(label)),
+            "svmd_ovo_votes")
+    return dec, label
+
+
+def ovo_predict(Xs: torch.Tensor, ns: torch.Tensor, Xq: torch.Tensor, nq: torch.Tensor, gamma: float,
+                start: torch.Tensor, coef: torch.Tensor, rho: torch.Tensor, want_dec: bool = True,
+                max_rows: int = 0) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    """One-vs-one prediction from rows (svmd_ovo_predict): the cross-kernel K(Xq, Xs) in row chunks (at most
+    512 MB; ``max_rows`` > 0 caps a chunk at that many rows, rounded up to 128) and ``ovo_votes``' kernel on
+    every chunk.  Xs (nsv, ld): the class-grouped support vectors' scaled rows, ns their squared norms; Xq / nq
+    the scaled query rows.  Returns (dec (m, P) or None, label index (m,) int32)."""
+    _check_rows(Xq, "Xq")
+    nsv = Xs.shape[0]
+    if nsv:
+        _check_rows(Xs, "Xs")
+        if Xs.shape[1] != Xq.shape[1]:
+            raise ValueError("Xs and Xq row lengths differ")
+    k = _ovo_args(start, coef, rho, nsv, Xq.device)
+    m, P = Xq.shape[0], k * (k - 1) // 2
+    dec = torch.empty((m, P), dtype=torch.float64, device=Xq.device) if want_dec else None
+    label = torch.empty(m, dtype=torch.int32, device=Xq.device)
+    ctx = _ctx_for(Xq)
+    N.check(ctx.lib.svmd_ovo_predict(ctx.bind(), N.ptr(Xs) if nsv else None, N.ptr(ns) if nsv else None, nsv,
+                                     Xq.shape[1], N.ptr(Xq), N.ptr(nq), m, Xq.shape[1], Xq.shape[1], float(gamma), k,
+                                     N.ptr(start), N.ptr(coef) if nsv else None, coef.stride(0), N.ptr(rho),
+                                     int(max_rows), N.ptr(dec), N.ptr(label)), "svmd_ovo_predict")
+    return dec, label
+
+
 def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """dst[k] = src[idx[k]] (device row gather, idx int64 on the same device)."""
     _check_rows(src, "src")
