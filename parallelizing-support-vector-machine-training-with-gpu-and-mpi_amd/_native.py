@@ -229,6 +229,7 @@ _CORE_SIGS = {
                                                 c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64), _P,
                                                 POINTER(SvmDecompTrace)]),
     "svm_platt_fit": (c_int32, [_P, _P, _P, c_int64, POINTER(SvmPlatt)]),
+    "svm_ovo_couple": (c_int32, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int64, _P, _P, c_int32]),
     "svm_decomp_twin_fold": (c_int32, [_P, _P, c_int32, c_int64, _P, _P, POINTER(c_int32)]),
     "svm_crash_handler_install": (c_int32, [c_char_p]),
     "svm_decomp_gemv_ref": (c_int32, [_P, c_int64, c_int64, _P, _P, c_int64, _P]),
@@ -318,6 +319,8 @@ _HIP_SIGS = {
                                             POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                             POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
     "svmd_platt_fit": (c_int32, [c_void_p, _P, _P, _P, c_int64, POINTER(SvmPlatt)]),
+    "svmd_platt_fit_batch": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, POINTER(SvmPlatt)]),
+    "svmd_ovo_couple": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, _P, _P, _P, c_int64, _P, _P]),
     "svmd_decomp_twin_step_u8": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, c_double, _P, _P, c_int32, _P,
                                            POINTER(c_int32)]),
     "svmd_decomp_newton_probe": (c_int32, [c_void_p, _P, _P, c_int32, _P, _P, c_double, c_double, c_int32, c_int32,

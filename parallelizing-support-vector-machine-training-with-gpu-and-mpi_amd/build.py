@@ -8,7 +8,8 @@ Targets
   lib/libsvm355_core.so   g++   CPU oracle + data I/O + synthetic data + model files
   lib/libsvm355_hip.so    hipcc CDNA4 kernels (MFMA f64 RBF Gram, fused WSS, SMO step, predict)
                                  and the device-resident SMO driver (hipGraph replay); every csrc/hip/*.hip
-                                 (platt.hip, the one-workgroup sigmoid fit, among them)
+                                 (platt.hip, the one-workgroup sigmoid fit and its batch of P, and
+                                 ovo_proba.hip, the one-wave-per-row pairwise coupling, among them)
   bin/svm_serial          g++   main3.cpp-equivalent CLI
   bin/svm_gpu             hipcc gpu_svm_main3/4-equivalent CLI (--n-limit sweep)
   bin/svm_cascade         hipcc mpi_svm_main2/3-equivalent: one process, a thread per GPU, RCCL

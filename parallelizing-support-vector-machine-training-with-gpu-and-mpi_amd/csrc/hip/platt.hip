@@ -11,6 +11,9 @@
 // order, a wave folds its 64 partials by a fixed butterfly (every lane ends with the same bits), the 16 wave
 // sums go through LDS and every thread adds them in wave order.  So every thread holds the same sums, solves
 // the same 2 x 2 system and takes the same branches, and two runs give the same bits.
+//
+// platt_fit_batch_kernel is the same fit for P segments of concatenated arrays at once, one workgroup each (the
+// one-vs-one pairs' sigmoids: P launches with a host round trip each would cost more than the fits).
 #include <cmath>
 
 #include "ctx.h"
@@ -79,12 +82,13 @@ struct PlattPairs {
   }
 };
 
+// The whole fit of one workgroup: the n pairs at dec / y / use (use may be null) to *out.  lds: 5 kPlattWaves
+// doubles of the workgroup's.  Shared by the one-fit kernel and the batched one, so that a segment of a batch
+// is fitted by the very code -- and to the very bits -- of a fit of its own.
 template <bool RES>
-__global__ __launch_bounds__(kPlattNT) void platt_fit_kernel(const double* __restrict__ dec,
-                                                             const int32_t* __restrict__ y,
-                                                             const uint8_t* __restrict__ use, int64_t n,
-                                                             svm_platt* __restrict__ out) {
-  __shared__ double lds[5 * kPlattWaves];
+__device__ __forceinline__ void platt_fit_body(const double* __restrict__ dec, const int32_t* __restrict__ y,
+                                               const uint8_t* __restrict__ use, int64_t n,
+                                               svm_platt* __restrict__ out, double* lds) {
   PlattPairs<RES> P{dec, y, use, n, {}, {}};
   P.load();
   // the class counts (exact in FP64 below 2^53) and the decisions' range
@@ -174,6 +178,31 @@ __global__ __launch_bounds__(kPlattNT) void platt_fit_kernel(const double* __res
   }
 }
 
+template <bool RES>
+__global__ __launch_bounds__(kPlattNT) void platt_fit_kernel(const double* __restrict__ dec,
+                                                             const int32_t* __restrict__ y,
+                                                             const uint8_t* __restrict__ use, int64_t n,
+                                                             svm_platt* __restrict__ out) {
+  __shared__ double lds[5 * kPlattWaves];
+  platt_fit_body<RES>(dec, y, use, n, out, lds);
+}
+
+// P fits in one launch: workgroup p fits the segment [off[p], off[p + 1]) of the concatenated arrays to out[p],
+// register-resident or streamed by its own length (the rule of svmd_platt_fit).  The choice is uniform over the
+// workgroup, so the body's barriers are met by all of its threads.
+__global__ __launch_bounds__(kPlattNT) void platt_fit_batch_kernel(const double* __restrict__ dec,
+                                                                   const int32_t* __restrict__ y,
+                                                                   const uint8_t* __restrict__ use,
+                                                                   const int64_t* __restrict__ off,
+                                                                   svm_platt* __restrict__ out) {
+  __shared__ double lds[5 * kPlattWaves];
+  const int64_t o = off[blockIdx.x], n = off[blockIdx.x + 1] - o;
+  if (n <= int64_t(kPlattNT) * kPlattRegs)
+    platt_fit_body<true>(dec + o, y + o, use ? use + o : nullptr, n, out + blockIdx.x, lds);
+  else
+    platt_fit_body<false>(dec + o, y + o, use ? use + o : nullptr, n, out + blockIdx.x, lds);
+}
+
 }  // namespace
 }  // namespace svm355
 
@@ -200,6 +229,45 @@ extern "C" SVM_API int svmd_platt_fit(void* h, const double* dec_d, const int32_
     hipLaunchKernelGGL(platt_fit_kernel<false>, dim3(1), dim3(kPlattNT), 0, s, dec_d, y_d, use_d, n, out_d);
   SVMD_LAUNCH_CHECK();
   SVMD_CHECK(hipMemcpyAsync(out, out_d, sizeof(svm_platt), hipMemcpyDeviceToHost, s));
+  SVMD_CHECK(hipStreamSynchronize(s));
+  return ctx->end();
+}
+
+// P sigmoids in one launch (svm355_device.h): segment p of the concatenated dec_d / y_d / use_d is
+// [offsets[p], offsets[p + 1]) (host int64[P + 1], ascending, no empty segment); out[p] (host) is what
+// svmd_platt_fit gives on that segment alone, bit for bit.  One launch of P workgroups, one copy back.
+extern "C" SVM_API int svmd_platt_fit_batch(void* h, const double* dec_d, const int32_t* y_d, const uint8_t* use_d,
+                                            const int64_t* offsets, int64_t P, svm_platt* out) {
+  SVMD_CTX(h);
+  if (!dec_d || !y_d || !offsets || !out || P < 1 || P > INT32_MAX) {
+    set_error("svmd_platt_fit_batch: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  if (offsets[0] < 0) {
+    set_error("svmd_platt_fit_batch: offsets[0] = %lld is negative", (long long)offsets[0]);
+    return SVM_ERR_ARG;
+  }
+  for (int64_t p = 0; p < P; ++p)
+    if (offsets[p + 1] <= offsets[p]) {
+      set_error("svmd_platt_fit_batch: segment %lld is empty or descends (offsets %lld, %lld)", (long long)p,
+                (long long)offsets[p], (long long)offsets[p + 1]);
+      return SVM_ERR_ARG;
+    }
+  int rc = ctx->begin();
+  if (rc) return rc;
+  svm_platt* out_d = nullptr;
+  int64_t* off_d = nullptr;
+  if ((rc = carve_ws(ctx, [&](WsCarver& c) {
+         out_d = c.take<svm_platt>(size_t(P));
+         off_d = c.take<int64_t>(size_t(P) + 1);
+       })))
+    return rc;
+  hipStream_t s = ctx->stream;
+  // offsets is the caller's pageable memory: the copy is complete for the host when the call returns
+  SVMD_CHECK(hipMemcpyAsync(off_d, offsets, size_t(P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(platt_fit_batch_kernel, dim3(unsigned(P)), dim3(kPlattNT), 0, s, dec_d, y_d, use_d, off_d, out_d);
+  SVMD_LAUNCH_CHECK();
+  SVMD_CHECK(hipMemcpyAsync(out, out_d, size_t(P) * sizeof(svm_platt), hipMemcpyDeviceToHost, s));
   SVMD_CHECK(hipStreamSynchronize(s));
   return ctx->end();
 }

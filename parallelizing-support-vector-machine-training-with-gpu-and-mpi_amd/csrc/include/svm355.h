@@ -245,6 +245,16 @@ typedef struct svm_platt {
 // The host fit, every sum in ascending order.  y: labels, > 0 is the positive class; use: optional n bytes,
 // nonzero = the pair counts (null: all of them).
 SVM_API int svm_platt_fit(const double* dec, const int32_t* y, const uint8_t* use, int64_t n, svm_platt* out);
+// Pairwise coupling: class probabilities from the P = k (k - 1) / 2 one-vs-one pair decisions of each of m rows
+// (dec, m x ldd, LIBSVM's pair order (0,1), (0,2), ..., (k-2,k-1); 2 <= k <= 64), Wu, Lin and Weng's second
+// method as in LIBSVM.  For the pair p = (a, b): z = dec A[p] + B[p], r_ab = 1 / (1 + e^z) in its overflow-safe
+// form, clamped to [1e-7, 1 - 1e-7], r_ba = 1 - r_ab; A = B = null: dec holds r_ab (clamped all the same).  p
+// starts at 1 / k and is swept at most max(100, k) times, until every |(Qp)_t - p'Qp| < 0.005 / k
+// (core/ovo_couple.cpp has the order of every sum).  k = 2: [r_01, r_10], no sweep.  proba (m x ldp), label
+// (optional: first index of the largest) and iters (optional: sweeps taken; the cap means not converged).  A row
+// with a NaN decision comes out NaN with iters = the cap.
+SVM_API int svm_ovo_couple(const double* dec, int64_t ldd, int64_t m, int64_t k, const double* A, const double* B,
+                           double* proba, int64_t ldp, int32_t* label, int32_t* iters, int32_t n_threads);
 
 // ---------------------------------------------------------------- evaluation (L4)
 // out[i] = sum_k alphas[k]*ys[k]*K(Xq_i, Xs_k) - b, summed in SV order from -b (main3.cpp:391-402).

@@ -105,6 +105,12 @@ SVM_API int svmd_train_decomp_heldout(void* ctx, const void* X_d, int32_t is_u8,
 // (nonzero = the pair counts); *out (host) holds A, B, the iterations and the status on return.
 SVM_API int svmd_platt_fit(void* ctx, const double* dec_d, const int32_t* y_d, const uint8_t* use_d, int64_t n,
                            svm_platt* out);
+// P fits in one launch of P workgroups and one copy back: segment p of the concatenated dec_d / y_d / use_d is
+// [offsets[p], offsets[p + 1]) (host int64[P + 1], ascending from >= 0, no empty segment) and out[p] (host) is
+// what svmd_platt_fit gives on that segment alone, bit for bit (the same device function fits both).  A
+// degenerate segment reports SVM_PLATT_DEGENERATE in its own out[p] only.
+SVM_API int svmd_platt_fit_batch(void* ctx, const double* dec_d, const int32_t* y_d, const uint8_t* use_d,
+                                 const int64_t* offsets, int64_t P, svm_platt* out);
 // The twin mode's moved-column fold and f update alone (tests): a moved list of m <= 1024 distinct virtual ids
 // (host), f_io = the 2n points' f (host, in and out).
 SVM_API int svmd_decomp_twin_step_u8(void* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, const double* mn_h,
@@ -227,6 +233,13 @@ SVM_API int svmd_ovo_predict(void* ctx, const double* Xs_d, const double* ns_d, 
                              const double* Xq_d, const double* nq_d, int64_t m, int64_t ldq, int64_t kdim,
                              double gamma, int64_t k, const int32_t* start_d, const double* coef_d, int64_t ldc,
                              const double* rho_d, int64_t max_rows, double* dec_d, int32_t* label_d);
+// Pairwise coupling (csrc/hip/ovo_proba.hip; svm355.h's svm_ovo_couple is the host twin and has the method):
+// dec_d (m x ldd, ldd >= P) the pair decisions in the order above, A_d / B_d (P) the pairs' sigmoids -- both
+// null: dec_d already holds the pair probabilities r_ab -- proba_d (m x ldp, ldp >= k) the class probabilities,
+// label_d (optional int32[m]) the first index of the largest, iters_d (optional int32[m]) the sweeps taken
+// (max(100, k): not converged).  One wave per row; bit-identical to the twin once r is given.
+SVM_API int svmd_ovo_couple(void* ctx, const double* dec_d, int64_t ldd, int64_t m, int64_t k, const double* A_d,
+                            const double* B_d, double* proba_d, int64_t ldp, int32_t* label_d, int32_t* iters_d);
 
 // dst[k] = src[idx[k]] rows (device gather), for SV compaction and cascade training-set assembly.
 SVM_API int svmd_gather_rows(void* ctx, const double* src_d, int64_t ld, const int64_t* idx_d,

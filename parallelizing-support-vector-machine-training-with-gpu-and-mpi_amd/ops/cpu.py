@@ -361,6 +361,40 @@ def ovo_labels(dec: np.ndarray, k: int) -> np.ndarray:
     return np.argmax(votes, axis=1).astype(np.int32)
 
 
+def _couple_k(P: int) -> int:
+    """The k of P = k (k - 1) / 2 pair columns (2 .. 64), or ValueError."""
+    k = int(round((1.0 + (1.0 + 8.0 * P) ** 0.5) / 2.0))
+    if k < 2 or k > 64 or k * (k - 1) // 2 != P:
+        raise ValueError(f"ovo_couple: {P} pair columns are not k (k - 1) / 2 for a k in 2 .. 64")
+    return k
+
+
+def ovo_couple(dec: np.ndarray, A: Optional[np.ndarray] = None, B: Optional[np.ndarray] = None,
+               n_threads: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Pairwise coupling on the host (svm_ovo_couple; the twin of the device kernel in csrc/hip/ovo_proba.hip):
+    class probabilities from (m, P) one-vs-one pair decisions in LIBSVM's pair order, Wu, Lin and Weng's second
+    method as LIBSVM runs it.  A, B (P,): the pairs' sigmoids, P(first class | dec) = 1 / (1 + exp(A dec + B));
+    both None: ``dec`` already holds the pair probabilities r_ab.  Returns (proba (m, k), label index (m,) int32:
+    the first largest probability, iters (m,) int32: the sweeps taken -- max(100, k) means not converged)."""
+    dec = _c64(dec)
+    if dec.ndim != 2:
+        raise ValueError("ovo_couple: dec must be (m, P)")
+    m, P = dec.shape
+    k = _couple_k(P)
+    if (A is None) != (B is None):
+        raise ValueError("ovo_couple: A and B come together")
+    if A is not None:
+        A, B = _c64(A), _c64(B)
+        if A.shape != (P,) or B.shape != (P,):
+            raise ValueError(f"ovo_couple: A and B must have shape ({P},)")
+    proba = np.empty((m, k))
+    label = np.empty(m, dtype=np.int32)
+    iters = np.empty(m, dtype=np.int32)
+    N.check(N.core().svm_ovo_couple(N.ptr(dec), P, m, k, N.ptr(A), N.ptr(B), N.ptr(proba), k, N.ptr(label),
+                                    N.ptr(iters), int(n_threads)), "svm_ovo_couple")
+    return proba, label, iters
+
+
 def sv_indices(alpha: np.ndarray, tol: float = 1e-8) -> np.ndarray:
     alpha = _c64(alpha)
     out = np.empty(alpha.shape[0], dtype=np.int64)

@@ -611,6 +611,73 @@ def platt_fit(dec: torch.Tensor, y: torch.Tensor, use: Optional[torch.Tensor] = 
     return PlattResult.from_struct(o)
 
 
+def platt_fit_batch(dec: torch.Tensor, y: torch.Tensor, offsets, use: Optional[torch.Tensor] = None
+                    ) -> List[PlattResult]:
+    """P sigmoid fits in one launch (svmd_platt_fit_batch, platt.hip): segment p of the concatenated dec / y / use
+    (as ``platt_fit``) is [offsets[p], offsets[p + 1]); offsets: P + 1 host integers ascending from >= 0 to at
+    most len(dec), no empty segment.  One workgroup per segment and one copy back; result p is ``platt_fit`` on
+    that segment alone, bit for bit.  Synchronises."""
+    n = dec.shape[0]
+    for name, t, dt in (("dec", dec, torch.float64), ("y", y, torch.int32), ("use", use, torch.uint8)):
+        if t is not None and (t.dtype != dt or t.shape != (n,) or not t.is_contiguous() or t.device != dec.device):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({n},) on one device")
+    off = np.ascontiguousarray(np.asarray(offsets), dtype=np.int64)
+    if off.ndim != 1 or off.shape[0] < 2:
+        raise ValueError("offsets must hold P + 1 >= 2 segment bounds")
+    if off[0] < 0 or off[-1] > n or np.any(np.diff(off) < 1):
+        raise ValueError(f"offsets must ascend strictly from >= 0 to at most {n} (no empty segment), got {off.tolist()}")
+    P = off.shape[0] - 1
+    ctx = _ctx_for(dec)
+    out = (N.SvmPlatt * P)()
+    N.check(ctx.lib.svmd_platt_fit_batch(ctx.bind(), N.ptr(dec), N.ptr(y), N.ptr(use), N.ptr(off), P, out),
+            "svmd_platt_fit_batch")
+    return [PlattResult.from_struct(o) for o in out]
+
+
+def ovo_couple(dec: torch.Tensor, A: Optional[torch.Tensor] = None, B: Optional[torch.Tensor] = None,
+               want_label: bool = True, proba: Optional[torch.Tensor] = None, label: Optional[torch.Tensor] = None,
+               iters: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """Pairwise coupling on the device (svmd_ovo_couple, ovo_proba.hip): class probabilities from the (m, P) pair
+    decisions of ``ovo_predict`` / ``ovo_votes`` (a row-strided view of a wider tensor is taken as it is), one
+    wave per row.  A, B (P,) float64 on the device: the pairs' sigmoids; both None: ``dec`` holds the pair
+    probabilities, and the result is ``ops.cpu.ovo_couple``'s bit for bit.  Returns (proba (m, k), label index
+    (m,) int32 or None without ``want_label``, iters (m,) int32: max(100, k) means not converged).  proba / label
+    / iters: optional tensors to write into (proba may be a row-strided view with at least k columns)."""
+    if dec.dtype != torch.float64 or dec.dim() != 2 or (dec.shape[1] > 1 and dec.stride(1) != 1):
+        raise ValueError("dec must be a 2-D float64 tensor with unit column stride")
+    m, P = dec.shape
+    k = int(round((1.0 + (1.0 + 8.0 * P) ** 0.5) / 2.0))
+    if k < 2 or k > 64 or k * (k - 1) // 2 != P:
+        raise ValueError(f"{P} pair columns are not k (k - 1) / 2 for a k in 2 .. 64")
+    if (A is None) != (B is None):
+        raise ValueError("A and B come together")
+    for name, t in (("A", A), ("B", B)):
+        if t is not None and (t.dtype != torch.float64 or t.shape != (P,) or not t.is_contiguous()
+                              or t.device != dec.device):
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape ({P},) on the decisions' device")
+    if proba is None:
+        proba = torch.empty((m, k), dtype=torch.float64, device=dec.device)
+    elif (proba.dtype != torch.float64 or proba.dim() != 2 or proba.shape[0] < m or proba.shape[1] != k
+          or proba.stride(1) != 1 or proba.device != dec.device):
+        raise ValueError(f"proba must be a float64 (>= {m}, {k}) tensor with unit column stride on the decisions' device")
+    if label is None and want_label:
+        label = torch.empty(m, dtype=torch.int32, device=dec.device)
+    if iters is None:
+        iters = torch.empty(m, dtype=torch.int32, device=dec.device)
+    for name, t in (("label", label), ("iters", iters)):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < m or not t.is_contiguous()
+                              or t.device != dec.device):
+            raise ValueError(f"{name} must be a contiguous int32 tensor of at least {m} entries on the decisions' device")
+    ldd = dec.stride(0) if m > 1 else max(dec.stride(0), P)
+    ldp = proba.stride(0) if proba.shape[0] > 1 else max(proba.stride(0), k)
+    if ldd < P or ldp < k:
+        raise ValueError("dec / proba rows overlap")
+    ctx = _ctx_for(dec)
+    N.check(ctx.lib.svmd_ovo_couple(ctx.bind(), N.ptr(dec), ldd, m, k, N.ptr(A), N.ptr(B), N.ptr(proba), ldp,
+                                    N.ptr(label), N.ptr(iters)), "svmd_ovo_couple")
+    return proba, label, iters
+
+
 def decomp_twin_step_u8(Xu: torch.Tensor, mn, mx, gamma: float, cols: np.ndarray, coef: np.ndarray,
                         f: np.ndarray) -> Optional[np.ndarray]:
     """The twin mode's fold and f update alone (svmd_decomp_twin_step_u8): the moved list ``cols`` (distinct

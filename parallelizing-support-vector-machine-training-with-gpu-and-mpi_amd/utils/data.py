@@ -186,6 +186,30 @@ def check_folds(folds, y: np.ndarray) -> np.ndarray:
     return f.astype(np.int32, copy=False)
 
 
+def check_folds_multiclass(folds, cls: np.ndarray, n_classes: int) -> np.ndarray:
+    """A fold array for the class indices ``cls`` (0 .. n_classes - 1) as int32 (n,): ids 0 .. K - 1 with K >= 2,
+    every id used, and every class with rows outside every fold -- so the training part of every one-vs-one pair
+    in every fold keeps both of its classes.  ValueError otherwise."""
+    f = np.ascontiguousarray(folds)
+    cls = np.asarray(cls)
+    n = cls.shape[0]
+    if f.shape != (n,) or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError(f"folds must be an integer array of shape ({n},)")
+    K = int(f.max()) + 1 if n else 0
+    if K < 2 or f.min() < 0:
+        raise ValueError(f"cross-validation needs fold ids 0 .. K - 1 with K >= 2, got ids {int(f.min())} .. {K - 1}")
+    per = np.zeros((int(n_classes), K), dtype=np.int64)  # rows of class c in fold j
+    np.add.at(per, (cls, f), 1)
+    empty = np.flatnonzero(per.sum(0) == 0)
+    if empty.size:
+        raise ValueError(f"fold {int(empty[0])} of {K} is empty")
+    c, j = np.nonzero(per == per.sum(1, keepdims=True))
+    if c.size:
+        raise ValueError(f"class index {int(c[0])} has all its rows in fold {int(j[0])}: that fold's training part "
+                         "lacks the class")
+    return f.astype(np.int32, copy=False)
+
+
 def one_vs_rest(labels: np.ndarray, positive_label: int = 1) -> np.ndarray:
     """label == positive_label -> +1, else -1 (main3.cpp:49-52 with positive_label = 1)."""
     return np.where(np.asarray(labels) == positive_label, 1, -1).astype(np.int32)
