@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "../cascade/cascade_capi.h"
+#include "decomp_mode.h"
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
 #include "internal.h"
@@ -181,94 +182,60 @@ void fold_twins(const int32_t* cols, const double* coef, int64_t cnt, int64_t n,
 // updates f for its own rows.  The block partition is the one-rank partition for world | 8, so the
 // trajectory is the one-rank trajectory bit for bit.  Returns SVM_OK or an error code (set_error);
 // transport failures throw (TransportError / CascadeAborted).
-// Twin mode (twin_z: the n regression targets, twin_eps: the tube's half width): y is not read, alpha holds
-// the 2n virtual points' values and the trace's snapshots are 2n long; f64_rows: the f update sums in the
-// FP64-row path's order (rowsum_update_f64) instead of the exact-integer GEMV's.
+// The mode (decomp_mode.h): in twin mode y is not read, alpha holds the 2n virtual points' values and the trace's
+// snapshots are 2n long; mode.heldout_out (optional) takes the final f.  f64_rows: the f update sums in the FP64-row
+// path's order (rowsum_update_f64) instead of the exact-integer GEMV's.
 int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, double* alpha, int32_t warm,
                  const svm_params& p, int32_t qws, double tau_frac, int32_t inner_wss, svm_result* res,
-                 int64_t* stats, svm_decomp_trace* tr, Transport* t, const double* twin_z = nullptr,
-                 double twin_eps = 0.0, bool f64_rows = false, double oneclass_nu = 0.0,
-                 const uint8_t* heldout = nullptr, double* f_out = nullptr) {
+                 int64_t* stats, svm_decomp_trace* tr, Transport* t, const DecompMode& mode = {},
+                 bool f64_rows = false) {
+  static const char* const entry[] = {"svm_decomp_train_gram", "svm_decomp_train_gram_svr",
+                                      "svm_decomp_train_gram_oneclass", "svm_decomp_train_gram_heldout"};
+  const char* who = entry[int(mode.kind)];
   const int world = t ? t->world() : 1, rank = t ? t->rank() : 0;
-  const bool twin = twin_z != nullptr, oneclass = oneclass_nu > 0.0;
+  const bool twin = mode.twin(), oneclass = mode.kind == DecompModeKind::oneclass;
   if (!K || (!y && !twin && !oneclass) || !alpha || n < 2 || ldk < n) {
-    set_error("svm_decomp_train_gram: bad arguments");
+    set_error("%s: bad arguments", who);
     return SVM_ERR_ARG;
   }
+  double Cp, Cn;  // the boxes of the y = +1 / y = -1 rows
+  if (const int rc = svm_class_boxes(&p, &Cp, &Cn)) return rc;
+  const auto set = [](double w) { return w != 0.0 && w != 1.0; };
+  const DecompFeatures asked = decomp_features(
+      p, world, warm != 0, mode.kind == DecompModeKind::classify ? Cp != Cn : set(p.weight_pos) || set(p.weight_neg));
+  if (const int rc = decomp_mode_check(who, mode, y, asked, n, DecompBackend::cpu_oracle)) return rc;
   const int64_t nr = n;  // kernel rows: point id's row is id mod nr (twin mode), id itself otherwise
-  std::vector<int32_t> sgn;
-  if (twin) {
-    const char* what = world != 1                               ? "the distributed solve (world > 1)"
-                       : warm                                   ? "a warm start"
-                       : shrink_cfg(p).on                       ? "shrinking"
-                       : newton_cfg(p).on                       ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                       : (p.weight_pos != 0.0 && p.weight_pos != 1.0) || (p.weight_neg != 0.0 && p.weight_neg != 1.0)
-                           ? "class weights"
-                           : nullptr;
-    if (what) {
-      set_error("svm_decomp_train_gram_svr: the regression (twin) solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-    if (!(twin_eps >= 0.0) || !std::isfinite(twin_eps) || 2 * nr > int64_t(INT32_MAX)) {
-      set_error("svm_decomp_train_gram_svr: epsilon must be finite and >= 0, and 2 n <= 2^31 - 1");
-      return SVM_ERR_ARG;
-    }
-    for (int64_t i = 0; i < nr; ++i)
-      if (!std::isfinite(twin_z[i])) {
-        set_error("svm_decomp_train_gram_svr: target %lld is not finite", (long long)i);
-        return SVM_ERR_ARG;
-      }
-    n = 2 * nr;
-    sgn.resize(size_t(n));
-    for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = i < nr ? 1 : -1;
-    y = sgn.data();
-  }
+  n = mode.points(nr);
+  // the solve's signs: the init kernels' analogue (ws_twin_init_kernel, ws_oneclass_init_kernel,
+  // ws_heldout_init_kernel)
+  std::vector<int32_t> sgn(mode.own_signs() ? size_t(n) : 0);
   int64_t oc_full = 0;
   double oc_frac = 0.0;
-  if (oneclass) {  // the caller (svm_decomp_train_gram_oneclass) has set C = 1 and cleared the weights
-    const char* what = world != 1           ? "the distributed solve (world > 1)"
-                       : twin               ? "the regression (twin) solve"
-                       : warm               ? "a warm start"
-                       : shrink_cfg(p).on   ? "shrinking"
-                       : newton_cfg(p).on   ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                                            : nullptr;
-    if (what) {
-      set_error("svm_decomp_train_gram_oneclass: the one-class solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-    if (const int rc = svm_oneclass_start(oneclass_nu, n, &oc_full, &oc_frac)) return rc;
-    sgn.assign(size_t(n), 1);
-    y = sgn.data();
+  switch (mode.kind) {
+    case DecompModeKind::classify: break;
+    case DecompModeKind::twin:
+      for (int64_t i = 0; i < nr; ++i)
+        if (!std::isfinite(mode.twin_z[i])) {
+          set_error("%s: target %lld is not finite", who, (long long)i);
+          return SVM_ERR_ARG;
+        }
+      for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = i < nr ? 1 : -1;
+      break;
+    case DecompModeKind::oneclass:  // the caller (svm_decomp_train_gram_oneclass) has set C = 1 and cleared the weights
+      if (const int rc = svm_oneclass_start(mode.oneclass_nu, n, &oc_full, &oc_frac)) return rc;
+      sgn.assign(size_t(n), 1);
+      break;
+    case DecompModeKind::heldout:  // label 0: held out, never selected
+      for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = mode.heldout[i] ? 0 : y[i];
+      break;
   }
-  if (heldout) {  // label 0: held out, never selected
-    const char* what = world != 1           ? "the distributed solve (world > 1)"
-                       : twin               ? "the regression (twin) solve"
-                       : oneclass           ? "the one-class solve"
-                       : warm               ? "a warm start"
-                       : shrink_cfg(p).on   ? "shrinking"
-                       : newton_cfg(p).on   ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                                            : nullptr;
-    if (what) {
-      set_error("svm_decomp_train_gram_heldout: the held-out solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-    sgn.resize(size_t(n));
-    for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = heldout[i] ? 0 : y[i];
-    y = sgn.data();
-  }
+  if (mode.own_signs()) y = sgn.data();
   if (!(tau_frac >= 0.0 && tau_frac < 0.5)) {
     set_error("svm_decomp_train_gram: tau_frac must be in [0, 0.5)");
     return SVM_ERR_ARG;
   }
   if (tr && world != 1) {
     set_error("svm_decomp_train_gram: a trace needs one rank");
-    return SVM_ERR_ARG;
-  }
-  double Cp, Cn;  // the boxes of the y = +1 / y = -1 rows
-  if (const int rc = svm_class_boxes(&p, &Cp, &Cn)) return rc;
-  if (Cp != Cn && (shrink_cfg(p).on || newton_cfg(p).on)) {
-    set_error("svm_decomp_train_gram: class weights are not supported with %s (unweighted)",
-              shrink_cfg(p).on ? "shrinking" : "the Newton polish (SVM355_DECOMP_NEWTON)");
     return SVM_ERR_ARG;
   }
   const Shape sh = shape(n, qws > 0 ? qws : kMaxWS, world);
@@ -317,8 +284,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   };
   if (twin) {  // ws_twin_init_kernel
     for (int64_t k = 0; k < nr; ++k) {
-      f[size_t(k)] = twin_eps - twin_z[k];
-      f[size_t(k + nr)] = -twin_eps - twin_z[k];
+      f[size_t(k)] = mode.twin_eps - mode.twin_z[k];
+      f[size_t(k + nr)] = -mode.twin_eps - mode.twin_z[k];
     }
     for (int64_t i = 0; i < n; ++i) alpha[i] = 0.0;
   } else if (oneclass) {  // ws_oneclass_init_kernel, then nz_update
@@ -716,7 +683,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     stats[13] = chain_it;
     stats[14] = eta_floored;
   }
-  if (f_out) std::copy(f.begin(), f.begin() + nloc, f_out + lo);
+  if (mode.heldout_out) std::copy(f.begin(), f.begin() + nloc, mode.heldout_out + lo);
   if (res) {
     res->iterations = inner_total + 1;
     res->b_high = bh;
@@ -756,7 +723,7 @@ extern "C" SVM_API int svm_decomp_train_gram_rows(const double* K, int64_t ldk, 
                                                   int32_t inner_wss, int32_t f64_rows, svm_result* res,
                                                   int64_t* stats, svm_decomp_trace* tr) {
   return decomp_solve(K, ldk, y, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
-                      nullptr, nullptr, 0.0, f64_rows != 0);
+                      nullptr, {}, f64_rows != 0);
 }
 
 // The regression (epsilon-SVR) form of svm_decomp_train_gram: twin mode over the n x n kernel matrix K and
@@ -766,12 +733,12 @@ extern "C" SVM_API int svm_decomp_train_gram_svr(const double* K, int64_t ldk, c
                                                  double epsilon, double* alpha, const svm_params* pp, int32_t qws,
                                                  double tau_frac, int32_t inner_wss, int32_t f64_rows, svm_result* res,
                                                  int64_t* stats, svm_decomp_trace* tr) {
-  if (!z) {
-    set_error("svm_decomp_train_gram_svr: bad arguments");
-    return SVM_ERR_ARG;
-  }
+  DecompMode mode;
+  mode.kind = DecompModeKind::twin;
+  mode.twin_z = z;
+  mode.twin_eps = epsilon;
   return decomp_solve(K, ldk, nullptr, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
-                      nullptr, z, epsilon, f64_rows != 0);
+                      nullptr, mode, f64_rows != 0);
 }
 
 // The one-class form of svm_decomp_train_gram (svm355.h): y = +1, C = 1, no linear term, LIBSVM's start.
@@ -779,15 +746,14 @@ extern "C" SVM_API int svm_decomp_train_gram_oneclass(const double* K, int64_t l
                                                       double* alpha, const svm_params* pp, int32_t qws,
                                                       double tau_frac, int32_t inner_wss, int32_t f64_rows,
                                                       svm_result* res, int64_t* stats, svm_decomp_trace* tr) {
-  if (!(nu > 0.0 && nu < 1.0)) {
-    set_error("svm_decomp_train_gram_oneclass: nu must be in (0, 1), got %g", nu);
-    return SVM_ERR_ARG;
-  }
   svm_params p = params_or_default(pp);
   p.C = 1.0;
   p.weight_pos = p.weight_neg = 0.0;
-  return decomp_solve(K, ldk, nullptr, n, alpha, 0, p, qws, tau_frac, inner_wss, res, stats, tr, nullptr, nullptr, 0.0,
-                      f64_rows != 0, nu);
+  DecompMode mode;
+  mode.kind = DecompModeKind::oneclass;
+  mode.oneclass_nu = nu;
+  return decomp_solve(K, ldk, nullptr, n, alpha, 0, p, qws, tau_frac, inner_wss, res, stats, tr, nullptr, mode,
+                      f64_rows != 0);
 }
 
 // The held-out form of svm_decomp_train_gram_rows (svm355.h): label 0 on the masked points, the final f out.
@@ -796,12 +762,12 @@ extern "C" SVM_API int svm_decomp_train_gram_heldout(const double* K, int64_t ld
                                                      const svm_params* pp, int32_t qws, double tau_frac,
                                                      int32_t inner_wss, int32_t f64_rows, svm_result* res,
                                                      int64_t* stats, double* f_out, svm_decomp_trace* tr) {
-  if (!heldout || !y) {
-    set_error("svm_decomp_train_gram_heldout: bad arguments");
-    return SVM_ERR_ARG;
-  }
+  DecompMode mode;
+  mode.kind = DecompModeKind::heldout;
+  mode.heldout = heldout;
+  mode.heldout_out = f_out;
   return decomp_solve(K, ldk, y, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr, nullptr,
-                      nullptr, 0.0, f64_rows != 0, 0.0, heldout, f_out);
+                      mode, f64_rows != 0);
 }
 
 // Twin mode's moved-column fold alone (tests): cnt <= 1024 virtual ids in [0, 2n) and their coefficients to one

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "decomp_mode.h"
 
 namespace svm355 {
 
@@ -51,29 +52,7 @@ struct DecompOpts {
   svm_decomp_trace* trace = nullptr;
   DecompSolo* solo = nullptr;  // world > 1 rehearsal on one GPU: per-rank solo timing (above)
   double* host_wait_ms = nullptr;  // out: host time blocked in the per-batch waits (all outer iterations)
-  // Twin mode (epsilon-SVR): twin_z = the n targets on the device, twin_eps = the tube's half width.  The
-  // solve then runs over 2n virtual points that share the n kernel rows -- point k is a_k with sign +1, point
-  // k + n its twin a*_k with sign -1, both on row k -- from f_k = eps - z_k, f_{k+n} = -eps - z_k.  run_decomp
-  // takes n rows as always, reads no y (it keeps the signs itself), and alpha holds 2n values: a, then a*.
-  // One GPU, cold start, no shrinking, no Newton polish, no class weights: anything else is SVM_ERR_ARG.
-  const double* twin_z = nullptr;
-  double twin_eps = 0.0;
-  bool twin() const { return twin_z != nullptr; }
-  // One-class mode (LIBSVM's -s 2; svm355.h has the problem): oneclass_nu > 0 selects it.  Every sign is +1, the
-  // box is 1 (p.C is not read), there is no linear term, and the solve starts from LIBSVM's feasible alpha with
-  // f = K[:, nz] alpha_nz summed by the chunked start.  run_decomp takes n rows, reads no y (it keeps the signs
-  // itself), and alpha holds n values (out).  One GPU, no caller's warm start, no shrinking, no Newton polish,
-  // no class weights, not together with twin mode, 0 < nu < 1: anything else is SVM_ERR_ARG.
-  double oneclass_nu = 0.0;
-  bool oneclass() const { return oneclass_nu > 0.0; }
-  // Held-out mode (svm355.h): heldout = device uint8[n], 1 = point i is out of the fit, and heldout_dec = n
-  // doubles on the device, out.  The solve keeps its own signs (0 on the held-out points: never selected, alpha
-  // exactly 0, f collecting every update) and does not read the caller's y after the start; after the last
-  // outer iteration heldout_dec_i = f_i - b for the held-out points and 0.0 for the others.  One GPU, cold
-  // start, no shrinking, no Newton polish, not with twin or one-class mode: anything else is SVM_ERR_ARG.
-  // Class weights are allowed.  The training part must hold both classes (the caller checks).
-  const uint8_t* heldout = nullptr;
-  double* heldout_dec = nullptr;
+  DecompMode mode;  // what the solve is of (decomp_mode.h): the classifier, or the twin, one-class or held-out mode
 };
 
 // The rows a solve reads its kernel values from: the exact-integer plan's quantised rows (Q; int8

@@ -1168,21 +1168,16 @@ struct Solve {
   int64_t n = 0, NBr = 0, lo = 0, nloc = 0, Lr = 0, nchunks = 0;
   DecompKnobs k;
   bool wide_select = false, kww_narrow = false, pack_on = false;
-  // twin mode (DecompOpts): n, lo, nloc and the selection shape are those of the 2 nrow virtual points; the
-  // kernel rows -- what the GEMV, the column store and the column cache run over -- are the nrow rows
-  bool twin = false;
+  // the mode (decomp_mode.h).  With its own signs, y is the workspace's (alloc_solve) and y_in the caller's labels.
+  // twin mode: n, lo, nloc and the selection shape are those of the 2 nrow virtual points; the kernel rows -- what
+  // the GEMV, the column store and the column cache run over -- are the nrow rows.  one-class mode: the boxes are
+  // 1, and the start is (oc_full, oc_frac) followed by the chunked start (nz_update)
+  DecompMode mode;
   int64_t nrow = 0;
-  const double* twin_z = nullptr;
-  double twin_eps = 0.0;
-  int64_t rows() const { return twin ? nrow : nloc; }  // this GPU's kernel rows
-  // one-class mode (DecompOpts): y is the workspace's signs (all +1), the boxes are 1, and the start is
-  // (oc_full, oc_frac) followed by the chunked start (nz_update), so the workspace is a warm solve's
-  bool oneclass = false;
+  int64_t rows() const { return mode.twin() ? nrow : nloc; }  // this GPU's kernel rows
+  int64_t cols() const { return mode.twin() ? nrow : n; }     // the kernel columns
   int64_t oc_full = 0;
   double oc_frac = 0.0;
-  // held-out mode (DecompOpts): y is the workspace's signs (0 on the masked points), y_in the caller's labels
-  const uint8_t* heldout = nullptr;
-  double* heldout_dec = nullptr;
   const int32_t* y_in = nullptr;
   ShrinkCfg shc;
   InnerVariant inner;
@@ -1222,7 +1217,7 @@ struct PackState {
 int size_col_cache(const Solve& S, bool warm, ColCache* out) {
   DeviceCtx* ctx = S.ctx;
   const DecompKnobs& k = S.k;
-  const int64_t n = S.twin ? S.nrow : S.n, nloc = S.rows();  // slots per kernel row
+  const int64_t n = S.cols(), nloc = S.rows();  // slots per kernel row
   *out = ColCache{};
   if (S.f64 || nloc <= 0) return SVM_OK;
   if (!(k.ccache >= 0 ? k.ccache != 0 : nloc * int64_t(S.kq) > (int64_t(192) << 20))) return SVM_OK;
@@ -1275,7 +1270,7 @@ int size_col_cache(const Solve& S, bool warm, ColCache* out) {
 void layout_ws(Solve& S, bool warm, WsCarver& c) {
   DecompWs& w = S.w;
   const size_t nl1 = size_t(std::max<int64_t>(S.nloc, 1)), n = size_t(S.n), kq = size_t(S.kq), ld = size_t(S.R.ld);
-  const size_t nr1 = size_t(std::max<int64_t>(S.rows(), 1)), ncol = S.twin ? size_t(S.nrow) : n;  // kernel rows / columns
+  const size_t nr1 = size_t(std::max<int64_t>(S.rows(), 1)), ncol = size_t(S.cols());  // kernel rows / columns
   const bool f64 = S.f64, q8 = !f64, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
   w.f = c.take<double>(nl1);
   w.own = c.take<CandRec>(size_t(S.Lr));
@@ -1321,10 +1316,19 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.Qa = c.take<int8_t>(nl1 * kq, pack);
   w.N0a = c.take<int32_t>(nl1, pack);
   w.WNa = c.take<double>(nl1, pack);
-  w.sgn = c.take<int32_t>(n, S.twin || S.oneclass || S.heldout);
-  w.fcols = c.take<int32_t>(kMaxWS, S.twin);
-  w.fcoef = c.take<double>(kMaxWS, S.twin);
-  w.fcount = c.take<int32_t>(64, S.twin);
+  w.sgn = c.take<int32_t>(n, S.mode.own_signs());
+  w.fcols = c.take<int32_t>(kMaxWS, S.mode.twin());
+  w.fcoef = c.take<double>(kMaxWS, S.mode.twin());
+  w.fcount = c.take<int32_t>(64, S.mode.twin());
+}
+
+// What the solve is asked to run with (decomp_mode.h); the class weights' range check comes with the boxes.
+int mode_features(const DecompOpts& o, const svm_params& p, DecompFeatures* f) {
+  double cp = 0.0, cn = 0.0;
+  if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
+  const bool classify = o.mode.kind == DecompModeKind::classify;
+  *f = decomp_features(p, o.world, o.warm, classify ? cp != cn : cp != p.C || cn != p.C);
+  return SVM_OK;
 }
 
 // The checks, the shape and this GPU's slice of it, the knobs and what follows from them.
@@ -1332,65 +1336,17 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
                 const svm_params& p, int qws, const DecompOpts& o) {
   const int world = o.world, rank = o.rank;
   const int64_t nrow = n;  // the kernel rows; n below counts the points the solve selects among
-  if (o.twin()) {  // everything twin mode does not cover is refused here, before any device work
-    double cp = 0.0, cn = 0.0;
-    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
-    const char* what = world != 1                 ? "the distributed solve (world > 1)"
-                       : o.warm                   ? "a warm start"
-                       : shrink_cfg(p).on         ? "shrinking"
-                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                       : (cp != p.C || cn != p.C) ? "class weights"
-                                                  : nullptr;
-    if (what) {
-      set_error("decomposition SMO: the regression (twin) solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-    if (!(o.twin_eps >= 0.0) || !std::isfinite(o.twin_eps) || nrow < 2 || 2 * nrow > int64_t(INT32_MAX)) {
-      set_error("decomposition SMO: the regression (twin) solve needs a finite epsilon >= 0 and 2 <= n with "
-                "2 n <= 2^31 - 1 (n = %lld)", (long long)nrow);
-      return SVM_ERR_ARG;
-    }
-    n = 2 * nrow;
-  }
+  DecompFeatures ft;  // everything the mode does not cover is refused here, before any device work
+  int rc = mode_features(o, p, &ft);
+  if (rc || (rc = decomp_mode_check("decomposition SMO", o.mode, y, ft, nrow, DecompBackend::device))) return rc;
+  n = o.mode.points(nrow);
   svm_params p1 = p;  // the solve's parameters (one-class mode: the box is 1 whatever p.C says)
   int64_t oc_full = 0;
   double oc_frac = 0.0;
-  if (o.oneclass()) {  // everything one-class mode does not cover is refused here, before any device work
-    double cp = 0.0, cn = 0.0;
-    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
-    // shrinking: its unshrink rebuilds f from -y
-    const char* what = world != 1                 ? "the distributed solve (world > 1)"
-                       : o.twin()                 ? "the regression (twin) solve"
-                       : o.warm                   ? "a warm start"
-                       : shrink_cfg(p).on         ? "shrinking"
-                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                       : (cp != p.C || cn != p.C) ? "class weights"
-                                                  : nullptr;
-    if (what) {
-      set_error("decomposition SMO: the one-class solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-    if (const int rc = svm_oneclass_start(o.oneclass_nu, n, &oc_full, &oc_frac)) return rc;
+  if (o.mode.kind == DecompModeKind::oneclass) {
+    if ((rc = svm_oneclass_start(o.mode.oneclass_nu, n, &oc_full, &oc_frac))) return rc;
     p1.C = 1.0;
     p1.weight_pos = p1.weight_neg = 0.0;
-  }
-  if (o.heldout) {  // everything held-out mode does not cover is refused here, before any device work
-    // shrinking: its unshrink rebuilds f from the nonzero alphas, the polish: untested on label 0
-    const char* what = world != 1                 ? "the distributed solve (world > 1)"
-                       : o.twin()                 ? "the regression (twin) solve"
-                       : o.oneclass()             ? "the one-class solve"
-                       : o.warm                   ? "a warm start"
-                       : shrink_cfg(p).on         ? "shrinking"
-                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                                                  : nullptr;
-    if (what) {
-      set_error("decomposition SMO: the held-out solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-    if (!o.heldout_dec || !y) {
-      set_error("decomposition SMO: the held-out solve needs labels and a buffer for the held-out decisions");
-      return SVM_ERR_ARG;
-    }
   }
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !o.allgather)) {
     set_error("decomposition SMO: bad world / rank / exchange");
@@ -1412,25 +1368,19 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
               "world <= 64)", (long long)n, (long long)sh.L, kMaxWS);
     return SVM_ERR_ARG;
   }
-  int rc = read_knobs(sh, &S.k);
-  if (rc) return rc;
+  if ((rc = read_knobs(sh, &S.k))) return rc;
   if ((rc = svm_class_boxes(&p1, &S.Cp, &S.Cn))) return rc;
   S.ctx = ctx;
   S.s = ctx->stream;
   S.R = R;
   S.f64 = f64;
   S.kq = f64 ? 0 : R.P->kq;
-  S.y = y;  // twin mode: the signs, in the workspace (alloc_solve)
+  S.y = y;  // a mode with its own signs: those, in the workspace (alloc_solve)
   S.alpha = alpha;
-  S.twin = o.twin();
+  S.mode = o.mode;
   S.nrow = nrow;
-  S.twin_z = o.twin_z;
-  S.twin_eps = o.twin_eps;
-  S.oneclass = o.oneclass();
   S.oc_full = oc_full;
   S.oc_frac = oc_frac;
-  S.heldout = o.heldout;
-  S.heldout_dec = o.heldout_dec;
   S.y_in = y;
   S.n = n;
   S.p = p1;
@@ -1450,22 +1400,11 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   const NewtonCfg nwc = newton_cfg(p);
   S.nwd = NwDev{nwc.on ? 1 : 0, nwc.every, nwc.per_solve, nwc.repeat, nwc.max_free, 0, nwc.frac};
   S.inner = InnerVariant{S.k.inner_nt, S.k.prof, S.k.wss2, S.k.dp, S.k.j2s, nwc.on, S.Cp != S.Cn};
-  if (S.inner.weighted) {
-    // class weights: what is unweighted refuses them -- it never solves another problem in silence
-    const char* what = world > 1     ? "the distributed solve (world > 1)"
-                       : S.shc.on    ? "shrinking"
-                       : nwc.on      ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                                     : nullptr;
-    if (what) {
-      set_error("decomposition SMO: class weights are not supported with %s", what);
-      return SVM_ERR_ARG;
-    }
-    if (!ws_inner_weighted_built(S.inner)) {
-      set_error("decomposition SMO: the weighted inner solve is not built for SVM355_DECOMP_NT=%d SVM355_DECOMP_WSS=%d "
-                "SVM355_DECOMP_PROF=%d (built: NT=256 with WSS=1, 2 or 3, PROF=0)",
-                S.k.inner_nt, S.k.j2s ? 4 : S.k.dp ? 3 : S.k.wss2 ? 2 : 1, S.k.prof ? 1 : 0);
-      return SVM_ERR_ARG;
-    }
+  if (S.inner.weighted && !ws_inner_weighted_built(S.inner)) {
+    set_error("decomposition SMO: the weighted inner solve is not built for SVM355_DECOMP_NT=%d SVM355_DECOMP_WSS=%d "
+              "SVM355_DECOMP_PROF=%d (built: NT=256 with WSS=1, 2 or 3, PROF=0)",
+              S.k.inner_nt, S.k.j2s ? 4 : S.k.dp ? 3 : S.k.wss2 ? 2 : 1, S.k.prof ? 1 : 0);
+    return SVM_ERR_ARG;
   }
   S.allgather = &o.allgather;
   S.tr = tr;
@@ -1481,7 +1420,7 @@ int alloc_solve(Solve& S, bool warm) {
   int rc = size_col_cache(S, warm, &S.cc);
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
-  if (S.twin || S.oneclass || S.heldout) S.y = S.w.sgn;
+  if (S.mode.own_signs()) S.y = S.w.sgn;
   if ((rc = S.ctx->ensure_pinned(sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl) + 64))) return rc;
   char* pin = static_cast<char*>(S.ctx->pinned);
   S.hs = reinterpret_cast<DecompHost*>(pin);
@@ -1507,7 +1446,7 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
   // twin mode: cl / cf / cnt are the folded list (rows, one entry each), the kernel work runs over the nrow
   // rows exactly as a classification of them would, and the sums' TWIN instantiations add each row's sum to
   // both of its points
-  const bool twin = S.twin;
+  const bool twin = S.mode.twin();
   const int64_t lo = S.lo, nloc = S.rows();
   if (nloc <= 0) return SVM_OK;
   if (S.f64) {
@@ -1557,7 +1496,7 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
 int cache_reset(const Solve& S) {  // no point has a slot, the first free slot is 0
   if (!S.cc.slab) return SVM_OK;
   const DecompWs& w = S.w;
-  SVMD_CHECK(hipMemsetAsync(w.cslot, 0xFF, size_t(S.twin ? S.nrow : S.n) * 4, S.s));
+  SVMD_CHECK(hipMemsetAsync(w.cslot, 0xFF, size_t(S.cols()) * 4, S.s));
   SVMD_CHECK(hipMemsetAsync(w.cst, 0, 64, S.s));
   if (w.cmeta) {  // owners and stamps -1, CLOCK bits clear
     SVMD_CHECK(hipMemsetAsync(w.cmeta, 0xFF, size_t(S.cc.cap) * 8, S.s));
@@ -1617,20 +1556,26 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
   int rc = cache_reset(S);  // a fresh cache per fit
   if (rc) return rc;
   if (w.shr) SVMD_CHECK(hipMemsetAsync(w.shr, 0, size_t(std::max<int64_t>(S.nloc, 1)), s));
-  if (S.twin)
-    hipLaunchKernelGGL(ws_twin_init_kernel, dim3(unsigned((S.nrow + 255) / 256)), dim3(256), 0, s, S.twin_z, S.twin_eps,
-                       S.nrow, w.sgn, S.alpha, w.f, w.ctl);
-  else if (S.oneclass)
-    hipLaunchKernelGGL(ws_oneclass_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.oc_full,
-                       S.oc_frac, S.n, w.sgn, S.alpha, w.f, w.ctl);
-  else if (S.heldout)
-    hipLaunchKernelGGL(ws_heldout_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y_in, S.heldout,
-                       S.n, w.sgn, S.alpha, w.f, w.ctl);
-  else
-    hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo,
-                       S.nloc, S.n, int(warm), w.ctl);
+  switch (S.mode.kind) {
+    case DecompModeKind::twin:
+      hipLaunchKernelGGL(ws_twin_init_kernel, dim3(unsigned((S.nrow + 255) / 256)), dim3(256), 0, s, S.mode.twin_z,
+                         S.mode.twin_eps, S.nrow, w.sgn, S.alpha, w.f, w.ctl);
+      break;
+    case DecompModeKind::oneclass:
+      hipLaunchKernelGGL(ws_oneclass_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.oc_full,
+                         S.oc_frac, S.n, w.sgn, S.alpha, w.f, w.ctl);
+      break;
+    case DecompModeKind::heldout:
+      hipLaunchKernelGGL(ws_heldout_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y_in,
+                         S.mode.heldout, S.n, w.sgn, S.alpha, w.f, w.ctl);
+      break;
+    case DecompModeKind::classify:
+      hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo,
+                         S.nloc, S.n, int(warm), w.ctl);
+      break;
+  }
   SVMD_LAUNCH_CHECK();
-  if ((warm || S.oneclass) && (rc = nz_update(S, ps, warm_cols))) return rc;
+  if (S.mode.chunked_start(warm) && (rc = nz_update(S, ps, warm_cols))) return rc;
   return SVM_OK;
 }
 
@@ -1733,13 +1678,13 @@ int enqueue_kww(const Solve& S) {
   int32_t* gate = &w.ctl->stop;
   // twin mode: a point's row is its id mod nrow, and two twins in W get the diagonal's 1 between them
   auto twin_diag = [&]() -> int {
-    if (!S.twin) return SVM_OK;
+    if (!S.mode.twin()) return SVM_OK;
     hipLaunchKernelGGL(ws_twin_kww_kernel, dim3(1), dim3(kMaxWS), 0, s, w.W, w.ctl, S.nrow, w.Kw, kLdw);
     SVMD_LAUNCH_CHECK();
     return SVM_OK;
   };
   if (S.f64) {
-    if (S.twin)
+    if (S.mode.twin())
       hipLaunchKernelGGL(ws_gather_f64_twin_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W,
                          &w.ctl->m, gate, w.Xw, w.nw, S.nrow);
     else
@@ -1752,7 +1697,7 @@ int enqueue_kww(const Solve& S) {
     return rc ? rc : twin_diag();
   }
   const QuantPlan& P = *R.P;
-  if (S.twin)
+  if (S.mode.twin())
     hipLaunchKernelGGL(ws_gather_twin_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.Q, R.N0, R.WN, P.kq, w.W, w.ctl,
                        w.Qw, w.N0w, w.WNw, S.nrow);
   else
@@ -1811,7 +1756,7 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
                                       w.gAw, w.Wf, w.nAmat, S.nwd, S.Cn})))
     return rc;
   SVMD_LAUNCH_CHECK();
-  if (S.twin) {  // the moved points folded to one entry per kernel row
+  if (S.mode.twin()) {  // the moved points folded to one entry per kernel row
     hipLaunchKernelGGL(ws_twin_fold_kernel, dim3(1), dim3(kMaxWS), 0, s, w.cols, w.coef, w.mcount, S.nrow, w.fcols,
                        w.fcoef, w.fcount);
     SVMD_LAUNCH_CHECK();
@@ -1937,7 +1882,7 @@ int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* al
   S.t0 = std::chrono::steady_clock::now();
   int rc = setup_solve(S, ctx, R, y, alpha, n, p, qws, o);
   if (rc) return rc;
-  if ((rc = alloc_solve(S, o.warm || S.oneclass))) return rc;  // one-class: sized as a warm solve (its start's columns)
+  if ((rc = alloc_solve(S, S.mode.chunked_start(o.warm)))) return rc;  // sized by the start's columns
   hipStream_t s = S.s;
   svm_decomp_trace* tr = S.tr;
   PackState ps(S.nloc);
@@ -2001,9 +1946,9 @@ int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* al
       return SVM_ERR_INTERNAL;
     }
   }
-  if (S.heldout) {  // behind the queued no-op batch on the stream: the control block and f are final
-    hipLaunchKernelGGL(ws_heldout_dec_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.w.f, S.heldout, S.n,
-                       S.w.ctl, S.heldout_dec);
+  if (S.mode.kind == DecompModeKind::heldout) {  // behind the queued no-op batch: the control block and f are final
+    hipLaunchKernelGGL(ws_heldout_dec_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.w.f, S.mode.heldout,
+                       S.n, S.w.ctl, S.mode.heldout_out);
     SVMD_LAUNCH_CHECK();
   }
   return finish_solve(S, ps, *fin, warm_cols, r, stats);
@@ -2022,7 +1967,7 @@ int decomp_solve(DeviceCtx* ctx, const DecompRows& R, const int32_t* y_d, double
   }
   if (r) {  // twin mode: the points with a_k or a*_k above the tolerance (never both of a row at a solution)
     int64_t c = 0;
-    const int rc = count_sv(ctx, alpha_d, o.twin() ? 2 * n : n, 1, p.sv_tol, &c);
+    const int rc = count_sv(ctx, alpha_d, o.mode.points(n), 1, p.sv_tol, &c);
     if (rc) return rc;
     r->n_sv = c;
   }
@@ -2083,7 +2028,7 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
                     int64_t* stats, bool* used, double* prep_ms, const DecompOpts& o) {
   const auto t0 = std::chrono::steady_clock::now();
   *used = false;
-  if (!decomp_shape(o.twin() ? 2 * n : n, q, o.world).ok) return SVM_OK;  // beyond the solver's shapes: the caller's fallback
+  if (!decomp_shape(o.mode.points(n), q, o.world).ok) return SVM_OK;  // beyond the solver's shapes: the caller's fallback
   const char* fe = getenv("SVM355_DECOMP_F64");
   const bool force_f64 = fe && atoi(fe) == 1;
   QuantPlan P;
@@ -2141,7 +2086,7 @@ int decomp_fit_u8(DeviceCtx* ctx, const uint8_t* Xu_d, int64_t n, int64_t d, con
   *used = false;
   // outside the solver's shapes (n < 2 or n >= 2^31 - 1, decomp_shape): nothing runs, the caller takes
   // the pairwise solver (SVC(solver="auto"))
-  if (!decomp_shape(o.twin() ? 2 * n : n, q, o.world).ok) return SVM_OK;
+  if (!decomp_shape(o.mode.points(n), q, o.world).ok) return SVM_OK;
   QuantPlan P;
   if (!plan_quant(mn_h, mx_h, d, &P) || P.kq > 32 * 128) return SVM_OK;  // igram's LDS table bound
   QuantBufs b;
@@ -2165,13 +2110,15 @@ namespace {
 
 // The C entries' one body after their argument checks: uint8 rows (X_d n x d) or min-max scaled FP64 rows
 // (X_d n x ld), the parameters or the defaults, the fit between the context's stream joins, the timing.
-int train_decomp(DeviceCtx* ctx, const void* X_d, bool is_u8, int64_t n, int64_t ld, int64_t d, const double* mn_h,
+// What the mode refuses is SVM_ERR_ARG under the entry's name (`who`) before the context's stream is joined:
+// nothing is enqueued.  (setup_solve makes the same call for the solves that do not come through here.)
+int train_decomp(DeviceCtx* ctx, const char* who, const void* X_d, bool is_u8, int64_t n, int64_t ld, int64_t d, const double* mn_h,
                  const double* mx_h, const int32_t* y_d, double* alpha_d, const svm_params* pp, int32_t q,
                  const DecompOpts& o, svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used_out) {
   const svm_params p = params_or_default(pp);
-  double cp, cn;  // the class weights' range check, before anything runs
-  int rc = svm_class_boxes(&p, &cp, &cn);
-  if (rc) return rc;
+  DecompFeatures ft;
+  int rc = mode_features(o, p, &ft);
+  if (rc || (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device))) return rc;
   const auto t0 = std::chrono::steady_clock::now();
   if ((rc = ctx->begin())) return rc;
   bool used = false;
@@ -2211,7 +2158,7 @@ SVM_API int svmd_train_decomp_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_
     set_error("svmd_train_decomp_u8: bad arguments");
     return SVM_ERR_ARG;
   }
-  return train_decomp(ctx, Xu_d, true, n, 0, d, mn_h, mx_h, y_d, alpha_d, pp, q, {}, r, timing, stats, used_out);
+  return train_decomp(ctx, "svmd_train_decomp_u8", Xu_d, true, n, 0, d, mn_h, mx_h, y_d, alpha_d, pp, q, {}, r, timing, stats, used_out);
 }
 
 // The same solve from min-max scaled FP64 rows on the device (X_d: n x ld; mn_h / mx_h the training
@@ -2226,29 +2173,40 @@ SVM_API int svmd_train_decomp_rows(void* h, const double* X_d, int64_t n, int64_
     set_error("svmd_train_decomp_rows: bad arguments");
     return SVM_ERR_ARG;
   }
-  return train_decomp(ctx, X_d, false, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, {}, r, timing, stats, used_out);
+  return train_decomp(ctx, "svmd_train_decomp_rows", X_d, false, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, {}, r, timing, stats, used_out);
+}
+
+// The general entries' one body: the arguments they all take checked (own_ok: the entry's own pointers), then the
+// fit in the entry's mode.  *used = 0 and nothing done without an exact-integer plan.
+static int train_decomp_entry(const char* who, void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld,
+                              int64_t d, const double* mn_h, const double* mx_h, bool own_ok, const int32_t* y_d,
+                              double* alpha_d, const svm_params* pp, int32_t q, DecompOpts o, svm_result* r,
+                              svmd_timing* timing, int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
+  SVMD_CTX(h);
+  if (used_out) *used_out = 0;
+  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !alpha_d || !own_ok) {
+    set_error("%s: bad arguments", who);
+    return SVM_ERR_ARG;
+  }
+  o.trace = trace;
+  return train_decomp(ctx, who, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, o, r, timing, stats,
+                      used_out);
 }
 
 // The general entry: uint8 rows (is_u8, X_d n x d) or min-max scaled FP64 rows (X_d n x ld), cold or
 // warm start (alpha_d holds the start), an optional per-outer-iteration trace (tests: one
-// synchronisation per outer iteration).  *used = 0 and nothing done without an exact-integer plan.
+// synchronisation per outer iteration).
 SVM_API int svmd_train_decomp(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
                               const double* mn_h, const double* mx_h, const int32_t* y_d, double* alpha_d,
                               const svm_params* pp, int32_t q, int32_t warm, svm_result* r, svmd_timing* timing,
                               int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
-  SVMD_CTX(h);
-  if (used_out) *used_out = 0;
-  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !y_d || !alpha_d) {
-    set_error("svmd_train_decomp: bad arguments");
-    return SVM_ERR_ARG;
-  }
   DecompOpts o;
   o.warm = warm != 0;
-  o.trace = trace;
-  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, o, r, timing, stats, used_out);
+  return train_decomp_entry("svmd_train_decomp", h, X_d, is_u8, n, ld, d, mn_h, mx_h, y_d != nullptr, y_d, alpha_d, pp,
+                            q, o, r, timing, stats, used_out, trace);
 }
 
-// The regression (epsilon-SVR) form of svmd_train_decomp: twin mode (DecompOpts) over the n rows and the n
+// The regression (epsilon-SVR) form of svmd_train_decomp: twin mode (decomp_mode.h) over the n rows and the n
 // targets z_d (device FP64).  alpha_d: 2n doubles, out -- a (first n), then a* (last n); the model is beta =
 // a - a*, a prediction sum_k beta_k K(x_k, x) - r->b.  r->n_sv counts the points of either half above sv_tol.
 // A trace's W / cols / coef hold virtual ids (k and k + n) and its snapshots are 2n long (trace->n = 2n).  Cold
@@ -2257,105 +2215,42 @@ SVM_API int svmd_train_decomp_svr(void* h, const void* X_d, int32_t is_u8, int64
                                   const double* mn_h, const double* mx_h, const double* z_d, double epsilon,
                                   double* alpha_d, const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
                                   int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
-  SVMD_CTX(h);
-  if (used_out) *used_out = 0;
-  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !z_d || !alpha_d) {
-    set_error("svmd_train_decomp_svr: bad arguments");
-    return SVM_ERR_ARG;
-  }
-  if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) {
-    set_error("svmd_train_decomp_svr: epsilon must be finite and >= 0, got %g", epsilon);
-    return SVM_ERR_ARG;
-  }
-  if (2 * n > int64_t(INT32_MAX)) {
-    set_error("svmd_train_decomp_svr: n = %lld rows are 2 n > 2^31 - 1 points", (long long)n);
-    return SVM_ERR_ARG;
-  }
-  {  // what twin mode refuses, before any device work (setup_solve checks the same)
-    const svm_params p = params_or_default(pp);
-    double cp = 0.0, cn = 0.0;
-    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
-    const char* what = shrink_cfg(p).on           ? "shrinking"
-                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                       : (cp != p.C || cn != p.C) ? "class weights"
-                                                  : nullptr;
-    if (what) {
-      set_error("svmd_train_decomp_svr: the regression (twin) solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-  }
   DecompOpts o;
-  o.trace = trace;
-  o.twin_z = z_d;
-  o.twin_eps = epsilon;
-  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, nullptr, alpha_d, pp, q, o, r, timing, stats, used_out);
+  o.mode.kind = DecompModeKind::twin;
+  o.mode.twin_z = z_d;
+  o.mode.twin_eps = epsilon;
+  return train_decomp_entry("svmd_train_decomp_svr", h, X_d, is_u8, n, ld, d, mn_h, mx_h, z_d != nullptr, nullptr,
+                            alpha_d, pp, q, o, r, timing, stats, used_out, trace);
 }
 
-// The one-class form of svmd_train_decomp (LIBSVM's -s 2; svm355.h has the problem): one-class mode (DecompOpts)
-// over the n rows.  alpha_d: n doubles, out; r->b is rho, and a decision value is sum_k alpha_k K(x_k, x) - rho.
-// The same row paths and *used contract as svmd_train_decomp_svr.  pp->C is not read (the box is 1).  stats[7]:
-// the start's columns.  One GPU; shrinking, the Newton polish and class weights in *pp are SVM_ERR_ARG, as is
-// nu outside (0, 1).
+// The one-class form of svmd_train_decomp (LIBSVM's -s 2; svm355.h has the problem): one-class mode
+// (decomp_mode.h) over the n rows.  alpha_d: n doubles, out; r->b is rho, and a decision value is sum_k alpha_k
+// K(x_k, x) - rho.  The same row paths and *used contract as svmd_train_decomp_svr.  pp->C is not read (the box
+// is 1).  stats[7]: the start's columns.  One GPU; shrinking, the Newton polish and class weights in *pp are
+// SVM_ERR_ARG, as is nu outside (0, 1).
 SVM_API int svmd_train_decomp_oneclass(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
                                        const double* mn_h, const double* mx_h, double nu, double* alpha_d,
                                        const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
                                        int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
-  SVMD_CTX(h);
-  if (used_out) *used_out = 0;
-  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !alpha_d) {
-    set_error("svmd_train_decomp_oneclass: bad arguments");
-    return SVM_ERR_ARG;
-  }
-  if (!(nu > 0.0 && nu < 1.0)) {
-    set_error("svmd_train_decomp_oneclass: nu must be in (0, 1), got %g", nu);
-    return SVM_ERR_ARG;
-  }
-  {  // what one-class mode refuses, before any device work (setup_solve checks the same)
-    const svm_params p = params_or_default(pp);
-    double cp = 0.0, cn = 0.0;
-    if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
-    const char* what = shrink_cfg(p).on           ? "shrinking"
-                       : newton_cfg(p).on         ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                       : (cp != p.C || cn != p.C) ? "class weights"
-                                                  : nullptr;
-    if (what) {
-      set_error("svmd_train_decomp_oneclass: the one-class solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-  }
   DecompOpts o;
-  o.trace = trace;
-  o.oneclass_nu = nu;
-  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, nullptr, alpha_d, pp, q, o, r, timing, stats, used_out);
+  o.mode.kind = DecompModeKind::oneclass;
+  o.mode.oneclass_nu = nu;
+  return train_decomp_entry("svmd_train_decomp_oneclass", h, X_d, is_u8, n, ld, d, mn_h, mx_h, true, nullptr, alpha_d,
+                            pp, q, o, r, timing, stats, used_out, trace);
 }
 
-// The held-out form of svmd_train_decomp (svm355_device.h): held-out mode (DecompOpts) over the n rows.
+// The held-out form of svmd_train_decomp (svm355_device.h): held-out mode (decomp_mode.h) over the n rows.
 SVM_API int svmd_train_decomp_heldout(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
                                       const double* mn_h, const double* mx_h, const int32_t* y_d,
                                       const uint8_t* heldout_d, double* alpha_d, double* dec_out_d,
                                       const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
                                       int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
-  SVMD_CTX(h);
-  if (used_out) *used_out = 0;
-  if (!X_d || n < 2 || d <= 0 || (!is_u8 && ld < d) || !mn_h || !mx_h || !y_d || !heldout_d || !alpha_d || !dec_out_d) {
-    set_error("svmd_train_decomp_heldout: bad arguments");
-    return SVM_ERR_ARG;
-  }
-  {  // what held-out mode refuses, before any device work (setup_solve checks the same)
-    const svm_params p = params_or_default(pp);
-    const char* what = shrink_cfg(p).on   ? "shrinking"
-                       : newton_cfg(p).on ? "the Newton polish (SVM355_DECOMP_NEWTON)"
-                                          : nullptr;
-    if (what) {
-      set_error("svmd_train_decomp_heldout: the held-out solve does not support %s", what);
-      return SVM_ERR_ARG;
-    }
-  }
   DecompOpts o;
-  o.trace = trace;
-  o.heldout = heldout_d;
-  o.heldout_dec = dec_out_d;
-  return train_decomp(ctx, X_d, is_u8 != 0, n, ld, d, mn_h, mx_h, y_d, alpha_d, pp, q, o, r, timing, stats, used_out);
+  o.mode.kind = DecompModeKind::heldout;
+  o.mode.heldout = heldout_d;
+  o.mode.heldout_out = dec_out_d;
+  return train_decomp_entry("svmd_train_decomp_heldout", h, X_d, is_u8, n, ld, d, mn_h, mx_h,
+                            y_d && heldout_d && dec_out_d, y_d, alpha_d, pp, q, o, r, timing, stats, used_out, trace);
 }
 
 // The decomposition solver's f update alone (tests): the uint8 rows quantised as a solve would, then
@@ -2410,7 +2305,7 @@ static int gemv_probe_u8(DeviceCtx* ctx, const uint8_t* Xu_d, int64_t n, int64_t
   S.n = twin ? 2 * n : n;
   S.lo = lo;
   S.nloc = twin ? 2 * n : nloc;
-  S.twin = twin;
+  S.mode.kind = twin ? DecompModeKind::twin : DecompModeKind::classify;
   S.nrow = n;
   S.p.gamma = gamma;
   const char* vc = getenv("SVM355_GEMV_VIA_CACHE");

@@ -433,6 +433,41 @@ def train_u8(Xu: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: SVM
                                       "rows": "uint8"}
 
 
+def _decomp_rows(X: torch.Tensor) -> int:
+    """The rows of a decomposition solve checked (uint8 pixel rows, or padded FP64 rows); their number."""
+    if X.dtype != torch.uint8:
+        _check_rows(X)
+    return X.shape[0]
+
+
+def _train_decomp(entry: str, solver: str, X: torch.Tensor, mn, mx, mode_args, params: SVMParams, working_set: int,
+                  trace, extra=lambda st: {}, after_ws=()) -> Optional[Tuple[SMOResult, dict]]:
+    """The body the ``svmd_train_decomp*`` wrappers share: the rows checked, the host statistics and the out
+    structs built, the entry called -- handle, rows and statistics, ``mode_args`` (the entry's own: labels or
+    targets, alpha, ...), parameters, working set, ``after_ws``, the out structs, the trace -- and the timing dict
+    with the wrapper's ``solver`` name and ``extra(stats)`` keys.  None when nothing ran."""
+    n, u8 = _decomp_rows(X), X.dtype == torch.uint8
+    ld = X.shape[1]
+    ctx = _ctx_for(X)
+    a, b, dd = _host_stats(mn, mx)
+    d = ld if u8 else dd
+    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
+    st = (ctypes.c_int64 * 16)()
+    p = params.to_struct()
+    N.check(getattr(ctx.lib, entry)(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), *mode_args,
+                                    ctypes.byref(p), int(working_set), *after_ws, ctypes.byref(r), ctypes.byref(tm),
+                                    st, ctypes.byref(used),
+                                    ctypes.byref(trace.struct) if trace is not None else None), entry)
+    if not used.value:
+        return None
+    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
+                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
+                                      "rows": "uint8" if u8 else "fp64", "solver": solver,
+                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
+                                      "working_set": int(st[2]), "update_columns": int(st[4]),
+                                      "inner_threads": int(st[5]), **extra(st)}
+
+
 def train_decomp(X: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
                  working_set: int = 1024, warm: bool = False,
                  trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:
@@ -444,29 +479,9 @@ def train_decomp(X: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: 
     ``N.DecompTrace`` filled per outer iteration (tests).  FP64 rows without an exact-integer plan
     (real-valued data) are solved with FP64-MFMA kernel values (``gram_path`` "fp64"); uint8 rows
     without one return None (the caller widens them)."""
-    u8 = X.dtype == torch.uint8
-    if not u8:
-        _check_rows(X)
-    n, ld = X.shape
-    ctx = _ctx_for(X)
-    a, b, dd = _host_stats(mn, mx)
-    d = ld if u8 else dd
-    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
-    st = (ctypes.c_int64 * 16)()
-    p = params.to_struct()
-    N.check(ctx.lib.svmd_train_decomp(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), N.ptr(y),
-                                      N.ptr(alpha), ctypes.byref(p), int(working_set), int(warm), ctypes.byref(r),
-                                      ctypes.byref(tm), st, ctypes.byref(used),
-                                      ctypes.byref(trace.struct) if trace is not None else None), "svmd_train_decomp")
-    if not used.value:
-        return None
-    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
-                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
-                                      "rows": "uint8" if u8 else "fp64", "solver": "decomp", "warm_start": bool(warm),
-                                      "warm_columns": int(st[7]), "outer_iterations": int(st[0]),
-                                      "inner_iterations": int(st[1]), "working_set": int(st[2]),
-                                      "update_columns": int(st[4]), "inner_threads": int(st[5]),
-                                      **N.shrink_stats(st)}
+    return _train_decomp("svmd_train_decomp", "decomp", X, mn, mx, (N.ptr(y), N.ptr(alpha)), params, working_set, trace,
+                         lambda st: {"warm_start": bool(warm), "warm_columns": int(st[7]), **N.shrink_stats(st)},
+                         after_ws=(int(warm),))
 
 
 def train_decomp_u8(Xu: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
@@ -490,33 +505,13 @@ def train_decomp_svr(X: torch.Tensor, z: torch.Tensor, alpha: torch.Tensor, para
     update runs over the n rows, as a classification of them.  Cold start only; shrinking, the Newton polish and
     class weights raise.  trace: an ``N.DecompTrace`` of 2n-long snapshots (tests).  None when nothing ran
     (uint8 rows without an exact-integer plan; FP64 rows whose workspace does not fit)."""
-    u8 = X.dtype == torch.uint8
-    if not u8:
-        _check_rows(X)
-    n, ld = X.shape
+    n = _decomp_rows(X)
     if z.dtype != torch.float64 or z.shape != (n,) or not z.is_contiguous():
         raise ValueError(f"z must be a contiguous float64 tensor of shape ({n},)")
     if alpha.dtype != torch.float64 or alpha.shape != (2 * n,) or not alpha.is_contiguous():
         raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({2 * n},): a, then a*")
-    ctx = _ctx_for(X)
-    a, b, dd = _host_stats(mn, mx)
-    d = ld if u8 else dd
-    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
-    st = (ctypes.c_int64 * 16)()
-    p = params.to_struct()
-    N.check(ctx.lib.svmd_train_decomp_svr(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), N.ptr(z),
-                                          float(epsilon), N.ptr(alpha), ctypes.byref(p), int(working_set),
-                                          ctypes.byref(r), ctypes.byref(tm), st, ctypes.byref(used),
-                                          ctypes.byref(trace.struct) if trace is not None else None),
-            "svmd_train_decomp_svr")
-    if not used.value:
-        return None
-    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
-                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
-                                      "rows": "uint8" if u8 else "fp64", "solver": "decomp-svr",
-                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
-                                      "working_set": int(st[2]), "update_columns": int(st[4]),
-                                      "inner_threads": int(st[5])}
+    return _train_decomp("svmd_train_decomp_svr", "decomp-svr", X, mn, mx, (N.ptr(z), float(epsilon), N.ptr(alpha)),
+                         params, working_set, trace)
 
 
 def train_decomp_oneclass(X: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx, nu: float = 0.5,
@@ -529,31 +524,11 @@ def train_decomp_oneclass(X: torch.Tensor, alpha: torch.Tensor, params: SVMParam
     raise.  The timing dict's "start_columns" counts the start's nonzero alphas (one f update per 1,024 of
     them before the first selection).  None when nothing ran (uint8 rows without an exact-integer plan; FP64
     rows whose workspace does not fit)."""
-    u8 = X.dtype == torch.uint8
-    if not u8:
-        _check_rows(X)
-    n, ld = X.shape
+    n = _decomp_rows(X)
     if alpha.dtype != torch.float64 or alpha.shape != (n,) or not alpha.is_contiguous():
         raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({n},)")
-    ctx = _ctx_for(X)
-    a, b, dd = _host_stats(mn, mx)
-    d = ld if u8 else dd
-    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
-    st = (ctypes.c_int64 * 16)()
-    p = params.to_struct()
-    N.check(ctx.lib.svmd_train_decomp_oneclass(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), float(nu),
-                                               N.ptr(alpha), ctypes.byref(p), int(working_set), ctypes.byref(r),
-                                               ctypes.byref(tm), st, ctypes.byref(used),
-                                               ctypes.byref(trace.struct) if trace is not None else None),
-            "svmd_train_decomp_oneclass")
-    if not used.value:
-        return None
-    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
-                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
-                                      "rows": "uint8" if u8 else "fp64", "solver": "decomp-oneclass",
-                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
-                                      "working_set": int(st[2]), "update_columns": int(st[4]),
-                                      "inner_threads": int(st[5]), "start_columns": int(st[7])}
+    return _train_decomp("svmd_train_decomp_oneclass", "decomp-oneclass", X, mn, mx, (float(nu), N.ptr(alpha)), params,
+                         working_set, trace, lambda st: {"start_columns": int(st[7])})
 
 
 def train_decomp_heldout(X: torch.Tensor, y: torch.Tensor, heldout: torch.Tensor, alpha: torch.Tensor,
@@ -566,34 +541,13 @@ def train_decomp_heldout(X: torch.Tensor, y: torch.Tensor, heldout: torch.Tensor
     decision values under a model that never saw them, from the training's own kernel values -- and 0.0 on the
     others.  Class weights are allowed; shrinking and the Newton polish raise.  The training part must hold both
     classes (check it on the host).  None when nothing ran, as ``train_decomp``."""
-    u8 = X.dtype == torch.uint8
-    if not u8:
-        _check_rows(X)
-    n, ld = X.shape
+    n = _decomp_rows(X)
     for name, t, dt in (("y", y, torch.int32), ("heldout", heldout, torch.uint8), ("alpha", alpha, torch.float64),
                         ("dec", dec, torch.float64)):
         if t.dtype != dt or t.shape != (n,) or not t.is_contiguous() or t.device != X.device:
             raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({n},) on the rows' device")
-    ctx = _ctx_for(X)
-    a, b, dd = _host_stats(mn, mx)
-    d = ld if u8 else dd
-    r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
-    st = (ctypes.c_int64 * 16)()
-    p = params.to_struct()
-    N.check(ctx.lib.svmd_train_decomp_heldout(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), N.ptr(y),
-                                              N.ptr(heldout), N.ptr(alpha), N.ptr(dec), ctypes.byref(p),
-                                              int(working_set), ctypes.byref(r), ctypes.byref(tm), st,
-                                              ctypes.byref(used),
-                                              ctypes.byref(trace.struct) if trace is not None else None),
-            "svmd_train_decomp_heldout")
-    if not used.value:
-        return None
-    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
-                                      "kcache": "none", "gram_path": "fp64" if st[6] else "int8-exact",
-                                      "rows": "uint8" if u8 else "fp64", "solver": "decomp-heldout",
-                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
-                                      "working_set": int(st[2]), "update_columns": int(st[4]),
-                                      "inner_threads": int(st[5])}
+    return _train_decomp("svmd_train_decomp_heldout", "decomp-heldout", X, mn, mx,
+                         (N.ptr(y), N.ptr(heldout), N.ptr(alpha), N.ptr(dec)), params, working_set, trace)
 
 
 def platt_fit(dec: torch.Tensor, y: torch.Tensor, use: Optional[torch.Tensor] = None) -> PlattResult:

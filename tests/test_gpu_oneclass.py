@@ -21,6 +21,7 @@ from svm355.ops import cpu as C
 from svm355.ops import device as D
 from svm355.utils.data import synthetic_mnist
 
+from decomp_mode_checks import check_refusal, pixel_rows
 from oneclass_checks import FIXTURE_DEC_TOL, FIXTURES, check_kkt, load_fixture
 from svr_checks import real_rows
 
@@ -197,3 +198,11 @@ def test_gpu_refusals(monkeypatch):
     monkeypatch.setenv("SVM355_DECOMP_NEWTON", "1")
     with pytest.raises(N.NativeError, match="Newton"):
         D.train_decomp_oneclass(Xd, alpha, SVMParams(), mn, mx, nu=0.3)
+
+
+@pytest.mark.parametrize("feature", ["shrinking", "newton", "weights"])
+def test_entry_refuses_under_its_name_and_enqueues_nothing(feature, monkeypatch):
+    rows = pixel_rows(DEV)
+    alpha = torch.empty(64, dtype=torch.float64, device=DEV)
+    check_refusal("svmd_train_decomp_oneclass", "one-class", feature,
+                  lambda p: D.train_decomp_oneclass(rows[0], alpha, p, rows[1], rows[2], nu=0.3), rows, monkeypatch)

@@ -14,6 +14,8 @@ from svm355.ops import cpu as C
 from svm355.ops import device as D
 from svm355.utils.data import synthetic_mnist
 
+from decomp_mode_checks import check_refusal
+from decomp_mode_checks import pixel_rows as mode_rows
 from probability_checks import (FIXTURES, GRAD_TOL, block0_mask, check_fixture, load_fixture, platt_gradient,
                                 proba_rows, synthetic_pairs)
 
@@ -293,3 +295,14 @@ def test_estimator_refusals_on_the_gpu():
         SVC(device="cuda:0", probability=True).fit(X, y, folds=np.where(y == 1, 0, 1 + np.arange(80) % 3))
     with pytest.raises(ValueError, match="predict_proba needs"):
         SVC(device="cuda:0").fit(X, y).predict_proba(X)
+
+
+@pytest.mark.parametrize("feature", ["shrinking", "newton"])  # class weights are allowed
+def test_entry_refuses_under_its_name_and_enqueues_nothing(feature, monkeypatch):
+    rows = mode_rows(DEV)
+    mask = torch.from_numpy((np.arange(64) % 4 == 3).astype(np.uint8)).to(DEV)
+    alpha = torch.empty(64, dtype=torch.float64, device=DEV)
+    dec = torch.empty(64, dtype=torch.float64, device=DEV)
+    check_refusal("svmd_train_decomp_heldout", "held-out", feature,
+                  lambda p: D.train_decomp_heldout(rows[0], rows[3], mask, alpha, dec, p, rows[1], rows[2]), rows,
+                  monkeypatch)

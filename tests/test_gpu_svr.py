@@ -24,6 +24,7 @@ from svm355.ops import device as D
 from svm355.utils.data import synthetic_mnist
 
 from svr_checks import FIXTURE_PRED_TOL, check_kkt, load_fixture, real_rows
+from decomp_mode_checks import check_refusal, pixel_rows
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -264,3 +265,12 @@ def test_gpu_refusals(monkeypatch):
     monkeypatch.setenv("SVM355_DECOMP_NEWTON", "1")
     with pytest.raises(N.NativeError, match="Newton"):
         D.train_decomp_svr(Xd, zd, alpha, SVMParams(), mn.cpu().numpy(), mx.cpu().numpy())
+
+
+@pytest.mark.parametrize("feature", ["shrinking", "newton", "weights"])
+def test_entry_refuses_under_its_name_and_enqueues_nothing(feature, monkeypatch):
+    rows = pixel_rows(DEV)
+    z = torch.linspace(0.0, 1.0, 64, dtype=torch.float64, device=DEV)
+    alpha = torch.empty(128, dtype=torch.float64, device=DEV)
+    check_refusal("svmd_train_decomp_svr", "regression (twin)", feature,
+                  lambda p: D.train_decomp_svr(rows[0], z, alpha, p, rows[1], rows[2]), rows, monkeypatch)
