@@ -31,13 +31,16 @@ import os
 import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
 from typing import List, Optional
 
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
-from ..utils.data import MinMaxScaler, check_finite_bounds
+from ..utils.data import MinMaxScaler
 from ..utils.trace import trace_range
+from ._device import (TrainRows, _resolve_device, check_query_shape, device_model_from_host, scale_queries, scaled_cpu,
+                      solve_on_rows)
 
 
 _POOL_LOCK = threading.Lock()
@@ -107,6 +110,37 @@ def _thread_stream(device):
     return ss[key]
 
 
+@contextmanager
+def pool_stream(device, frac: float):
+    """The body of a solve on a pool thread: the thread's column-cache share set to ``frac``, its stream entered
+    (and yielded), and that stream synchronised on the way out."""
+    import torch
+
+    from .. import _native as N
+    from ..ops import device as D
+
+    s = _thread_stream(device)
+    ctx = D.DeviceContext.get(device)
+    N.check(ctx.lib.svmd_set_ccache_frac(ctx.handle, frac), "svmd_set_ccache_frac")
+    with torch.cuda.stream(s):
+        yield s
+    s.synchronize()
+
+
+def pool_shape(n_tasks: int, concurrent_solves: Optional[int], n: int, d: int):
+    """(width, frac) of the pool for ``n_tasks`` solves on n x d rows.  Width: ``concurrent_solves``, or all
+    tasks side by side while the rows sit in the last-level cache (the solves are bound by their one-CU inner
+    chains); past 192 MiB of pixel rows (where the column cache turns on) they are bound by HBM passes over the
+    rows and two at a time is fastest (1M: 5.7 s against 7.6 s one at a time and 9-14 s all ten,
+    profiles/r5_ovr_large_n.txt); never more than ``n_tasks``.  frac: every solving thread's context keeps one
+    column-cache slab for all its solves and for the next fit -- freeing and re-allocating a tens-of-GB slab made
+    the later solves' caches 2-7x slower per outer iteration (profiles/r5_ovr_large_n.txt) -- the slabs of a
+    pool together capped at half the HBM; release_solver_caches() hands them back."""
+    big = n * d > (192 << 20)
+    width = max(1, min(int(concurrent_solves or (2 if big else n_tasks)), n_tasks))
+    return width, min(0.25, 0.5 / width)
+
+
 class OneVsRestSVC:
     def __init__(self, C: float = 10.0, gamma: float = 0.00125, tol: float = 1e-5, eps: float = 1e-12,
                  sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
@@ -148,11 +182,7 @@ class OneVsRestSVC:
         self.gram = gram
 
     def _dev(self) -> str:
-        if self.device == "auto":
-            import torch
-
-            return "cuda" if torch.cuda.is_available() else "cpu"
-        return self.device
+        return _resolve_device(self.device)
 
     # ------------------------------------------------------------------ fit
     def fit(self, X: np.ndarray, labels: np.ndarray, classes: Optional[List[int]] = None,
@@ -214,9 +244,7 @@ class OneVsRestSVC:
     def _fit_cpu(self, X, labels):
         from ..ops import cpu as C
 
-        self.scaler_ = MinMaxScaler().fit(X)
-        check_finite_bounds(self.scaler_.min_, self.scaler_.max_)
-        Xs = self.scaler_.transform(X)
+        Xs, self.scaler_ = scaled_cpu(X)
         K = C.rbf_matrix(Xs, Xs, self.params.gamma, self.params.n_threads)
         ys = self._ys(labels)
         alphas = np.zeros((len(ys), X.shape[0]))
@@ -243,31 +271,23 @@ class OneVsRestSVC:
             return self._fit_cuda_decomp(X, labels, device)
         if self.class_weight is not None:
             raise ValueError("class_weight is not supported by the GPU pairwise solvers (batched / streams)")
-        t0 = time.perf_counter()
-        d = X.shape[1]
-        Xu = K = None
-        if X.dtype == np.uint8 and self.gram in ("auto", "int") and os.environ.get("SVM355_U8_TRAIN", "1") != "0":
-            # byte path (as SVC._fit_cuda_u8): min/max, quantisation and Gram from the device bytes
-            Xu = D.upload_u8(X, device)
-            mn, mx = D.minmax_u8(Xu)
-            mm = torch.cat([mn, mx]).cpu().numpy()
-            mn_h, mx_h = mm[:d].copy(), mm[d:].copy()
+        n = X.shape[0]
+
+        def gram(r: TrainRows):
+            nonlocal t1
             t1 = time.perf_counter()
-            with trace_range("svm355.ovr.gram"):
-                K = D.rbf_gram_u8(Xu, self.params.gamma, mn_h, mx_h, out=D.gram_buffer(X.shape[0], device))
-            path = "int8-exact"
-        if K is None:
-            Xu = None
-            t0 = time.perf_counter()
-            Xd = D.upload_rows(X, device)
-            mn, mx, sqn = D.minmax_scale_(Xd, d)
-            check_finite_bounds(mn.cpu().numpy(), mx.cpu().numpy())
-            t1 = time.perf_counter()
-            K, path = D.rbf_gram_sym(Xd, sqn, self.params.gamma, mn=mn, mx=mx, gram=self.gram,
-                                     out=D.gram_buffer(X.shape[0], device))
+            if r.sqn is None:  # byte rows (as SVC's byte path): quantisation and Gram from the device bytes
+                with trace_range("svm355.ovr.gram"):
+                    K = D.rbf_gram_u8(r.rows, self.params.gamma, r.mn_h, r.mx_h, out=D.gram_buffer(n, device))
+                return None if K is None else (K, "int8-exact")
+            return D.rbf_gram_sym(r.rows, r.sqn, self.params.gamma, mn=r.mn, mx=r.mx, gram=self.gram,
+                                  out=D.gram_buffer(n, device))
+
+        t1 = 0.0
+        rows, (K, path) = solve_on_rows(X, device, gram, bytes_ok=self.gram in ("auto", "int")
+                                        and os.environ.get("SVM355_U8_TRAIN", "1") != "0")
         torch.cuda.synchronize(device)
         t2 = time.perf_counter()
-        n = X.shape[0]
         alphas = torch.zeros((len(self.classes_), n), dtype=torch.float64, device=device)
         ys = self._ys(labels)
         ys_d = [torch.from_numpy(y).to(device) for y in ys]
@@ -314,14 +334,9 @@ class OneVsRestSVC:
         Y = np.stack(ys, 0)
         sup = np.flatnonzero((a > self.params.sv_tol).any(0)).astype(np.int64)
         self._finish(sup, (a * Y).T, bs, iters, stops)
-        idx = torch.from_numpy(self.support_).to(device)
-        Xs, ns = D.sv_rows_u8(Xu, idx, mn, mx) if Xu is not None else (D.gather_rows(Xd, idx), sqn[idx].contiguous())
-        self._dev_model = {"Xs": Xs, "ns": ns,
-                           "coef": torch.from_numpy(np.ascontiguousarray(self.dual_coef_)).to(device),
-                           "b": torch.tensor(self.intercepts_b_, dtype=torch.float64, device=device),
-                           "mn": mn, "mx": mx, "d": d, "device": device}
-        self.scaler_ = MinMaxScaler(mn.cpu().numpy(), mx.cpu().numpy())
-        self.timings_ = {"upload_preprocess_ms": (t1 - t0) * 1e3, "gram_ms": (t2 - t1) * 1e3,
+        self._dev_model = rows.model(self.support_, self.dual_coef_, b=self.intercepts_b_)
+        self.scaler_ = rows.scaler()
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, "gram_ms": (t2 - t1) * 1e3,
                          "smo_ms_all_classes": (t3 - t2) * 1e3, "gram_path": path,
                          "smo_solver": "batched" if self.batched_ else "streams"}
 
@@ -332,20 +347,7 @@ class OneVsRestSVC:
         from .. import _native as N
         from ..ops import device as D
 
-        t0 = time.perf_counter()
-        d = X.shape[1]
-        Xu = Xd = sqn = None
-        if X.dtype == np.uint8:
-            Xu = D.upload_u8(X, device)
-            mn, mx = D.minmax_u8(Xu)
-            rows = Xu
-        else:
-            Xd = D.upload_rows(X, device)
-            mn, mx, sqn = D.minmax_scale_(Xd, d)
-            check_finite_bounds(mn.cpu().numpy(), mx.cpu().numpy())
-            rows = Xd
-        mm = torch.cat([mn, mx]).cpu().numpy()
-        mn_h, mx_h = mm[:d].copy(), mm[d:].copy()
+        rows = TrainRows.upload(X, device)
         t1 = time.perf_counter()
         n = X.shape[0]
         ys = self._ys(labels)
@@ -353,27 +355,11 @@ class OneVsRestSVC:
         alphas = torch.zeros((len(self.classes_), n), dtype=torch.float64, device=device)
         torch.cuda.synchronize(device)
         mine = [k for k in range(len(ys)) if self._mine(k)]
-
-        # all classes side by side while the rows sit in the last-level cache (the solves are bound by their
-        # one-CU inner chains); past 192 MiB of pixel rows (where the column cache turns on) they are bound
-        # by HBM passes over the rows and two at a time is fastest (1M: 5.7 s against 7.6 s one at a time
-        # and 9-14 s all ten, profiles/r5_ovr_large_n.txt)
-        big = X.shape[0] * X.shape[1] > (192 << 20)
-        workers = self.concurrent_solves or (2 if big else len(mine))
-        width = min(workers, max(1, len(mine)))
-        # Large n: every solving thread's context keeps one column-cache slab for all its classes and for the
-        # next fit -- freeing and re-allocating a tens-of-GB slab made the later solves' caches 2-7x slower
-        # per outer iteration (per class, and again per fit: profiles/r5_ovr_large_n.txt) -- the slabs of a
-        # pool together capped at half the HBM; release_solver_caches() hands them back.
-        frac = min(0.25, 0.5 / width)
+        width, frac = pool_shape(len(mine), self.concurrent_solves, *X.shape)
 
         def solve(k):
-            s = _thread_stream(device)
-            ctx = D.DeviceContext.get(device)
-            N.check(ctx.lib.svmd_set_ccache_frac(ctx.handle, frac), "svmd_set_ccache_frac")
-            with torch.cuda.stream(s):
-                out = D.train_decomp(rows, ys_d[k], alphas[k], self._class_params[k], mn_h, mx_h)
-            s.synchronize()
+            with pool_stream(device, frac):
+                out = D.train_decomp(rows.rows, ys_d[k], alphas[k], self._class_params[k], rows.mn_h, rows.mx_h)
             if out is None:
                 raise N.NativeError(f"class {self.classes_[k]}: the decomposition solver declined these rows "
                                     "(no exact-integer plan for uint8 rows, or beyond its shapes); use "
@@ -392,16 +378,11 @@ class OneVsRestSVC:
         Y = np.stack(ys, 0)
         sup = np.flatnonzero((a > self.params.sv_tol).any(0)).astype(np.int64)
         self._finish(sup, (a * Y).T, bs, iters, stops)
-        idx = torch.from_numpy(self.support_).to(device)
-        Xs, ns = D.sv_rows_u8(Xu, idx, mn, mx) if Xu is not None else (D.gather_rows(Xd, idx), sqn[idx].contiguous())
-        self._dev_model = {"Xs": Xs, "ns": ns,
-                           "coef": torch.from_numpy(np.ascontiguousarray(self.dual_coef_)).to(device),
-                           "b": torch.tensor(self.intercepts_b_, dtype=torch.float64, device=device),
-                           "mn": mn, "mx": mx, "d": d, "device": device}
-        self.scaler_ = MinMaxScaler(mn_h, mx_h)
+        self._dev_model = rows.model(self.support_, self.dual_coef_, b=self.intercepts_b_)
+        self.scaler_ = rows.scaler()
         self.batched_ = False
         self.class_timings_ = {int(self.classes_[k]): outs[k][1] for k in outs}
-        self.timings_ = {"upload_preprocess_ms": (t1 - t0) * 1e3, "gram_ms": 0.0,
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, "gram_ms": 0.0,
                          "smo_ms_all_classes": (t2 - t1) * 1e3, "gram_path": "none (decomposition)",
                          "smo_solver": "decomp"}
 
@@ -495,19 +476,7 @@ class OneVsRestSVC:
         if m._dev() != "cpu":
             if m.scaler_ is None:
                 raise ValueError("a device model needs the saved scaler (scaler.npz)")
-            import torch
-
-            from ..ops import device as D
-
-            dev = torch.device(m._dev())
-            k, dd = m.support_vectors_.shape
-            Xs = D.upload_rows(m.support_vectors_, dev)
-            mm = np.concatenate([m.scaler_.min_, m.scaler_.max_]).astype(np.float64)
-            mmd = torch.from_numpy(mm).to(dev)
-            m._dev_model = {"Xs": Xs, "ns": D.row_norms(Xs, dd),
-                            "coef": torch.from_numpy(np.ascontiguousarray(coef)).to(dev),
-                            "b": torch.tensor(m.intercepts_b_, dtype=torch.float64, device=dev),
-                            "mn": mmd[:dd], "mx": mmd[dd:], "d": dd, "device": dev}
+            m._dev_model = device_model_from_host(m.support_vectors_, m.scaler_, coef, m._dev(), b=m.intercepts_b_)
         return m
 
     # ------------------------------------------------------------------ inference
@@ -515,23 +484,19 @@ class OneVsRestSVC:
         """(m, classes) decision values sum_k coef_kc K(x, sv_k) - b_c."""
         d = (int(self._dev_model["d"]) if self._dev_model is not None else
              int(np.size(self.scaler_.min_)) if self.scaler_ is not None else int(np.shape(self.support_vectors_)[1]))
-        if np.ndim(X) != 2 or np.shape(X)[1] != d:
-            raise ValueError(f"X must be (m, {d}) like the training rows, got shape {np.shape(X)}")
-        X = np.ascontiguousarray(X, dtype=np.uint8 if (self._dev_model is not None and X.dtype == np.uint8)
-                                 else np.float64)
+        check_query_shape(X, d)
         if self._dev_model is not None:
             import torch
 
             from ..ops import device as D
 
             dm = self._dev_model
-            Xq = D.upload_rows(X, dm["device"])
-            _, _, nq = D.minmax_scale_(Xq, dm["d"], dm["mn"], dm["mx"])
+            Xq, nq = scale_queries(dm, X)
             Kq = D.rbf_gram(Xq, nq, dm["Xs"], dm["ns"], self.params.gamma)[:, : dm["Xs"].shape[0]]
             return (torch.matmul(Kq, dm["coef"]) - dm["b"]).cpu().numpy()
         from ..ops import cpu as C
 
-        Xq = self.scaler_.transform(X)
+        Xq = self.scaler_.transform(np.ascontiguousarray(X, dtype=np.float64))
         Kq = C.rbf_matrix(Xq, self.support_vectors_, self.params.gamma, self.params.n_threads)
         return Kq @ self.dual_coef_ - self.intercepts_b_
 

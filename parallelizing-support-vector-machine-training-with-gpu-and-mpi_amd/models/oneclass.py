@@ -16,18 +16,16 @@ from __future__ import annotations
 
 import os
 import time
-from typing import Optional
 
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
-from ..utils.data import MinMaxScaler, check_finite_bounds
-from .svc import _is_u8, _resolve_device
+from ._device import KernelEstimator, _is_u8, _resolve_device, solve_on_rows
 
 KIND = "oneclass"  # model files' kind marker (model_io)
 
 
-class OneClassSVM:
+class OneClassSVM(KernelEstimator):
     def __init__(self, nu: float = 0.5, gamma: float = 0.00125, tol: float = 1e-5, eps: float = 1e-12,
                  sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
                  scale: bool = True, working_set: int = 1024):
@@ -40,9 +38,6 @@ class OneClassSVM:
         self.device = device
         self.scale = scale
         self.working_set = int(working_set)
-        self.scaler_ = None
-        self._sv_host = None
-        self._dev = None  # device-side model state (torch tensors)
 
     # ------------------------------------------------------------------ fit
     def fit(self, X: np.ndarray, y=None) -> "OneClassSVM":
@@ -80,15 +75,7 @@ class OneClassSVM:
     def _fit_cpu(self, X):
         from ..ops import cpu as C
 
-        if self.scale:
-            self.scaler_ = MinMaxScaler().fit(X)
-            check_finite_bounds(self.scaler_.min_, self.scaler_.max_)
-            Xs = self.scaler_.transform(X)
-        else:
-            if not np.all(np.isfinite(X)):
-                raise ValueError("X holds NaN or infinite values")
-            self.scaler_ = None
-            Xs = X
+        Xs = self._scaled_cpu(X)
         alpha, res = C.smo_train_oneclass(Xs, self.params, self.nu)
         self._finish(alpha, res)
         self._dev = None
@@ -101,75 +88,28 @@ class OneClassSVM:
         from ..ops import device as D
 
         device = torch.device(dev)
-        n, d = X.shape
-        t0 = time.perf_counter()
-        alpha = torch.empty(n, dtype=torch.float64, device=device)  # the start is written on the device
-        out = None
-        if X.dtype == np.uint8:  # pixel rows stay bytes on the device (the exact-integer plan reads them)
-            Xu = D.upload_u8(X, device)
-            mmd = torch.empty(2 * d, dtype=torch.float64, device=device)
-            mn, mx = D.minmax_u8(Xu, out=mmd)
-            mm_h = mmd.cpu().numpy()
-            check_finite_bounds(mm_h[:d], mm_h[d:])
-            t1 = time.perf_counter()
-            out = D.train_decomp_oneclass(Xu, alpha, self.params, mm_h[:d], mm_h[d:], nu=self.nu,
-                                          working_set=self.working_set)
-            if out is not None:
-                sv_rows = lambda idx: D.sv_rows_u8(Xu, idx, mn, mx)  # noqa: E731
-        if out is None:  # FP64 rows: scaled on the device, quantised when they admit the plan, else FP64 MFMA
-            Xd = D.upload_rows(X, device)
-            mn, mx, sqn = D.minmax_scale_(Xd, d)
-            mm_h = mn.as_strided((2 * d,), (1,)).cpu().numpy()  # both bounds (one buffer), one copy
-            check_finite_bounds(mm_h[:d], mm_h[d:])
-            torch.cuda.synchronize(device)
-            t1 = time.perf_counter()
-            out = D.train_decomp_oneclass(Xd, alpha, self.params, mm_h[:d], mm_h[d:], nu=self.nu,
-                                          working_set=self.working_set)
-            if out is None:
-                raise ValueError("OneClassSVM: the decomposition solver does not cover these rows (its FP64-row "
-                                 "workspace, n x 1024 doubles, does not fit the device)")
-            sv_rows = lambda idx: (D.gather_rows(Xd, idx), sqn[idx].contiguous())  # noqa: E731
+        alpha = torch.empty(X.shape[0], dtype=torch.float64, device=device)  # the start is written on the device
+        # pixel rows stay bytes on the device (the exact-integer plan reads them); FP64 rows are scaled there and
+        # quantised when they admit the plan, else solved with FP64-MFMA kernel values
+        rows, out = solve_on_rows(X, device, lambda r: D.train_decomp_oneclass(
+            r.rows, alpha, self.params, r.mn_h, r.mx_h, nu=self.nu, working_set=self.working_set))
+        if out is None:
+            raise ValueError("OneClassSVM: the decomposition solver does not cover these rows (its FP64-row "
+                             "workspace, n x 1024 doubles, does not fit the device)")
         res, tm = out
         self._finish(alpha.cpu().numpy(), res)
-        idx = torch.from_numpy(self.support_).to(device)
-        Xs, ns = sv_rows(idx)
-        self._dev = {"Xs": Xs, "ns": ns, "coef": torch.from_numpy(self.dual_coef_).to(device), "mn": mn, "mx": mx,
-                     "d": d, "device": device}
-        self.scaler_ = MinMaxScaler(mm_h[:d].copy(), mm_h[d:].copy())
-        self._sv_host = None  # scaled SV rows stay on the device; copied to the host on first access
-        self.timings_ = {"upload_preprocess_ms": (t1 - t0) * 1e3, **tm}
-
-    @property
-    def support_vectors_(self) -> np.ndarray:
-        """Scaled support-vector rows (host copy, fetched lazily from the device model)."""
-        if self._sv_host is None and self._dev is not None:
-            self._sv_host = self._dev["Xs"][:, : self._dev["d"]].cpu().numpy()
-        return self._sv_host
-
-    @support_vectors_.setter
-    def support_vectors_(self, value) -> None:
-        self._sv_host = value
+        self._adopt_rows(rows)
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 
     # ------------------------------------------------------------------ inference
-    def _n_features(self) -> Optional[int]:
-        if self._dev is not None:
-            return int(self._dev["d"])
-        if self.scaler_ is not None and self.scaler_.min_ is not None:
-            return int(np.size(self.scaler_.min_))
-        sv = self.support_vectors_
-        return int(sv.shape[1]) if sv is not None and np.ndim(sv) == 2 else None
-
     def decision_function(self, X: np.ndarray) -> np.ndarray:
         """sum_k alpha_k K(x_k, x) - rho over the support vectors."""
-        d = self._n_features()
-        if np.ndim(X) != 2 or (d is not None and np.shape(X)[1] != d):
-            raise ValueError(f"X must be (m, {d}) like the training rows, got shape {np.shape(X)}")
+        self._check_X(X)
         if self._dev is not None:
             from ..ops import device as D
 
             dv = self._dev
-            Xq = D.upload_rows(np.ascontiguousarray(X, dtype=np.uint8 if _is_u8(X) else np.float64), dv["device"])
-            _, _, nq = D.minmax_scale_(Xq, dv["d"], dv["mn"], dv["mx"])
+            Xq, nq = self._device_queries(X)
             return D.decision(dv["Xs"], dv["ns"], dv["coef"], Xq, nq, self.params.gamma, self.rho_).cpu().numpy()
         from ..ops import cpu as C
 
@@ -220,16 +160,6 @@ class OneClassSVM:
         return oc
 
     def _upload_model(self, dev: str) -> None:
-        import torch
-
-        from ..ops import device as D
-
         if self.scaler_ is None:
             raise ValueError("OneClassSVM on a GPU needs a scaled model (scale=True)")
-        device = torch.device(dev)
-        d = self.support_vectors_.shape[1]
-        Xs = D.upload_rows(self.support_vectors_, device)  # sum alpha = nu n > 0: there is always a support vector
-        self._dev = {"Xs": Xs, "ns": D.row_norms(Xs, d),
-                     "coef": torch.from_numpy(np.ascontiguousarray(self.dual_coef_)).to(device),
-                     "mn": torch.from_numpy(self.scaler_.min_).to(device),
-                     "mx": torch.from_numpy(self.scaler_.max_).to(device), "d": d, "device": device}
+        super()._upload_model(dev)

@@ -51,8 +51,10 @@ from typing import List, Optional
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
-from ..utils.data import MinMaxScaler, check_finite_bounds, check_folds_multiclass, stratified_folds
+from ..utils.data import MinMaxScaler, check_folds_multiclass, stratified_folds
 from ..utils.trace import trace_range
+from ._device import (TrainRows, _resolve_device, check_query_shape, device_model_from_host, platt_probability,
+                      scale_queries, scaled_cpu)
 
 MAX_CLASSES = 64  # the vote kernel keeps the k (k - 1) segment sums of a query row in LDS (32 KB at 64)
 FORMAT = "svm355-ovo-v1"
@@ -103,11 +105,7 @@ class OneVsOneSVC:
         self._dev_model = None
 
     def _dev(self) -> str:
-        if self.device == "auto":
-            import torch
-
-            return "cuda" if torch.cuda.is_available() else "cpu"
-        return self.device
+        return _resolve_device(self.device)
 
     # ------------------------------------------------------------------ fit
     def fit(self, X: np.ndarray, labels: np.ndarray, classes: Optional[List[int]] = None,
@@ -159,9 +157,8 @@ class OneVsOneSVC:
     def _fit_cpu(self, X, order, cstart, folds=None):
         from ..ops import cpu as C
 
-        self.scaler_ = MinMaxScaler().fit(X)
-        check_finite_bounds(self.scaler_.min_, self.scaler_.max_)
-        Xg = self.scaler_.transform(X)[order]  # scaled, class-grouped
+        Xg, self.scaler_ = scaled_cpu(X)
+        Xg = Xg[order]  # scaled, class-grouped
         K = C.rbf_matrix(Xg, Xg, self.params.gamma, self.params.n_threads)
         alphas, results, timings = [], [], {}
         for p, (a, b) in enumerate(self._pairs):
@@ -230,29 +227,18 @@ class OneVsOneSVC:
 
         from .. import _native as N
         from ..ops import device as D
-        from .multiclass import _pool, _thread_stream
+        from .multiclass import _pool, pool_shape, pool_stream
 
         device = torch.device(self._dev())
         t0 = time.perf_counter()
-        d = X.shape[1]
-        order_d = torch.from_numpy(order).to(device)
-        Xu = Xd = sqn = None
-        if X.dtype == np.uint8:
-            Xu = D.upload_u8(X, device)
-            mn, mx = D.minmax_u8(Xu)
-            grouped = Xu[order_d].contiguous()  # the one row gather
-        else:
-            Xd = D.upload_rows(X, device)
-            mn, mx, sqn = D.minmax_scale_(Xd, d)
-            grouped = D.gather_rows(Xd, order_d)
-        mm = torch.cat([mn, mx]).cpu().numpy()
-        mn_h, mx_h = mm[:d].copy(), mm[d:].copy()
-        check_finite_bounds(mn_h, mx_h)
+        rows = TrainRows.upload(X, device)
+        mn_h, mx_h = rows.mn_h, rows.mx_h
+        grouped = rows.take(order)  # the one row gather
         torch.cuda.synchronize(device)
         t1 = time.perf_counter()
         P = len(self._pairs)
         width = max(1, min(int(self.concurrent_solves or 10), P))
-        frac = min(0.25, 0.5 / width)
+        frac = pool_shape(P, width, *X.shape)[1]
 
         # Tasks, pair-major: a pair's own solve (j = -1: train_decomp, what cv=None runs), then with folds its
         # fold solves (the held-out mode on the same packed rows; a fold with none of the pair's rows is skipped).
@@ -296,11 +282,8 @@ class OneVsOneSVC:
 
         def solve(task):
             p, j = task
-            s = _thread_stream(device)
-            ctx = D.DeviceContext.get(device)
-            N.check(ctx.lib.svmd_set_ccache_frac(ctx.handle, frac), "svmd_set_ccache_frac")
             al = dec = None
-            with torch.cuda.stream(s):
+            with pool_stream(device, frac) as s:
                 st = packed(p, s)
                 alpha = torch.zeros(sizes[p], dtype=torch.float64, device=device)
                 if j < 0:
@@ -311,7 +294,6 @@ class OneVsOneSVC:
                     dec = torch.zeros(sizes[p], dtype=torch.float64, device=device)
                     out = D.train_decomp_heldout(st["rows"], st["y"], (st["folds"] == j).to(torch.uint8), alpha, dec,
                                                  self.params, mn_h, mx_h, working_set=self.working_set)
-            s.synchronize()
             if out is None:
                 raise N.NativeError(f"pair {self._pair_label(p)}: the decomposition solver declined these rows (no "
                                     "exact-integer plan for uint8 rows, or beyond its shapes); pass the rows as "
@@ -335,10 +317,8 @@ class OneVsOneSVC:
         t2 = time.perf_counter()
         outs = [o for t, o in zip(tasks, every) if t[1] < 0]
         keep = self._finish([o[0] for o in outs], [o[1] for o in outs], order, cstart)
-        idx = torch.from_numpy(self.support_).to(device)
-        Xs, ns = D.sv_rows_u8(Xu, idx, mn, mx) if Xu is not None else (D.gather_rows(Xd, idx), sqn[idx].contiguous())
-        self.scaler_ = MinMaxScaler(mn_h, mx_h)
-        self._set_dev_model(Xs, ns, mn, mx, d, device)
+        self._dev_model = rows.model(self.support_, self.dual_coef_, start=self._start(), rho=self.rho_)
+        self.scaler_ = rows.scaler()
         self.pair_timings_ = {self._pair_label(p): outs[p][2] for p in range(P)}
         paths = sorted({o[2]["gram_path"] for o in outs})
         self.timings_ = {"upload_preprocess_ms": (t1 - t0) * 1e3, "smo_ms_all_pairs": (t2 - t1) * 1e3,
@@ -382,14 +362,6 @@ class OneVsOneSVC:
 
     def _start(self) -> np.ndarray:
         return np.concatenate([[0], np.cumsum(self.n_support_)]).astype(np.int32)
-
-    def _set_dev_model(self, Xs, ns, mn, mx, d, device) -> None:
-        import torch
-
-        self._dev_model = {"Xs": Xs, "ns": ns, "mn": mn, "mx": mx, "d": d, "device": device,
-                           "start": torch.from_numpy(self._start()).to(device),
-                           "coef": torch.from_numpy(np.ascontiguousarray(self.dual_coef_)).to(device),
-                           "rho": torch.from_numpy(np.ascontiguousarray(self.rho_)).to(device)}
 
     # ------------------------------------------------------------------ persistence
     def _host_sv_rows(self) -> np.ndarray:
@@ -463,30 +435,19 @@ class OneVsOneSVC:
         m.stop_reasons_ = list(info.get("stop_reasons", [""] * len(m._pairs)))
         m._dev_model = None
         if m._dev() != "cpu":
-            import torch
-
-            from ..ops import device as D
-
-            dev = torch.device(m._dev())
-            dd = int(np.size(m.scaler_.min_))
-            Xs = D.upload_rows(m.support_vectors_.reshape(S, dd), dev)
-            mmd = torch.from_numpy(np.concatenate([m.scaler_.min_, m.scaler_.max_]).astype(np.float64)).to(dev)
-            m._set_dev_model(Xs, D.row_norms(Xs, dd), mmd[:dd], mmd[dd:], dd, dev)
+            m._dev_model = device_model_from_host(m.support_vectors_.reshape(S, int(np.size(m.scaler_.min_))), m.scaler_,
+                                                  m.dual_coef_, m._dev(), start=m._start(), rho=m.rho_)
         return m
 
     # ------------------------------------------------------------------ inference
     def _decide(self, X: np.ndarray, want_dec: bool, on_device: bool = False):
         d = int(np.size(self.scaler_.min_))
-        if np.ndim(X) != 2 or np.shape(X)[1] != d:
-            raise ValueError(f"X must be (m, {d}) like the training rows, got shape {np.shape(X)}")
-        X = np.ascontiguousarray(X, dtype=np.uint8 if (self._dev_model is not None and X.dtype == np.uint8)
-                                 else np.float64)
+        check_query_shape(X, d)
         if self._dev_model is not None:
             from ..ops import device as D
 
             dm = self._dev_model
-            Xq = D.upload_rows(X, dm["device"])
-            _, _, nq = D.minmax_scale_(Xq, dm["d"], dm["mn"], dm["mx"])
+            Xq, nq = scale_queries(dm, X)
             dec, lab = D.ovo_predict(dm["Xs"], dm["ns"], Xq, nq, self.params.gamma, dm["start"], dm["coef"],
                                      dm["rho"], want_dec=want_dec)
             if on_device:
@@ -497,7 +458,7 @@ class OneVsOneSVC:
         # the CPU oracle's arithmetic, pair by pair: from -rho over the pair's support vectors in ascending
         # training-row order (svm_decision), so that k = 2 is SVC(device="cpu") bit for bit; the vote is
         # ovo_votes' rule
-        Xq = self.scaler_.transform(X)
+        Xq = self.scaler_.transform(np.ascontiguousarray(X, dtype=np.float64))
         sv = self.support_vectors_.reshape(len(self.support_), d)
         start = self._start()
         dec = np.empty((Xq.shape[0], len(self._pairs)))
@@ -540,11 +501,10 @@ class OneVsOneSVC:
             return D.ovo_couple(dec, dm["probA"], dm["probB"], want_label=False)[0].cpu().numpy()
         from ..ops import cpu as C
 
-        # The pair probabilities by the expression of SVC.predict_proba (numpy's exp, which is not libm's), so
-        # that k = 2 gives SVC's P(+1) bit for bit; the twin takes them as they are (A = B = None).
+        # The pair probabilities P(+1) by SVC.predict_proba's own expression, so that k = 2 gives them bit for
+        # bit; the twin takes them as they are (A = B = None).
         z = self._decide(X, True)[0] * self.probA_ + self.probB_
-        e = np.exp(-np.abs(z))
-        return C.ovo_couple(np.where(z >= 0, e / (1.0 + e), 1.0 / (1.0 + e)), n_threads=self.params.n_threads)[0]
+        return C.ovo_couple(np.ascontiguousarray(platt_probability(z)[..., 1]), n_threads=self.params.n_threads)[0]
 
     def score(self, X: np.ndarray, labels: np.ndarray) -> float:
         return float(np.mean(self.predict(X) == np.asarray(labels)))

@@ -25,23 +25,11 @@ from typing import Optional
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
-from ..utils.data import (MinMaxScaler, check_finite_bounds, check_folds, check_warm_start, resolve_class_weight,
-                          stratified_folds)
+from ..utils.data import check_folds, check_warm_start, resolve_class_weight, stratified_folds
+from ._device import KernelEstimator, _is_u8, _resolve_device, platt_probability, scaled_cpu, solve_on_rows
 
 
-def _resolve_device(device: str) -> str:
-    if device == "auto":
-        import torch
-
-        return "cuda" if torch.cuda.is_available() else "cpu"
-    return device
-
-
-def _is_u8(X) -> bool:
-    return isinstance(X, np.ndarray) and X.dtype == np.uint8
-
-
-class SVC:
+class SVC(KernelEstimator):
     def __init__(self, C: float = 10.0, gamma: float = 0.00125, tol: float = 1e-5, eps: float = 1e-12,
                  sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
                  scale: bool = True, zero_is_positive: bool = False, gram: str = "auto", kcache: str = "auto",
@@ -176,20 +164,11 @@ class SVC:
             fold_ms.append((time.perf_counter() - t0) * 1e3)
         return dec, fold_ms
 
-    def _scaled_cpu(self, X: np.ndarray) -> np.ndarray:
-        if self.scale:
-            sc = MinMaxScaler().fit(X)
-            check_finite_bounds(sc.min_, sc.max_)
-            return sc.transform(X)
-        if not np.all(np.isfinite(X)):
-            raise ValueError("X holds NaN or infinite values")
-        return X
-
     def _fit_probability_cpu(self, X, y, folds) -> None:
         from ..ops import cpu as C
 
         t0 = time.perf_counter()
-        dec, fold_ms = self._cv_cpu(self._scaled_cpu(X), y, folds)
+        dec, fold_ms = self._cv_cpu(scaled_cpu(X, self.scale)[0], y, folds)
         t1 = time.perf_counter()
         self._set_platt(C.platt_fit(dec, y), dec, folds)
         self.timings_.update({"cv_ms": (t1 - t0) * 1e3, "platt_ms": (time.perf_counter() - t1) * 1e3,
@@ -205,59 +184,35 @@ class SVC:
         """The fold solves on the GPU, and with ``final`` the model's own solve beside them: the rows go to the
         device once, and every solve is the decomposition solver on them -- a fold's with its rows' labels masked
         to 0 (held-out mode: their f - b is their held-out decision value, no prediction pass) -- one per host
-        thread and stream through the one-vs-rest pool.  Returns a dict: the rows and their statistics, "dec"
-        (device, n: the folds' disjoint held-out vectors summed), "final" ((alpha, result, timing) or None),
-        "fold_timings", "cv_ms"."""
+        thread and stream through the one-vs-rest pool (its width rule and column-cache share).  Returns the
+        TrainRows and a dict: "yd", "dec" (device, n: the folds' disjoint held-out vectors summed), "final" ((alpha,
+        result, timing) or None), "fold_timings", "cv_ms", "width"."""
         import torch
 
-        from .. import _native as N
         from ..ops import device as D
-        from .multiclass import _pool, _thread_stream
+        from .multiclass import _pool, pool_shape, pool_stream
 
-        n, d = X.shape
+        n = X.shape[0]
         k = int(folds.max()) + 1
         masks_h = np.stack([(folds == j).astype(np.uint8) for j in range(k)], 0)
+        tasks = ([-1] if final else []) + list(range(k))
+        width, frac = pool_shape(len(tasks), concurrent_solves, *X.shape)
 
-        def rows_of(Xh):
-            if Xh.dtype == np.uint8:
-                Xu = D.upload_u8(Xh, device)
-                mn, mx = D.minmax_u8(Xu)
-                return Xu, mn, mx, None
-            Xd = D.upload_rows(Xh, device)
-            mn, mx, sqn = D.minmax_scale_(Xd, d)
-            return Xd, mn, mx, sqn
-
-        def attempt(Xh):
-            t0 = time.perf_counter()
-            rows, mn, mx, sqn = rows_of(Xh)
-            mm = torch.cat([mn, mx]).cpu().numpy()
-            mn_h, mx_h = mm[:d].copy(), mm[d:].copy()
-            check_finite_bounds(mn_h, mx_h)
+        def solve_all(rows):
             yd = torch.from_numpy(y).to(device)
             masks = torch.from_numpy(masks_h).to(device)
             alphas = torch.zeros((k + 1, n), dtype=torch.float64, device=device)
             decs = torch.zeros((k, n), dtype=torch.float64, device=device)
             torch.cuda.synchronize(device)
             t1 = time.perf_counter()
-            tasks = ([-1] if final else []) + list(range(k))
-            # side by side while the rows sit in the last-level cache, two at a time beyond it (the one-vs-rest
-            # pool's rule and its column-cache share, models/multiclass.py)
-            big = n * d > (192 << 20)
-            width = max(1, min(concurrent_solves or (2 if big else len(tasks)), len(tasks)))
-            frac = min(0.25, 0.5 / width)
 
             def solve(j):
-                s = _thread_stream(device)
-                ctx = D.DeviceContext.get(device)
-                N.check(ctx.lib.svmd_set_ccache_frac(ctx.handle, frac), "svmd_set_ccache_frac")
-                with torch.cuda.stream(s):
+                with pool_stream(device, frac):
                     if j < 0:
-                        out = D.train_decomp(rows, yd, alphas[k], self.params, mn_h, mx_h, working_set=self.working_set)
-                    else:
-                        out = D.train_decomp_heldout(rows, yd, masks[j], alphas[j], decs[j], self.params, mn_h, mx_h,
-                                                     working_set=self.working_set)
-                s.synchronize()
-                return out
+                        return D.train_decomp(rows.rows, yd, alphas[k], self.params, rows.mn_h, rows.mx_h,
+                                              working_set=self.working_set)
+                    return D.train_decomp_heldout(rows.rows, yd, masks[j], alphas[j], decs[j], self.params, rows.mn_h,
+                                                  rows.mx_h, working_set=self.working_set)
 
             outs = dict(zip(tasks, _pool(width).map(solve, tasks)))
             torch.cuda.synchronize(device)
@@ -265,20 +220,16 @@ class SVC:
                 return None
             dec = decs.sum(0)  # disjoint and zero elsewhere: exact in any order
             torch.cuda.synchronize(device)
-            t2 = time.perf_counter()
-            return {"rows": rows, "mn": mn, "mx": mx, "sqn": sqn, "mn_h": mn_h, "mx_h": mx_h, "yd": yd, "dec": dec,
-                    "final": (alphas[k],) + outs[-1] if final else None,
-                    "fold_timings": [outs[j][1] for j in range(k)],
-                    "upload_preprocess_ms": (t1 - t0) * 1e3, "cv_ms": (t2 - t1) * 1e3, "width": width}
+            return {"yd": yd, "dec": dec, "final": (alphas[k],) + outs[-1] if final else None,
+                    "fold_timings": [outs[j][1] for j in range(k)], "cv_ms": (time.perf_counter() - t1) * 1e3,
+                    "width": width}
 
-        out = attempt(X)
-        if out is None and X.dtype == np.uint8:  # no exact-integer plan for these bytes: the FP64 rows
-            out = attempt(np.ascontiguousarray(X, dtype=np.float64))
+        rows, out = solve_on_rows(X, device, solve_all)
         if out is None:
             raise ValueError("the decomposition solver does not cover these rows (n beyond its shapes, or the "
                              "FP64-row solve's workspace does not fit the device); cross-validation on a GPU "
                              "needs it")
-        return out
+        return rows, out
 
     def _fit_cuda_probability(self, X, y, folds, dev) -> None:
         import torch
@@ -286,24 +237,15 @@ class SVC:
         from ..ops import device as D
 
         device = torch.device(dev)
-        cv = self._cv_device(X, y, folds, device, final=True)
+        rows, cv = self._cv_device(X, y, folds, device, final=True)
         alpha, res, tm = cv["final"]
         t0 = time.perf_counter()
         pl = D.platt_fit(cv["dec"], cv["yd"])
         platt_ms = (time.perf_counter() - t0) * 1e3
         self._finish(alpha.cpu().numpy(), y, res)
-        idx = torch.from_numpy(self.support_).to(device)
-        rows, mn, mx, d = cv["rows"], cv["mn"], cv["mx"], X.shape[1]
-        if rows.dtype == torch.uint8:
-            Xs, ns = D.sv_rows_u8(rows, idx, mn, mx)
-        else:
-            Xs, ns = D.gather_rows(rows, idx), cv["sqn"][idx].contiguous()
-        self._dev = {"Xs": Xs, "ns": ns, "coef": torch.from_numpy(self.dual_coef_).to(device), "mn": mn, "mx": mx,
-                     "d": d, "device": device}
-        self.scaler_ = MinMaxScaler(cv["mn_h"], cv["mx_h"])
-        self._sv_host = None
+        self._adopt_rows(rows)
         self._set_platt(pl, cv["dec"].cpu().numpy(), folds)
-        self.timings_ = {"upload_preprocess_ms": cv["upload_preprocess_ms"], **tm, "cv_ms": cv["cv_ms"],
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm, "cv_ms": cv["cv_ms"],
                          "platt_ms": platt_ms, "fold_ms": [t["total_ms"] for t in cv["fold_timings"]],
                          "concurrent_solves": cv["width"]}
 
@@ -328,10 +270,10 @@ class SVC:
         self._check_cv(dev)
         folds = self._folds(y, cv, seed, folds)
         if dev == "cpu":
-            return self._cv_cpu(self._scaled_cpu(X), y, folds)[0]
+            return self._cv_cpu(scaled_cpu(X, self.scale)[0], y, folds)[0]
         import torch
 
-        out = self._cv_device(X, y, folds, torch.device(dev), final=False, concurrent_solves=concurrent_solves)
+        _, out = self._cv_device(X, y, folds, torch.device(dev), final=False, concurrent_solves=concurrent_solves)
         self.cv_timings_ = {"cv_ms": out["cv_ms"], "fold_ms": [t["total_ms"] for t in out["fold_timings"]],
                             "concurrent_solves": out["width"]}
         return out["dec"].cpu().numpy()
@@ -349,10 +291,7 @@ class SVC:
         its overflow-safe form, on the host."""
         if self.probA_ is None:
             raise ValueError("predict_proba needs a model fitted with probability=True")
-        z = self.probA_ * self.decision_function(X) + self.probB_
-        e = np.exp(-np.abs(z))
-        big, small = 1.0 / (1.0 + e), e / (1.0 + e)
-        return np.stack([np.where(z >= 0, big, small), np.where(z >= 0, small, big)], 1)
+        return platt_probability(self.probA_ * self.decision_function(X) + self.probB_)
 
     def _check_weighted(self, dev: str) -> None:
         """Class weights run on the CPU oracle and on the GPU decomposition solver (no shrinking); everything
@@ -385,15 +324,7 @@ class SVC:
 
         if self.solver == "decomp":
             raise ValueError("solver='decomp' runs on the GPU (device='cuda'); the CPU oracle is the pairwise SMO")
-        if self.scale:
-            self.scaler_ = MinMaxScaler().fit(X)
-            check_finite_bounds(self.scaler_.min_, self.scaler_.max_)
-            Xs = self.scaler_.transform(X)
-        else:
-            if not np.all(np.isfinite(X)):
-                raise ValueError("X holds NaN or infinite values")
-            self.scaler_ = None
-            Xs = X
+        Xs = self._scaled_cpu(X)
         alpha, res, _ = C.smo_train(Xs, y, self.params, alpha=alpha0, warm=alpha0 is not None)
         self._finish(alpha, y, res)
         self.support_vectors_ = Xs[self.support_].copy()
@@ -409,146 +340,55 @@ class SVC:
         # selection, a forced Gram path or the row cache)
         decomp = self.solver == "decomp" or (self.solver == "auto" and self.params.wss != 2 and self.gram == "auto"
                                              and self.kcache == "auto")
-        weighted = self.params.weighted  # then the decomposition or an error: never the pairwise solver
-        if decomp:
-            if not self.scale:
-                if self.solver == "decomp":
-                    raise ValueError("solver='decomp' needs scale=True (min-max scaled rows: its exact-integer "
-                                     "plan, or the FP64 rows it solves on)")
-                decomp = False  # auto without scaling: the pairwise solver
-            elif X.dtype == np.uint8 and self._fit_cuda_u8(X, y, alpha0, device, decomp=True):
-                return
-            # FP64 host rows (the reference's format): scaled on the device, then quantised into the
-            # same integers as the byte path (the same trajectory and model), or -- real-valued data --
-            # solved on the FP64 rows with FP64-MFMA kernel values
-        if (not decomp and X.dtype == np.uint8 and self.scale and self.gram in ("auto", "int")
-                and self.kcache in ("auto", "full")
-                and os.environ.get("SVM355_U8_TRAIN", "1") != "0" and self._fit_cuda_u8(X, y, alpha0, device)):
-            return
-        t0 = time.perf_counter()
-        Xd = D.upload_rows(X, device)
+        if decomp and not self.scale:
+            if self.solver == "decomp":
+                raise ValueError("solver='decomp' needs scale=True (min-max scaled rows: its exact-integer "
+                                 "plan, or the FP64 rows it solves on)")
+            decomp = False  # auto without scaling: the pairwise solver
+        # uint8 pixel rows stay bytes on the device -- min/max, the exact-integer quantisation and the solver (the
+        # decomposition, or the pairwise one on a resident exact-integer Gram) read them directly, and only the
+        # support vectors are ever widened to scaled FP64 (for prediction): the same trajectory and model as from
+        # the FP64 rows, minus their widen / scale / FP64-quantise passes.  FP64 host rows (the reference's
+        # format), and bytes the solver declined, are scaled on the device, then quantised into the same integers
+        # or -- real-valued data -- solved with FP64-MFMA kernel values.
+        bytes_ok = X.dtype == np.uint8 and self.scale and (decomp or (
+            self.gram in ("auto", "int") and self.kcache in ("auto", "full")
+            and os.environ.get("SVM355_U8_TRAIN", "1") != "0"
+            and (self.kcache != "auto" or D.gram_fits(X.shape[0], device))))
+        warm = alpha0 is not None
         yd = torch.from_numpy(y).to(device)
-        d = X.shape[1]
-        if self.scale:
-            mn, mx, sqn = D.minmax_scale_(Xd, d)
-            mm_h = mn.as_strided((2 * d,), (1,)).cpu().numpy()  # both bounds (one buffer), one copy
-            check_finite_bounds(mm_h[:d], mm_h[d:])
-        else:
-            mn = mx = None
-            sqn = D.row_norms(Xd, d)
-            if not np.all(np.isfinite(sqn.cpu().numpy())):  # a NaN / inf anywhere makes its row's norm one
-                raise ValueError("X holds NaN or infinite values")
-        if alpha0 is not None:
+        if warm:
             alpha = torch.from_numpy(np.ascontiguousarray(alpha0, dtype=np.float64)).to(device)
         else:
             alpha = torch.empty(X.shape[0], dtype=torch.float64, device=device)  # the cold start zeroes it
-        torch.cuda.synchronize(device)
-        t1 = time.perf_counter()
-        out = None
-        if decomp:
-            out = D.train_decomp_rows(Xd, yd, alpha, self.params, mm_h[:d], mm_h[d:], working_set=self.working_set,
-                                      warm=alpha0 is not None)
-            if out is None and self.solver == "decomp":
-                raise ValueError("solver='decomp': the device rows' stride is not a multiple of 16, n is beyond the "
-                                 "solver's 2^31 - 1 rows, or the FP64-row solve's workspace (n x 1024 doubles) does "
-                                 "not fit the device")
-        if out is not None:
-            res, tm = out
-        elif weighted:
-            self.params.refuse_weights("the GPU pairwise solver, which this fit falls back to (the decomposition "
-                                       "solver does not cover these rows)")
-        else:  # the pairwise solver (also solver="auto" when the decomposition's workspace does not fit)
-            res, tm = D.train(Xd, sqn, yd, alpha, self.params, warm=alpha0 is not None, mn=mn, mx=mx, gram=self.gram,
-                              kcache=self.kcache)
-        a = alpha.cpu().numpy()
-        self._finish(a, y, res)
-        idx = torch.from_numpy(self.support_).to(device)
-        self._dev = {
-            "Xs": D.gather_rows(Xd, idx),
-            "ns": sqn[idx].contiguous(),
-            "coef": torch.from_numpy(self.dual_coef_).to(device),
-            "mn": mn,
-            "mx": mx,
-            "d": d,
-            "device": device,
-        }
-        if self.scale:
-            self.scaler_ = MinMaxScaler(mm_h[:d].copy(), mm_h[d:].copy())
-        else:
-            self.scaler_ = None
-        self._sv_host = None  # scaled SV rows stay on the device; copied to the host on first access
-        self.timings_ = {"upload_preprocess_ms": (t1 - t0) * 1e3, **tm}
 
-    def _fit_cuda_u8(self, X, y, alpha0, device, decomp: bool = False) -> bool:
-        """uint8 pixel rows, resident Gram: the rows stay bytes on the device -- min/max, the exact-integer
-        quantisation and the Gram read them directly, and only the support vectors are ever widened
-        to scaled FP64 (for prediction).  Same Gram, trajectory and model as the FP64-row path, minus
-        its widen / scale / FP64-quantise passes.  False (nothing fitted) when it does not apply."""
-        import torch
+        def solve(r):
+            u8 = r.sqn is None
+            out = None
+            if decomp:
+                out = D.train_decomp(r.rows, yd, alpha, self.params, r.mn_h, r.mx_h, working_set=self.working_set,
+                                     warm=warm)
+                if out is None and not u8 and self.solver == "decomp":
+                    raise ValueError("solver='decomp': the device rows' stride is not a multiple of 16, n is beyond the "
+                                     "solver's 2^31 - 1 rows, or the FP64-row solve's workspace (n x 1024 doubles) does "
+                                     "not fit the device")
+            elif u8:
+                out = D.train_u8(r.rows, yd, alpha, self.params, r.mn_h, r.mx_h, warm=warm)
+            if out is not None or u8:  # bytes that nothing ran on (not an integer plan): the FP64 rows take over
+                return out
+            if self.params.weighted:  # then the decomposition or an error: never the pairwise solver
+                self.params.refuse_weights("the GPU pairwise solver, which this fit falls back to (the decomposition "
+                                           "solver does not cover these rows)")
+            # the pairwise solver (also solver="auto" when the decomposition's workspace does not fit)
+            return D.train(r.rows, r.sqn, yd, alpha, self.params, warm=warm, mn=r.mn, mx=r.mx, gram=self.gram,
+                           kcache=self.kcache)
 
-        from ..ops import device as D
-
-        n, d = X.shape
-        if not decomp and self.kcache == "auto" and not D.gram_fits(n, device):
-            return False
-        # No PyTorch kernel runs on this path (copies and the library's own kernels only): a process's
-        # first PyTorch kernel loads PyTorch's code objects, ~95 ms of a cold first fit
-        # (profiles/r3_cold_fit_probe.txt).
-        t0 = time.perf_counter()
-        Xu = D.upload_u8(X, device)
-        yd = torch.from_numpy(y).to(device)
-        mmd = torch.empty(2 * d, dtype=torch.float64, device=device)
-        mn, mx = D.minmax_u8(Xu, out=mmd)
-        if alpha0 is not None:
-            alpha = torch.from_numpy(np.ascontiguousarray(alpha0, dtype=np.float64)).to(device)
-        else:
-            alpha = torch.empty(n, dtype=torch.float64, device=device)  # the cold start zeroes it
-        mm = mmd.cpu().numpy()  # one D2H (synchronises) for the plan and the scaler
-        mn_h, mx_h = mm[:d].copy(), mm[d:].copy()
-        t1 = time.perf_counter()
-        if decomp:
-            out = D.train_decomp_u8(Xu, yd, alpha, self.params, mn_h, mx_h, working_set=self.working_set,
-                                    warm=alpha0 is not None)
-        else:
-            out = D.train_u8(Xu, yd, alpha, self.params, mn_h, mx_h, warm=alpha0 is not None)
-        if out is None:  # nothing ran (not an integer plan): the FP64-row path takes over
-            return False
-        res, tm = out
+        rows, (res, tm) = solve_on_rows(X, device, solve, scale=self.scale, bytes_ok=bytes_ok)
         self._finish(alpha.cpu().numpy(), y, res)
-        idx = torch.from_numpy(self.support_).to(device)
-        Xs, ns = D.sv_rows_u8(Xu, idx, mn, mx)
-        self._dev = {"Xs": Xs, "ns": ns, "coef": torch.from_numpy(self.dual_coef_).to(device), "mn": mn, "mx": mx,
-                     "d": d, "device": device}
-        self.scaler_ = MinMaxScaler(mn_h, mx_h)
-        self._sv_host = None
-        self.timings_ = {"upload_preprocess_ms": (t1 - t0) * 1e3, **tm}
-        return True
-
-    @property
-    def support_vectors_(self) -> np.ndarray:
-        """Scaled support-vector rows (host copy, fetched lazily from the device model)."""
-        if self._sv_host is None and self._dev is not None:
-            self._sv_host = self._dev["Xs"][:, : self._dev["d"]].cpu().numpy()
-        return self._sv_host
-
-    @support_vectors_.setter
-    def support_vectors_(self, value) -> None:
-        self._sv_host = value
+        self._adopt_rows(rows)
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 
     # ------------------------------------------------------------------ inference
-    def _n_features(self) -> Optional[int]:
-        if self._dev is not None:
-            return int(self._dev["d"])
-        if self.scaler_ is not None and self.scaler_.min_ is not None:
-            return int(np.size(self.scaler_.min_))
-        sv = self.support_vectors_
-        return int(sv.shape[1]) if sv is not None and np.ndim(sv) == 2 else None
-
-    def _check_X(self, X) -> None:
-        d = self._n_features()
-        if np.ndim(X) != 2 or (d is not None and np.shape(X)[1] != d):
-            raise ValueError(f"X must be (m, {d}) like the training rows, got shape {np.shape(X)}")
-
     def decision_function(self, X: np.ndarray) -> np.ndarray:
         self._check_X(X)
         if self._dev is not None:
@@ -559,13 +399,8 @@ class SVC:
         """Decision values as a device tensor (device models only)."""
         from ..ops import device as D
 
-        X = np.ascontiguousarray(X, dtype=np.uint8 if _is_u8(X) else np.float64)
         dv = self._dev
-        Xq = D.upload_rows(X, dv["device"])
-        if self.scale:
-            _, _, nq = D.minmax_scale_(Xq, dv["d"], dv["mn"], dv["mx"])
-        else:
-            nq = D.row_norms(Xq, dv["d"])
+        Xq, nq = self._device_queries(X)
         return D.decision(dv["Xs"], dv["ns"], dv["coef"], Xq, nq, self.params.gamma, self.b_)
 
     def _host_decision(self, X: np.ndarray) -> np.ndarray:
@@ -633,46 +468,3 @@ class SVC:
         if _resolve_device(device) != "cpu":
             svc._upload_model(_resolve_device(device))
         return svc
-
-    def _device_model_from_u8(self, X_sv: np.ndarray, dev: str) -> None:
-        """The device model of a fit whose rows are uint8 pixels and whose alphas, b and scaler are set
-        (the distributed trainers): only the SV rows' bytes cross PCIe, widened and scaled on the device
-        (svmd_sv_rows_u8) -- no host FP64 transform and no FP64 upload (~1 MB instead of 8.6 MB at 60k).
-        No PyTorch kernel runs (copies and the library's own kernels only)."""
-        import torch
-
-        from ..ops import device as D
-
-        device = torch.device(dev)
-        X_sv = np.ascontiguousarray(X_sv, dtype=np.uint8)
-        k, d = X_sv.shape
-        mm = torch.from_numpy(np.concatenate([self.scaler_.min_, self.scaler_.max_]).astype(np.float64)).to(device)
-        mn, mx = mm[:d], mm[d:]
-        if k:
-            Xu = D.upload_u8(X_sv, device)
-            idx = torch.from_numpy(np.arange(k, dtype=np.int64)).to(device)
-            Xs, ns = D.sv_rows_u8(Xu, idx, mn, mx)
-        else:
-            Xs = torch.empty((0, D.padded_dim(d)), dtype=torch.float64, device=device)
-            ns = torch.empty(0, dtype=torch.float64, device=device)
-        self._dev = {"Xs": Xs, "ns": ns, "coef": torch.from_numpy(np.ascontiguousarray(self.dual_coef_)).to(device),
-                     "mn": mn, "mx": mx, "d": d, "device": device}
-        self._sv_host = None
-
-    def _upload_model(self, dev: str) -> None:
-        import torch
-
-        from ..ops import device as D
-
-        device = torch.device(dev)
-        d = self.support_vectors_.shape[1]
-        Xs = D.upload_rows(self.support_vectors_, device)
-        self._dev = {
-            "Xs": Xs,
-            "ns": D.row_norms(Xs, d),
-            "coef": torch.from_numpy(np.ascontiguousarray(self.dual_coef_)).to(device),
-            "mn": torch.from_numpy(self.scaler_.min_).to(device) if self.scaler_ is not None else None,
-            "mx": torch.from_numpy(self.scaler_.max_).to(device) if self.scaler_ is not None else None,
-            "d": d,
-            "device": device,
-        }

@@ -484,18 +484,6 @@ def train_decomp(X: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: 
                          after_ws=(int(warm),))
 
 
-def train_decomp_u8(Xu: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
-                    working_set: int = 1024, warm: bool = False) -> Optional[Tuple[SMOResult, dict]]:
-    """``train_decomp`` from device uint8 pixel rows."""
-    return train_decomp(Xu, y, alpha, params, mn, mx, working_set, warm)
-
-
-def train_decomp_rows(X: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
-                      working_set: int = 1024, warm: bool = False) -> Optional[Tuple[SMOResult, dict]]:
-    """``train_decomp`` from min-max scaled FP64 rows on the device (the reference's host row format)."""
-    return train_decomp(X, y, alpha, params, mn, mx, working_set, warm)
-
-
 def train_decomp_svr(X: torch.Tensor, z: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
                      epsilon: float = 0.1, working_set: int = 1024,
                      trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where the cold fit's extra upload time goes: the steps of SVC._fit_cuda_u8's upload, each synchronised
+"""Where the cold fit's extra upload time goes: the steps of the byte path's upload (models/_device.py TrainRows.upload), each synchronised
 and timed, in a fresh process after the bench's device initialisation; then the same steps again."""
 import sys
 import time

@@ -251,7 +251,7 @@ def test_headline_shape_60k_default_solver_equals_graph_replay(dev, D, monkeypat
     m = SVC(device="cuda:0", solver="smo").fit(tr.X, tr.y)
     assert m.n_iter_ == r1.iterations and m.b_ == r1.b
     assert m.timings_["gram_path"] == "int8-exact" and m.timings_["kcache"] == "full"
-    assert m.timings_.get("rows") == "uint8"  # bench.py's byte path (SVC._fit_cuda_u8)
+    assert m.timings_.get("rows") == "uint8"  # bench.py's byte path (SVC on TrainRows' byte rows)
 
 
 def test_device_smo_warm_start_bit_identical(dev, D, mn_data):
@@ -479,7 +479,7 @@ def test_svc_u8_rows_bit_identical_to_fp64_rows(dev, mn_data):
 
 def test_svc_byte_path_equals_fp64_row_path(dev, mn_data, monkeypatch):
     """uint8 rows take the byte path (min/max, quantisation and Gram straight from the bytes, only the
-    SVs widened; SVC._fit_cuda_u8); with SVM355_U8_TRAIN=0 the same rows go through the FP64-row path.
+    SVs widened; models/_device.py TrainRows); with SVM355_U8_TRAIN=0 the same rows go through the FP64-row path.
     The models -- alphas, b, SV rows and norms, decisions -- must be identical bit for bit."""
     tr, te = mn_data
     Xc = tr.compact().X
