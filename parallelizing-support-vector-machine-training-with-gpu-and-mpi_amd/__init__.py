@@ -52,9 +52,10 @@ from .models.ovo import OneVsOneSVC
 from .models.svc import SVC
 from .models.svr import SVR
 from .models.oneclass import OneClassSVM
+from .models.nusvm import NuSVC, NuSVR
 
 __all__ = ["SVMParams", "Dataset", "MinMaxScaler", "load_csv", "one_vs_rest", "synthetic_mnist", "write_csv",
-           "SVC", "SVR", "OneClassSVM", "OneVsRestSVC", "OneVsOneSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
+           "SVC", "SVR", "OneClassSVM", "NuSVC", "NuSVR", "OneVsRestSVC", "OneVsOneSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
 __version__ = "0.1.0"
 
 

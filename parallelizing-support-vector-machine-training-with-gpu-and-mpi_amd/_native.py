@@ -225,6 +225,12 @@ _CORE_SIGS = {
     "svm_decomp_train_gram_oneclass": (c_int32, [_P, c_int64, c_int64, c_double, _P, POINTER(SvmParams), c_int32,
                                                  c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
                                                  POINTER(SvmDecompTrace)]),
+    "svm_decomp_train_gram_nusvc": (c_int32, [_P, c_int64, _P, c_int64, c_double, _P, _P, POINTER(SvmParams), c_int32,
+                                              c_double, c_int32, POINTER(SvmResult), POINTER(c_int64),
+                                              POINTER(SvmDecompTrace)]),
+    "svm_decomp_train_gram_nusvr": (c_int32, [_P, c_int64, _P, c_int64, c_double, _P, _P, POINTER(SvmParams), c_int32,
+                                              c_double, c_int32, POINTER(SvmResult), POINTER(c_int64),
+                                              POINTER(SvmDecompTrace)]),
     "svm_decomp_train_gram_heldout": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, POINTER(SvmParams), c_int32,
                                                 c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64), _P,
                                                 POINTER(SvmDecompTrace)]),
@@ -315,6 +321,13 @@ _HIP_SIGS = {
     "svmd_train_decomp_oneclass": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, c_double, _P,
                                              POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                              POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
+    "svmd_train_decomp_nusvc": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, c_int64,
+                                          c_double, _P, _P, POINTER(SvmParams), c_int32, POINTER(SvmResult),
+                                          POINTER(SvmdTiming), POINTER(c_int64), POINTER(c_int32),
+                                          POINTER(SvmDecompTrace)]),
+    "svmd_train_decomp_nusvr": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, c_double, _P,
+                                          _P, POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
+                                          POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
     "svmd_train_decomp_heldout": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P,
                                             POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                             POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),

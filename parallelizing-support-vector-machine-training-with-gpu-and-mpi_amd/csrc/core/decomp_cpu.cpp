@@ -35,6 +35,11 @@
 //     takes (in_high / in_low below are false for it), so their alpha stays 0 and their f collects every update:
 //     f - b is their held-out decision value (ws_heldout_init_kernel, ws_heldout_dec_kernel).  Cold start, one
 //     rank, no shrinking, no Newton polish; class weights are allowed.
+//   * the nu modes (svm_decomp_train_gram_nusvc / _nusvr; decomp_nu.hip): two equalities, so every selection runs
+//     per sign class -- four candidate lists of Tc = q / (4 NB) picks per block (nu_select), the stop test on the
+//     larger class gap, the inner solve by LIBSVM's Solver_NU rule (nu_inner) -- from LIBSVM's start walk
+//     (nu_start_walk), and r and rho at the end (nu-SVC: alpha / r).  One rank, cold start, no shrinking, no Newton
+//     polish, no class weights.
 // The kernel values themselves come from the caller (the device Gram on the exact-integer path).
 #include <chrono>
 #include <climits>
@@ -174,6 +179,137 @@ void fold_twins(const int32_t* cols, const double* coef, int64_t cnt, int64_t n,
   }
 }
 
+// ---- the nu modes (nu-SVC, nu-SVR: decomp_nu.hip's kernels) ------------------------------------------------
+// Pairs of one sign: every selection runs per sign class, sides 0 = I_high +, 1 = I_high -, 2 = I_low +, 3 =
+// I_low -.  A point of sign s and alpha a is on side `sd`:
+inline bool nu_on_side(int sd, int32_t s, double a, double c_hi, double c_lo) {
+  const bool p = s == 1;
+  if (p != (sd == 0 || sd == 2)) return false;
+  return (sd < 2) == p ? a < c_hi : a > c_lo;  // + in I_high / - in I_low: below the box; the others: above 0
+}
+
+// ws_select_nu_kernel: per block, Tc picks for each of the four lists in (value, lowest index) order, list-major.
+void nu_select(int64_t n, int64_t per, int64_t NB, int Tc, const int32_t* y, const double* alpha, const double* f,
+               double c_hi, double c_lo, Cand* out, WorkerTeam& team) {
+  const double inf = std::numeric_limits<double>::infinity();
+  team.parallel_for(NB, [&](int64_t blo, int64_t bhi) {
+    std::vector<char> taken;
+    for (int64_t b = blo; b < bhi; ++b) {
+      const int64_t b0 = std::min<int64_t>(n, b * per), b1 = std::min<int64_t>(n, b0 + per);
+      for (int sd = 0; sd < 4; ++sd) {
+        taken.assign(size_t(b1 - b0), 0);
+        for (int k = 0; k < Tc; ++k) {
+          double bv = sd < 2 ? inf : -inf;
+          int64_t bi = -1;
+          for (int64_t i = b0; i < b1; ++i)
+            if (!taken[size_t(i - b0)] && nu_on_side(sd, y[i], alpha[i], c_hi, c_lo) && (sd < 2 ? f[i] < bv : f[i] > bv)) {
+              bv = f[i];
+              bi = i;
+            }
+          out[size_t((sd * NB + b) * Tc + k)] = bi >= 0 ? Cand{bv, bi} : Cand{0.0, -1};
+          if (bi >= 0) taken[size_t(bi - b0)] = 1;
+        }
+      }
+    }
+  });
+}
+
+// The larger class gap from the four extremes {b_high +, b_high -, b_low +, b_low -}; a class with an empty side
+// has none.
+inline double nu_gap(const double b[4]) {
+  const double inf = std::numeric_limits<double>::infinity();
+  const double gp = b[0] < inf && b[2] > -inf ? b[2] - b[0] : -inf;
+  const double gn = b[1] < inf && b[3] > -inf ? b[3] - b[1] : -inf;
+  return gp > gn ? gp : gn;
+}
+
+// ws_inner_nu_kernel on the working set's positions (a, ft, yw by position; K(W, W) through Wr): LIBSVM's
+// Solver_NU rule -- i_c = argmin f over I_high of class c, the second-order gain of every I_low point of class c
+// above f(i_c) on row i_c, the (i, j) of smallest gain over both classes (lowest position on ties) -- and the
+// classifier's clip / eta floor / update with both labels equal.  Returns the iterations; *reason as the kernel's.
+int64_t nu_inner(const double* K, int64_t ldk, const std::vector<int32_t>& Wr, std::vector<double>& a,
+                 std::vector<double>& ft, const std::vector<int32_t>& yw, double C, double eps, double tau_in,
+                 int64_t max_inner, int32_t* reason, int64_t* eta_floored) {
+  const int m = int(Wr.size());
+  const double inf = std::numeric_limits<double>::infinity(), c_hi = C - eps, c_lo = 0.0 + eps;
+  int64_t it = 0;
+  *reason = SVM_STOP_CONVERGED;
+  for (;;) {
+    double b[4] = {inf, inf, -inf, -inf};
+    int at_[4] = {-1, -1, -1, -1};
+    for (int k = 0; k < m; ++k)
+      for (int sd = 0; sd < 4; ++sd)
+        if (nu_on_side(sd, yw[size_t(k)], a[size_t(k)], c_hi, c_lo) &&
+            (sd < 2 ? ft[size_t(k)] < b[sd] : ft[size_t(k)] > b[sd])) {
+          b[sd] = ft[size_t(k)];
+          at_[sd] = k;
+        }
+    const bool has_p = at_[0] >= 0 && at_[2] >= 0, has_n = at_[1] >= 0 && at_[3] >= 0;
+    if (!has_p && !has_n) {
+      *reason = SVM_STOP_NO_CANDIDATE;
+      break;
+    }
+    const double gp = has_p ? b[2] - b[0] : -inf, gn = has_n ? b[3] - b[1] : -inf;
+    if ((gp > gn ? gp : gn) <= 2.0 * tau_in) break;
+    if (it >= max_inner) {
+      *reason = SVM_STOP_MAX_ITER;
+      break;
+    }
+    double gv = inf;
+    int il = -1;
+    for (int k = 0; k < m; ++k) {
+      const int c = yw[size_t(k)] == 1 ? 0 : 1;
+      if (at_[c] < 0 || !nu_on_side(2 + c, yw[size_t(k)], a[size_t(k)], c_hi, c_lo) || !(ft[size_t(k)] > b[c])) continue;
+      const double bb = ft[size_t(k)] - b[c];
+      double at = 2.0 - 2.0 * K[int64_t(Wr[size_t(at_[c])]) * ldk + Wr[size_t(k)]];
+      at = at < eps ? eps : at;
+      const double gain = -(bb * bb) / at;
+      if (gain < gv) {
+        gv = gain;
+        il = k;
+      }
+    }
+    if (il < 0) {
+      *reason = SVM_STOP_NO_CANDIDATE;
+      break;
+    }
+    const int32_t yl = yw[size_t(il)];
+    const int ih = at_[yl == 1 ? 0 : 1];
+    const double bh = b[yl == 1 ? 0 : 1], bl_upd = ft[size_t(il)];
+    const double* Ki = K + int64_t(Wr[size_t(ih)]) * ldk;
+    const double* Kj = K + int64_t(Wr[size_t(il)]) * ldk;
+    const double K12 = Ki[Wr[size_t(il)]];
+    const double ah = a[size_t(ih)], al = a[size_t(il)];
+    double eta = 1.0 + 1.0 - 2.0 * K12;
+    const double U = std::fmax(0.0, al + ah - C), V = std::fmin(C, al + ah);
+    if (!(U <= V + 1e-12)) {
+      *reason = SVM_STOP_INFEASIBLE;
+      break;
+    }
+    if (eta <= eps) {
+      eta = eps;
+      ++*eta_floored;
+    }
+    double al_new = al + double(yl) * (bh - bl_upd) / eta;
+    if (al_new > V) al_new = V;
+    if (al_new < U) al_new = U;
+    const double ah_new = ah + (al - al_new);
+    const double ch = (ah_new - ah) * double(yl);
+    const double cl = (al_new - al) * double(yl);
+    for (int k = 0; k < m; ++k) ft[size_t(k)] += ch * Ki[Wr[size_t(k)]] + cl * Kj[Wr[size_t(k)]];
+    a[size_t(ih)] = ah_new;
+    a[size_t(il)] = al_new;
+    ++it;
+  }
+  return it;
+}
+
+// A class's multiplier from its two bounds (ws_nu_finish_kernel): the midpoint, or the side that exists.
+inline double nu_mid(double bh, double bl) {
+  const double inf = std::numeric_limits<double>::infinity();
+  return bh < inf && bl > -inf ? (bh + bl) / 2 : (bh < inf ? bh : bl);
+}
+
 // The solve of one rank (t == nullptr: one rank).  Distributed (decomp.hip run_decomp, world > 1):
 // this rank owns the blocks [rank NB / world, (rank + 1) NB / world) of the global block partition,
 // keeps f for their points only, selects their candidates, and ONE all-gather of the candidate records
@@ -190,10 +326,12 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
                  int64_t* stats, svm_decomp_trace* tr, Transport* t, const DecompMode& mode = {},
                  bool f64_rows = false) {
   static const char* const entry[] = {"svm_decomp_train_gram", "svm_decomp_train_gram_svr",
-                                      "svm_decomp_train_gram_oneclass", "svm_decomp_train_gram_heldout"};
+                                      "svm_decomp_train_gram_oneclass", "svm_decomp_train_gram_heldout",
+                                      "svm_decomp_train_gram_nusvc", "svm_decomp_train_gram_nusvr"};
   const char* who = entry[int(mode.kind)];
   const int world = t ? t->world() : 1, rank = t ? t->rank() : 0;
-  const bool twin = mode.twin(), oneclass = mode.kind == DecompModeKind::oneclass;
+  const bool twin = mode.twin(), oneclass = mode.kind == DecompModeKind::oneclass, nu = mode.nu_pairs();
+  const bool nusvc = mode.kind == DecompModeKind::nu_classify;
   if (!K || (!y && !twin && !oneclass) || !alpha || n < 2 || ldk < n) {
     set_error("%s: bad arguments", who);
     return SVM_ERR_ARG;
@@ -213,7 +351,11 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   double oc_frac = 0.0;
   switch (mode.kind) {
     case DecompModeKind::classify: break;
+    case DecompModeKind::nu_classify:  // ws_nu_start_svc_kernel's signs
+      for (int64_t i = 0; i < n; ++i) sgn[size_t(i)] = y[i] == 1 ? 1 : -1;
+      break;
     case DecompModeKind::twin:
+    case DecompModeKind::nu_twin:
       for (int64_t i = 0; i < nr; ++i)
         if (!std::isfinite(mode.twin_z[i])) {
           set_error("%s: target %lld is not finite", who, (long long)i);
@@ -238,14 +380,19 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     set_error("svm_decomp_train_gram: a trace needs one rank");
     return SVM_ERR_ARG;
   }
-  const Shape sh = shape(n, qws > 0 ? qws : kMaxWS, world);
+  Shape sh = shape(n, qws > 0 ? qws : kMaxWS, world);
+  if (sh.ok && nu) {  // four lists of Tc picks per block (decomp.hip setup_solve)
+    sh.T = int(std::max<int64_t>(1, sh.q / (4 * sh.NB)));
+    sh.L = 4 * sh.NB * sh.T;
+    sh.ok = sh.L <= kMaxWS && sh.per <= kSelPts;
+  }
   if (!sh.ok) {
     set_error("svm_decomp_train_gram: n = %lld is outside the solver's shapes", (long long)n);
     return SVM_ERR_ARG;
   }
   const int64_t NBr = sh.NB / world, bb0 = rank * NBr;
   const int64_t lo = std::min<int64_t>(n, bb0 * sh.per), hi = std::min<int64_t>(n, (bb0 + NBr) * sh.per);
-  const int64_t nloc = hi - lo, Lr = 2 * NBr * sh.T, LhR = NBr * sh.T;
+  const int64_t nloc = hi - lo, Lr = (nu ? 4 : 2) * NBr * sh.T, LhR = NBr * sh.T;
   // fault injection (tests): rank SVM355_DECOMP_FAIL_RANK fails at the start of outer iteration
   // SVM355_DECOMP_FAIL_OUTER (default 0); its peers must leave their all-gather with an error
   int fail_outer = -1;
@@ -268,7 +415,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   // f = -y + K (alpha y) over the nonzero alphas (ascending ids, chunks of kMaxWS columns): the warm
   // start, and the recomputation when the solve unshrinks
   auto f_from_alpha = [&]() -> int64_t {
-    for (int64_t i = lo; i < hi; ++i) f[size_t(i - lo)] = oneclass ? 0.0 : -static_cast<double>(y[i]);
+    for (int64_t i = lo; i < hi; ++i) f[size_t(i - lo)] = oneclass || nusvc ? 0.0 : -static_cast<double>(y[i]);
     std::vector<int32_t> nzc;
     std::vector<double> nzv;
     for (int64_t j = 0; j < n; ++j)
@@ -282,7 +429,22 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
           int64_t(std::min<size_t>(kMaxWS, nzc.size() - c0)), f.data(), team, nullptr);
     return int64_t(nzc.size());
   };
-  if (twin) {  // ws_twin_init_kernel
+  if (nu) {  // ws_nu_start_svc_kernel (then nz_update) / ws_nu_start_twin_kernel
+    int64_t full = 0;
+    double frac = 0.0;
+    nu_start_walk((nusvc ? 1.0 : C) * mode.nu * double(nr) / 2.0, nusvc ? 1.0 : C, nr, &full, &frac);
+    int64_t rank[2] = {0, 0};  // the points of each class so far (nu-SVR: one walk over the rows)
+    for (int64_t k = 0; k < nr; ++k) {
+      int64_t& r = rank[nusvc && y[k] != 1 ? 1 : 0];
+      alpha[k] = r < full ? (nusvc ? 1.0 : C) : r == full ? frac : 0.0;
+      ++r;
+      if (!nusvc) {
+        alpha[k + nr] = alpha[k];
+        f[size_t(k)] = f[size_t(k + nr)] = -mode.twin_z[k];
+      }
+    }
+    if (nusvc) warm_cols = f_from_alpha();
+  } else if (twin) {  // ws_twin_init_kernel
     for (int64_t k = 0; k < nr; ++k) {
       f[size_t(k)] = mode.twin_eps - mode.twin_z[k];
       f[size_t(k + nr)] = -mode.twin_eps - mode.twin_z[k];
@@ -312,6 +474,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   nwc.on = nwc.on && inner_wss == 3;  // the device polishes in its default inner solve (second order + second pair)
   int32_t last_reason = SVM_STOP_CONVERGED, stop = SVM_STOP_RUNNING;
   double bh = inf, bl = -inf;
+  double nub[4] = {inf, inf, -inf, -inf};  // the nu modes' extremes {b_high +, b_high -, b_low +, b_low -}
   std::vector<Cand> cown(size_t(std::max<int64_t>(Lr, 1))), call(size_t(sh.L));
   std::vector<int32_t> W, Wr;  // the working set's point ids and their kernel rows (id mod nr)
   std::vector<double> a, a0, ft, kh, kl;
@@ -324,6 +487,9 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       return SVM_ERR_INTERNAL;
     }
     // ---- selection over this rank's blocks: per block, T picks per side in (value, lowest index) order
+    if (nu)
+      nu_select(n, sh.per, sh.NB, sh.T, y, alpha, f.data(), chp, c_lo, cown.data(), team);
+    else
     team.parallel_for(NBr, [&](int64_t blo, int64_t bhi) {
       std::vector<char> th, tl;
       for (int64_t bl_ = blo; bl_ < bhi; ++bl_) {
@@ -362,12 +528,17 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     // ---- build: bounds, stop test, the sorted de-duplicated working set
     bh = inf;
     bl = -inf;
+    nub[0] = nub[1] = inf;
+    nub[2] = nub[3] = -inf;
     std::vector<std::pair<int64_t, double>> ids;
     ids.reserve(call.size());
     for (int64_t u = 0; u < sh.L; ++u) {
       const Cand& c = call[size_t(u)];
       if (c.id < 0) continue;
-      if (u % Lr < LhR)
+      if (nu) {  // list-major: LhR records per list
+        const int sd = int(u / LhR);
+        nub[sd] = sd < 2 ? std::fmin(nub[sd], c.f) : std::fmax(nub[sd], c.f);
+      } else if (u % Lr < LhR)
         bh = std::fmin(bh, c.f);
       else
         bl = std::fmax(bl, c.f);
@@ -385,11 +556,16 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     Wr.assign(W.begin(), W.end());
     if (twin)
       for (int32_t& id : Wr) id = int32_t(id % nr);
+    if (nu) {  // the trace's bounds are the + class's; the stop test is on the larger class gap (ws_build_nu_kernel)
+      bh = nub[0];
+      bl = nub[2];
+    }
+    const double gap = nu ? nu_gap(nub) : bl - bh;
     if (outer > 0 && last_inner_it == 0)
       stop = last_reason == SVM_STOP_CONVERGED ? SVM_STOP_NO_CANDIDATE : last_reason;
-    else if (!(bh < inf) || !(bl > -inf))
+    else if (nu ? false : !(bh < inf) || !(bl > -inf))
       stop = SVM_STOP_NO_CANDIDATE;
-    else if (bl <= bh + 2.0 * tau)
+    else if (nu ? gap <= 2.0 * tau : bl <= bh + 2.0 * tau)
       stop = SVM_STOP_CONVERGED;
     else if (inner_total + 1 > p.max_iter)
       stop = SVM_STOP_MAX_ITER;
@@ -412,7 +588,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       continue;
     }
     if (stop != SVM_STOP_RUNNING) break;
-    const double tau_in = std::fmax(tau, tau_frac * (bl - bh));
+    const double tau_in = std::fmax(tau, tau_frac * gap);
     const int64_t max_inner = std::min<int64_t>(int64_t(20) * m, p.max_iter - inner_total);
 
     // ---- inner solve on W (positions 0..m-1 = ascending ids)
@@ -431,6 +607,9 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     // the Newton polish of W's free variables (decomp_newton.h): `since` counts chain iterations with no
     // bound-status change, and starts at `every` after a long inner solve
     int32_t since = newton_since0(nwc, last_inner_it, last_m), ntrig = 0;
+    if (nu)
+      it = nu_inner(K, ldk, Wr, a, ft, yw, C, eps, tau_in, max_inner, &reason, &eta_floored);
+    else
     for (;;) {
       double hv = inf, lv = -inf;
       int ih = -1, il = -1;
@@ -684,11 +863,28 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     stats[14] = eta_floored;
   }
   if (mode.heldout_out) std::copy(f.begin(), f.begin() + nloc, mode.heldout_out + lo);
+  double nu_b = 0.0;
+  if (nu) {  // ws_nu_finish_kernel and run_decomp's check: r, rho, and nu-SVC's alpha / r
+    const double bp = nu_mid(nub[0], nub[2]), bn = nu_mid(nub[1], nub[3]);
+    const double r = (bp - bn) / 2, rho = (bp + bn) / 2;
+    if (!std::isfinite(r) || !std::isfinite(rho) || (nusvc && !(r > 0.0))) {
+      set_error("%s: the %s solve ended with r = %g, rho = %g (%s)", who, nusvc ? "nu-SVC" : "nu-SVR", r, rho,
+                nusvc ? "nu-SVC needs r > 0: the classes are not separated at this nu" : "a class has no bound");
+      return SVM_ERR_INTERNAL;
+    }
+    if (nusvc)
+      for (int64_t i = 0; i < n; ++i) alpha[i] = alpha[i] / r;
+    nu_b = nusvc ? rho / r : rho;
+    if (mode.nu_out) {
+      mode.nu_out[0] = r;
+      mode.nu_out[1] = rho;
+    }
+  }
   if (res) {
     res->iterations = inner_total + 1;
     res->b_high = bh;
     res->b_low = bl;
-    res->b = (bh + bl) / 2;
+    res->b = nu ? nu_b : (bh + bl) / 2;
     res->stop_reason = stop;
     res->reserved = 0;
     res->n_sv = svm_sv_indices(alpha, n, p.sv_tol, nullptr);
@@ -754,6 +950,33 @@ extern "C" SVM_API int svm_decomp_train_gram_oneclass(const double* K, int64_t l
   mode.oneclass_nu = nu;
   return decomp_solve(K, ldk, nullptr, n, alpha, 0, p, qws, tau_frac, inner_wss, res, stats, tr, nullptr, mode,
                       f64_rows != 0);
+}
+
+// The nu-SVC and nu-SVR forms (svm355.h): the nu modes, whose outer iteration is decomp_nu.hip's.
+extern "C" SVM_API int svm_decomp_train_gram_nusvc(const double* K, int64_t ldk, const int32_t* y, int64_t n, double nu,
+                                                   double* alpha, double* nu_out, const svm_params* pp, int32_t qws,
+                                                   double tau_frac, int32_t f64_rows, svm_result* res, int64_t* stats,
+                                                   svm_decomp_trace* tr) {
+  svm_params p = params_or_default(pp);
+  p.C = 1.0;  // the box is 1; class weights are refused, not cleared
+  DecompMode mode;
+  mode.kind = DecompModeKind::nu_classify;
+  mode.nu = nu;
+  mode.nu_out = nu_out;
+  return decomp_solve(K, ldk, y, n, alpha, 0, p, qws, tau_frac, 2, res, stats, tr, nullptr, mode, f64_rows != 0);
+}
+
+extern "C" SVM_API int svm_decomp_train_gram_nusvr(const double* K, int64_t ldk, const double* z, int64_t n, double nu,
+                                                   double* alpha, double* nu_out, const svm_params* pp, int32_t qws,
+                                                   double tau_frac, int32_t f64_rows, svm_result* res, int64_t* stats,
+                                                   svm_decomp_trace* tr) {
+  DecompMode mode;
+  mode.kind = DecompModeKind::nu_twin;
+  mode.twin_z = z;
+  mode.nu = nu;
+  mode.nu_out = nu_out;
+  return decomp_solve(K, ldk, nullptr, n, alpha, 0, params_or_default(pp), qws, tau_frac, 2, res, stats, tr, nullptr,
+                      mode, f64_rows != 0);
 }
 
 // The held-out form of svm_decomp_train_gram_rows (svm355.h): label 0 on the masked points, the final f out.

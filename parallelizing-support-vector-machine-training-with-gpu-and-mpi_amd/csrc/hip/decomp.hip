@@ -1178,6 +1178,11 @@ struct Solve {
   int64_t cols() const { return mode.twin() ? nrow : n; }     // the kernel columns
   int64_t oc_full = 0;
   double oc_frac = 0.0;
+  // the nu modes (decomp_nu.hip): the start walk's two numbers (nu_start_walk), and the finish kernel's {r, rho} in
+  // pinned memory as the host and the device address it
+  int64_t nu_full = 0;
+  double nu_frac = 0.0;
+  double *nu_h = nullptr, *nu_pub = nullptr;
   const int32_t* y_in = nullptr;
   ShrinkCfg shc;
   InnerVariant inner;
@@ -1348,6 +1353,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     p1.C = 1.0;
     p1.weight_pos = p1.weight_neg = 0.0;
   }
+  if (o.mode.kind == DecompModeKind::nu_classify) p1.C = 1.0;  // the box is 1 (the class weights are refused above)
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && !o.allgather)) {
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
@@ -1362,7 +1368,12 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     set_error("decomposition SMO: a trace needs one GPU and snapshots of n = %lld", (long long)n);
     return SVM_ERR_ARG;
   }
-  const DecompShape sh = decomp_shape(n, qws, world);
+  DecompShape sh = decomp_shape(n, qws, world);
+  if (sh.ok && o.mode.nu_pairs()) {  // four lists of Tc picks per block: L = 4 NB Tc (decomp_mode_check capped n)
+    sh.T = int(std::max<int64_t>(1, sh.q / (4 * sh.NB)));
+    sh.L = 4 * sh.NB * sh.T;
+    sh.ok = sh.L <= kMaxWS && sh.per <= int64_t(kSelNT) * kSelE;
+  }
   if (!sh.ok) {
     set_error("decomposition SMO: n = %lld is outside the solver's shapes (2 <= n < 2^31 - 1, %lld candidates <= %d, "
               "world <= 64)", (long long)n, (long long)sh.L, kMaxWS);
@@ -1391,9 +1402,13 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   const int64_t b0 = rank * S.NBr;
   S.lo = std::min<int64_t>(n, b0 * sh.per);
   S.nloc = std::min<int64_t>(n, (b0 + S.NBr) * sh.per) - S.lo;
-  S.Lr = 2 * S.NBr * sh.T;  // this GPU's candidate records (I_high picks, then I_low)
+  S.Lr = (o.mode.nu_pairs() ? 4 : 2) * S.NBr * sh.T;  // this GPU's candidate records (I_high picks, then I_low)
+  if (o.mode.kind == DecompModeKind::nu_classify)
+    nu_start_walk(o.mode.nu * double(nrow) / 2.0, 1.0, nrow, &S.nu_full, &S.nu_frac);
+  if (o.mode.kind == DecompModeKind::nu_twin)
+    nu_start_walk(p1.C * o.mode.nu * double(nrow) / 2.0, p1.C, nrow, &S.nu_full, &S.nu_frac);
   S.nchunks = (n + kMaxWS - 1) / kMaxWS;
-  S.wide_select = sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select;
+  S.wide_select = !o.mode.nu_pairs() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select);
   S.kww_narrow = !f64 && !S.k.kww_sym && S.kq <= 1536;
   S.shc = shrink_cfg(p);
   S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
@@ -1426,6 +1441,8 @@ int alloc_solve(Solve& S, bool warm) {
   S.hs = reinterpret_cast<DecompHost*>(pin);
   S.ctl_h = reinterpret_cast<DecompCtl*>(pin + sizeof(DecompHost) * 2);
   S.nz_h = reinterpret_cast<int64_t*>(pin + sizeof(DecompHost) * 2 + 2 * sizeof(DecompCtl));
+  S.nu_h = reinterpret_cast<double*>(S.nz_h + 2);  // 16 of the 64 bytes after the control blocks
+  SVMD_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&S.nu_pub), S.nu_h, 0));
   SVMD_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&S.ctl_pub), S.ctl_h, 0));  // as the device addresses it
   return SVM_OK;
 }
@@ -1535,6 +1552,13 @@ int nz_update(const Solve& S, const PackState& ps, int64_t* nz_out) {
   return SVM_OK;
 }
 
+// What the nu modes' launchers read of a solve (decomp_dev.h).
+NuArgs nu_args(const Solve& S, DecompCtl* pub) {
+  const DecompWs& w = S.w;
+  return NuArgs{w.f, S.alpha, w.sgn, S.n, S.sh.per, int(S.NBr), S.sh.T, S.Cp, S.p.eps, S.p.tau, S.k.tau_frac,
+                int64_t(S.p.max_iter), w.own, w.W, w.Wf, w.ctl, pub, w.mcount};
+}
+
 // The start of a solve on the stream: the control block running with its counters 0, a fresh cache,
 // alpha (cold start) and f = -y, and a warm start's f (*warm_cols = its columns).  One-class mode: its own
 // alpha, f = 0, and always the chunked start (*warm_cols = the start's columns).
@@ -1572,6 +1596,12 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
     case DecompModeKind::classify:
       hipLaunchKernelGGL(ws_init_kernel, dim3(unsigned((S.n + 255) / 256)), dim3(256), 0, s, S.y, S.alpha, w.f, S.lo,
                          S.nloc, S.n, int(warm), w.ctl);
+      break;
+    case DecompModeKind::nu_classify:
+      launch_ws_nu_start_svc(s, nu_args(S, nullptr), w.f, S.y_in, S.nu_full, S.nu_frac);
+      break;
+    case DecompModeKind::nu_twin:
+      launch_ws_nu_start_twin(s, nu_args(S, nullptr), w.f, S.mode.twin_z, S.nu_full, S.nu_frac);
       break;
   }
   SVMD_LAUNCH_CHECK();
@@ -1737,6 +1767,41 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
     if ((rc = repack(S, ps))) return rc;
   const bool packed = ps.pk >= 0;
   const int32_t* act = packed ? w.act[ps.pk] : nullptr;
+  if (S.mode.nu_pairs()) {  // one GPU, no packed rows: decomp_nu.hip's select / build / inner trio
+    const NuArgs na = nu_args(S, pub);
+    launch_ws_select_nu(s, na);
+    SVMD_LAUNCH_CHECK();
+    launch_ws_build_nu(s, na);
+    SVMD_LAUNCH_CHECK();
+    if ((rc = enqueue_kww(S))) return rc;
+    InnerArgs ia{};
+    ia.Kw = w.Kw;
+    ia.ldw = kLdw;
+    ia.W = w.W;
+    ia.ctl = w.ctl;
+    ia.y = S.y;
+    ia.alpha = S.alpha;
+    ia.Wf = w.Wf;
+    ia.C = S.Cp;
+    ia.eps = p.eps;
+    ia.cols = w.cols;
+    ia.coef = w.coef;
+    ia.mcount = w.mcount;
+    ia.pub = pub;
+    launch_ws_inner_nu(s, ia);
+    SVMD_LAUNCH_CHECK();
+    if (S.mode.twin()) {
+      hipLaunchKernelGGL(ws_twin_fold_kernel, dim3(1), dim3(kMaxWS), 0, s, w.cols, w.coef, w.mcount, S.nrow, w.fcols,
+                         w.fcoef, w.fcount);
+      SVMD_LAUNCH_CHECK();
+      rc = f_update(S, ps, w.fcols, w.fcoef, w.fcount, index < 4);
+    } else {
+      rc = f_update(S, ps, w.cols, w.coef, w.mcount, index < 4);
+    }
+    if (rc) return rc;
+    ++ps.o_dev;
+    return solo.end(1);
+  }
   if (NBr > 0)
     hipLaunchKernelGGL(S.wide_select ? ws_select_wide_kernel : ws_select_kernel, dim3(unsigned(NBr)), dim3(kSelNT), 0, s,
                        w.f, S.alpha, S.y, lo, nloc, S.sh.per, T, S.Cp, S.Cn, p.eps, w.own, w.own + NBr * T, w.ctl, act,
@@ -1951,7 +2016,28 @@ int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* al
                        S.n, S.w.ctl, S.mode.heldout_out);
     SVMD_LAUNCH_CHECK();
   }
-  return finish_solve(S, ps, *fin, warm_cols, r, stats);
+  double nu_r = 0.0, nu_rho = 0.0;
+  if (S.mode.nu_pairs()) {  // behind the queued no-op batch: r and rho, and nu-SVC's alpha / r
+    if (fin->stop == kStopInternal) return finish_solve(S, ps, *fin, warm_cols, r, stats);
+    const bool svc = S.mode.kind == DecompModeKind::nu_classify;
+    launch_ws_nu_finish(s, nu_args(S, nullptr), svc ? 1 : 0, S.nu_pub);
+    SVMD_LAUNCH_CHECK();
+    SVMD_CHECK(hipStreamSynchronize(s));
+    nu_r = S.nu_h[0];
+    nu_rho = S.nu_h[1];
+    if (!std::isfinite(nu_r) || !std::isfinite(nu_rho) || (svc && !(nu_r > 0.0))) {
+      set_error("decomposition SMO: the %s solve ended with r = %g, rho = %g (%s)", svc ? "nu-SVC" : "nu-SVR", nu_r,
+                nu_rho, svc ? "nu-SVC needs r > 0: the classes are not separated at this nu" : "a class has no bound");
+      return SVM_ERR_INTERNAL;
+    }
+    if (S.mode.nu_out) {
+      S.mode.nu_out[0] = nu_r;
+      S.mode.nu_out[1] = nu_rho;
+    }
+  }
+  rc = finish_solve(S, ps, *fin, warm_cols, r, stats);
+  if (!rc && r && S.mode.nu_pairs()) r->b = S.mode.kind == DecompModeKind::nu_classify ? nu_rho / nu_r : nu_rho;
+  return rc;
 }
 
 // ---- the fit entries ------------------------------------------------------------------------------------
@@ -2237,6 +2323,42 @@ SVM_API int svmd_train_decomp_oneclass(void* h, const void* X_d, int32_t is_u8, 
   o.mode.oneclass_nu = nu;
   return train_decomp_entry("svmd_train_decomp_oneclass", h, X_d, is_u8, n, ld, d, mn_h, mx_h, true, nullptr, alpha_d,
                             pp, q, o, r, timing, stats, used_out, trace);
+}
+
+// The nu-SVC form of svmd_train_decomp (LIBSVM's -s 1; svm355.h has the problem): the nu_classify mode
+// (decomp_mode.h, decomp_nu.hip) over the n rows and their +1 / -1 labels y_d; n_pos = how many labels are +1 (the
+// caller counts its host labels: an infeasible nu is refused before any device work).  alpha_d: n doubles, out,
+// already divided by r; r->b = rho / r and a decision value is sum_k alpha_k y_k K(x_k, x) - r->b; nu_out (2
+// doubles, host): {r, rho}.  pp->C is not read (the box is 1).  One GPU, cold start; shrinking, the Newton polish
+// and class weights are SVM_ERR_ARG, as are nu outside (0, 1] and n > 1,048,576.
+SVM_API int svmd_train_decomp_nusvc(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                    const double* mn_h, const double* mx_h, const int32_t* y_d, int64_t n_pos,
+                                    double nu, double* alpha_d, double* nu_out, const svm_params* pp, int32_t q,
+                                    svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used_out,
+                                    svm_decomp_trace* trace) {
+  DecompOpts o;
+  o.mode.kind = DecompModeKind::nu_classify;
+  o.mode.nu = nu;
+  o.mode.nu_npos = n_pos;
+  o.mode.nu_out = nu_out;
+  return train_decomp_entry("svmd_train_decomp_nusvc", h, X_d, is_u8, n, ld, d, mn_h, mx_h, y_d && nu_out, y_d, alpha_d,
+                            pp, q, o, r, timing, stats, used_out, trace);
+}
+
+// The nu-SVR form (LIBSVM's -s 4): the nu_twin mode over the n rows and the n targets z_d.  alpha_d: 2n doubles,
+// out -- a, then a*, unscaled; r->b = rho, a prediction is sum_k (a_k - a*_k) K(x_k, x) - rho, and the tube found
+// is epsilon = -nu_out[0] (nu_out: {r, rho}).  The box is pp->C.  The same refusals, with 2n <= 1,048,576.
+SVM_API int svmd_train_decomp_nusvr(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                    const double* mn_h, const double* mx_h, const double* z_d, double nu,
+                                    double* alpha_d, double* nu_out, const svm_params* pp, int32_t q, svm_result* r,
+                                    svmd_timing* timing, int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
+  DecompOpts o;
+  o.mode.kind = DecompModeKind::nu_twin;
+  o.mode.twin_z = z_d;
+  o.mode.nu = nu;
+  o.mode.nu_out = nu_out;
+  return train_decomp_entry("svmd_train_decomp_nusvr", h, X_d, is_u8, n, ld, d, mn_h, mx_h, z_d && nu_out, nullptr,
+                            alpha_d, pp, q, o, r, timing, stats, used_out, trace);
 }
 
 // The held-out form of svmd_train_decomp (svm355_device.h): held-out mode (decomp_mode.h) over the n rows.

@@ -37,6 +37,7 @@ struct DecompCtl {
   int64_t passes;            // shrink passes run
   int32_t last_m, pad2;      // the last inner solve's working-set size (the Newton polish's arming)
   int64_t newton_steps;      // Newton polish steps applied (decomp_newton.h)
+  double b_high_n, b_low_n;  // the nu modes (decomp_nu.hip): the sign -1 class's bounds (b_high / b_low: the +1 class's)
 };
 
 // The Newton polish's knobs on the device (NewtonCfg).
@@ -110,5 +111,40 @@ int launch_ws_inner(hipStream_t s, const InnerVariant& v, const InnerArgs& a);
 bool ws_newton_probe_built(int nt);
 int launch_ws_newton_probe(hipStream_t s, int nt, int m, const double* Kw, int64_t ldw, const int32_t* y, double* gA,
                            double* gF, double* Amat, double C, double eps, int max_free, int32_t* code_out, int64_t* prof);
+
+// ---- the nu modes (decomp_nu.hip): nu-SVC and nu-SVR, pairs of one sign ------------------------------------
+// What the nu kernels' launchers read (as InnerArgs: the control blocks are file-local types, so they travel in a
+// struct).  The candidates are four lists of NB Tc records, list-major: I_high of sign +1, I_high of sign -1, I_low
+// of +1, I_low of -1 (L = 4 NB Tc <= kMaxWS, at most kSelNT x kSelE points per block; the caller has checked both).
+// sgn: the solve's own signs, +1 / -1 for every point.  The callers check the launches (SVMD_LAUNCH_CHECK).
+struct NuArgs {
+  const double* f;       // all n points' f
+  double* alpha;
+  int32_t* sgn;
+  int64_t n, per;        // points, points per selection block
+  int NB, Tc;
+  double C, eps, tau, tau_frac;
+  int64_t max_iter;
+  CandRec* cand;         // 4 NB Tc records
+  int32_t* W;
+  double* Wf;
+  DecompCtl *ctl, *pub;
+  int32_t* mcount;
+};
+void launch_ws_select_nu(hipStream_t s, const NuArgs& a);
+void launch_ws_build_nu(hipStream_t s, const NuArgs& a);
+// One inner solve (256 threads x 4 points).  Of `a` it reads Kw, ldw, W, ctl, y (the signs), alpha, Wf, C, eps,
+// cols, coef, mcount and pub.
+void launch_ws_inner_nu(hipStream_t s, const InnerArgs& a);
+// The starts (of `a`: n, sgn, alpha, f, ctl).  nu-SVC: per class of y (+1, else -1) in ascending index, alpha = 1
+// for the class's first `full` points, `frac` for the next, 0 beyond; sgn; f = 0 (the chunked start adds K[:, nz]
+// (alpha sgn)_nz).  nu-SVR over nrow = n / 2 targets z: a_k = a*_k = a.C for k < full, frac at k = full, 0 beyond;
+// f_k = f_{k+nrow} = -z_k; signs +1, -1.  (f is written here: the solve's own buffer.)
+void launch_ws_nu_start_svc(hipStream_t s, const NuArgs& a, double* f, const int32_t* y, int64_t full, double frac);
+void launch_ws_nu_start_twin(hipStream_t s, const NuArgs& a, double* f, const double* z, int64_t full, double frac);
+// The finish (one workgroup): b_c = (b_high_c + b_low_c) / 2 per class (the finite one when a side is empty), r =
+// (b_+ - b_-) / 2, rho = (b_+ + b_-) / 2 to out[0], out[1] (pinned host memory, as the device addresses it), and,
+// with `rescale` and r > 0, alpha_i /= r over the n points.
+void launch_ws_nu_finish(hipStream_t s, const NuArgs& a, int rescale, double* out);
 
 }  // namespace svm355

@@ -15,7 +15,7 @@ namespace svm355 {
 
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 
-enum class DecompModeKind { classify, twin, oneclass, heldout };
+enum class DecompModeKind { classify, twin, oneclass, heldout, nu_classify, nu_twin };
 enum class DecompBackend { device, cpu_oracle };
 
 // What a solve is of, beyond the classifier's n labelled points.  n rows go in as always.
@@ -32,18 +32,32 @@ enum class DecompBackend { device, cpu_oracle };
 //     caller's y after the start.  heldout_out = n doubles, out: on the device f_i - b for the held-out points
 //     after the last outer iteration and 0.0 for the others; on the oracle the final f of every point, optional.
 //     The training part must hold both classes (the caller checks).
+//   * nu_classify (LIBSVM's -s 1, nu-SVC) and nu_twin (-s 4, nu-SVR; svm355.h has both problems): 0 < nu <= 1.  Two
+//     equalities (y'a = 0 and e'a = const), so a step moves a pair of points of one sign, the stop test is the larger
+//     of the two per-class gaps, and two multipliers come out: nu_out (2 doubles, host, out) = {r, rho}.  nu_classify
+//     reads the caller's y for its start (each class walked in ascending index, a_i = min(1, what is left of nu n /
+//     2); box 1, p.C is not read; f = K[:, nz] (a y)_nz by the chunked start) and keeps signs of its own; at the end
+//     alpha is divided by r.  nu_twin is twin's layout with twin_z the targets: a_k = a*_k = min(C, what is left of
+//     C nu n / 2), f_k = f_{k+n} = -z_k.  The kernels of these two modes are decomp_nu.hip's.
 struct DecompMode {
   DecompModeKind kind = DecompModeKind::classify;
   const double* twin_z = nullptr;
   double twin_eps = 0.0;
   double oneclass_nu = 0.0;
+  double nu = 0.0;
+  int64_t nu_npos = -1;  // nu_classify on the device: how many labels are +1 (the caller counts its host labels)
+  double* nu_out = nullptr;
   const uint8_t* heldout = nullptr;
   double* heldout_out = nullptr;
-  bool twin() const { return kind == DecompModeKind::twin; }
+  bool twin() const { return kind == DecompModeKind::twin || kind == DecompModeKind::nu_twin; }
+  // the same-sign-pair modes: four candidate lists, two gaps, decomp_nu.hip's select / build / inner kernels
+  bool nu_pairs() const { return kind == DecompModeKind::nu_classify || kind == DecompModeKind::nu_twin; }
   // the solve keeps its own signs (its y is not the caller's)
   bool own_signs() const { return kind != DecompModeKind::classify; }
   // the start sums f over the nonzero alphas in chunks, as a warm start does (sized as one)
-  bool chunked_start(bool warm) const { return warm || kind == DecompModeKind::oneclass; }
+  bool chunked_start(bool warm) const {
+    return warm || kind == DecompModeKind::oneclass || kind == DecompModeKind::nu_classify;
+  }
   // the points the solve selects among, over nrow kernel rows
   int64_t points(int64_t nrow) const { return twin() ? 2 * nrow : nrow; }
 };
@@ -62,13 +76,38 @@ inline DecompFeatures decomp_features(const svm_params& p, int world, bool warm,
 // another problem in silence -- and is where the backends differ: the oracle runs weighted ranks, the device's
 // distributed solve does not.  One-class mode: shrinking's unshrink rebuilds f from -y (the oracle's entry
 // clears the weights, so its `weighted` is never set).  Held-out mode: shrinking's unshrink rebuilds f from
-// the nonzero alphas, the polish is untested on label 0; class weights are allowed.
-constexpr DecompFeatures kDecompRefuses[4][2] = {
+// the nonzero alphas, the polish is untested on label 0; class weights are allowed.  The nu modes: their kernels
+// have one pair per iteration and one box, no shrink pass, no polish, and their start is their own.
+constexpr DecompFeatures kDecompRefuses[6][2] = {
     /* classify */ {{true, false, true, true, false}, {false, false, true, true, false}},
     /* twin     */ {{true, true, true, true, true}, {true, true, true, true, true}},
     /* oneclass */ {{true, true, true, true, true}, {true, true, true, true, true}},
     /* heldout  */ {{true, true, true, true, false}, {true, true, true, true, false}},
+    /* nu-SVC   */ {{true, true, true, true, true}, {true, true, true, true, true}},
+    /* nu-SVR   */ {{true, true, true, true, true}, {true, true, true, true, true}},
 };
+
+// The nu modes' selection: NB blocks of at most kNuBlockPoints points give Tc picks to each of four lists, and the
+// 4 NB Tc candidates must fit one working set (SVM_DECOMP_MAX_WS): at most 256 blocks, 1,048,576 points.
+constexpr int64_t kNuBlockPoints = 4096;
+constexpr int64_t kNuMaxPoints = int64_t(SVM_DECOMP_MAX_WS) / 4 * kNuBlockPoints;
+// LIBSVM's start walk (solve_nu_svc, solve_nu_svr) over `cap` points in ascending index: a_i = min(box, what is
+// left of `total`), in its own arithmetic (repeated subtraction).  The first `full` points get the box, point
+// `full` (if any) gets `frac` < box, the rest 0 -- the two numbers the device's start kernels take.
+inline void nu_start_walk(double total, double box, int64_t cap, int64_t* full, double* frac) {
+  double left = total;
+  int64_t k = 0;
+  while (k < cap && left >= box) {
+    left -= box;
+    ++k;
+  }
+  *full = k;
+  *frac = k < cap ? left : 0.0;
+}
+// nu-SVC's feasibility: nu n / 2 of alpha per class, at most 1 per point.  Counts the caller's host labels.
+inline bool nu_svc_feasible(double nu, int64_t n, int64_t n_pos, int64_t n_neg) {
+  return nu * double(n) / 2.0 <= double(n_pos < n_neg ? n_pos : n_neg);
+}
 
 // The first feature the kind refuses, in this fixed order, or nullptr.
 inline const char* decomp_mode_refuses(DecompModeKind kind, const DecompFeatures& f, DecompBackend backend) {
@@ -86,7 +125,7 @@ inline const char* decomp_mode_refuses(DecompModeKind kind, const DecompFeatures
 // SVM_ERR_ARG with `who` as the message's prefix, before the caller does any work.
 inline int decomp_mode_check(const char* who, const DecompMode& m, const int32_t* y, const DecompFeatures& f,
                              int64_t nrow, DecompBackend backend) {
-  static const char* const solve[] = {nullptr, "regression (twin)", "one-class", "held-out"};
+  static const char* const solve[] = {nullptr, "regression (twin)", "one-class", "held-out", "nu-SVC", "nu-SVR"};
   if (const char* what = decomp_mode_refuses(m.kind, f, backend)) {
     if (m.kind == DecompModeKind::classify)
       set_error("%s: class weights are not supported with %s", who, what);
@@ -112,6 +151,37 @@ inline int decomp_mode_check(const char* who, const DecompMode& m, const int32_t
         return SVM_ERR_ARG;
       }
       break;
+    case DecompModeKind::nu_classify:
+    case DecompModeKind::nu_twin: {
+      const bool tw = m.kind == DecompModeKind::nu_twin;
+      if (!(m.nu > 0.0 && m.nu <= 1.0)) {
+        set_error("%s: nu must be in (0, 1], got %g", who, m.nu);
+        return SVM_ERR_ARG;
+      }
+      if (nrow < 2 || m.points(nrow) > kNuMaxPoints) {
+        set_error("%s: the %s solve takes 2 <= n and at most %lld points (%lld here): its four candidate lists of "
+                  "every 4096-point block must fit one working set", who, solve[int(m.kind)], (long long)kNuMaxPoints,
+                  (long long)m.points(nrow));
+        return SVM_ERR_ARG;
+      }
+      if (tw ? !m.twin_z : !y) {
+        set_error("%s: the %s solve needs %s", who, solve[int(m.kind)], tw ? "targets" : "labels");
+        return SVM_ERR_ARG;
+      }
+      if (!tw) {  // the oracle's labels are the host's; the device's entry brings the count of its +1 labels
+        int64_t np = m.nu_npos;
+        if (backend == DecompBackend::cpu_oracle) {
+          np = 0;
+          for (int64_t i = 0; i < nrow; ++i) np += y[i] == 1 ? 1 : 0;
+        }
+        if (np < 0 || np > nrow || !nu_svc_feasible(m.nu, nrow, np, nrow - np)) {
+          set_error("%s: specified nu is infeasible (nu = %g, %lld points of class +1 and %lld of class -1: nu n / 2 "
+                    "must not exceed the smaller class)", who, m.nu, (long long)np, (long long)(nrow - np));
+          return SVM_ERR_ARG;
+        }
+      }
+      break;
+    }
   }
   return SVM_OK;
 }

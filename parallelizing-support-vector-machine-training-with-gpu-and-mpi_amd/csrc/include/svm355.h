@@ -215,6 +215,36 @@ SVM_API int svm_decomp_train_gram_oneclass(const double* K, int64_t ldk, int64_t
                                            const svm_params* p, int32_t q, double tau_frac, int32_t inner_wss,
                                            int32_t f64_rows, svm_result* r, int64_t* stats, svm_decomp_trace* trace);
 
+// ---------------------------------------------------------------- nu-SVC and nu-SVR (L3)
+// LIBSVM's -s 1 and -s 4, in its scaling and this project's f convention: signs s_i = +-1, f_i = sum_j a_j s_j K_ij
+// + p_i.  Both duals have TWO equalities, s'a = 0 and e'a = const, so a feasible step moves a pair of points of one
+// sign; with I_high / I_low the classifier's sets taken per sign class c, b_high_c = min f over I_high of c and
+// b_low_c = max f over I_low of c, the stop test is max_c (b_low_c - b_high_c) <= 2 tau (a class with an empty side
+// has no gap).  At the end b_c = (b_high_c + b_low_c) / 2, r = (b_+ - b_-) / 2 and rho = (b_+ + b_-) / 2.
+//   nu-SVC: labels y, 0 < nu <= 1, box 1, p = 0, e'a = nu n.  Start (solve_nu_svc): each class walked in ascending
+//           index, a_i = min(1, what is left of nu n / 2); f = K[:, nz] (a y)_nz summed as the one-class start.
+//           Infeasible -- SVM_ERR_ARG, "specified nu is infeasible" -- when nu n / 2 exceeds the smaller class.
+//           r <= 0 at the end is an error.  alpha (n, out) is a / r, res->b = rho / r, and the decision value of x
+//           is sum_i alpha_i y_i K(x_i, x) - b: a free point of either class has decision +-1.
+//   nu-SVR: targets z, box C, 0 < nu <= 1, on the twin layout (point k sign +1, point k + n sign -1, both on row
+//           k), e'(a + a*) = C nu n.  Start: a_k = a*_k = min(C, what is left of C nu n / 2), so f_k = f_{k+n} =
+//           -z_k.  alpha (2n, out: a, then a*) is unscaled, res->b = rho, the prediction is sum (a - a*) K - b and
+//           the tube found is epsilon = -r.
+// The pair rule is LIBSVM's Solver_NU::select_working_set: i_c = argmin f over I_high of c; over the I_low points t
+// of c with f_t > f_{i_c} the gain -(f_t - f_{i_c})^2 / max(eps, 2 - 2 K(i_c, t)); the (i, j) of smallest gain over
+// both classes, lowest position on ties; then the classifier's clip / eta floor / update with equal labels.
+// The decomposition oracle's nu modes on the n x n kernel matrix K (the device's own kernel values for a bit-for-bit
+// comparison with svmd_train_decomp_nusvc / _nusvr; f64_rows as svm_decomp_train_gram_oneclass); nu_out (2 doubles,
+// optional): {r, rho}.  On a host FP64 Gram they are the estimators' device="cpu" backend.  One rank, cold start;
+// shrinking, the Newton polish, class weights, nu outside (0, 1] and more than 1,048,576 points (nusvr: 2n) are
+// SVM_ERR_ARG.
+SVM_API int svm_decomp_train_gram_nusvc(const double* K, int64_t ldk, const int32_t* y, int64_t n, double nu,
+                                        double* alpha, double* nu_out, const svm_params* p, int32_t q, double tau_frac,
+                                        int32_t f64_rows, svm_result* r, int64_t* stats, svm_decomp_trace* trace);
+SVM_API int svm_decomp_train_gram_nusvr(const double* K, int64_t ldk, const double* z, int64_t n, double nu,
+                                        double* alpha, double* nu_out, const svm_params* p, int32_t q, double tau_frac,
+                                        int32_t f64_rows, svm_result* r, int64_t* stats, svm_decomp_trace* trace);
+
 // ---------------------------------------------------------------- held-out points and Platt scaling (L3)
 // The held-out form of svm_decomp_train_gram_rows (cold start): heldout[i] != 0 takes point i out of the fit.  In
 // THIS entry (and the device's svmd_train_decomp_heldout) only, such a point runs with label 0, which means "held

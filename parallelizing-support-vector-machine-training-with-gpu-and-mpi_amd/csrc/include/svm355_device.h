@@ -89,6 +89,24 @@ SVM_API int svmd_train_decomp_oneclass(void* ctx, const void* X_d, int32_t is_u8
                                        const double* mn_h, const double* mx_h, double nu, double* alpha_d,
                                        const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
                                        int64_t* stats, int32_t* used, svm_decomp_trace* trace);
+// nu-SVC and nu-SVR (LIBSVM's -s 1 and -s 4, svm355.h) on the decomposition solver's nu modes, whose selection,
+// build and inner solve are kernels of their own (decomp_nu.hip: pairs of one sign, four candidate lists, the stop
+// test on the larger class gap).  Rows as above.  nu_out: 2 host doubles, out: {r, rho}.
+//   nusvc: y_d the +1 / -1 labels, n_pos how many are +1 (counted by the caller on the host: an infeasible nu --
+//          nu n / 2 above the smaller class -- is SVM_ERR_ARG before any device work).  alpha_d: n doubles, out,
+//          already divided by r; r->b = rho / r.  p->C is not read (the box is 1).
+//   nusvr: z_d the n targets.  alpha_d: 2n doubles, out: a, then a*; r->b = rho; the tube found is -nu_out[0].
+// One GPU, cold start; shrinking, the Newton polish, class weights, nu outside (0, 1] and more than 1,048,576 points
+// (nusvr: 2n) are SVM_ERR_ARG.  *used as svmd_train_decomp_svr.
+SVM_API int svmd_train_decomp_nusvc(void* ctx, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                    const double* mn_h, const double* mx_h, const int32_t* y_d, int64_t n_pos,
+                                    double nu, double* alpha_d, double* nu_out, const svm_params* p, int32_t q,
+                                    svm_result* r, svmd_timing* timing, int64_t* stats, int32_t* used,
+                                    svm_decomp_trace* trace);
+SVM_API int svmd_train_decomp_nusvr(void* ctx, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                    const double* mn_h, const double* mx_h, const double* z_d, double nu,
+                                    double* alpha_d, double* nu_out, const svm_params* p, int32_t q, svm_result* r,
+                                    svmd_timing* timing, int64_t* stats, int32_t* used, svm_decomp_trace* trace);
 // The held-out form of svmd_train_decomp (svm355.h: label 0 means "held out, never selected" in this entry only):
 // heldout_d uint8[n], 1 = out of the fit; dec_out_d n doubles, out: f_i - r->b for the held-out points (the decision
 // value of a model that never saw them, from the training's own kernel values), 0.0 for the others.  The solve keeps

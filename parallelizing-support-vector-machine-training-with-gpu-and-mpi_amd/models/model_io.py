@@ -9,7 +9,8 @@ stores the scaled SV rows (``sv_rows.npy``) and the scaler (``scaler.npz``) in n
 pickle-free formats, plus ``model.json`` with the hyper-parameters and the model's kind: "svc" (a
 classifier; also what a file without the marker is), "svr" (an epsilon-SVR, stored with labels = sign(beta)
 and alphas = |beta|) or "oneclass" (a one-class SVM: labels all +1, alphas = alpha, b = rho, ``meta["nu"]``).
-Each class loads its own kind only.
+"nusvc" / "nusvr" (``NuSVC`` / ``NuSVR``: labels = sign(dual_coef_), alphas = |dual_coef_|, ``meta["nu"]``, ``meta["r"]``,
+``meta["rho"]``).  Each class loads its own kind only.
 """
 from __future__ import annotations
 

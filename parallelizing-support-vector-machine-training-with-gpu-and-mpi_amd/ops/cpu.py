@@ -206,6 +206,43 @@ def decomp_train_gram_oneclass(K: np.ndarray, params: SVMParams, nu: float = 0.5
     return a, SMOResult.from_struct(r), {**_decomp_stats(st), "start_columns": int(st[7])}, tr
 
 
+def _decomp_train_gram_nu(entry: str, K: np.ndarray, target: np.ndarray, points: int, params: SVMParams, nu: float,
+                          q: int, tau_frac: float, trace_cap: int, snapshots: bool, fp64_rows: bool):
+    n = target.shape[0]
+    _gram_shape(K, n)
+    a = np.zeros(points)
+    out = np.zeros(2)
+    r = N.SvmResult()
+    st = (ctypes.c_int64 * 16)()
+    tr = N.DecompTrace(trace_cap, points if snapshots else 0) if trace_cap > 0 else None
+    p = params.to_struct()
+    N.check(getattr(N.core(), entry)(N.ptr(K), K.shape[1], N.ptr(target), n, float(nu), N.ptr(a), N.ptr(out),
+                                     ctypes.byref(p), int(q), float(tau_frac), int(bool(fp64_rows)), ctypes.byref(r),
+                                     st, ctypes.byref(tr.struct) if tr is not None else None), entry)
+    return a, SMOResult.from_struct(r), {**_decomp_stats(st), "start_columns": int(st[7])}, (out[0], out[1]), tr
+
+
+def decomp_train_gram_nusvc(K: np.ndarray, y: np.ndarray, params: SVMParams, nu: float = 0.5, q: int = 1024,
+                            tau_frac: float = 0.1, trace_cap: int = 0, snapshots: bool = False,
+                            fp64_rows: bool = False):
+    """The decomposition oracle's nu-SVC mode (svm_decomp_train_gram_nusvc) on the n x n kernel matrix K and the
+    +1 / -1 labels y.  Returns (alpha of n entries, already divided by r; SMOResult with b = rho / r; stats dict;
+    (r, rho); N.DecompTrace or None -- its alpha snapshots are before the division).  params.C is not read."""
+    return _decomp_train_gram_nu("svm_decomp_train_gram_nusvc", _c64(K), _c32(y), np.shape(y)[0], params, nu, q,
+                                 tau_frac, trace_cap, snapshots, fp64_rows)
+
+
+def decomp_train_gram_nusvr(K: np.ndarray, z: np.ndarray, params: SVMParams, nu: float = 0.5, q: int = 1024,
+                            tau_frac: float = 0.1, trace_cap: int = 0, snapshots: bool = False,
+                            fp64_rows: bool = False):
+    """The decomposition oracle's nu-SVR mode (svm_decomp_train_gram_nusvr) on the n x n kernel matrix K and the n
+    targets z.  Returns (alpha of 2n entries: a, then a*; SMOResult with b = rho; stats dict; (r, rho): the tube
+    found is -r; N.DecompTrace or None, with virtual ids and 2n-long snapshots).  The box is params.C."""
+    n = np.shape(z)[0]
+    return _decomp_train_gram_nu("svm_decomp_train_gram_nusvr", _c64(K), _targets(z, n), 2 * n, params, nu, q,
+                                 tau_frac, trace_cap, snapshots, fp64_rows)
+
+
 def decomp_train_gram_heldout(K: np.ndarray, y: np.ndarray, heldout: np.ndarray, params: SVMParams, q: int = 1024,
                               tau_frac: float = 0.1, inner_wss: int = 3, trace_cap: int = 0,
                               snapshots: bool = False, fp64_rows: bool = False):

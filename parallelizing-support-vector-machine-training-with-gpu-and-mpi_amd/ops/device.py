@@ -519,6 +519,46 @@ def train_decomp_oneclass(X: torch.Tensor, alpha: torch.Tensor, params: SVMParam
                          working_set, trace, lambda st: {"start_columns": int(st[7])})
 
 
+def train_decomp_nusvc(X: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
+                       nu: float = 0.5, n_pos: Optional[int] = None, working_set: int = 1024,
+                       trace: Optional["N.DecompTrace"] = None):
+    """nu-SVC on the decomposition solver's nu mode (svmd_train_decomp_nusvc; kernels: decomp_nu.hip) over the n rows
+    of X (as ``train_decomp``) and the +1 / -1 int32 labels y on the device.  n_pos: how many labels are +1 (the
+    caller's host count; None counts on the device) -- an infeasible nu raises before any solver work.  alpha (n
+    float64, out) is already divided by r; the result's b is rho / r.  Returns (SMOResult, timing dict, (r, rho)),
+    or None when nothing ran.  params.C is not read.  Shrinking, the Newton polish, class weights, nu outside
+    (0, 1] and n > 1,048,576 raise."""
+    n = _decomp_rows(X)
+    if y.dtype != torch.int32 or y.shape != (n,) or not y.is_contiguous() or y.device != X.device:
+        raise ValueError(f"y must be a contiguous int32 tensor of shape ({n},) on the rows' device")
+    if alpha.dtype != torch.float64 or alpha.shape != (n,) or not alpha.is_contiguous():
+        raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({n},)")
+    if n_pos is None:
+        n_pos = int((y == 1).sum().item())
+    out = np.zeros(2)
+    res = _train_decomp("svmd_train_decomp_nusvc", "decomp-nusvc", X, mn, mx,
+                        (N.ptr(y), int(n_pos), float(nu), N.ptr(alpha), N.ptr(out)), params, working_set, trace,
+                        lambda st: {"start_columns": int(st[7])})
+    return None if res is None else (*res, (float(out[0]), float(out[1])))
+
+
+def train_decomp_nusvr(X: torch.Tensor, z: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx,
+                       nu: float = 0.5, working_set: int = 1024, trace: Optional["N.DecompTrace"] = None):
+    """nu-SVR on the decomposition solver's nu mode (svmd_train_decomp_nusvr) over the n rows of X and the n float64
+    targets z on the device, on the twin layout of ``train_decomp_svr``.  alpha (2n float64, out): a, then a*,
+    unscaled; the result's b is rho and the tube found is -r.  Returns (SMOResult, timing dict, (r, rho)), or None
+    when nothing ran.  The box is params.C.  The refusals of ``train_decomp_nusvc``, with 2n <= 1,048,576."""
+    n = _decomp_rows(X)
+    if z.dtype != torch.float64 or z.shape != (n,) or not z.is_contiguous():
+        raise ValueError(f"z must be a contiguous float64 tensor of shape ({n},)")
+    if alpha.dtype != torch.float64 or alpha.shape != (2 * n,) or not alpha.is_contiguous():
+        raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({2 * n},): a, then a*")
+    out = np.zeros(2)
+    res = _train_decomp("svmd_train_decomp_nusvr", "decomp-nusvr", X, mn, mx,
+                        (N.ptr(z), float(nu), N.ptr(alpha), N.ptr(out)), params, working_set, trace)
+    return None if res is None else (*res, (float(out[0]), float(out[1])))
+
+
 def train_decomp_heldout(X: torch.Tensor, y: torch.Tensor, heldout: torch.Tensor, alpha: torch.Tensor,
                          dec: torch.Tensor, params: SVMParams, mn, mx, working_set: int = 1024,
                          trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:
