@@ -14,6 +14,9 @@ re-designed for gfx950:
 * ``svm355.SVR``                     epsilon-SVR on the same solvers: the 2n-variable problem whose twins a_k / a*_k
                                      share a kernel row, so on the GPU the decomposition solver's kernel work
                                      runs over n rows, not 2n (the CPU oracle is the pairwise solver)
+* ``svm355.CSR``                     sparse rows for ``SVC`` / ``SVR`` (any object with data / indices / indptr / shape
+                                     is taken, ``scipy.sparse.csr_matrix`` too): the solver's kernel values come
+                                     from the CSR rows against a transposed panel of the working set
 * ``svm355.OneClassSVM``             one-class SVM (novelty detection on unlabelled rows, LIBSVM's -s 2): the
                                      classifier's dual with every sign +1, box 1 and no linear term, solved by
                                      the decomposition solver's one-class mode from LIBSVM's feasible start
@@ -53,8 +56,9 @@ from .models.svc import SVC
 from .models.svr import SVR
 from .models.oneclass import OneClassSVM
 from .models.nusvm import NuSVC, NuSVR
+from .utils.sparse import CSR
 
-__all__ = ["SVMParams", "Dataset", "MinMaxScaler", "load_csv", "one_vs_rest", "synthetic_mnist", "write_csv",
+__all__ = ["SVMParams", "CSR", "Dataset", "MinMaxScaler", "load_csv", "one_vs_rest", "synthetic_mnist", "write_csv",
            "SVC", "SVR", "OneClassSVM", "NuSVC", "NuSVR", "OneVsRestSVC", "OneVsOneSVC", "CascadeSVM", "DistributedSVC", "DistributedDecompSVC"]
 __version__ = "0.1.0"
 

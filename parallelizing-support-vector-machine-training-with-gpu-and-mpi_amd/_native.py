@@ -301,6 +301,15 @@ _HIP_SIGS = {
     "svmd_decision_int": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, _P, _P, _P, c_int64, c_double, _P,
                                     POINTER(c_int32)]),
     "svmd_gather_rows": (c_int32, [c_void_p, _P, c_int64, _P, c_int64, _P]),
+    "svmd_csr_prepare": (c_int32, [c_void_p, _P, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P, _P, _P]),
+    "svmd_rbf_block_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P,
+                                     c_double, c_int32, _P, c_int64]),
+    "svmd_decision_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64,
+                                    c_double, c_double, _P]),
+    "svmd_csr_rows_dense": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P]),
+    "svmd_train_decomp_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_double, _P,
+                                        POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
+                                        POINTER(c_int64), POINTER(SvmDecompTrace)]),
     "svmd_ovo_votes": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P]),
     "svmd_ovo_predict": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, c_double,
                                    c_int64, _P, _P, c_int64, _P, c_int64, _P, _P]),

@@ -57,7 +57,9 @@ struct DecompOpts {
 
 // The rows a solve reads its kernel values from: the exact-integer plan's quantised rows (Q; int8
 // MFMA, igram.hip) or the min-max scaled FP64 rows themselves (X, n x ld, ld a multiple of 16, and
-// their squared norms nrm; FP64 MFMA, gram_mfma.hip) -- the latter for real-valued data.
+// their squared norms nrm; FP64 MFMA, gram_mfma.hip) -- the latter for real-valued data -- or sparse rows in CSR
+// form (indptr n + 1, indices sorted and in [0, d), values min-max scaled so that zeros stay zeros, and nrm;
+// csr_rbf.hip: kernel values against a d x 1024 transposed panel of the working set; one GPU, cold start).
 struct DecompRows {
   const int8_t* Q = nullptr;
   const int32_t* N0 = nullptr;
@@ -67,7 +69,12 @@ struct DecompRows {
   const double* X = nullptr;
   const double* nrm = nullptr;
   int64_t ld = 0;
+  const int64_t* indptr = nullptr;
+  const int32_t* indices = nullptr;
+  const double* values = nullptr;
+  int64_t d = 0, dpad = 0;  // CSR: the features, and the panel's feature rows (d rounded up to 16)
   bool fp64() const { return X != nullptr; }
+  bool csr() const { return indptr != nullptr; }
 };
 
 // stats: SVM_DECOMP_STATS int64 (see run_decomp).

@@ -32,6 +32,7 @@
 #include <mutex>
 #include <vector>
 
+#include "csr_rbf.h"
 #include "decomp.h"
 #include "decomp_dev.h"
 #include "decomp_newton.h"
@@ -1142,6 +1143,10 @@ struct DecompWs {
   // twin mode (epsilon-SVR): the 2n points' signs (the solve's y) and the folded moved list (one entry per row)
   int32_t *sgn = nullptr, *fcols = nullptr, *fcount = nullptr;
   double* fcoef = nullptr;
+  // sparse rows: the transposed panel (dpad x kMaxWS), its rows' norms, and the rows it holds now (ids, count)
+  double *PT = nullptr, *nP = nullptr;
+  int32_t *pprev = nullptr, *pcnt = nullptr;
+  CsrPanel panel() const { return CsrPanel{PT, kMaxWS, nP, pprev, pcnt}; }
 };
 
 // The f update's kernel columns K(this GPU's rows, j) kept in HBM (size_col_cache); slab null: no cache.
@@ -1157,6 +1162,7 @@ struct Solve {
   hipStream_t s = nullptr;
   DecompRows R;
   bool f64 = false;
+  bool csr = false;  // sparse rows (csr_rbf.hip): neither of the two dense formats
   int kq = 0;  // the quantised rows' bytes (exact-integer rows)
   const int32_t* y = nullptr;
   double* alpha = nullptr;
@@ -1276,7 +1282,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   DecompWs& w = S.w;
   const size_t nl1 = size_t(std::max<int64_t>(S.nloc, 1)), n = size_t(S.n), kq = size_t(S.kq), ld = size_t(S.R.ld);
   const size_t nr1 = size_t(std::max<int64_t>(S.rows(), 1)), ncol = size_t(S.cols());  // kernel rows / columns
-  const bool f64 = S.f64, q8 = !f64, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
+  const bool f64 = S.f64, q8 = !f64 && !S.csr, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
   w.f = c.take<double>(nl1);
   w.own = c.take<CandRec>(size_t(S.Lr));
   w.all = c.take<CandRec>(size_t(S.sh.L));
@@ -1325,6 +1331,10 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.fcols = c.take<int32_t>(kMaxWS, S.mode.twin());
   w.fcoef = c.take<double>(kMaxWS, S.mode.twin());
   w.fcount = c.take<int32_t>(64, S.mode.twin());
+  w.PT = c.take<double>(size_t(S.R.dpad) * kMaxWS, S.csr);
+  w.nP = c.take<double>(kMaxWS, S.csr);
+  w.pprev = c.take<int32_t>(kMaxWS, S.csr);
+  w.pcnt = c.take<int32_t>(64, S.csr);
 }
 
 // What the solve is asked to run with (decomp_mode.h); the class weights' range check comes with the boxes.
@@ -1334,6 +1344,21 @@ int mode_features(const DecompOpts& o, const svm_params& p, DecompFeatures* f) {
   const bool classify = o.mode.kind == DecompModeKind::classify;
   *f = decomp_features(p, o.world, o.warm, classify ? cp != cn : cp != p.C || cn != p.C);
   return SVM_OK;
+}
+
+// Sparse (CSR) rows cover the classifier (class weights included) and the twin mode, on one GPU from a cold
+// start; everything else is SVM_ERR_ARG under `who` before any device work, as decomp_mode_check's refusals.
+int csr_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& ft) {
+  const char* what = (o.mode.kind != DecompModeKind::classify && o.mode.kind != DecompModeKind::twin)
+                         ? "this mode (the classifier and the regression (twin) solve only)"
+                     : ft.distributed ? "the distributed solve (world > 1)"
+                     : ft.warm        ? "a warm start"
+                     : ft.shrinking   ? "shrinking"
+                     : ft.newton      ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                      : nullptr;
+  if (!what) return SVM_OK;
+  set_error("%s: sparse (CSR) rows do not support %s", who, what);
+  return SVM_ERR_ARG;
 }
 
 // The checks, the shape and this GPU's slice of it, the knobs and what follows from them.
@@ -1358,11 +1383,13 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
   }
-  const bool f64 = R.fp64();
-  if (f64 ? (R.ld % 16 != 0 || !R.nrm) : (!R.Q || !R.P)) {
+  const bool f64 = R.fp64(), csr = R.csr();
+  if (csr ? (f64 || !R.indices || !R.values || !R.nrm || R.d < 1 || R.dpad < R.d || R.d >= int64_t(INT32_MAX))
+          : f64 ? (R.ld % 16 != 0 || !R.nrm) : (!R.Q || !R.P)) {
     set_error("decomposition SMO: bad row source");
     return SVM_ERR_ARG;
   }
+  if (csr && (rc = csr_rows_check("decomposition SMO", o, ft))) return rc;
   svm_decomp_trace* tr = o.trace;
   if (tr && (world != 1 || tr->cap < 0 || (tr->n != 0 && tr->n != n))) {
     set_error("decomposition SMO: a trace needs one GPU and snapshots of n = %lld", (long long)n);
@@ -1380,12 +1407,17 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     return SVM_ERR_ARG;
   }
   if ((rc = read_knobs(sh, &S.k))) return rc;
+  if (csr && S.k.ccache == 1) {
+    set_error("decomposition SMO: sparse (CSR) rows do not support the column cache (SVM355_DECOMP_CCACHE=1)");
+    return SVM_ERR_ARG;
+  }
   if ((rc = svm_class_boxes(&p1, &S.Cp, &S.Cn))) return rc;
   S.ctx = ctx;
   S.s = ctx->stream;
   S.R = R;
   S.f64 = f64;
-  S.kq = f64 ? 0 : R.P->kq;
+  S.csr = csr;
+  S.kq = (f64 || csr) ? 0 : R.P->kq;
   S.y = y;  // a mode with its own signs: those, in the workspace (alloc_solve)
   S.alpha = alpha;
   S.mode = o.mode;
@@ -1409,7 +1441,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     nu_start_walk(p1.C * o.mode.nu * double(nrow) / 2.0, p1.C, nrow, &S.nu_full, &S.nu_frac);
   S.nchunks = (n + kMaxWS - 1) / kMaxWS;
   S.wide_select = !o.mode.nu_pairs() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select);
-  S.kww_narrow = !f64 && !S.k.kww_sym && S.kq <= 1536;
+  S.kww_narrow = !f64 && !csr && !S.k.kww_sym && S.kq <= 1536;
   S.shc = shrink_cfg(p);
   S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
   const NewtonCfg nwc = newton_cfg(p);
@@ -1432,7 +1464,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
 int alloc_solve(Solve& S, bool warm) {
   static std::mutex alloc_mu;
   std::lock_guard<std::mutex> alloc_lock(alloc_mu);
-  int rc = size_col_cache(S, warm, &S.cc);
+  int rc = S.csr ? SVM_OK : size_col_cache(S, warm, &S.cc);  // sparse rows: no cache (refused when forced)
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
   if (S.mode.own_signs()) S.y = S.w.sgn;
@@ -1446,6 +1478,9 @@ int alloc_solve(Solve& S, bool warm) {
   SVMD_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&S.ctl_pub), S.ctl_h, 0));  // as the device addresses it
   return SVM_OK;
 }
+
+// The solve's sparse rows as csr_rbf.hip's launchers take them (n kernel rows).
+CsrRows csr_rows(const DecompRows& R, int64_t n) { return CsrRows{R.indptr, R.indices, R.values, R.nrm, n, R.d}; }
 
 // f += K(this GPU's rows, cols[0:*cnt]) coef: the exact-integer GEMV (column-half partials summed in
 // order) or, for FP64 rows, the moved columns' rows gathered, their block on FP64 MFMA and a row sum
@@ -1466,6 +1501,21 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
   const bool twin = S.mode.twin();
   const int64_t lo = S.lo, nloc = S.rows();
   if (nloc <= 0) return SVM_OK;
+  if (S.csr) {  // the moved columns' rows into the panel (the working set's leave it), then the fused block + sum
+    const CsrRows A = csr_rows(R, S.rows());
+    int rc = launch_csr_panel_scatter(s, A, cl, cnt, nullptr, 0, w.panel());
+    if (rc) return rc;
+    CsrBlock b;
+    b.arow0 = b.row_off = lo;
+    b.m = nloc;
+    b.ncap = kMaxWS;
+    b.ncount = cnt;
+    b.pid = cl;
+    b.gamma = S.p.gamma;
+    b.coef = cf;
+    b.f = w.f;
+    return launch_csr_rbf(s, twin ? CsrEpilogue::sum_twin : CsrEpilogue::sum, A, w.panel(), b);
+  }
   if (S.f64) {
     hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, cl, cnt,
                        nullptr, w.Xc, w.nc);
@@ -1568,6 +1618,10 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
   std::memset(S.hs, 0, sizeof(DecompHost));
   SVMD_CHECK(hipMemsetAsync(w.ctl, 0, sizeof(DecompCtl), s));  // stop = SVM_STOP_RUNNING, counters 0
   if (S.f64) SVMD_CHECK(hipMemsetAsync(w.Xw, 0, size_t(kMaxWS) * S.R.ld * 8, s));  // rows beyond m stay finite
+  if (S.csr) {  // the panel is cleared whole once per fit; after that only by re-walking the rows it held
+    SVMD_CHECK(hipMemsetAsync(w.PT, 0, size_t(S.R.dpad) * kMaxWS * 8, s));
+    SVMD_CHECK(hipMemsetAsync(w.pcnt, 0, 4, s));
+  }
   if (S.kww_narrow) {
     static const std::vector<int32_t> ident = [] {
       std::vector<int32_t> v(kMaxWS + 1);
@@ -1713,6 +1767,26 @@ int enqueue_kww(const Solve& S) {
     SVMD_LAUNCH_CHECK();
     return SVM_OK;
   };
+  if (S.csr) {  // W's rows into the panel, then K(W's rows, panel) stored with the unit diagonal by position
+    const CsrRows A = csr_rows(R, S.rows());
+    const int64_t tw = S.mode.twin() ? S.nrow : 0;
+    int rc = launch_csr_panel_scatter(s, A, w.W, &w.ctl->m, gate, tw, w.panel());
+    if (rc) return rc;
+    CsrBlock b;
+    b.m = kMaxWS;
+    b.rowlist = w.W;
+    b.rowcount = &w.ctl->m;
+    b.twin_nrow = tw;
+    b.ncap = kMaxWS;
+    b.ncount = &w.ctl->m;
+    b.gate = gate;
+    b.gamma = S.p.gamma;
+    b.K = w.Kw;
+    b.ldk = kLdw;
+    b.sym = true;
+    rc = launch_csr_rbf(s, CsrEpilogue::store, A, w.panel(), b);
+    return rc ? rc : twin_diag();
+  }
   if (S.f64) {
     if (S.mode.twin())
       hipLaunchKernelGGL(ws_gather_f64_twin_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W,
@@ -1906,7 +1980,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
     stats[3] = int64_t(ms_since(S.t0) * 1000.0);
     stats[4] = fin.changed_total;
     stats[5] = S.k.inner_nt;
-    stats[6] = S.f64 ? 1 : 0;
+    stats[6] = S.csr ? 2 : S.f64 ? 1 : 0;
     stats[7] = warm_cols;
     stats[8] = ps.unshrinks;
     stats[9] = fin.passes;
@@ -1939,7 +2013,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
 // updates f for its own points.  With world dividing 8 the trajectory is the one-GPU trajectory.
 // stats (kDecompStats = SVM_DECOMP_STATS int64, 13 written): outer iterations, inner iterations, working-set
 // capacity, solve microseconds, columns of the f updates (points moved, summed over the outer iterations),
-// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA), warm-start columns,
+// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA, 2 sparse rows), warm-start columns,
 // unshrinks, shrink passes, the fewest active rows, repacks, Newton polish steps.
 int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n, const svm_params& p,
                int qws, svm_result* r, int64_t* stats, const DecompOpts& o) {
@@ -2359,6 +2433,56 @@ SVM_API int svmd_train_decomp_nusvr(void* h, const void* X_d, int32_t is_u8, int
   o.mode.nu_out = nu_out;
   return train_decomp_entry("svmd_train_decomp_nusvr", h, X_d, is_u8, n, ld, d, mn_h, mx_h, z_d && nu_out, nullptr,
                             alpha_d, pp, q, o, r, timing, stats, used_out, trace);
+}
+
+// The solve on sparse rows (svm355_device.h): n CSR rows of d features on the device, already scaled by their
+// column maxima (svmd_csr_prepare) with their norms.  kind 0: the classifier over the labels y_d (alpha_d: n
+// doubles, out; class weights in *pp allowed); kind 1: epsilon-SVR over the targets z_d (alpha_d: 2n doubles, a
+// then a*, as svmd_train_decomp_svr).  Kernel values come from csr_rbf.hip against a d x 1024 panel; no rows x
+// 1024 block is stored.  One GPU, cold start; shrinking and the Newton polish are SVM_ERR_ARG.
+SVM_API int svmd_train_decomp_csr(void* h, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
+                                  const double* nrm_d, int64_t n, int64_t d, int32_t kind, const int32_t* y_d,
+                                  const double* z_d, double epsilon, double* alpha_d, const svm_params* pp, int32_t q,
+                                  svm_result* r, svmd_timing* timing, int64_t* stats, svm_decomp_trace* trace) {
+  const char* who = "svmd_train_decomp_csr";
+  SVMD_CTX(h);
+  if (!indptr_d || !indices_d || !values_d || !nrm_d || n < 2 || d < 1 || d >= int64_t(INT32_MAX) || !alpha_d ||
+      (kind != 0 && kind != 1) || (kind == 0 ? !y_d : !z_d)) {
+    set_error("%s: bad arguments", who);
+    return SVM_ERR_ARG;
+  }
+  const svm_params p = params_or_default(pp);
+  DecompOpts o;
+  o.trace = trace;
+  if (kind == 1) {
+    o.mode.kind = DecompModeKind::twin;
+    o.mode.twin_z = z_d;
+    o.mode.twin_eps = epsilon;
+  }
+  DecompFeatures ft;
+  int rc = mode_features(o, p, &ft);
+  if (rc || (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device)) ||
+      (rc = csr_rows_check(who, o, ft)))
+    return rc;
+  if (!decomp_shape(o.mode.points(n), q > 0 ? q : 1024, 1).ok) {
+    set_error("%s: n = %lld is outside the solver's shapes", who, (long long)n);
+    return SVM_ERR_ARG;
+  }
+  DecompRows R;
+  R.indptr = indptr_d;
+  R.indices = indices_d;
+  R.values = values_d;
+  R.nrm = nrm_d;
+  R.d = d;
+  R.dpad = padded_dim(d);
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = ctx->begin())) return rc;
+  if ((rc = decomp_solve(ctx, R, kind == 0 ? y_d : nullptr, alpha_d, n, p, q, r, stats, o))) return rc;
+  if (timing) {
+    timing->gram_ms = 0.0;  // nothing is prepared here: the rows arrive scaled
+    timing->total_ms = timing->smo_ms = ms_since(t0);
+  }
+  return ctx->end();
 }
 
 // The held-out form of svmd_train_decomp (svm355_device.h): held-out mode (decomp_mode.h) over the n rows.

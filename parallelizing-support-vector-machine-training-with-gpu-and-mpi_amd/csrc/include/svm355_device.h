@@ -259,6 +259,40 @@ SVM_API int svmd_ovo_predict(void* ctx, const double* Xs_d, const double* ns_d, 
 SVM_API int svmd_ovo_couple(void* ctx, const double* dec_d, int64_t ldd, int64_t m, int64_t k, const double* A_d,
                             const double* B_d, double* proba_d, int64_t ldp, int32_t* label_d, int32_t* iters_d);
 
+// ---- Sparse rows (csrc/hip/csr_rbf.hip).  n CSR rows of d features on the device: indptr (int64[n + 1]), indices
+// (int32, sorted and unique within a row, every one in [0, d): the caller checks them on the host before upload),
+// values (FP64).  Kernel values come from the rows against a dense transposed panel of at most 1024 other rows.
+// svmd_csr_prepare, mode 0: nrm_d[i] = row i's squared norm.  mode 1 (training rows, stored values >= 0): per
+// column the minimum over all n rows (implicit zeros included), the maximum and the stored count into colmin_d /
+// colmax_d / colcnt_d (d each), then values_d /= max_c in place (a maximum below 1e-12 divides by 1, the dense
+// scaler's rule) and the norms of the scaled rows.  mode 2 (queries): values_d scaled by the given colmax_d.
+SVM_API int svmd_csr_prepare(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, double* values_d, int64_t n,
+                             int64_t d, int64_t nnz, int32_t mode, double* colmin_d, double* colmax_d,
+                             int32_t* colcnt_d, double* nrm_d);
+// K_d[i * ldk + j] = K(row i of A, row j of B), m rows of A, 1 <= nb <= 1024 rows of B.  idsB_d (optional): B row j
+// is training row idsB_d[j] and A row i is training row row_off + i; that pair's value is exactly 1.  sym: K_ii = 1.
+SVM_API int svmd_rbf_block_csr(void* ctx, const int64_t* a_indptr_d, const int32_t* a_indices_d,
+                               const double* a_values_d, const double* a_nrm_d, int64_t m, int64_t row_off,
+                               const int64_t* b_indptr_d, const int32_t* b_indices_d, const double* b_values_d,
+                               const double* b_nrm_d, int64_t nb, int64_t d, const int32_t* idsB_d, double gamma,
+                               int32_t sym, double* K_d, int64_t ldk);
+// out_d[i] = sum_k coef_d[k] K(query row i, Xs row k) - b: m CSR queries (scaled, norms nq_d) against a model's
+// dense support vectors (nsv x lds, lds >= d), 1024 at a time, summed in a fixed order.
+SVM_API int svmd_decision_csr(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
+                              const double* nq_d, int64_t m, int64_t d, const double* Xs_d, const double* ns_d,
+                              const double* coef_d, int64_t nsv, int64_t lds, double gamma, double b, double* out_d);
+// Xs_d (k x ld, ld >= d, written whole) = the CSR rows ids_d[0 : k] as dense rows, ns_d[k] their norms.
+SVM_API int svmd_csr_rows_dense(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
+                                const double* nrm_d, int64_t n, int64_t d, const int64_t* ids_d, int64_t k,
+                                double* Xs_d, int64_t ld, double* ns_d);
+// The decomposition solver on prepared (mode 1) sparse rows.  kind 0: the classifier over y_d (alpha_d: n doubles,
+// out; class weights allowed); kind 1: epsilon-SVR over z_d (alpha_d: 2n doubles, a then a*).  One GPU, cold
+// start; shrinking, the Newton polish and a forced column cache are SVM_ERR_ARG.  stats[6] = 2.
+SVM_API int svmd_train_decomp_csr(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
+                                  const double* nrm_d, int64_t n, int64_t d, int32_t kind, const int32_t* y_d,
+                                  const double* z_d, double epsilon, double* alpha_d, const svm_params* p, int32_t q,
+                                  svm_result* r, svmd_timing* timing, int64_t* stats, svm_decomp_trace* trace);
+
 // dst[k] = src[idx[k]] rows (device gather), for SV compaction and cascade training-set assembly.
 SVM_API int svmd_gather_rows(void* ctx, const double* src_d, int64_t ld, const int64_t* idx_d,
                              int64_t k, double* dst_d);

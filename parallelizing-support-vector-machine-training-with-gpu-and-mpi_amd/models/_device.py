@@ -1,5 +1,5 @@
 """The estimators' plumbing between host rows and the native solvers: training rows on the device
-(``TrainRows``), the byte-rows-then-FP64-rows attempt (``solve_on_rows``), the device model dict
+(``TrainRows``; ``SparseTrainRows`` for CSR input), the byte-rows-then-FP64-rows attempt (``solve_on_rows``), the device model dict
 (``device_model*``), the query prologue (``scale_queries``) and the members ``SVC``, ``SVR`` and
 ``OneClassSVM`` share (``KernelEstimator``).  ``OneVsRestSVC`` and ``OneVsOneSVC`` use the functions."""
 from __future__ import annotations
@@ -10,6 +10,7 @@ from typing import Optional
 import numpy as np
 
 from ..utils.data import MinMaxScaler, check_finite_bounds
+from ..utils.sparse import check_csr, check_zero_min, is_sparse
 
 
 def _resolve_device(device: str) -> str:
@@ -104,6 +105,50 @@ class TrainRows:
         return MinMaxScaler(self.mn_h, self.mx_h) if self.mn_h is not None else None
 
 
+class SparseTrainRows:
+    """Training rows given in CSR form, on the device as CSR (``csr``: a ``DeviceCSR``), scaled there by their
+    column maxima with their squared norms.  Min-max scaling keeps zeros zero only when every column's minimum is
+    0 (``check_zero_min``, on the host before the upload), so ``mn`` is all zeros and the scaler an ordinary
+    ``MinMaxScaler``: the model is the one the dense FP64 path fits on ``X.toarray()``, up to rounding."""
+
+    def __init__(self, csr, mn, mx, mn_h, mx_h, device, upload_ms):
+        self.csr, self.mn, self.mx, self.mn_h, self.mx_h = csr, mn, mx, mn_h, mx_h
+        self.d, self.device, self.upload_ms = csr.d, device, upload_ms
+
+    @classmethod
+    def upload(cls, X, device) -> "SparseTrainRows":
+        import torch
+
+        from ..ops import device as D
+
+        t0 = time.perf_counter()
+        X = check_csr(X)
+        check_zero_min(X)
+        csr = D.upload_csr(X, device)
+        mn, mx, _ = D.csr_prepare(csr)
+        mm = mn.as_strided((2 * csr.d,), (1,)).cpu().numpy()  # both bounds (one buffer), one copy; synchronises
+        mn_h, mx_h = mm[:csr.d].copy(), mm[csr.d:].copy()
+        check_finite_bounds(mn_h, mx_h)
+        return cls(csr, mn, mx, mn_h, mx_h, torch.device(device), (time.perf_counter() - t0) * 1e3)
+
+    def sv(self, idx):
+        """(Xs, ns): rows ``idx`` scattered into dense, padded FP64 rows, and their norms: a model keeps its
+        support vectors dense, so the device model, ``support_vectors_`` and save / load are those of dense fits."""
+        import torch
+
+        from ..ops import device as D
+
+        if not isinstance(idx, torch.Tensor):
+            idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))
+        return D.csr_rows_dense(self.csr, idx.to(self.device))
+
+    def model(self, support, coef, **extra) -> dict:
+        return device_model(self.sv(support), coef, self.mn, self.mx, self.d, self.device, **extra)
+
+    def scaler(self) -> MinMaxScaler:
+        return MinMaxScaler(self.mn_h, self.mx_h)
+
+
 def solve_on_rows(X: np.ndarray, device, solve, scale: bool = True, bytes_ok: bool = True):
     """``solve(rows)`` on the device rows of X: the byte rows first when X is uint8 (and ``bytes_ok`` and
     ``scale``), and when ``solve`` returns None (nothing ran: no exact-integer plan for these bytes) the FP64 rows
@@ -182,6 +227,10 @@ def device_model_from_u8(X_sv: np.ndarray, scaler: MinMaxScaler, coef, device, *
 
 
 def check_query_shape(X, d: Optional[int]) -> None:
+    if is_sparse(X):
+        if len(X.shape) != 2 or (d is not None and X.shape[1] != d):
+            raise ValueError(f"X must be (m, {d}) like the training rows, got shape {tuple(X.shape)}")
+        return
     if np.ndim(X) != 2 or (d is not None and np.shape(X)[1] != d):
         raise ValueError(f"X must be (m, {d}) like the training rows, got shape {np.shape(X)}")
 
@@ -195,6 +244,20 @@ def scale_queries(dm: dict, X, scaled: bool = True):
     if scaled:
         return Xq, D.minmax_scale_(Xq, dm["d"], dm["mn"], dm["mx"])[2]
     return Xq, D.row_norms(Xq, dm["d"])
+
+
+def sparse_queries(dm: dict, X, scaled: bool = True):
+    """The CSR query rows on the model's device (a ``DeviceCSR``), scaled by the model's column maxima, with their
+    norms.  Zeros stay zeros only under bounds whose minimum is 0 -- those of a fit on sparse rows, or of dense
+    rows with such columns; any other model raises (densify the queries)."""
+    from ..ops import device as D
+
+    if scaled and bool((dm["mn"] != 0).any().item()):
+        raise ValueError("sparse queries need a model whose scaling keeps zeros zero (every column minimum 0); "
+                         "pass the dense array (X.toarray()) instead")
+    Q = D.upload_csr(X, dm["device"])
+    D.csr_prepare(Q, mx=dm["mx"].contiguous() if scaled else None, scale=scaled)
+    return Q
 
 
 def scaled_cpu(X: np.ndarray, scale: bool = True):
@@ -268,3 +331,15 @@ class KernelEstimator:
 
     def _device_queries(self, X):
         return scale_queries(self._dev, X, self.scale)
+
+    def _device_decide(self, X):
+        """sum_k coef_k K(x_k, x) - b_ on the device model, as a device tensor: dense queries on the MFMA cross
+        kernel, CSR queries on the CSR x panel kernel against the same dense support vectors."""
+        from ..ops import device as D
+
+        dv = self._dev
+        if is_sparse(X):
+            return D.decision_csr(dv["Xs"], dv["ns"], dv["coef"], sparse_queries(dv, X, self.scale),
+                                  self.params.gamma, self.b_)
+        Xq, nq = self._device_queries(X)
+        return D.decision(dv["Xs"], dv["ns"], dv["coef"], Xq, nq, self.params.gamma, self.b_)

@@ -38,6 +38,7 @@ import numpy as np
 
 from ..utils.config import SVMParams, default_threads
 from ..utils.data import MinMaxScaler
+from ..utils.sparse import refuse_sparse
 from ..utils.trace import trace_range
 from ._device import (TrainRows, _resolve_device, check_query_shape, device_model_from_host, scale_queries, scaled_cpu,
                       solve_on_rows)
@@ -191,6 +192,7 @@ class OneVsRestSVC:
         passes the same rows, solves the classes k with k % world == rank on its own Gram, and the
         per-class alphas, b and iteration counts are all-reduced, so every rank ends with the whole
         model (identical to a single-rank fit)."""
+        refuse_sparse(X)
         self._transport = transport
         cuda = self._dev() != "cpu"
         X = np.ascontiguousarray(X, dtype=np.uint8 if (cuda and X.dtype == np.uint8) else np.float64)

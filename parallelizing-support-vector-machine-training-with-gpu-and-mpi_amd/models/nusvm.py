@@ -26,6 +26,7 @@ import time
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
+from ..utils.sparse import refuse_sparse
 from ._device import KernelEstimator, _is_u8, _resolve_device, solve_on_rows
 
 MAX_POINTS = 1048576  # the nu modes' selection: four candidate lists of every 4,096-point block in one working set
@@ -168,6 +169,7 @@ class NuSVC(_NuEstimator):
         self._init(nu, 1.0, gamma, tol, eps, sv_tol, max_iter, device, n_threads, scale, working_set)
 
     def fit(self, X: np.ndarray, y: np.ndarray) -> "NuSVC":
+        refuse_sparse(X)
         y = np.ascontiguousarray(y)
         if not np.all((y == 1) | (y == -1)):
             raise ValueError("NuSVC takes labels +1 / -1")
@@ -213,6 +215,7 @@ class NuSVR(_NuEstimator):
         self._init(nu, C, gamma, tol, eps, sv_tol, max_iter, device, n_threads, scale, working_set)
 
     def fit(self, X: np.ndarray, z: np.ndarray) -> "NuSVR":
+        refuse_sparse(X)
         z = np.ascontiguousarray(z, dtype=np.float64)
         if not np.all(np.isfinite(z)):
             raise ValueError("the targets z hold NaN or infinite values")

@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
+from ..utils.sparse import refuse_sparse
 from ._device import KernelEstimator, _is_u8, _resolve_device, solve_on_rows
 
 KIND = "oneclass"  # model files' kind marker (model_io)
@@ -42,6 +43,7 @@ class OneClassSVM(KernelEstimator):
     # ------------------------------------------------------------------ fit
     def fit(self, X: np.ndarray, y=None) -> "OneClassSVM":
         """Fits on the unlabelled rows X (y is ignored, as scikit-learn's)."""
+        refuse_sparse(X)
         dev = _resolve_device(self.device)
         X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         if X.ndim != 2:

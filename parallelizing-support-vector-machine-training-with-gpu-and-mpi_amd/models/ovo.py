@@ -52,6 +52,7 @@ import numpy as np
 
 from ..utils.config import SVMParams, default_threads
 from ..utils.data import MinMaxScaler, check_folds_multiclass, stratified_folds
+from ..utils.sparse import refuse_sparse
 from ..utils.trace import trace_range
 from ._device import (TrainRows, _resolve_device, check_query_shape, device_model_from_host, platt_probability,
                       scale_queries, scaled_cpu)
@@ -112,6 +113,7 @@ class OneVsOneSVC:
             transport=None, folds: Optional[np.ndarray] = None) -> "OneVsOneSVC":
         """folds (with ``cv`` only): an explicit fold id per training row in place of
         ``stratified_folds(class index, cv, cv_seed)``."""
+        refuse_sparse(X)
         _refuse("transport", transport)
         if folds is not None and self.cv is None:
             raise ValueError("folds= is the cross-validation of a calibrated fit: pass cv= to the constructor")

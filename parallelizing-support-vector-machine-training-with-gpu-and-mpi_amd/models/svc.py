@@ -26,7 +26,9 @@ import numpy as np
 
 from ..utils.config import SVMParams, default_threads
 from ..utils.data import check_folds, check_warm_start, resolve_class_weight, stratified_folds
-from ._device import KernelEstimator, _is_u8, _resolve_device, platt_probability, scaled_cpu, solve_on_rows
+from ..utils.sparse import is_sparse, toarray
+from ._device import (KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, platt_probability, scaled_cpu,
+                      solve_on_rows)
 
 
 class SVC(KernelEstimator):
@@ -84,10 +86,15 @@ class SVC(KernelEstimator):
             folds: Optional[np.ndarray] = None) -> "SVC":
         """folds (probability=True only): an explicit fold id per row instead of stratified_folds(y, cv, cv_seed)."""
         dev = _resolve_device(self.device)
-        # uint8 pixel rows stay compact up to the device (8x less H2D; widened to FP64 there)
-        X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
+        sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
+        if sparse and dev == "cpu":
+            X, sparse = toarray(X), False
+        if sparse:
+            self._check_sparse(alpha0)
+        else:  # uint8 pixel rows stay compact up to the device (8x less H2D; widened to FP64 there)
+            X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         y = np.ascontiguousarray(y, dtype=np.int32)
-        if X.ndim != 2 or y.shape != (X.shape[0],):
+        if len(X.shape) != 2 or y.shape != (X.shape[0],):
             raise ValueError("X must be (n, d) and y (n,)")
         if not np.all(np.abs(y) == 1):
             raise ValueError("labels must be +1/-1 (use svm355.utils.data.one_vs_rest)")
@@ -113,10 +120,22 @@ class SVC(KernelEstimator):
                 self._fit_cuda_probability(X, y, folds, dev)
         elif dev == "cpu":
             self._fit_cpu(X, y, alpha0)
+        elif sparse:
+            self._fit_cuda_sparse(X, y, dev)
         else:
             self._fit_cuda(X, y, alpha0, dev)
         self.fit_time_ = time.perf_counter() - t0
         return self
+
+    def _check_sparse(self, alpha0=None) -> None:
+        """What a fit on CSR rows does not cover raises here, before any device work."""
+        what = "sparse rows run on the GPU decomposition solver from a cold start, which"
+        for name, on in (("solver='smo'", self.solver == "smo"), ("a warm start (alpha0)", alpha0 is not None),
+                         ("probability=True", self.probability), ("shrinking", self.params._shrink_code() > 0),
+                         ("scale=False", not self.scale), ("wss='second'", self.params.wss == 2),
+                         (f"gram={self.gram!r}", self.gram != "auto"), (f"kcache={self.kcache!r}", self.kcache != "auto")):
+            if on:
+                raise ValueError(f"{what} {name} rules out (densify the rows: X.toarray())")
 
     # ------------------------------------------------------------------ cross-validation and probabilities
     def _check_cv(self, dev: str, alpha0=None) -> None:
@@ -257,6 +276,8 @@ class SVC(KernelEstimator):
         resolves on all labels.  Fits no sigmoid and leaves the estimator's own model alone.  On a GPU the folds
         run ``concurrent_solves`` at a time (default: all of them while the rows fit the last-level cache)."""
         dev = _resolve_device(self.device)
+        if is_sparse(X):
+            raise ValueError("cross-validation does not take sparse rows (densify them: X.toarray())")
         X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         y = np.ascontiguousarray(y, dtype=np.int32)
         if X.ndim != 2 or y.shape != (X.shape[0],):
@@ -388,6 +409,21 @@ class SVC(KernelEstimator):
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 
+    def _fit_cuda_sparse(self, X, y, dev):
+        """CSR rows: scaled by their column maxima on the device, kernel values from the CSR x panel kernel."""
+        import torch
+
+        from ..ops import device as D
+
+        device = torch.device(dev)
+        rows = SparseTrainRows.upload(X, device)
+        alpha = torch.empty(rows.csr.n, dtype=torch.float64, device=device)  # the cold start zeroes it
+        res, tm = D.train_decomp_csr(rows.csr, alpha, self.params, y=torch.from_numpy(y).to(device),
+                                     working_set=self.working_set)
+        self._finish(alpha.cpu().numpy(), y, res)
+        self._adopt_rows(rows)
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
+
     # ------------------------------------------------------------------ inference
     def decision_function(self, X: np.ndarray) -> np.ndarray:
         self._check_X(X)
@@ -397,16 +433,12 @@ class SVC(KernelEstimator):
 
     def _device_decision(self, X: np.ndarray):
         """Decision values as a device tensor (device models only)."""
-        from ..ops import device as D
-
-        dv = self._dev
-        Xq, nq = self._device_queries(X)
-        return D.decision(dv["Xs"], dv["ns"], dv["coef"], Xq, nq, self.params.gamma, self.b_)
+        return self._device_decide(X)
 
     def _host_decision(self, X: np.ndarray) -> np.ndarray:
         from ..ops import cpu as C
 
-        X = np.ascontiguousarray(X, dtype=np.float64)
+        X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
         return C.decision(self.support_vectors_, self.support_labels_, self.alpha_[self.support_], Xq,
                           self.params.gamma, self.b_, self.params.n_threads)

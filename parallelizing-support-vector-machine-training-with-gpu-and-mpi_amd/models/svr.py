@@ -21,7 +21,8 @@ import time
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
-from ._device import KernelEstimator, _is_u8, _resolve_device, solve_on_rows
+from ..utils.sparse import is_sparse, toarray
+from ._device import KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, solve_on_rows
 
 KIND = "svr"  # model files' kind marker (model_io)
 
@@ -51,9 +52,13 @@ class SVR(KernelEstimator):
     # ------------------------------------------------------------------ fit
     def fit(self, X: np.ndarray, z: np.ndarray) -> "SVR":
         dev = _resolve_device(self.device)
-        X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
+        sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
+        if sparse and dev == "cpu":
+            X, sparse = toarray(X), False
+        if not sparse:
+            X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         z = np.ascontiguousarray(z, dtype=np.float64)
-        if X.ndim != 2 or z.shape != (X.shape[0],):
+        if len(X.shape) != 2 or z.shape != (X.shape[0],):
             raise ValueError("X must be (n, d) and z (n,)")
         if not np.all(np.isfinite(z)):
             raise ValueError("the targets z hold NaN or infinite values")
@@ -68,7 +73,10 @@ class SVR(KernelEstimator):
                                  "exact-integer plan, or the FP64 rows it solves on)")
             if X.shape[0] < 2:
                 raise ValueError("SVR on a GPU needs at least 2 rows")
-            self._fit_cuda(X, z, dev)
+            if sparse:
+                self._fit_cuda_sparse(X, z, dev)
+            else:
+                self._fit_cuda(X, z, dev)
         self.fit_time_ = time.perf_counter() - t0
         return self
 
@@ -113,19 +121,30 @@ class SVR(KernelEstimator):
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 
+    def _fit_cuda_sparse(self, X, z, dev):
+        """CSR rows: scaled by their column maxima on the device, kernel values from the CSR x panel kernel."""
+        import torch
+
+        from ..ops import device as D
+
+        device = torch.device(dev)
+        rows = SparseTrainRows.upload(X, device)
+        alpha = torch.empty(2 * rows.csr.n, dtype=torch.float64, device=device)
+        res, tm = D.train_decomp_csr(rows.csr, alpha, self.params, z=torch.from_numpy(z).to(device),
+                                     epsilon=self.epsilon, working_set=self.working_set)
+        self._finish(alpha.cpu().numpy(), res)
+        self._adopt_rows(rows)
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
+
     # ------------------------------------------------------------------ inference
     def predict(self, X: np.ndarray) -> np.ndarray:
         """sum_k beta_k K(x_k, x) - b over the support vectors (a model without any predicts -b)."""
         self._check_X(X)
         if self._dev is not None:
-            from ..ops import device as D
-
-            dv = self._dev
-            Xq, nq = self._device_queries(X)
-            return D.decision(dv["Xs"], dv["ns"], dv["coef"], Xq, nq, self.params.gamma, self.b_).cpu().numpy()
+            return self._device_decide(X).cpu().numpy()
         from ..ops import cpu as C
 
-        X = np.ascontiguousarray(X, dtype=np.float64)
+        X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
         return C.decision(self.support_vectors_, np.where(self.dual_coef_ > 0, 1, -1), np.abs(self.dual_coef_), Xq,
                           self.params.gamma, self.b_, self.params.n_threads)

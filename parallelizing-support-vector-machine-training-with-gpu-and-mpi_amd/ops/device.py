@@ -893,3 +893,128 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         N.check(ctx.lib.svmd_gather_rows(ctx.bind(), N.ptr(src), src.shape[1], N.ptr(idx), idx.numel(),
                                          N.ptr(out)), "svmd_gather_rows")
     return out
+
+
+# ---- sparse rows (csr_rbf.hip) ------------------------------------------------------------------------------
+@dataclass
+class DeviceCSR:
+    """n CSR rows of d features on the device: indptr (int64, n + 1), indices (int32), values (float64; at least one
+    element is allocated, so the pointers are never null) and, once prepared, the rows' squared norms."""
+    indptr: torch.Tensor
+    indices: torch.Tensor
+    values: torch.Tensor
+    n: int
+    d: int
+    nnz: int
+    nrm: Optional[torch.Tensor] = None
+
+    def args(self):
+        return N.ptr(self.indptr), N.ptr(self.indices), N.ptr(self.values), N.ptr(self.nrm)
+
+
+def upload_csr(X, device) -> DeviceCSR:
+    """Host CSR rows (anything ``utils.sparse.is_sparse`` takes) checked on the host -- monotone indptr, sorted
+    unique indices in [0, d), finite values: ValueError otherwise -- and copied to the device."""
+    from ..utils.sparse import check_csr
+
+    X = check_csr(X)
+    nnz = X.data.shape[0]
+    pad = lambda a: a if nnz else np.zeros(1, dtype=a.dtype)  # noqa: E731
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    return DeviceCSR(up(X.indptr), up(pad(X.indices)), up(pad(X.data)), X.shape[0], X.shape[1], nnz)
+
+
+def csr_prepare(A: DeviceCSR, mx: Optional[torch.Tensor] = None, scale: bool = True):
+    """The rows' squared norms into ``A.nrm``; with ``scale`` the values are first divided in place by their column
+    maximum -- ``mx`` (a model's, d float64 on the device) when given, else the rows' own.  Returns (colmin, colmax,
+    colcount) device tensors of the rows' own statistics, or None when none were collected."""
+    ctx = _ctx_for(A.values)
+    dev = A.values.device
+    A.nrm = torch.empty(max(A.n, 1), dtype=torch.float64, device=dev)
+    stats = None
+    mode = 0 if not scale else (2 if mx is not None else 1)
+    if mode == 1:
+        mm = torch.empty(2 * A.d, dtype=torch.float64, device=dev)  # min, max: one buffer, one copy to the host
+        stats = (mm[:A.d], mm[A.d:], torch.empty(A.d, dtype=torch.int32, device=dev))
+    cmin, cmax, ccnt = stats if stats else (None, mx, None)
+    if mx is not None and (mx.dtype != torch.float64 or mx.numel() != A.d or not mx.is_contiguous()):
+        raise ValueError(f"mx must be {A.d} contiguous float64 values")
+    N.check(ctx.lib.svmd_csr_prepare(ctx.bind(), N.ptr(A.indptr), N.ptr(A.indices), N.ptr(A.values), A.n, A.d, A.nnz,
+                                     mode, N.ptr(cmin), N.ptr(cmax), N.ptr(ccnt), N.ptr(A.nrm)), "svmd_csr_prepare")
+    return stats
+
+
+def rbf_block_csr(A: DeviceCSR, B: DeviceCSR, gamma: float, ids: Optional[torch.Tensor] = None, row_off: int = 0,
+                  sym: bool = False) -> torch.Tensor:
+    """K (m, nb) = the RBF values of A's rows against B's (nb <= 1024, both prepared): B's rows scattered into the
+    transposed panel, then the store kernel.  ids (int32, nb): B row j is training row ids[j] and A row i is row
+    row_off + i, whose value is exactly 1; sym: K[i, i] = 1."""
+    if A.d != B.d or not (1 <= B.n <= 1024) or A.n < 1 or A.nrm is None or B.nrm is None:
+        raise ValueError("rbf_block_csr: prepared rows of one d, 1 <= nb <= 1024")
+    if ids is not None and (ids.dtype != torch.int32 or ids.numel() != B.n or not ids.is_contiguous()):
+        raise ValueError("ids must be contiguous int32 of length nb")
+    K = torch.empty((A.n, B.n), dtype=torch.float64, device=A.values.device)
+    ctx = _ctx_for(A.values)
+    N.check(ctx.lib.svmd_rbf_block_csr(ctx.bind(), *A.args(), A.n, int(row_off), *B.args(), B.n, A.d, N.ptr(ids),
+                                       float(gamma), int(sym), N.ptr(K), B.n), "svmd_rbf_block_csr")
+    return K
+
+
+def decision_csr(Xs: torch.Tensor, ns: torch.Tensor, coef: torch.Tensor, Q: DeviceCSR, gamma: float,
+                 b: float) -> torch.Tensor:
+    """out[i] = sum_k coef[k] K(Q_i, Xs_k) - b for prepared CSR queries against a model's dense support vectors:
+    1024 of them at a time through the transposed panel, summed in a fixed order (bit-identical run to run)."""
+    out = torch.empty(Q.n, dtype=torch.float64, device=Q.values.device)
+    nsv = Xs.shape[0]
+    ctx = _ctx_for(Q.values)
+    N.check(ctx.lib.svmd_decision_csr(ctx.bind(), *Q.args(), Q.n, Q.d, N.ptr(Xs) if nsv else None,
+                                      N.ptr(ns) if nsv else None, N.ptr(coef) if nsv else None, nsv, Xs.shape[1],
+                                      float(gamma), float(b), N.ptr(out)), "svmd_decision_csr")
+    return out
+
+
+def csr_rows_dense(A: DeviceCSR, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(Xs, ns): the rows ``idx`` (int64, device) as dense zero-padded FP64 rows (k, padded_dim(d)) and their norms."""
+    idx = idx.to(device=A.values.device, dtype=torch.int64).contiguous()
+    k, ld = idx.numel(), padded_dim(A.d)
+    if k * ld * 8 > torch.cuda.mem_get_info(A.values.device)[0]:
+        raise ValueError(f"sparse rows: the {k} support vectors as dense rows ({k} x {ld} doubles) do not fit the "
+                         "device (a model keeps its support vectors dense)")
+    Xs = device_empty((k, ld), torch.float64, A.values.device)
+    ns = torch.empty(k, dtype=torch.float64, device=A.values.device)
+    if k:
+        ctx = _ctx_for(A.values)
+        N.check(ctx.lib.svmd_csr_rows_dense(ctx.bind(), *A.args(), A.n, A.d, N.ptr(idx), k, N.ptr(Xs), ld, N.ptr(ns)),
+                "svmd_csr_rows_dense")
+    return Xs, ns
+
+
+def train_decomp_csr(A: DeviceCSR, alpha: torch.Tensor, params: SVMParams, y: Optional[torch.Tensor] = None,
+                     z: Optional[torch.Tensor] = None, epsilon: float = 0.1, working_set: int = 1024,
+                     trace: Optional["N.DecompTrace"] = None) -> Tuple[SMOResult, dict]:
+    """The decomposition solver on prepared sparse rows (svmd_train_decomp_csr): the classifier over the int32
+    labels ``y`` (alpha: n, out) or epsilon-SVR over the float64 targets ``z`` (alpha: 2n, a then a*).  Kernel
+    values come from the CSR x panel kernel; cold start, one GPU; shrinking and the Newton polish raise."""
+    if (y is None) == (z is None):
+        raise ValueError("train_decomp_csr takes labels y or targets z")
+    t = y if z is None else z
+    want = A.n if z is None else 2 * A.n
+    if t.shape != (A.n,) or not t.is_contiguous() or t.dtype != (torch.int32 if z is None else torch.float64):
+        raise ValueError(f"y must be int32 / z float64, contiguous, of shape ({A.n},)")
+    if alpha.dtype != torch.float64 or alpha.shape != (want,) or not alpha.is_contiguous():
+        raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({want},)")
+    ctx = _ctx_for(A.values)
+    r, tm = N.SvmResult(), N.SvmdTiming()
+    st = (ctypes.c_int64 * 16)()
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_train_decomp_csr(ctx.bind(), *A.args(), A.n, A.d, 0 if z is None else 1, N.ptr(y), N.ptr(z),
+                                          float(epsilon), N.ptr(alpha), ctypes.byref(p), int(working_set),
+                                          ctypes.byref(r), ctypes.byref(tm), st,
+                                          ctypes.byref(trace.struct) if trace is not None else None),
+            "svmd_train_decomp_csr")
+    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
+                                      "kcache": "none", "gram_path": "csr-fp64", "rows": "csr",
+                                      "solver": "decomp" if z is None else "decomp-svr",
+                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
+                                      "working_set": int(st[2]), "update_columns": int(st[4]),
+                                      "inner_threads": int(st[5])}
