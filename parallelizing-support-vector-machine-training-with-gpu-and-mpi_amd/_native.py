@@ -48,6 +48,9 @@ class SvmParams(ctypes.Structure):
         ("shrink", c_int32),
         ("weight_pos", c_double),
         ("weight_neg", c_double),
+        ("kernel", c_int32),
+        ("degree", c_int32),
+        ("coef0", c_double),
     ]
 
 
@@ -306,6 +309,10 @@ _HIP_SIGS = {
                                      c_double, c_int32, _P, c_int64]),
     "svmd_decision_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64,
                                     c_double, c_double, _P]),
+    "svmd_kfun_block": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, POINTER(SvmParams),
+                                  c_int32, c_int32, c_int32, _P, c_int64, _P, _P]),
+    "svmd_decision_kfun": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64,
+                                     POINTER(SvmParams), c_double, _P]),
     "svmd_csr_rows_dense": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P]),
     "svmd_train_decomp_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_double, _P,
                                         POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
@@ -522,6 +529,8 @@ def shrink_stats(st) -> dict:
 
 
 def params_struct(C=10.0, gamma=0.00125, tau=1e-5, eps=1e-12, sv_tol=1e-8, max_iter=100000,
-                  n_threads=1, verbose=0, wss=1, shrink=0, weight_pos=1.0, weight_neg=1.0) -> SvmParams:
+                  n_threads=1, verbose=0, wss=1, shrink=0, weight_pos=1.0, weight_neg=1.0, kernel=0, degree=3,
+                  coef0=0.0) -> SvmParams:
     return SvmParams(float(C), float(gamma), float(tau), float(eps), float(sv_tol), int(max_iter),
-                     int(n_threads), int(verbose), int(wss), int(shrink), float(weight_pos), float(weight_neg))
+                     int(n_threads), int(verbose), int(wss), int(shrink), float(weight_pos), float(weight_neg),
+                     int(kernel), int(degree), float(coef0))

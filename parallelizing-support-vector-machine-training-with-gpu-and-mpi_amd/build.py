@@ -46,6 +46,7 @@ HIP_EXTRA: dict = {
     # FP64 and integer code only: packed FP32 instructions are switched off for the file, not relied on to be absent
     "decomp_nu.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "csr_rbf.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "decomp_kfun.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 CORE_SRCS = sorted((CSRC / "core").glob("*.cpp")) + sorted((CSRC / "cascade").glob("*.cpp"))

@@ -107,6 +107,9 @@ SVM_API void svm_default_params(svm_params* p) {
   p->shrink = 0;
   p->weight_pos = 1.0;
   p->weight_neg = 1.0;
+  p->kernel = 0;
+  p->degree = 3;
+  p->coef0 = 0.0;
 }
 
 SVM_API int svm_class_boxes(const svm_params* p, double* c_pos, double* c_neg) {

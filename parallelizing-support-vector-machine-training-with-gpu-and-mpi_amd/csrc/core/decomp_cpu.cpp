@@ -158,6 +158,31 @@ void rowsum_update_f64(const double* K, int64_t ldk, int64_t n, const int32_t* c
   });
 }
 
+// The dot-product kernels' f update (kfun_block_kernel's sum epilogues, hip/decomp_kfun.hip): per row, lane l of 16
+// sums its terms k = l, l + 16, ... from 0.0 in that order, then the 16-lane xor butterfly (8, 4, 2, 1) as lane 0
+// sees it, and one add into f (and into the twin's f).
+void rowsum_update_kfun(const double* K, int64_t ldk, int64_t n, const int32_t* cols, const double* coef, int64_t cnt,
+                        double* f, WorkerTeam& team, double* f2) {
+  if (cnt <= 0) return;
+  team.parallel_for(n, [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i) {
+      const double* Ki = K + i * ldk;
+      double v[16], w[16];
+      for (int l = 0; l < 16; ++l) {
+        double acc = 0.0;
+        for (int64_t k = l; k < cnt; k += 16) acc += coef[k] * Ki[cols[k]];
+        v[l] = acc;
+      }
+      for (int off = 8; off > 0; off >>= 1) {
+        for (int l = 0; l < 16; ++l) w[l] = v[l] + v[l ^ off];
+        for (int l = 0; l < 16; ++l) v[l] = w[l];
+      }
+      f[i] += v[0];
+      if (f2) f2[i] += v[0];
+    }
+  });
+}
+
 // Twin mode's moved-column fold (ws_twin_fold_kernel): the moved list of virtual ids (k: a_k, k + n: a*_k)
 // and their coefficients becomes one entry per kernel row, at the position of the row's first occurrence;
 // when both twins moved their coefficients are added, coef_k + coef_{k+n}.
@@ -342,6 +367,15 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   const DecompFeatures asked = decomp_features(
       p, world, warm != 0, mode.kind == DecompModeKind::classify ? Cp != Cn : set(p.weight_pos) || set(p.weight_neg));
   if (const int rc = decomp_mode_check(who, mode, y, asked, n, DecompBackend::cpu_oracle)) return rc;
+  // a dot-product kernel (p.kernel != 0): K_ii comes from the Gram, the rule is the second-order single pair
+  // (ws_inner_kfun_kernel) and the f update sums in the sum epilogue's order, whatever f64_rows says
+  const bool kf = p.kernel != kKernelRbf;
+  if (const int rc = decomp_kfun_check(who, p, mode.kind, asked, false)) return rc;
+  if (kf && inner_wss != 2) {
+    set_error("%s: a dot-product kernel runs the second-order single pair (inner_wss = 2), got %d", who, inner_wss);
+    return SVM_ERR_ARG;
+  }
+  const auto f_sum = kf ? rowsum_update_kfun : f64_rows ? rowsum_update_f64 : gemv_update;
   const int64_t nr = n;  // kernel rows: point id's row is id mod nr (twin mode), id itself otherwise
   n = mode.points(nr);
   // the solve's signs: the init kernels' analogue (ws_twin_init_kernel, ws_oneclass_init_kernel,
@@ -424,7 +458,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         nzv.push_back(alpha[j] * double(y[j]));
       }
     for (size_t c0 = 0; c0 < nzc.size(); c0 += kMaxWS)
-      (f64_rows ? rowsum_update_f64 : gemv_update)(
+      f_sum(
           K + lo * ldk, ldk, nloc, nzc.data() + c0, nzv.data() + c0,
           int64_t(std::min<size_t>(kMaxWS, nzc.size() - c0)), f.data(), team, nullptr);
     return int64_t(nzc.size());
@@ -685,6 +719,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       }
       const double* Ki = K + int64_t(Wr[size_t(ih)]) * ldk;
       for (int k = 0; k < m; ++k) kh[size_t(k)] = Ki[Wr[size_t(k)]];
+      const double Kii = kf ? Ki[Wr[size_t(ih)]] : 1.0;  // the chosen i's diagonal entry (the RBF's is 1)
       double bl_upd = lv;
       if (inner_wss != 1) {
         double gv = inf;
@@ -692,7 +727,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         for (int k = 0; k < m; ++k) {
           if (!in_low(yw[size_t(k)], a[size_t(k)]) || !(ft[size_t(k)] > hv)) continue;
           const double bb = ft[size_t(k)] - hv;
-          double at = 2.0 - 2.0 * kh[size_t(k)];
+          double at = kf ? Kii + K[int64_t(Wr[size_t(k)]) * (ldk + 1)] - 2.0 * kh[size_t(k)]
+                         : 2.0 - 2.0 * kh[size_t(k)];
           at = at <= 0.0 ? eps : at;
           const double gain = -(bb * bb) / at;
           if (gain < gv) {
@@ -713,7 +749,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       const double ah = a[size_t(ih)], al = a[size_t(il)];
       const int32_t yh = yw[size_t(ih)], yl = yw[size_t(il)];
       const int s = yh * yl;
-      double eta = 1.0 + 1.0 - 2.0 * K12;
+      double eta = kf ? Kii + Kj[Wr[size_t(il)]] - 2.0 * K12 : 1.0 + 1.0 - 2.0 * K12;
       const double Ch = yh == 1 ? Cp : Cn, Cl = yl == 1 ? Cp : Cn;
       double U, V;
       if (s == -1) {
@@ -800,11 +836,9 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     last_reason = reason;
     if (twin) {  // one entry per kernel row, every row's sum to both twins
       fold_twins(cols.data(), coef.data(), int64_t(cols.size()), nr, fcols, fcoef);
-      (f64_rows ? rowsum_update_f64 : gemv_update)(K, ldk, nr, fcols.data(), fcoef.data(), int64_t(fcols.size()),
-                                                   f.data(), team, f.data() + nr);
+      f_sum(K, ldk, nr, fcols.data(), fcoef.data(), int64_t(fcols.size()), f.data(), team, f.data() + nr);
     } else {
-      (f64_rows ? rowsum_update_f64 : gemv_update)(K + lo * ldk, ldk, nloc, cols.data(), coef.data(),
-                                                   int64_t(cols.size()), f.data(), team, nullptr);
+      f_sum(K + lo * ldk, ldk, nloc, cols.data(), coef.data(), int64_t(cols.size()), f.data(), team, nullptr);
     }
     if (shc.pass_after(outer, origin)) {  // shrink pass with this outer iteration's bounds
       int64_t drop = 0;

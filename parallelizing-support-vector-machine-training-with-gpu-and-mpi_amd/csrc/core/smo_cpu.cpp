@@ -269,6 +269,11 @@ SVM_API int svm_smo_train(const double* X, const int32_t* y, int64_t n, int64_t 
     set_error("svm_smo_train: bad X/d");
     return SVM_ERR_ARG;
   }
+  if (p && p->kernel != 0) {  // these rows are the RBF's: another kernel comes in as its Gram (svm_smo_train_gram)
+    set_error("svm_smo_train: rows are solved with the RBF kernel; pass the Gram of kernel = %d to svm_smo_train_gram",
+              p->kernel);
+    return SVM_ERR_ARG;
+  }
   XRows rows{X, d, p ? p->gamma : 0.00125};
   return smo_solve(rows, y, n, alpha, warm, p, r, trace, trace_cap);
 }
@@ -278,6 +283,11 @@ SVM_API int svm_smo_train_gram(const double* K, int64_t ldk, const int32_t* y, i
                                int64_t* trace, int64_t trace_cap) {
   if (!K || ldk < n) {
     set_error("svm_smo_train_gram: bad K/ldk");
+    return SVM_ERR_ARG;
+  }
+  if (p && p->kernel != 0 && p->wss == 2) {  // the second-order arm has the unit diagonal in its gain (K11 + 1.0)
+    set_error("svm_smo_train_gram: wss = 2 has the RBF's unit diagonal in its arithmetic; kernel = %d needs wss = 1",
+              p->kernel);
     return SVM_ERR_ARG;
   }
   GramRows rows{K, ldk};

@@ -14,13 +14,19 @@
 using namespace svm355;
 
 namespace svm355 {
-// The solvers without per-class boxes (the pairwise device solvers, the distributed and cascade trainers)
-// refuse class weights that differ from 1 -- none solves the unweighted problem in their place.  SVM_OK
-// when both weights are 1 (or 0, which reads as 1).
-int refuse_class_weights(const svm_params& p, const char* who) {
+// The solvers without per-class boxes and with the RBF's unit diagonal in their arithmetic (the pairwise device
+// solvers, the distributed and cascade trainers) refuse class weights that differ from 1 and the dot-product
+// kernels (svm_params.kernel != 0) -- none solves the unweighted or the RBF problem in their place.  SVM_OK when
+// both weights are 1 (or 0, which reads as 1) and the kernel is the RBF.
+int refuse_weights_and_kernels(const svm_params& p, const char* who) {
   double cp, cn;
   const int rc = svm_class_boxes(&p, &cp, &cn);
   if (rc) return rc;
+  if (p.kernel != 0) {  // the same callers have the RBF's unit diagonal in their arithmetic
+    set_error("%s: the linear, polynomial and sigmoid kernels (kernel = %d) are supported by the decomposition solver "
+              "on one GPU and the CPU pairwise solver only", who, p.kernel);
+    return SVM_ERR_ARG;
+  }
   if (cp != p.C || cn != p.C) {
     set_error("%s: class weights (weight_pos = %g, weight_neg = %g) are supported by the decomposition solver on one "
               "GPU and the CPU solvers only", who, p.weight_pos, p.weight_neg);
@@ -354,7 +360,7 @@ SVM_API int svmd_smo(void* h, const double* K_d, int64_t ldk, const int32_t* y_d
   SVMD_CTX(h);
   TraceRange tr("svm355:smo");
   const svm_params q = params_or_default(p);
-  int rc = refuse_class_weights(q, "svmd_smo");
+  int rc = refuse_weights_and_kernels(q, "svmd_smo");
   if (rc) return rc;
   if ((rc = ctx->begin())) return rc;
   rc = run_smo(ctx, K_d, ldk, y_d, n, alpha_d, warm, q, r, trace_host, trace_cap);
@@ -373,7 +379,7 @@ SVM_API int svmd_smo_multi(void* h, const double* K_d, int64_t ldk, const int32_
   SVMD_CTX(h);
   TraceRange tr("svm355:smo_multi");
   const svm_params q = params_or_default(p);
-  int rc = refuse_class_weights(q, "svmd_smo_multi");
+  int rc = refuse_weights_and_kernels(q, "svmd_smo_multi");
   if (rc) return rc;
   if ((rc = ctx->begin())) return rc;
   rc = run_smo_multi(ctx, K_d, ldk, Y_d, n, nclass, A_d, q, r, batched);
@@ -504,7 +510,7 @@ SVM_API int svmd_train(void* h, const double* X_d, const double* sqn_d, int64_t 
                        const int32_t* y_d, double* alpha_d, int32_t warm, const svm_params* p,
                        svm_result* r, double* K_d, int64_t ldk, svmd_timing* timing) {
   SVMD_CTX(h);
-  if (const int rc = refuse_class_weights(params_or_default(p), "svmd_train")) return rc;
+  if (const int rc = refuse_weights_and_kernels(params_or_default(p), "svmd_train")) return rc;
   return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, params_or_default(p), r, K_d, ldk, timing, nullptr,
                     nullptr, 0, 1, nullptr);
 }
@@ -514,7 +520,7 @@ SVM_API int svmd_train_q(void* h, const double* X_d, const double* sqn_d, int64_
                          double* K_d, int64_t ldk, svmd_timing* timing, const double* mn_h, const double* mx_h,
                          int64_t d, int32_t gram_mode, int32_t* gram_used) {
   SVMD_CTX(h);
-  if (const int rc = refuse_class_weights(params_or_default(p), "svmd_train_q")) return rc;
+  if (const int rc = refuse_weights_and_kernels(params_or_default(p), "svmd_train_q")) return rc;
   return train_impl(ctx, X_d, sqn_d, n, ld, kdim, y_d, alpha_d, warm, params_or_default(p), r, K_d, ldk, timing, mn_h, mx_h,
                     d, gram_mode, gram_used);
 }
@@ -534,7 +540,7 @@ SVM_API int svmd_train_u8(void* h, const uint8_t* Xu_d, int64_t n, int64_t d, co
     return SVM_ERR_ARG;
   }
   const svm_params q = params_or_default(p);
-  int rc = refuse_class_weights(q, "svmd_train_u8");
+  int rc = refuse_weights_and_kernels(q, "svmd_train_u8");
   if (rc) return rc;
   const auto t0 = std::chrono::steady_clock::now();
   if ((rc = ctx->begin())) return rc;
@@ -632,7 +638,7 @@ SVM_API int svmd_train_rows(void* h, const double* X_d, const double* sqn_d, int
                             int32_t* gram_used, int64_t* trace_host, int64_t trace_cap) {
   SVMD_CTX(h);
   const svm_params q = params_or_default(p);
-  int rc = refuse_class_weights(q, "svmd_train_rows");
+  int rc = refuse_weights_and_kernels(q, "svmd_train_rows");
   if (rc) return rc;
   if ((rc = ctx->begin())) return rc;
   QuantPlan P;

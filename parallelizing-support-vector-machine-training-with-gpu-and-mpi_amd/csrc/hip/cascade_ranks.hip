@@ -375,7 +375,7 @@ SVM_API svm_cascade_out* svmd_cascade_group_fit(void* h, const void* X, int32_t 
     set_error("svmd_cascade_group_fit: bad arguments");
     return nullptr;
   }
-  if (c && refuse_class_weights(c->params, "svmd_cascade_group_fit")) return nullptr;
+  if (c && refuse_weights_and_kernels(c->params, "svmd_cascade_group_fit")) return nullptr;
   std::lock_guard<std::mutex> lk(g->mu);
   if (g->broken) {
     set_error("svmd_cascade_group_fit: the group's communicators were aborted by an earlier failure; create a new group");
@@ -445,7 +445,7 @@ static int group_decomp(void* h, const void* X, bool u8, const int32_t* y, int64
     return SVM_ERR_ARG;
   }
   const svm_params p = params_or_default(pp);
-  if (const int rc = refuse_class_weights(p, "svmd_cascade_group_decomp")) return rc;
+  if (const int rc = refuse_weights_and_kernels(p, "svmd_cascade_group_decomp")) return rc;
   const int P = g->world;
   std::vector<double> ms(static_cast<size_t>(P), 0.0);
   const char* serial = getenv("SVM355_CASCADE_SERIAL_SOLVES");
@@ -516,7 +516,7 @@ static int rank_decomp(void* h, const void* X, bool u8, const int32_t* y, int64_
     return SVM_ERR_ARG;
   }
   const svm_params p = params_or_default(pp);
-  if (const int rc = refuse_class_weights(p, "svmd_cascade_rank_decomp")) return rc;
+  if (const int rc = refuse_weights_and_kernels(p, "svmd_cascade_rank_decomp")) return rc;
   try {
     pr->guarded(pr->timeout_s, [&] {
       pr->host_wait_ms = 0.0;
@@ -632,7 +632,7 @@ SVM_API svm_cascade_out* svmd_cascade_rank_fit(void* h, const void* X, int32_t u
     set_error("svmd_cascade_rank_fit: bad arguments");
     return nullptr;
   }
-  if (c && refuse_class_weights(c->params, "svmd_cascade_rank_fit")) return nullptr;
+  if (c && refuse_weights_and_kernels(c->params, "svmd_cascade_rank_fit")) return nullptr;
   if (p->broken) {
     set_error("svmd_cascade_rank_fit: the communicator was aborted by an earlier failure");
     return nullptr;

@@ -171,9 +171,9 @@ inline svm_params params_or_default(const svm_params* p) {
   return q;
 }
 
-// SVM_ERR_ARG (with the error set) when p's class weights differ from 1: the check of every solver
-// without per-class boxes (capi.hip).
-int refuse_class_weights(const svm_params& p, const char* who);
+// SVM_ERR_ARG (with the error set) when p's class weights differ from 1 or its kernel is not the RBF: the check
+// of every solver without per-class boxes and with the unit diagonal in its arithmetic (capi.hip).
+int refuse_weights_and_kernels(const svm_params& p, const char* who);
 
 // Load every translation unit's code object on s (hip_util.h SVMD_TU_WARM): svmd_create.
 int tu_warm_all(hipStream_t s);

@@ -35,6 +35,7 @@
 #include "csr_rbf.h"
 #include "decomp.h"
 #include "decomp_dev.h"
+#include "decomp_kfun.h"
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
 #include "persist.h"
@@ -1163,6 +1164,7 @@ struct Solve {
   DecompRows R;
   bool f64 = false;
   bool csr = false;  // sparse rows (csr_rbf.hip): neither of the two dense formats
+  bool kfun = false;  // a dot-product kernel (p.kernel != 0, decomp_kfun.hip): FP64 rows, no norms, no unit diagonal
   int kq = 0;  // the quantised rows' bytes (exact-integer rows)
   const int32_t* y = nullptr;
   double* alpha = nullptr;
@@ -1301,7 +1303,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.nw = c.take<double>(kMaxWS, f64);
   w.Xc = c.take<double>(size_t(kMaxWS) * ld, f64);
   w.nc = c.take<double>(kMaxWS, f64);
-  w.Kc = c.take<double>(nr1 * kMaxWS, f64);
+  w.Kc = c.take<double>(nr1 * kMaxWS, f64 && !S.kfun);  // the dot-product kernels sum their block in registers
   w.cslot = c.take<int32_t>(ncol, cache);
   w.crd = c.take<int32_t>(kMaxWS, cache);
   w.cmid = c.take<int32_t>(kMaxWS, cache);
@@ -1337,6 +1339,22 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.pcnt = c.take<int32_t>(64, S.csr);
 }
 
+// The knob values a dot-product kernel's solve refuses (docs/KNOBS.md): its inner solve is one kernel, 256 threads
+// x 4 points with SVM355_DECOMP_WSS=2's rule, and it keeps no column cache.  Reads the environment only.
+int kfun_knobs_check(const char* who, const svm_params& p) {
+  if (p.kernel == kKernelRbf) return SVM_OK;
+  const char* wss = getenv("SVM355_DECOMP_WSS");
+  const char* nt = getenv("SVM355_DECOMP_NT");
+  const char* cc = getenv("SVM355_DECOMP_CCACHE");
+  const char* what = wss && atoi(wss) != 2  ? "SVM355_DECOMP_WSS other than 2 (its inner solve is the second-order single pair)"
+                     : nt && atoi(nt) != 256 ? "SVM355_DECOMP_NT other than 256"
+                     : cc && atoi(cc) != 0   ? "a forced column cache (SVM355_DECOMP_CCACHE=1)"
+                                             : nullptr;
+  if (!what) return SVM_OK;
+  set_error("%s: a dot-product kernel (kernel = %d) does not support %s", who, p.kernel, what);
+  return SVM_ERR_ARG;
+}
+
 // What the solve is asked to run with (decomp_mode.h); the class weights' range check comes with the boxes.
 int mode_features(const DecompOpts& o, const svm_params& p, DecompFeatures* f) {
   double cp = 0.0, cn = 0.0;
@@ -1369,6 +1387,8 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   DecompFeatures ft;  // everything the mode does not cover is refused here, before any device work
   int rc = mode_features(o, p, &ft);
   if (rc || (rc = decomp_mode_check("decomposition SMO", o.mode, y, ft, nrow, DecompBackend::device))) return rc;
+  if ((rc = decomp_kfun_check("decomposition SMO", p, o.mode.kind, ft, R.csr())) || (rc = kfun_knobs_check("decomposition SMO", p)))
+    return rc;
   n = o.mode.points(nrow);
   svm_params p1 = p;  // the solve's parameters (one-class mode: the box is 1 whatever p.C says)
   int64_t oc_full = 0;
@@ -1417,6 +1437,11 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.R = R;
   S.f64 = f64;
   S.csr = csr;
+  S.kfun = p.kernel != kKernelRbf;
+  if (S.kfun && !f64) {
+    set_error("decomposition SMO: the dot-product kernels run on FP64 rows");
+    return SVM_ERR_ARG;
+  }
   S.kq = (f64 || csr) ? 0 : R.P->kq;
   S.y = y;  // a mode with its own signs: those, in the workspace (alloc_solve)
   S.alpha = alpha;
@@ -1447,7 +1472,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   const NewtonCfg nwc = newton_cfg(p);
   S.nwd = NwDev{nwc.on ? 1 : 0, nwc.every, nwc.per_solve, nwc.repeat, nwc.max_free, 0, nwc.frac};
   S.inner = InnerVariant{S.k.inner_nt, S.k.prof, S.k.wss2, S.k.dp, S.k.j2s, nwc.on, S.Cp != S.Cn};
-  if (S.inner.weighted && !ws_inner_weighted_built(S.inner)) {
+  if (!S.kfun && S.inner.weighted && !ws_inner_weighted_built(S.inner)) {
     set_error("decomposition SMO: the weighted inner solve is not built for SVM355_DECOMP_NT=%d SVM355_DECOMP_WSS=%d "
               "SVM355_DECOMP_PROF=%d (built: NT=256 with WSS=1, 2 or 3, PROF=0)",
               S.k.inner_nt, S.k.j2s ? 4 : S.k.dp ? 3 : S.k.wss2 ? 2 : 1, S.k.prof ? 1 : 0);
@@ -1520,6 +1545,21 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
     hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, cl, cnt,
                        nullptr, w.Xc, w.nc);
     SVMD_LAUNCH_CHECK();
+    if (S.kfun) {  // the fused block and sum: no rows x 1024 block in HBM
+      KfunBlock b;
+      b.A = R.X + lo * R.ld;
+      b.m = nloc;
+      b.lda = R.ld;
+      b.B = w.Xc;
+      b.ncap = kMaxWS;
+      b.ldb = R.ld;
+      b.kdim = R.ld;
+      b.kf = kfun_of(S.p);
+      b.ncount = cnt;
+      b.coef = cf;
+      b.f = w.f;
+      return launch_kfun_block(s, twin ? KfunEpilogue::sum_twin : KfunEpilogue::sum, b);
+    }
     const int rc = launch_rbf_block_dev(s, R.X + lo * R.ld, R.nrm + lo, nloc, R.ld, w.Xc, w.nc, kMaxWS, R.ld, R.ld,
                                         S.p.gamma, w.Kc, kMaxWS, false, nullptr, cnt, cl, lo);
     if (rc) return rc;
@@ -1795,6 +1835,18 @@ int enqueue_kww(const Solve& S) {
       hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W, &w.ctl->m,
                          gate, w.Xw, w.nw);
     SVMD_LAUNCH_CHECK();
+    if (S.kfun) {  // a full launch: symmetric to the bit, and two twins get their row's diagonal (no ws_twin_kww_kernel)
+      KfunBlock b;
+      b.A = b.B = w.Xw;
+      b.m = b.ncap = kMaxWS;
+      b.lda = b.ldb = b.kdim = R.ld;
+      b.kf = kfun_of(S.p);
+      b.gate = gate;
+      b.ncount = &w.ctl->m;
+      b.K = w.Kw;
+      b.ldk = kLdw;
+      return launch_kfun_block(s, KfunEpilogue::store, b);
+    }
     // K(W, W) on FP64 MFMA, columns bounded by m, unit diagonal; skipped once stopped
     const int rc = launch_rbf_block_dev(s, w.Xw, w.nw, kMaxWS, R.ld, w.Xw, w.nw, kMaxWS, R.ld, R.ld, S.p.gamma, w.Kw,
                                         kLdw, true, gate, &w.ctl->m, nullptr, 0);
@@ -1889,10 +1941,12 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
                      p.tau, S.k.tau_frac, int64_t(p.max_iter), w.W, w.Wf, w.ctl, w.mcount, pub);
   SVMD_LAUNCH_CHECK();
   if ((rc = enqueue_kww(S))) return rc;
-  if ((rc = launch_ws_inner(s, S.inner,
-                            InnerArgs{w.Kw, kLdw, w.W, w.ctl, S.y, S.alpha, w.Wf, S.Cp, p.eps, w.cols, w.coef, w.mcount,
-                                      S.hs, pub, packed ? w.pos_of : nullptr, lo, nloc, packed ? w.cdiag : nullptr,
-                                      w.gAw, w.Wf, w.nAmat, S.nwd, S.Cn})))
+  const InnerArgs ia{w.Kw, kLdw, w.W, w.ctl, S.y, S.alpha, w.Wf, S.Cp, p.eps, w.cols, w.coef, w.mcount,
+                     S.hs, pub, packed ? w.pos_of : nullptr, lo, nloc, packed ? w.cdiag : nullptr,
+                     w.gAw, w.Wf, w.nAmat, S.nwd, S.Cn};
+  if (S.kfun)
+    launch_ws_inner_kfun(s, ia);
+  else if ((rc = launch_ws_inner(s, S.inner, ia)))
     return rc;
   SVMD_LAUNCH_CHECK();
   if (S.mode.twin()) {  // the moved points folded to one entry per kernel row
@@ -2192,7 +2246,8 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
   const char* fe = getenv("SVM355_DECOMP_F64");
   const bool force_f64 = fe && atoi(fe) == 1;
   QuantPlan P;
-  if (!force_f64 && mn_h && mx_h && plan_quant(mn_h, mx_h, d, &P) && P.kq <= 32 * 128) {
+  const bool kfun = p.kernel != kKernelRbf;  // the dot-product kernels: the FP64 rows, and no rows x 1024 block
+  if (!kfun && !force_f64 && mn_h && mx_h && plan_quant(mn_h, mx_h, d, &P) && P.kq <= 32 * 128) {
     QuantBufs b;
     int rc = decomp_quant_buffers(ctx, n, P, quantize_aux_bytes(P), &b);
     if (rc) return rc;
@@ -2215,7 +2270,7 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
   // doubles of workspace (8 GB at 1M rows).  When that does not fit 80 % of what the device has free
   // (plus the context's current workspace, which it would replace), nothing runs (*used = false) and
   // the caller takes the pairwise solver (SVC(solver="auto")).
-  {
+  if (!kfun) {
     size_t free_b = 0, total_b = 0;
     SVMD_CHECK(hipMemGetInfo(&free_b, &total_b));
     const double need = double(n) / double(std::max(1, o.world)) * double(kMaxWS) * 8.0 +
@@ -2278,7 +2333,13 @@ int train_decomp(DeviceCtx* ctx, const char* who, const void* X_d, bool is_u8, i
   const svm_params p = params_or_default(pp);
   DecompFeatures ft;
   int rc = mode_features(o, p, &ft);
-  if (rc || (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device))) return rc;
+  if (rc || (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device)) ||
+      (rc = decomp_kfun_check(who, p, o.mode.kind, ft, false)) || (rc = kfun_knobs_check(who, p)))
+    return rc;
+  if (p.kernel != kKernelRbf && is_u8) {
+    set_error("%s: the dot-product kernels take FP64 rows (widen and scale the uint8 rows on the device first)", who);
+    return SVM_ERR_ARG;
+  }
   const auto t0 = std::chrono::steady_clock::now();
   if ((rc = ctx->begin())) return rc;
   bool used = false;
@@ -2462,7 +2523,7 @@ SVM_API int svmd_train_decomp_csr(void* h, const int64_t* indptr_d, const int32_
   DecompFeatures ft;
   int rc = mode_features(o, p, &ft);
   if (rc || (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device)) ||
-      (rc = csr_rows_check(who, o, ft)))
+      (rc = csr_rows_check(who, o, ft)) || (rc = decomp_kfun_check(who, p, o.mode.kind, ft, true)))
     return rc;
   if (!decomp_shape(o.mode.points(n), q > 0 ? q : 1024, 1).ok) {
     set_error("%s: n = %lld is outside the solver's shapes", who, (long long)n);

@@ -9,6 +9,7 @@
 
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
+#include "kfun.h"
 #include "svm355.h"
 
 namespace svm355 {
@@ -86,6 +87,37 @@ constexpr DecompFeatures kDecompRefuses[6][2] = {
     /* nu-SVC   */ {{true, true, true, true, true}, {true, true, true, true, true}},
     /* nu-SVR   */ {{true, true, true, true, true}, {true, true, true, true, true}},
 };
+
+// The dot-product kernels (svm_params.kernel != 0: linear, polynomial, sigmoid; kfun.h, hip/decomp_kfun.hip): the
+// kinds that run with one (the classifier, class weights included, and the regression (twin) solve) and what such a
+// solve refuses whatever its kind, on both backends: one GPU, a cold start, no shrinking, no polish.
+constexpr bool kDecompKfunKinds[6] = {true, true, false, false, false, false};
+constexpr DecompFeatures kDecompKfunRefuses = {true, true, true, true, false};
+
+// A dot-product kernel's own arguments and everything such a solve does not cover (csr: sparse rows): SVM_ERR_ARG
+// with `who` as the message's prefix, before the caller does any work.  SVM_OK at once for the RBF.
+inline int decomp_kfun_check(const char* who, const svm_params& p, DecompModeKind kind, const DecompFeatures& f,
+                             bool csr) {
+  if (p.kernel == kKernelRbf) return SVM_OK;
+  static const char* const name[] = {"rbf", "linear", "poly", "sigmoid"};
+  if (!kfun_params_ok(p) || !(p.gamma > 0.0) || !std::isfinite(p.gamma)) {
+    set_error("%s: kernel must be 0 (rbf), 1 (linear), 2 (poly, 1 <= degree <= %d) or 3 (sigmoid) with a finite "
+              "coef0 and gamma > 0 (kernel = %d, degree = %d, coef0 = %g, gamma = %g)", who, kMaxDegree, p.kernel,
+              p.degree, p.coef0, p.gamma);
+    return SVM_ERR_ARG;
+  }
+  const DecompFeatures& r = kDecompKfunRefuses;
+  const char* what = !kDecompKfunKinds[int(kind)] ? "this mode (the classifier and the regression (twin) solve only)"
+                     : csr                        ? "sparse (CSR) rows"
+                     : f.distributed && r.distributed ? "the distributed solve (world > 1)"
+                     : f.warm && r.warm               ? "a warm start"
+                     : f.shrinking && r.shrinking     ? "shrinking"
+                     : f.newton && r.newton           ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                                      : nullptr;
+  if (!what) return SVM_OK;
+  set_error("%s: the %s kernel does not support %s", who, name[p.kernel], what);
+  return SVM_ERR_ARG;
+}
 
 // The nu modes' selection: NB blocks of at most kNuBlockPoints points give Tc picks to each of four lists, and the
 // 4 NB Tc candidates must fit one working set (SVM_DECOMP_MAX_WS): at most 256 blocks, 1,048,576 points.

@@ -58,6 +58,10 @@ typedef struct svm_params {
   double weight_pos; // class weights: row i's box is [0, C * weight_pos] where y_i = +1 and
   double weight_neg; //   [0, C * weight_neg] where y_i = -1 (LIBSVM's -wi); 0 reads as 1 (a zero-filled
                      //   struct from an older caller), negative or non-finite values are SVM_ERR_ARG
+  int32_t kernel;    // 0 = RBF exp(-gamma |x - z|^2) (a zero-filled struct from an older caller), 1 = linear x.z,
+                     //   2 = polynomial (gamma x.z + coef0)^degree, 3 = sigmoid tanh(gamma x.z + coef0) (kfun.h)
+  int32_t degree;    // the polynomial's, 1..16 (LIBSVM's repeated squaring)
+  double coef0;
 } svm_params;
 
 typedef struct svm_result {

@@ -281,6 +281,20 @@ SVM_API int svmd_rbf_block_csr(void* ctx, const int64_t* a_indptr_d, const int32
 SVM_API int svmd_decision_csr(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
                               const double* nq_d, int64_t m, int64_t d, const double* Xs_d, const double* ns_d,
                               const double* coef_d, int64_t nsv, int64_t lds, double gamma, double b, double* out_d);
+// ---- the dot-product kernels (svm_params.kernel = 1, 2, 3: linear, polynomial, sigmoid; hip/decomp_kfun.hip) ----
+// The svmd_train_decomp and svmd_train_decomp_svr entries take them on FP64 rows (one GPU, cold start; what they
+// refuse is SVM_ERR_ARG naming the combination, decomp_mode.h).
+// The kernel block alone (tests): A_d (m x lda) against B_d (nb x ldb), kdim doubles per row (a multiple of 16).
+// epi 0: K_d (m x ldk) = kfun(A B'); epi 1 / 2: f_d[i] += sum_j coef_d[j] kfun(A_i . B_j) (2: also f_d[i + m]).
+// count >= 0: a device-side column count of that value (< 0: all nb); gate != 0: the launch is a no-op.
+SVM_API int svmd_kfun_block(void* ctx, const double* A_d, int64_t m, int64_t lda, const double* B_d, int64_t nb,
+                            int64_t ldb, int64_t kdim, const svm_params* p, int32_t epi, int32_t count, int32_t gate,
+                            double* K_d, int64_t ldk, const double* coef_d, double* f_d);
+// out_d[i] = sum_k coef_d[k] kfun(Xs row k . Xq row i) - b: the fused block and sum over chunks of 1,024 support
+// vectors taken in order (bit-identical run to run).
+SVM_API int svmd_decision_kfun(void* ctx, const double* Xs_d, const double* coef_d, int64_t nsv, int64_t lds,
+                               const double* Xq_d, int64_t m, int64_t ldq, int64_t kdim, const svm_params* p, double b,
+                               double* out_d);
 // Xs_d (k x ld, ld >= d, written whole) = the CSR rows ids_d[0 : k] as dense rows, ns_d[k] their norms.
 SVM_API int svmd_csr_rows_dense(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
                                 const double* nrm_d, int64_t n, int64_t d, const int64_t* ids_d, int64_t k,

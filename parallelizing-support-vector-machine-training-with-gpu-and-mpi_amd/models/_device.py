@@ -281,6 +281,22 @@ def platt_probability(z: np.ndarray) -> np.ndarray:
     return np.stack([np.where(z >= 0, big, small), np.where(z >= 0, small, big)], -1)
 
 
+def check_dot_kernel(params, **off) -> None:
+    """What a dot-product kernel (linear, poly, sigmoid) does not cover raises here, before any device work: ``off``
+    maps each unsupported option's description to whether it was asked for."""
+    if params.dot_kernel:
+        for name, on in off.items():
+            if on:
+                raise ValueError(f"kernel={params.kernel!r} is not supported with {name.replace('_', ' ')} (the RBF only)")
+
+
+def host_kernel_decision(est, Xq: np.ndarray, coef: np.ndarray) -> np.ndarray:
+    """sum_k coef_k kfun(x_k . q) - b on the host for a dot-product kernel model, summed in support-vector order."""
+    from ..ops import cpu as C
+
+    return C.kernel_gram(Xq, est.support_vectors_, est.params) @ coef - est.b_
+
+
 class KernelEstimator:
     """What ``SVC``, ``SVR`` and ``OneClassSVM`` share: ``scale``, ``scaler_``, the device model ``_dev`` and the
     lazily fetched host copy of the support vectors."""
@@ -338,6 +354,10 @@ class KernelEstimator:
         from ..ops import device as D
 
         dv = self._dev
+        if self.params.dot_kernel:  # the model's kernel: the fused dot-product block and sum
+            if is_sparse(X):
+                raise ValueError(f"sparse queries are not supported with kernel={self.params.kernel!r} (densify them)")
+            return D.decision_kfun(dv["Xs"], dv["coef"], self._device_queries(X)[0], self.params, self.b_)
         if is_sparse(X):
             return D.decision_csr(dv["Xs"], dv["ns"], dv["coef"], sparse_queries(dv, X, self.scale),
                                   self.params.gamma, self.b_)

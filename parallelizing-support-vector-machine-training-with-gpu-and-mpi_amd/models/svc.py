@@ -27,8 +27,8 @@ import numpy as np
 from ..utils.config import SVMParams, default_threads
 from ..utils.data import check_folds, check_warm_start, resolve_class_weight, stratified_folds
 from ..utils.sparse import is_sparse, toarray
-from ._device import (KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, platt_probability, scaled_cpu,
-                      solve_on_rows)
+from ._device import (KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, check_dot_kernel,
+                      host_kernel_decision, platt_probability, scaled_cpu, solve_on_rows)
 
 
 class SVC(KernelEstimator):
@@ -36,7 +36,8 @@ class SVC(KernelEstimator):
                  sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto", n_threads: int = 0,
                  scale: bool = True, zero_is_positive: bool = False, gram: str = "auto", kcache: str = "auto",
                  wss: str = "first", solver: str = "auto", working_set: int = 1024, shrinking=False,
-                 class_weight=None, probability: bool = False, cv: int = 5, cv_seed: int = 0):
+                 class_weight=None, probability: bool = False, cv: int = 5, cv_seed: int = 0, kernel: str = "rbf",
+                 degree: int = 3, coef0: float = 0.0):
         if wss not in ("first", "second"):
             raise ValueError("wss must be 'first' (the reference's selection) or 'second'")
         if solver not in ("auto", "smo", "decomp"):
@@ -44,7 +45,12 @@ class SVC(KernelEstimator):
                              "decomposition) or 'smo' (the reference's pairwise SMO over all n points)")
         self.params = SVMParams(C=C, gamma=gamma, tau=tol, eps=eps, sv_tol=sv_tol, max_iter=max_iter,
                                 n_threads=n_threads if n_threads > 0 else default_threads(),
-                                wss=2 if wss == "second" else 1, shrinking=shrinking)
+                                wss=2 if wss == "second" else 1, shrinking=shrinking, kernel=kernel, degree=degree,
+                                coef0=coef0)
+        # kernel (scikit-learn's, LIBSVM's -t): "rbf" (the default, and the only one of everything but SVC and SVR),
+        # "linear", "poly" or "sigmoid" with degree and coef0 -- on the CPU the pairwise oracle on the host Gram, on
+        # a GPU the decomposition solver's dot-product kernels (decomp_kfun.hip) from a cold start; probability=True,
+        # cross-validation, sparse rows, shrinking, a warm start and the pairwise GPU solver raise with them.
         # class weights (scikit-learn's class_weight, LIBSVM's -wi): None, "balanced" (n / (2 n_c), resolved
         # per fit from the labels) or {1: w_pos, -1: w_neg}; row i's box is [0, C * w(y_i)].  The CPU oracle
         # and the GPU decomposition solver take them; the pairwise GPU solver, shrinking and the knobs that
@@ -89,6 +95,14 @@ class SVC(KernelEstimator):
         sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
         if sparse and dev == "cpu":
             X, sparse = toarray(X), False
+        # what the estimator itself rules out; the solver's own refusals (a warm start, shrinking, the knobs, CSR rows)
+        # come from the native table as ValueError.  wss='second' is the pairwise solvers' RBF-only second-order arm,
+        # and on a GPU solver='smo', gram=, kcache= and scale=False all select the pairwise solver, which is RBF only.
+        check_dot_kernel(self.params, probability=self.probability, sparse_rows=sparse, **{"wss='second'": self.params.wss == 2},
+                         **({} if dev == "cpu" else {"solver='smo'": self.solver == "smo",
+                                                     f"gram={self.gram!r}": self.gram != "auto",
+                                                     f"kcache={self.kcache!r}": self.kcache != "auto",
+                                                     "scale=False": not self.scale}))
         if sparse:
             self._check_sparse(alpha0)
         else:  # uint8 pixel rows stay compact up to the device (8x less H2D; widened to FP64 there)
@@ -276,6 +290,7 @@ class SVC(KernelEstimator):
         resolves on all labels.  Fits no sigmoid and leaves the estimator's own model alone.  On a GPU the folds
         run ``concurrent_solves`` at a time (default: all of them while the rows fit the last-level cache)."""
         dev = _resolve_device(self.device)
+        check_dot_kernel(self.params, cross_validation=True)
         if is_sparse(X):
             raise ValueError("cross-validation does not take sparse rows (densify them: X.toarray())")
         X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
@@ -346,7 +361,11 @@ class SVC(KernelEstimator):
         if self.solver == "decomp":
             raise ValueError("solver='decomp' runs on the GPU (device='cuda'); the CPU oracle is the pairwise SMO")
         Xs = self._scaled_cpu(X)
-        alpha, res, _ = C.smo_train(Xs, y, self.params, alpha=alpha0, warm=alpha0 is not None)
+        if self.params.dot_kernel:  # the pairwise oracle on the host Gram of the kernel (its first-order rule)
+            alpha, res, _ = C.smo_train_gram(C.kernel_gram(Xs, Xs, self.params), y, self.params, alpha=alpha0,
+                                             warm=alpha0 is not None)
+        else:
+            alpha, res, _ = C.smo_train(Xs, y, self.params, alpha=alpha0, warm=alpha0 is not None)
         self._finish(alpha, y, res)
         self.support_vectors_ = Xs[self.support_].copy()
         self.timings_ = {"smo_ms": res.seconds * 1e3}
@@ -372,7 +391,7 @@ class SVC(KernelEstimator):
         # the FP64 rows, minus their widen / scale / FP64-quantise passes.  FP64 host rows (the reference's
         # format), and bytes the solver declined, are scaled on the device, then quantised into the same integers
         # or -- real-valued data -- solved with FP64-MFMA kernel values.
-        bytes_ok = X.dtype == np.uint8 and self.scale and (decomp or (
+        bytes_ok = X.dtype == np.uint8 and self.scale and not self.params.dot_kernel and (decomp or (
             self.gram in ("auto", "int") and self.kcache in ("auto", "full")
             and os.environ.get("SVM355_U8_TRAIN", "1") != "0"
             and (self.kcache != "auto" or D.gram_fits(X.shape[0], device))))
@@ -440,6 +459,8 @@ class SVC(KernelEstimator):
 
         X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
+        if self.params.dot_kernel:
+            return host_kernel_decision(self, Xq, self.dual_coef_)
         return C.decision(self.support_vectors_, self.support_labels_, self.alpha_[self.support_], Xq,
                           self.params.gamma, self.b_, self.params.n_threads)
 
@@ -479,7 +500,8 @@ class SVC(KernelEstimator):
         p = m["params"]
         svc = cls(C=p.C, gamma=p.gamma, tol=p.tau, eps=p.eps, sv_tol=p.sv_tol, max_iter=p.max_iter, device=device,
                   scale=m["scaler"] is not None,
-                  class_weight={1: p.weight_pos, -1: p.weight_neg} if p.weighted else None)
+                  class_weight={1: p.weight_pos, -1: p.weight_neg} if p.weighted else None, kernel=p.kernel,
+                  degree=p.degree, coef0=p.coef0)
         svc.params = svc.params.replace(weight_pos=p.weight_pos, weight_neg=p.weight_neg)
         svc.class_weight_ = {1: p.weight_pos, -1: p.weight_neg}
         svc.scaler_ = m["scaler"]

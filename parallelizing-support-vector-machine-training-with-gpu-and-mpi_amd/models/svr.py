@@ -22,7 +22,8 @@ import numpy as np
 
 from ..utils.config import SVMParams, default_threads
 from ..utils.sparse import is_sparse, toarray
-from ._device import KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, solve_on_rows
+from ._device import (KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, check_dot_kernel,
+                      host_kernel_decision, solve_on_rows)
 
 KIND = "svr"  # model files' kind marker (model_io)
 
@@ -39,11 +40,13 @@ def split_twins(alpha2: np.ndarray, C: float):
 class SVR(KernelEstimator):
     def __init__(self, C: float = 10.0, gamma: float = 0.00125, epsilon: float = 0.1, tol: float = 1e-5,
                  eps: float = 1e-12, sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto",
-                 n_threads: int = 0, scale: bool = True, working_set: int = 1024):
+                 n_threads: int = 0, scale: bool = True, working_set: int = 1024, kernel: str = "rbf", degree: int = 3,
+                 coef0: float = 0.0):
         if not (np.isfinite(epsilon) and epsilon >= 0):
             raise ValueError(f"epsilon must be finite and >= 0, got {epsilon!r}")
         self.params = SVMParams(C=C, gamma=gamma, tau=tol, eps=eps, sv_tol=sv_tol, max_iter=max_iter,
-                                n_threads=n_threads if n_threads > 0 else default_threads())
+                                n_threads=n_threads if n_threads > 0 else default_threads(), kernel=kernel,
+                                degree=degree, coef0=coef0)  # kernel: as SVC's
         self.epsilon = float(epsilon)
         self.device = device
         self.scale = scale
@@ -55,6 +58,7 @@ class SVR(KernelEstimator):
         sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
         if sparse and dev == "cpu":
             X, sparse = toarray(X), False
+        check_dot_kernel(self.params, sparse_rows=sparse)
         if not sparse:
             X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         z = np.ascontiguousarray(z, dtype=np.float64)
@@ -95,7 +99,11 @@ class SVR(KernelEstimator):
         from ..ops import cpu as C
 
         Xs = self._scaled_cpu(X)
-        alpha2, res = C.smo_train_svr(Xs, z, self.params, self.epsilon)
+        if self.params.dot_kernel:  # the decomposition oracle's twin mode on the host Gram (its second-order pair)
+            alpha2, res, _, _ = C.decomp_train_gram_svr(C.kernel_gram(Xs, Xs, self.params), z, self.params,
+                                                        self.epsilon, q=self.working_set, inner_wss=2)
+        else:
+            alpha2, res = C.smo_train_svr(Xs, z, self.params, self.epsilon)
         self._finish(alpha2, res)
         self._dev = None
         self.support_vectors_ = Xs[self.support_].copy()
@@ -112,7 +120,8 @@ class SVR(KernelEstimator):
         # pixel rows stay bytes on the device (the exact-integer plan reads them); FP64 rows are scaled there and
         # quantised when they admit the plan, else solved with FP64-MFMA kernel values
         rows, out = solve_on_rows(X, device, lambda r: D.train_decomp_svr(
-            r.rows, zd, alpha, self.params, r.mn_h, r.mx_h, epsilon=self.epsilon, working_set=self.working_set))
+            r.rows, zd, alpha, self.params, r.mn_h, r.mx_h, epsilon=self.epsilon, working_set=self.working_set),
+            bytes_ok=not self.params.dot_kernel)  # a dot-product kernel: the FP64 rows, scaled on the device
         if out is None:
             raise ValueError("SVR: the decomposition solver does not cover these rows (its FP64-row workspace, "
                              "n x 1024 doubles, does not fit the device)")
@@ -146,6 +155,8 @@ class SVR(KernelEstimator):
 
         X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
+        if self.params.dot_kernel:
+            return host_kernel_decision(self, Xq, self.dual_coef_)
         return C.decision(self.support_vectors_, np.where(self.dual_coef_ > 0, 1, -1), np.abs(self.dual_coef_), Xq,
                           self.params.gamma, self.b_, self.params.n_threads)
 
@@ -174,7 +185,8 @@ class SVR(KernelEstimator):
             raise ValueError(f"{directory} holds a {m['kind']!r} model, not an SVR (load it with its own class)")
         p = m["params"]
         svr = cls(C=p.C, gamma=p.gamma, epsilon=m["meta"].get("epsilon", 0.1), tol=p.tau, eps=p.eps, sv_tol=p.sv_tol,
-                  max_iter=p.max_iter, device=device, scale=m["scaler"] is not None)
+                  max_iter=p.max_iter, device=device, scale=m["scaler"] is not None, kernel=p.kernel, degree=p.degree,
+                  coef0=p.coef0)
         svr.scaler_ = m["scaler"]
         svr.support_ = m["ids"]
         svr.dual_coef_ = m["alphas"] * m["labels"]

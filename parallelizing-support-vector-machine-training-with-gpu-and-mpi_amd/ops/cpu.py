@@ -60,6 +60,26 @@ def smo_train(X: np.ndarray, y: np.ndarray, params: SVMParams, alpha: Optional[n
     return a, res, trace
 
 
+def kernel_gram(A: np.ndarray, B: np.ndarray, params: SVMParams) -> np.ndarray:
+    """The host Gram K(A, B) of params' dot-product kernel (linear, poly, sigmoid) in float64; the polynomial's
+    integer power by LIBSVM's repeated squaring, as the native code multiplies."""
+    dot = _c64(A) @ _c64(B).T
+    if params.kernel == "linear":
+        return dot
+    t = params.gamma * dot + params.coef0
+    if params.kernel == "sigmoid":
+        return np.tanh(t)
+    if params.kernel != "poly":
+        raise ValueError(f"kernel_gram: a dot-product kernel, got {params.kernel!r}")
+    ret, q = np.ones_like(t), int(params.degree)
+    while q > 0:
+        if q % 2:
+            ret = ret * t
+        t = t * t
+        q //= 2
+    return ret
+
+
 def smo_train_gram(K: np.ndarray, y: np.ndarray, params: SVMParams, alpha: Optional[np.ndarray] = None,
                    warm: bool = False, trace_cap: int = 0) -> Tuple[np.ndarray, SMOResult, Optional[np.ndarray]]:
     K = _c64(K)

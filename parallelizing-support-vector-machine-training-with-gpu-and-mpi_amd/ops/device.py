@@ -440,6 +440,14 @@ def _decomp_rows(X: torch.Tensor) -> int:
     return X.shape[0]
 
 
+def _check_dot(params: SVMParams, rc: int, entry: str) -> None:
+    """``N.check``; what a solve with a dot-product kernel refuses (SVM_ERR_ARG: the native refusal table and
+    knob check, decomp_mode.h / decomp.hip -- the one copy of those rules) is a ``ValueError`` with its message."""
+    if rc == 2 and params.dot_kernel:
+        raise ValueError(f"{entry}: {N.last_error()}")
+    N.check(rc, entry)
+
+
 def _train_decomp(entry: str, solver: str, X: torch.Tensor, mn, mx, mode_args, params: SVMParams, working_set: int,
                   trace, extra=lambda st: {}, after_ws=()) -> Optional[Tuple[SMOResult, dict]]:
     """The body the ``svmd_train_decomp*`` wrappers share: the rows checked, the host statistics and the out
@@ -454,10 +462,10 @@ def _train_decomp(entry: str, solver: str, X: torch.Tensor, mn, mx, mode_args, p
     r, tm, used = N.SvmResult(), N.SvmdTiming(), ctypes.c_int32(0)
     st = (ctypes.c_int64 * 16)()
     p = params.to_struct()
-    N.check(getattr(ctx.lib, entry)(ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), *mode_args,
-                                    ctypes.byref(p), int(working_set), *after_ws, ctypes.byref(r), ctypes.byref(tm),
-                                    st, ctypes.byref(used),
-                                    ctypes.byref(trace.struct) if trace is not None else None), entry)
+    _check_dot(params, getattr(ctx.lib, entry)(
+        ctx.bind(), N.ptr(X), int(u8), n, ld, d, N.ptr(a), N.ptr(b), *mode_args, ctypes.byref(p), int(working_set),
+        *after_ws, ctypes.byref(r), ctypes.byref(tm), st, ctypes.byref(used),
+        ctypes.byref(trace.struct) if trace is not None else None), entry)
     if not used.value:
         return None
     return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
@@ -784,6 +792,46 @@ def decision(Xs: torch.Tensor, ns: torch.Tensor, coef: torch.Tensor, Xq: torch.T
     return out
 
 
+def kfun_block(A: torch.Tensor, B: torch.Tensor, params: SVMParams, epilogue: str = "store",
+               coef: Optional[torch.Tensor] = None, f: Optional[torch.Tensor] = None, count: int = -1,
+               gate: int = 0) -> torch.Tensor:
+    """The dot-product kernel block (svmd_kfun_block, decomp_kfun.hip) on padded FP64 device rows A (m, ld) and B
+    (nb, ld).  "store": returns K (m, nb) = kfun(A B').  "sum" / "sum_twin": f[i] += sum_j coef[j] kfun(A_i . B_j)
+    in place (twin: also f[i + m]) and returns f.  count >= 0: a device-side column count; gate != 0: a no-op."""
+    _check_rows(A, "A")
+    _check_rows(B, "B")
+    if A.shape[1] != B.shape[1]:
+        raise ValueError("A and B row lengths differ")
+    epi = ("store", "sum", "sum_twin").index(epilogue)
+    m, nb = A.shape[0], B.shape[0]
+    K = None
+    if epi == 0:
+        K = torch.zeros((m, nb), dtype=torch.float64, device=A.device)
+    elif (coef is None or f is None or coef.shape != (nb,) or f.shape != (m * epi,) or coef.dtype != torch.float64
+          or f.dtype != torch.float64 or not coef.is_contiguous() or not f.is_contiguous()):
+        raise ValueError(f"{epilogue}: coef ({nb},) and f ({m * epi},), contiguous float64")
+    ctx = _ctx_for(A)
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_kfun_block(ctx.bind(), N.ptr(A), m, A.shape[1], N.ptr(B), nb, B.shape[1], A.shape[1],
+                                    ctypes.byref(p), epi, int(count), int(gate), N.ptr(K), nb, N.ptr(coef), N.ptr(f)),
+            "svmd_kfun_block")
+    return K if epi == 0 else f
+
+
+def decision_kfun(Xs: torch.Tensor, coef: torch.Tensor, Xq: torch.Tensor, params: SVMParams, b: float) -> torch.Tensor:
+    """out[i] = sum_k coef[k] kfun(Xs_k . Xq_i) - b for a dot-product kernel (svmd_decision_kfun): the fused block
+    and sum over chunks of 1,024 support vectors in order; bit-identical run to run."""
+    _check_rows(Xq, "Xq")
+    m, nsv = Xq.shape[0], Xs.shape[0]
+    out = torch.empty(m, dtype=torch.float64, device=Xq.device)
+    ctx = _ctx_for(Xq)
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_decision_kfun(ctx.bind(), N.ptr(Xs) if nsv else None, N.ptr(coef) if nsv else None, nsv,
+                                       Xs.shape[1], N.ptr(Xq), m, Xq.shape[1], Xq.shape[1], ctypes.byref(p), float(b),
+                                       N.ptr(out)), "svmd_decision_kfun")
+    return out
+
+
 def decision_int(X: torch.Tensor, d: int, mn: torch.Tensor, mx: torch.Tensor, coef: torch.Tensor, gamma: float):
     """out[i] = sum_{k < nz} coef[k] K(X_i, X_k), nz = len(coef), on the exact-integer path (the
     Gram's own kernel values) for scaled pixel rows X; None when the rows are not integer pixels."""
@@ -1007,11 +1055,10 @@ def train_decomp_csr(A: DeviceCSR, alpha: torch.Tensor, params: SVMParams, y: Op
     r, tm = N.SvmResult(), N.SvmdTiming()
     st = (ctypes.c_int64 * 16)()
     p = params.to_struct()
-    N.check(ctx.lib.svmd_train_decomp_csr(ctx.bind(), *A.args(), A.n, A.d, 0 if z is None else 1, N.ptr(y), N.ptr(z),
-                                          float(epsilon), N.ptr(alpha), ctypes.byref(p), int(working_set),
-                                          ctypes.byref(r), ctypes.byref(tm), st,
-                                          ctypes.byref(trace.struct) if trace is not None else None),
-            "svmd_train_decomp_csr")
+    _check_dot(params, ctx.lib.svmd_train_decomp_csr(
+        ctx.bind(), *A.args(), A.n, A.d, 0 if z is None else 1, N.ptr(y), N.ptr(z), float(epsilon), N.ptr(alpha),
+        ctypes.byref(p), int(working_set), ctypes.byref(r), ctypes.byref(tm), st,
+        ctypes.byref(trace.struct) if trace is not None else None), "svmd_train_decomp_csr")
     return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
                                       "kcache": "none", "gram_path": "csr-fp64", "rows": "csr",
                                       "solver": "decomp" if z is None else "decomp-svr",

@@ -33,6 +33,9 @@ def default_threads(cap: int = 16) -> int:
     return max(1, min(cap, n))
 
 
+KERNELS = ("rbf", "linear", "poly", "sigmoid")  # svm_params.kernel = the index
+
+
 @dataclass
 class SVMParams:
     C: float = 10.0
@@ -55,8 +58,18 @@ class SVMParams:
     # solver take them; everything else refuses weights that differ from 1.
     weight_pos: float = 1.0
     weight_neg: float = 1.0
+    # the kernel function (LIBSVM's -t, scikit-learn's kernel=): "rbf" exp(-gamma |x - z|^2), "linear" x.z,
+    # "poly" (gamma x.z + coef0)^degree with 1 <= degree <= 16, "sigmoid" tanh(gamma x.z + coef0).  SVC and SVR
+    # take the last three on the CPU and on the one-GPU decomposition solver; everything else is RBF only.
+    kernel: str = "rbf"
+    degree: int = 3
+    coef0: float = 0.0
 
     def __post_init__(self):
+        if self.kernel not in KERNELS or not (isinstance(self.degree, (int, np.integer)) and 1 <= self.degree <= 16) \
+                or not np.isfinite(self.coef0):
+            raise ValueError(f"kernel must be one of {KERNELS} with 1 <= degree <= 16 and a finite coef0, got "
+                             f"kernel={self.kernel!r}, degree={self.degree!r}, coef0={self.coef0!r}")
         # the reference hard-codes these; as parameters they must keep the problem well posed:
         # C <= 0 empties the box, gamma <= 0 makes the kernel constant (eta = 0), tau <= 0 never stops
         bad = [f"{k}={v!r}" for k, v, ok in (("C", self.C, self.C > 0), ("gamma", self.gamma, self.gamma > 0),
@@ -103,7 +116,12 @@ class SVMParams:
     def to_struct(self, verbose: int = 0):
         return params_struct(self.C, self.gamma, self.tau, self.eps, self.sv_tol, self.max_iter,
                              self.n_threads, verbose, self.wss, self._shrink_code(), self.weight_pos,
-                             self.weight_neg)
+                             self.weight_neg, KERNELS.index(self.kernel), self.degree, self.coef0)
+
+    @property
+    def dot_kernel(self) -> bool:
+        """A kernel of x.z (linear, poly, sigmoid): its diagonal is not 1."""
+        return self.kernel != "rbf"
 
     def replace(self, **kw) -> "SVMParams":
         return dataclasses.replace(self, **kw)
