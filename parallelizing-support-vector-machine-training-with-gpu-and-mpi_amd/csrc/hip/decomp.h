@@ -59,7 +59,9 @@ struct DecompOpts {
 // MFMA, igram.hip) or the min-max scaled FP64 rows themselves (X, n x ld, ld a multiple of 16, and
 // their squared norms nrm; FP64 MFMA, gram_mfma.hip) -- the latter for real-valued data -- or sparse rows in CSR
 // form (indptr n + 1, indices sorted and in [0, d), values min-max scaled so that zeros stay zeros, and nrm;
-// csr_rbf.hip: kernel values against a d x 1024 transposed panel of the working set; one GPU, cold start).
+// csr_rbf.hip: kernel values against a d x 1024 transposed panel of the working set; one GPU, cold start) -- or the
+// rows as float32 (X32, n x ld floats, ld a multiple of 16, scaled and rounded once, with the FP64 norms nrm of the
+// rounded values; rows_f32.hip: FP32-MFMA dot products under an FP64 epilogue; one GPU, cold start).
 struct DecompRows {
   const int8_t* Q = nullptr;
   const int32_t* N0 = nullptr;
@@ -74,7 +76,9 @@ struct DecompRows {
   const double* values = nullptr;
   int64_t d = 0, dpad = 0;  // CSR: the features, and the panel's feature rows (d rounded up to 16)
   bool fp64() const { return X != nullptr; }
+  const float* X32 = nullptr;
   bool csr() const { return indptr != nullptr; }
+  bool f32() const { return X32 != nullptr; }
 };
 
 // stats: SVM_DECOMP_STATS int64 (see run_decomp).

@@ -39,6 +39,7 @@
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
 #include "persist.h"
+#include "rows_f32.h"
 #include "svm355_device.h"
 #include "trace.h"
 
@@ -1148,6 +1149,8 @@ struct DecompWs {
   double *PT = nullptr, *nP = nullptr;
   int32_t *pprev = nullptr, *pcnt = nullptr;
   CsrPanel panel() const { return CsrPanel{PT, kMaxWS, nP, pprev, pcnt}; }
+  // float32 rows: the working set's and the moved columns' rows gathered (kMaxWS x ld floats each; norms: nw, nc)
+  float *Xw32 = nullptr, *Xc32 = nullptr;
 };
 
 // The f update's kernel columns K(this GPU's rows, j) kept in HBM (size_col_cache); slab null: no cache.
@@ -1164,6 +1167,7 @@ struct Solve {
   DecompRows R;
   bool f64 = false;
   bool csr = false;  // sparse rows (csr_rbf.hip): neither of the two dense formats
+  bool f32 = false;  // float32 rows (rows_f32.hip): no rows x 1024 block, no column cache, no quantisation plan
   bool kfun = false;  // a dot-product kernel (p.kernel != 0, decomp_kfun.hip): FP64 rows, no norms, no unit diagonal
   int kq = 0;  // the quantised rows' bytes (exact-integer rows)
   const int32_t* y = nullptr;
@@ -1284,7 +1288,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   DecompWs& w = S.w;
   const size_t nl1 = size_t(std::max<int64_t>(S.nloc, 1)), n = size_t(S.n), kq = size_t(S.kq), ld = size_t(S.R.ld);
   const size_t nr1 = size_t(std::max<int64_t>(S.rows(), 1)), ncol = size_t(S.cols());  // kernel rows / columns
-  const bool f64 = S.f64, q8 = !f64 && !S.csr, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
+  const bool f64 = S.f64, q8 = !f64 && !S.csr && !S.f32, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
   w.f = c.take<double>(nl1);
   w.own = c.take<CandRec>(size_t(S.Lr));
   w.all = c.take<CandRec>(size_t(S.sh.L));
@@ -1337,6 +1341,12 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.nP = c.take<double>(kMaxWS, S.csr);
   w.pprev = c.take<int32_t>(kMaxWS, S.csr);
   w.pcnt = c.take<int32_t>(64, S.csr);
+  w.Xw32 = c.take<float>(size_t(kMaxWS) * ld, S.f32);
+  w.Xc32 = c.take<float>(size_t(kMaxWS) * ld, S.f32);
+  if (S.f32) {
+    w.nw = c.take<double>(kMaxWS);
+    w.nc = c.take<double>(kMaxWS);
+  }
 }
 
 // The knob values a dot-product kernel's solve refuses (docs/KNOBS.md): its inner solve is one kernel, 256 threads
@@ -1364,9 +1374,11 @@ int mode_features(const DecompOpts& o, const svm_params& p, DecompFeatures* f) {
   return SVM_OK;
 }
 
-// Sparse (CSR) rows cover the classifier (class weights included) and the twin mode, on one GPU from a cold
-// start; everything else is SVM_ERR_ARG under `who` before any device work, as decomp_mode_check's refusals.
-int csr_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& ft) {
+// The row sources with a fused block and sum of their own -- sparse (CSR) rows and float32 rows, `rows` naming
+// which -- cover the classifier (class weights included) and the twin mode, on one GPU from a cold start;
+// everything else is SVM_ERR_ARG under `who` before any device work, as decomp_mode_check's refusals.  The forced
+// column cache, a knob, is refused with them once the knobs are read (setup_solve).
+int fused_rows_check(const char* who, const char* rows, const DecompOpts& o, const DecompFeatures& ft) {
   const char* what = (o.mode.kind != DecompModeKind::classify && o.mode.kind != DecompModeKind::twin)
                          ? "this mode (the classifier and the regression (twin) solve only)"
                      : ft.distributed ? "the distributed solve (world > 1)"
@@ -1375,8 +1387,21 @@ int csr_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& f
                      : ft.newton      ? "the Newton polish (SVM355_DECOMP_NEWTON)"
                                       : nullptr;
   if (!what) return SVM_OK;
-  set_error("%s: sparse (CSR) rows do not support %s", who, what);
+  set_error("%s: %s do not support %s", who, rows, what);
   return SVM_ERR_ARG;
+}
+constexpr const char* kCsrRowsName = "sparse (CSR) rows";
+constexpr const char* kF32RowsName = "float32 rows";
+int csr_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& ft) {
+  return fused_rows_check(who, kCsrRowsName, o, ft);
+}
+// float32 rows: the same limits, and the RBF kernel only (the dot-product kernels read FP64 rows).
+int f32_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& ft, const svm_params& p) {
+  if (p.kernel != kKernelRbf) {
+    set_error("%s: %s do not support a dot-product kernel (kernel = %d; the RBF only)", who, kF32RowsName, p.kernel);
+    return SVM_ERR_ARG;
+  }
+  return fused_rows_check(who, kF32RowsName, o, ft);
 }
 
 // The checks, the shape and this GPU's slice of it, the knobs and what follows from them.
@@ -1403,13 +1428,15 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
   }
-  const bool f64 = R.fp64(), csr = R.csr();
-  if (csr ? (f64 || !R.indices || !R.values || !R.nrm || R.d < 1 || R.dpad < R.d || R.d >= int64_t(INT32_MAX))
-          : f64 ? (R.ld % 16 != 0 || !R.nrm) : (!R.Q || !R.P)) {
+  const bool f64 = R.fp64(), csr = R.csr(), f32 = R.f32();
+  if (csr ? (f64 || f32 || !R.indices || !R.values || !R.nrm || R.d < 1 || R.dpad < R.d || R.d >= int64_t(INT32_MAX))
+      : f32 ? (f64 || R.ld < 16 || R.ld % 16 != 0 || !R.nrm)
+      : f64 ? (R.ld % 16 != 0 || !R.nrm) : (!R.Q || !R.P)) {
     set_error("decomposition SMO: bad row source");
     return SVM_ERR_ARG;
   }
   if (csr && (rc = csr_rows_check("decomposition SMO", o, ft))) return rc;
+  if (f32 && (rc = f32_rows_check("decomposition SMO", o, ft, p))) return rc;
   svm_decomp_trace* tr = o.trace;
   if (tr && (world != 1 || tr->cap < 0 || (tr->n != 0 && tr->n != n))) {
     set_error("decomposition SMO: a trace needs one GPU and snapshots of n = %lld", (long long)n);
@@ -1427,8 +1454,9 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     return SVM_ERR_ARG;
   }
   if ((rc = read_knobs(sh, &S.k))) return rc;
-  if (csr && S.k.ccache == 1) {
-    set_error("decomposition SMO: sparse (CSR) rows do not support the column cache (SVM355_DECOMP_CCACHE=1)");
+  if ((csr || f32) && S.k.ccache == 1) {
+    set_error("decomposition SMO: %s do not support the column cache (SVM355_DECOMP_CCACHE=1)",
+              csr ? kCsrRowsName : kF32RowsName);
     return SVM_ERR_ARG;
   }
   if ((rc = svm_class_boxes(&p1, &S.Cp, &S.Cn))) return rc;
@@ -1437,12 +1465,13 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.R = R;
   S.f64 = f64;
   S.csr = csr;
+  S.f32 = f32;
   S.kfun = p.kernel != kKernelRbf;
   if (S.kfun && !f64) {
     set_error("decomposition SMO: the dot-product kernels run on FP64 rows");
     return SVM_ERR_ARG;
   }
-  S.kq = (f64 || csr) ? 0 : R.P->kq;
+  S.kq = (f64 || csr || f32) ? 0 : R.P->kq;
   S.y = y;  // a mode with its own signs: those, in the workspace (alloc_solve)
   S.alpha = alpha;
   S.mode = o.mode;
@@ -1466,7 +1495,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     nu_start_walk(p1.C * o.mode.nu * double(nrow) / 2.0, p1.C, nrow, &S.nu_full, &S.nu_frac);
   S.nchunks = (n + kMaxWS - 1) / kMaxWS;
   S.wide_select = !o.mode.nu_pairs() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select);
-  S.kww_narrow = !f64 && !csr && !S.k.kww_sym && S.kq <= 1536;
+  S.kww_narrow = !f64 && !csr && !f32 && !S.k.kww_sym && S.kq <= 1536;
   S.shc = shrink_cfg(p);
   S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
   const NewtonCfg nwc = newton_cfg(p);
@@ -1489,7 +1518,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
 int alloc_solve(Solve& S, bool warm) {
   static std::mutex alloc_mu;
   std::lock_guard<std::mutex> alloc_lock(alloc_mu);
-  int rc = S.csr ? SVM_OK : size_col_cache(S, warm, &S.cc);  // sparse rows: no cache (refused when forced)
+  int rc = (S.csr || S.f32) ? SVM_OK : size_col_cache(S, warm, &S.cc);  // sparse / float32 rows: no cache (refused when forced)
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
   if (S.mode.own_signs()) S.y = S.w.sgn;
@@ -1540,6 +1569,25 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
     b.coef = cf;
     b.f = w.f;
     return launch_csr_rbf(s, twin ? CsrEpilogue::sum_twin : CsrEpilogue::sum, A, w.panel(), b);
+  }
+  if (S.f32) {  // the moved columns' rows gathered, then the fused block + sum: no rows x 1024 block in HBM
+    int rc = launch_ws_gather_f32(s, R.X32, R.nrm, R.ld, cl, cnt, nullptr, 0, kMaxWS, w.Xc32, w.nc);
+    if (rc) return rc;
+    Rbf32Block b;
+    b.A = R.X32 + lo * R.ld;
+    b.nA = R.nrm + lo;
+    b.m = nloc;
+    b.B = w.Xc32;
+    b.nB = w.nc;
+    b.ncap = kMaxWS;
+    b.lda = b.ldb = b.kdim = R.ld;
+    b.ncount = cnt;
+    b.row_off = lo;
+    b.idb = cl;
+    b.gamma = S.p.gamma;
+    b.coef = cf;
+    b.f = w.f;
+    return launch_rbf32_block(s, twin ? Rbf32Epilogue::sum_twin : Rbf32Epilogue::sum, b);
   }
   if (S.f64) {
     hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, cl, cnt,
@@ -1658,6 +1706,10 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
   std::memset(S.hs, 0, sizeof(DecompHost));
   SVMD_CHECK(hipMemsetAsync(w.ctl, 0, sizeof(DecompCtl), s));  // stop = SVM_STOP_RUNNING, counters 0
   if (S.f64) SVMD_CHECK(hipMemsetAsync(w.Xw, 0, size_t(kMaxWS) * S.R.ld * 8, s));  // rows beyond m stay finite
+  if (S.f32) {  // rows beyond m stay finite
+    SVMD_CHECK(hipMemsetAsync(w.Xw32, 0, size_t(kMaxWS) * S.R.ld * 4, s));
+    SVMD_CHECK(hipMemsetAsync(w.nw, 0, size_t(kMaxWS) * 8, s));
+  }
   if (S.csr) {  // the panel is cleared whole once per fit; after that only by re-walking the rows it held
     SVMD_CHECK(hipMemsetAsync(w.PT, 0, size_t(S.R.dpad) * kMaxWS * 8, s));
     SVMD_CHECK(hipMemsetAsync(w.pcnt, 0, 4, s));
@@ -1826,6 +1878,24 @@ int enqueue_kww(const Solve& S) {
     b.sym = true;
     rc = launch_csr_rbf(s, CsrEpilogue::store, A, w.panel(), b);
     return rc ? rc : twin_diag();
+  }
+  if (S.f32) {  // W's rows gathered, then a full launch with A = B: symmetric to the bit, 1.0 by id (twins too)
+    const int64_t tw = S.mode.twin() ? S.nrow : 0;
+    int rc = launch_ws_gather_f32(s, R.X32, R.nrm, R.ld, w.W, &w.ctl->m, gate, tw, kMaxWS, w.Xw32, w.nw);
+    if (rc) return rc;
+    Rbf32Block b;
+    b.A = b.B = w.Xw32;
+    b.nA = b.nB = w.nw;
+    b.m = b.ncap = kMaxWS;
+    b.lda = b.ldb = b.kdim = R.ld;
+    b.gate = gate;
+    b.ncount = &w.ctl->m;
+    b.ida = b.idb = w.W;
+    b.twin_nrow = tw;
+    b.gamma = S.p.gamma;
+    b.K = w.Kw;
+    b.ldk = kLdw;
+    return launch_rbf32_block(s, Rbf32Epilogue::store, b);
   }
   if (S.f64) {
     if (S.mode.twin())
@@ -2034,7 +2104,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
     stats[3] = int64_t(ms_since(S.t0) * 1000.0);
     stats[4] = fin.changed_total;
     stats[5] = S.k.inner_nt;
-    stats[6] = S.csr ? 2 : S.f64 ? 1 : 0;
+    stats[6] = S.f32 ? 3 : S.csr ? 2 : S.f64 ? 1 : 0;
     stats[7] = warm_cols;
     stats[8] = ps.unshrinks;
     stats[9] = fin.passes;
@@ -2067,7 +2137,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
 // updates f for its own points.  With world dividing 8 the trajectory is the one-GPU trajectory.
 // stats (kDecompStats = SVM_DECOMP_STATS int64, 13 written): outer iterations, inner iterations, working-set
 // capacity, solve microseconds, columns of the f updates (points moved, summed over the outer iterations),
-// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA, 2 sparse rows), warm-start columns,
+// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA, 2 sparse rows, 3 float32 rows), warm-start columns,
 // unshrinks, shrink passes, the fewest active rows, repacks, Newton polish steps.
 int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n, const svm_params& p,
                int qws, svm_result* r, int64_t* stats, const DecompOpts& o) {
@@ -2536,6 +2606,51 @@ SVM_API int svmd_train_decomp_csr(void* h, const int64_t* indptr_d, const int32_
   R.nrm = nrm_d;
   R.d = d;
   R.dpad = padded_dim(d);
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = ctx->begin())) return rc;
+  if ((rc = decomp_solve(ctx, R, kind == 0 ? y_d : nullptr, alpha_d, n, p, q, r, stats, o))) return rc;
+  if (timing) {
+    timing->gram_ms = 0.0;  // nothing is prepared here: the rows arrive scaled
+    timing->total_ms = timing->smo_ms = ms_since(t0);
+  }
+  return ctx->end();
+}
+
+// The solve on float32 rows (svm355_device.h): n rows of ld floats on the device, scaled and rounded once
+// (svmd_preprocess_f32) with the FP64 norms of the rounded values.  kind 0 / kind 1, alpha_d and the limits as
+// svmd_train_decomp_csr; the RBF kernel only.  Kernel values come from rows_f32.hip; no rows x 1024 block is stored.
+SVM_API int svmd_train_decomp_f32(void* h, const float* X_d, const double* nrm_d, int64_t n, int64_t ld, int64_t d,
+                                  int32_t kind, const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d,
+                                  const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
+                                  svm_decomp_trace* trace) {
+  const char* who = "svmd_train_decomp_f32";
+  SVMD_CTX(h);
+  if (!X_d || !nrm_d || n < 2 || d < 1 || ld < d || ld % 16 != 0 || (reinterpret_cast<uintptr_t>(X_d) & 15) ||
+      !alpha_d || (kind != 0 && kind != 1) || (kind == 0 ? !y_d : !z_d)) {
+    set_error("%s: bad arguments (ld a multiple of 16, rows 16-byte aligned)", who);
+    return SVM_ERR_ARG;
+  }
+  const svm_params p = params_or_default(pp);
+  DecompOpts o;
+  o.trace = trace;
+  if (kind == 1) {
+    o.mode.kind = DecompModeKind::twin;
+    o.mode.twin_z = z_d;
+    o.mode.twin_eps = epsilon;
+  }
+  DecompFeatures ft;
+  int rc = mode_features(o, p, &ft);
+  if (rc || (rc = f32_rows_check(who, o, ft, p)) ||
+      (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device)))
+    return rc;
+  if (!decomp_shape(o.mode.points(n), q > 0 ? q : 1024, 1).ok) {
+    set_error("%s: n = %lld is outside the solver's shapes", who, (long long)n);
+    return SVM_ERR_ARG;
+  }
+  DecompRows R;
+  R.X32 = X_d;
+  R.nrm = nrm_d;
+  R.ld = ld;
   const auto t0 = std::chrono::steady_clock::now();
   if ((rc = ctx->begin())) return rc;
   if ((rc = decomp_solve(ctx, R, kind == 0 ? y_d : nullptr, alpha_d, n, p, q, r, stats, o))) return rc;

@@ -307,6 +307,35 @@ SVM_API int svmd_train_decomp_csr(void* ctx, const int64_t* indptr_d, const int3
                                   const double* z_d, double epsilon, double* alpha_d, const svm_params* p, int32_t q,
                                   svm_result* r, svmd_timing* timing, int64_t* stats, svm_decomp_trace* trace);
 
+// ---- Float32 rows (csrc/hip/rows_f32.hip).  Rows stay float32 on the device (n x ld floats, ld a multiple of 16,
+// zero padded, 16-byte aligned); the dot product of a kernel value runs on FP32 MFMA and everything after it is FP64.
+// Host float32 rows (n x d, contiguous) -> device rows (n x ld).
+SVM_API int svmd_upload_rows_f32(void* ctx, const float* X_host, int64_t n, int64_t d, float* X_d, int64_t ld);
+// Column min / max of the float32 values into mn_d / mx_d (d doubles), then in place x' = float((double(x) - mn) /
+// (mx - mn)) -- FP64 subtract and divide, one rounding; a range below 1e-12 divides by 1 -- and sqn_d[i] = the FP64
+// sum of squares of row i's rounded values.
+SVM_API int svmd_preprocess_f32(void* ctx, float* X_d, int64_t n, int64_t d, int64_t ld, double* mn_d, double* mx_d,
+                                double* sqn_d);
+// The kernel block on caller-given rows (tests): A (m x lda) against B (1 <= nb <= 1024 rows, ldb), kdim floats per
+// row (a multiple of 16); norms are computed here.  Ids: A row i is training row ida_d[i] (null: row_off + i), B row
+// j is idb_d[j] (null: no id), an id k standing for k mod twin_nrow when that is > 0; equal rows get exactly 1.
+// epi 0: K_d (m x ldk) = the block.  epi 1 / 2: f_d[i] += sum_j coef_d[j] K_ij (2: also f_d[i + m]), the same bits on
+// every run.  count >= 0: a device-side column count; gate != 0: the launch is a no-op.
+SVM_API int svmd_rbf_block_f32(void* ctx, const float* A_d, int64_t m, int64_t lda, const float* B_d, int64_t nb,
+                               int64_t ldb, int64_t kdim, const int32_t* ida_d, int64_t row_off, const int32_t* idb_d,
+                               int64_t twin_nrow, double gamma, int32_t epi, int32_t count, int32_t gate, double* K_d,
+                               int64_t ldk, const double* coef_d, double* f_d);
+// Xs_d (k x ld doubles, written whole) = the rows ids_d[0 : k] widened to FP64, ns_d[k] their norms.
+SVM_API int svmd_rows_f32_dense(void* ctx, const float* X_d, const double* nrm_d, int64_t n, int64_t ld,
+                                const int64_t* ids_d, int64_t k, double* Xs_d, double* ns_d);
+// The decomposition solver on preprocessed float32 rows.  kind 0: the classifier over y_d (alpha_d: n doubles, out;
+// class weights allowed); kind 1: epsilon-SVR over z_d (alpha_d: 2n doubles, a then a*).  The RBF kernel, one GPU,
+// cold start; shrinking, the Newton polish and a forced column cache are SVM_ERR_ARG.  stats[6] = 3.
+SVM_API int svmd_train_decomp_f32(void* ctx, const float* X_d, const double* nrm_d, int64_t n, int64_t ld, int64_t d,
+                                  int32_t kind, const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d,
+                                  const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
+                                  svm_decomp_trace* trace);
+
 // dst[k] = src[idx[k]] rows (device gather), for SV compaction and cascade training-set assembly.
 SVM_API int svmd_gather_rows(void* ctx, const double* src_d, int64_t ld, const int64_t* idx_d,
                              int64_t k, double* dst_d);

@@ -41,13 +41,23 @@ class TrainRows:
         self.rows, self.mn, self.mx, self.mn_h, self.mx_h, self.sqn = rows, mn, mx, mn_h, mx_h, sqn
         self.d, self.device, self.upload_ms = d, device, upload_ms
 
+    @property
+    def f32(self) -> bool:
+        """float32 rows (``row_dtype="float32"``): scaled and rounded once on the device, FP64 norms."""
+        import torch
+
+        return self.rows.dtype == torch.float32
+
     @classmethod
-    def upload(cls, X: np.ndarray, device, scale: bool = True, widen: bool = False) -> "TrainRows":
+    def upload(cls, X: np.ndarray, device, scale: bool = True, widen: bool = False,
+               row_dtype: str = "float64") -> "TrainRows":
         """uint8 host rows stay bytes on the device (min / max from the bytes; no PyTorch kernel runs: a
         process's first one loads PyTorch's code objects, ~95 ms of a cold first fit,
         profiles/r3_cold_fit_probe.txt), unless ``widen``: then they cross PCIe as bytes and are widened there
         into the FP64 rows that float64 host rows become.  ``scale=False`` (FP64 rows only): unscaled rows and
-        their norms, through which a NaN / inf anywhere shows."""
+        their norms, through which a NaN / inf anywhere shows.  ``row_dtype="float32"``: the rows cross PCIe and
+        stay on the device as float32 (any dtype, uint8 too, cast on the host once), min-max scaled there by
+        ``float32((float64(x) - mn) / range)`` with the FP64 norms of the rounded values."""
         import torch
 
         from ..ops import device as D
@@ -55,7 +65,12 @@ class TrainRows:
         t0 = time.perf_counter()
         d = X.shape[1]
         mn = mx = mn_h = mx_h = sqn = None
-        if _is_u8(X) and not widen:
+        if row_dtype == "float32":
+            if not scale:
+                raise ValueError("float32 device rows are min-max scaled rows (scale=True)")
+            rows = D.upload_rows_f32(X, device)
+            mn, mx, sqn = D.minmax_scale_f32_(rows, d)
+        elif _is_u8(X) and not widen:
             if not scale:
                 raise ValueError("uint8 device rows are min-max scaled rows (scale=True)")
             rows = D.upload_u8(X, device)
@@ -95,6 +110,8 @@ class TrainRows:
         idx = self._index(idx)
         if self.sqn is None:
             return D.sv_rows_u8(self.rows, idx, self.mn, self.mx)
+        if self.f32:  # widened: a model keeps FP64 support vectors, so everything after the fit is the FP64 code
+            return D.rows_f32_dense(self.rows, self.sqn, idx)
         return self.take(idx), self.sqn[idx].contiguous()
 
     def model(self, support, coef, **extra) -> dict:
@@ -272,6 +289,34 @@ def scaled_cpu(X: np.ndarray, scale: bool = True):
     return X, None
 
 
+ROW_DTYPES = ("float64", "float32")
+
+
+def check_row_dtype(row_dtype: str) -> str:
+    if row_dtype not in ROW_DTYPES:
+        raise ValueError(f"row_dtype must be 'float64' (the default) or 'float32', got {row_dtype!r}")
+    return row_dtype
+
+
+def check_f32_rows(**off) -> None:
+    """What ``row_dtype="float32"`` does not cover raises here, before any device work: ``off`` maps each
+    unsupported option's description to whether it was asked for.  The solver's own limits are the native table's
+    (``fused_rows_check`` in decomp.hip, shared with sparse rows); these are the estimator-level options that would
+    route a fit elsewhere."""
+    for name, on in off.items():
+        if on:
+            raise ValueError(f"row_dtype='float32' is not supported with {name} (float32 rows run on the RBF "
+                             "decomposition solver from a cold start, min-max scaled)")
+
+
+def scaled_cpu_f32(X: np.ndarray):
+    """``row_dtype="float32"`` on the CPU, the host twin of the device's float32 rows: X rounded to float32, min / max
+    of those values, ``float32((float64(x) - mn) / range)`` (the scaler's FP64 arithmetic, one rounding), widened.
+    Returns (rows, scaler) as ``scaled_cpu``."""
+    Xs, sc = scaled_cpu(np.ascontiguousarray(X, dtype=np.float32).astype(np.float64), True)
+    return Xs.astype(np.float32).astype(np.float64), sc
+
+
 def platt_probability(z: np.ndarray) -> np.ndarray:
     """Platt's sigmoid of z = A f + B in its overflow-safe form, on the host: P(y = -1) and P(y = +1) =
     1 / (1 + exp(z)) stacked on a new last axis.  The one expression of ``SVC`` and ``OneVsOneSVC`` (numpy's
@@ -302,6 +347,7 @@ class KernelEstimator:
     lazily fetched host copy of the support vectors."""
 
     scaler_ = None
+    row_dtype = "float64"  # SVC / SVR take "float32" (rows_f32.hip); the other estimators keep the default
     _dev = None  # device-side model state (device_model's dict)
     _sv_host = None
 
@@ -328,7 +374,7 @@ class KernelEstimator:
         check_query_shape(X, self._n_features())
 
     def _scaled_cpu(self, X: np.ndarray) -> np.ndarray:
-        Xs, self.scaler_ = scaled_cpu(X, self.scale)
+        Xs, self.scaler_ = scaled_cpu_f32(X) if self.row_dtype == "float32" else scaled_cpu(X, self.scale)
         return Xs
 
     def _adopt_rows(self, rows: TrainRows) -> None:

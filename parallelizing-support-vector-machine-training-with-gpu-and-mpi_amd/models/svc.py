@@ -27,8 +27,9 @@ import numpy as np
 from ..utils.config import SVMParams, default_threads
 from ..utils.data import check_folds, check_warm_start, resolve_class_weight, stratified_folds
 from ..utils.sparse import is_sparse, toarray
-from ._device import (KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, check_dot_kernel,
-                      host_kernel_decision, platt_probability, scaled_cpu, solve_on_rows)
+from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
+                      check_f32_rows, check_row_dtype, host_kernel_decision, platt_probability, scaled_cpu,
+                      solve_on_rows)
 
 
 class SVC(KernelEstimator):
@@ -37,7 +38,11 @@ class SVC(KernelEstimator):
                  scale: bool = True, zero_is_positive: bool = False, gram: str = "auto", kcache: str = "auto",
                  wss: str = "first", solver: str = "auto", working_set: int = 1024, shrinking=False,
                  class_weight=None, probability: bool = False, cv: int = 5, cv_seed: int = 0, kernel: str = "rbf",
-                 degree: int = 3, coef0: float = 0.0):
+                 degree: int = 3, coef0: float = 0.0, row_dtype: str = "float64"):
+        # row_dtype="float32": the training rows cross PCIe and stay on the device as float32, scaled there and
+        # rounded once; kernel values come from FP32-MFMA dot products under an FP64 epilogue (rows_f32.hip) with no
+        # rows x 1024 block in HBM.  The model (FP64 support vectors) and everything after the fit are unchanged.
+        self.row_dtype = check_row_dtype(row_dtype)
         if wss not in ("first", "second"):
             raise ValueError("wss must be 'first' (the reference's selection) or 'second'")
         if solver not in ("auto", "smo", "decomp"):
@@ -103,8 +108,13 @@ class SVC(KernelEstimator):
                                                      f"gram={self.gram!r}": self.gram != "auto",
                                                      f"kcache={self.kcache!r}": self.kcache != "auto",
                                                      "scale=False": not self.scale}))
+        f32 = self.row_dtype == "float32"
+        if f32:
+            self._check_f32(dev, sparse, alpha0)
         if sparse:
             self._check_sparse(alpha0)
+        elif f32 and dev != "cpu":  # as it is when it is float32; any other dtype (uint8 exactly) cast once
+            X = np.ascontiguousarray(X, dtype=np.float32)
         else:  # uint8 pixel rows stay compact up to the device (8x less H2D; widened to FP64 there)
             X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         y = np.ascontiguousarray(y, dtype=np.int32)
@@ -134,12 +144,24 @@ class SVC(KernelEstimator):
                 self._fit_cuda_probability(X, y, folds, dev)
         elif dev == "cpu":
             self._fit_cpu(X, y, alpha0)
+        elif f32:
+            self._fit_cuda_f32(X, y, dev)
         elif sparse:
             self._fit_cuda_sparse(X, y, dev)
         else:
             self._fit_cuda(X, y, alpha0, dev)
         self.fit_time_ = time.perf_counter() - t0
         return self
+
+    def _check_f32(self, dev: str, sparse: bool = False, alpha0=None, cv: bool = False) -> None:
+        """What row_dtype='float32' does not cover raises here, before any device work."""
+        gpu = dev != "cpu"
+        check_f32_rows(**{"sparse (CSR) rows": sparse, "a warm start (alpha0)": alpha0 is not None,
+                          "shrinking": self.params._shrink_code() > 0, "probability=True": self.probability,
+                          "cross-validation": cv, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                          "scale=False": not self.scale, "wss='second'": self.params.wss == 2,
+                          "solver='smo'": gpu and self.solver == "smo", f"gram={self.gram!r}": gpu and self.gram != "auto",
+                          f"kcache={self.kcache!r}": gpu and self.kcache != "auto"})
 
     def _check_sparse(self, alpha0=None) -> None:
         """What a fit on CSR rows does not cover raises here, before any device work."""
@@ -293,6 +315,8 @@ class SVC(KernelEstimator):
         check_dot_kernel(self.params, cross_validation=True)
         if is_sparse(X):
             raise ValueError("cross-validation does not take sparse rows (densify them: X.toarray())")
+        if self.row_dtype == "float32":
+            self._check_f32(dev, cv=True)
         X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         y = np.ascontiguousarray(y, dtype=np.int32)
         if X.ndim != 2 or y.shape != (X.shape[0],):
@@ -438,6 +462,21 @@ class SVC(KernelEstimator):
         rows = SparseTrainRows.upload(X, device)
         alpha = torch.empty(rows.csr.n, dtype=torch.float64, device=device)  # the cold start zeroes it
         res, tm = D.train_decomp_csr(rows.csr, alpha, self.params, y=torch.from_numpy(y).to(device),
+                                     working_set=self.working_set)
+        self._finish(alpha.cpu().numpy(), y, res)
+        self._adopt_rows(rows)
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
+
+    def _fit_cuda_f32(self, X, y, dev):
+        """float32 rows: scaled and rounded once on the device, kernel values from the FP32-MFMA block."""
+        import torch
+
+        from ..ops import device as D
+
+        device = torch.device(dev)
+        rows = TrainRows.upload(X, device, row_dtype="float32")
+        alpha = torch.empty(X.shape[0], dtype=torch.float64, device=device)  # the cold start zeroes it
+        res, tm = D.train_decomp_f32(rows.rows, rows.sqn, rows.d, alpha, self.params, y=torch.from_numpy(y).to(device),
                                      working_set=self.working_set)
         self._finish(alpha.cpu().numpy(), y, res)
         self._adopt_rows(rows)

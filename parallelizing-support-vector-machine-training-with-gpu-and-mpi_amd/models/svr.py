@@ -22,8 +22,8 @@ import numpy as np
 
 from ..utils.config import SVMParams, default_threads
 from ..utils.sparse import is_sparse, toarray
-from ._device import (KernelEstimator, SparseTrainRows, _is_u8, _resolve_device, check_dot_kernel,
-                      host_kernel_decision, solve_on_rows)
+from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
+                      check_f32_rows, check_row_dtype, host_kernel_decision, solve_on_rows)
 
 KIND = "svr"  # model files' kind marker (model_io)
 
@@ -41,7 +41,8 @@ class SVR(KernelEstimator):
     def __init__(self, C: float = 10.0, gamma: float = 0.00125, epsilon: float = 0.1, tol: float = 1e-5,
                  eps: float = 1e-12, sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto",
                  n_threads: int = 0, scale: bool = True, working_set: int = 1024, kernel: str = "rbf", degree: int = 3,
-                 coef0: float = 0.0):
+                 coef0: float = 0.0, row_dtype: str = "float64"):
+        self.row_dtype = check_row_dtype(row_dtype)  # "float32": as SVC's (float32 device rows, rows_f32.hip)
         if not (np.isfinite(epsilon) and epsilon >= 0):
             raise ValueError(f"epsilon must be finite and >= 0, got {epsilon!r}")
         self.params = SVMParams(C=C, gamma=gamma, tau=tol, eps=eps, sv_tol=sv_tol, max_iter=max_iter,
@@ -59,7 +60,13 @@ class SVR(KernelEstimator):
         if sparse and dev == "cpu":
             X, sparse = toarray(X), False
         check_dot_kernel(self.params, sparse_rows=sparse)
-        if not sparse:
+        f32 = self.row_dtype == "float32"
+        if f32:  # what float32 rows do not cover, before any device work
+            check_f32_rows(**{"sparse (CSR) rows": sparse, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                              "scale=False": not self.scale})
+        if f32 and dev != "cpu":  # as it is when it is float32; any other dtype (uint8 exactly) cast once
+            X = np.ascontiguousarray(X, dtype=np.float32)
+        elif not sparse:
             X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         z = np.ascontiguousarray(z, dtype=np.float64)
         if len(X.shape) != 2 or z.shape != (X.shape[0],):
@@ -77,7 +84,9 @@ class SVR(KernelEstimator):
                                  "exact-integer plan, or the FP64 rows it solves on)")
             if X.shape[0] < 2:
                 raise ValueError("SVR on a GPU needs at least 2 rows")
-            if sparse:
+            if f32:
+                self._fit_cuda_f32(X, z, dev)
+            elif sparse:
                 self._fit_cuda_sparse(X, z, dev)
             else:
                 self._fit_cuda(X, z, dev)
@@ -140,6 +149,21 @@ class SVR(KernelEstimator):
         rows = SparseTrainRows.upload(X, device)
         alpha = torch.empty(2 * rows.csr.n, dtype=torch.float64, device=device)
         res, tm = D.train_decomp_csr(rows.csr, alpha, self.params, z=torch.from_numpy(z).to(device),
+                                     epsilon=self.epsilon, working_set=self.working_set)
+        self._finish(alpha.cpu().numpy(), res)
+        self._adopt_rows(rows)
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
+
+    def _fit_cuda_f32(self, X, z, dev):
+        """float32 rows: scaled and rounded once on the device, kernel values from the FP32-MFMA block."""
+        import torch
+
+        from ..ops import device as D
+
+        device = torch.device(dev)
+        rows = TrainRows.upload(X, device, row_dtype="float32")
+        alpha = torch.empty(2 * X.shape[0], dtype=torch.float64, device=device)
+        res, tm = D.train_decomp_f32(rows.rows, rows.sqn, rows.d, alpha, self.params, z=torch.from_numpy(z).to(device),
                                      epsilon=self.epsilon, working_set=self.working_set)
         self._finish(alpha.cpu().numpy(), res)
         self._adopt_rows(rows)

@@ -1065,3 +1065,116 @@ def train_decomp_csr(A: DeviceCSR, alpha: torch.Tensor, params: SVMParams, y: Op
                                       "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
                                       "working_set": int(st[2]), "update_columns": int(st[4]),
                                       "inner_threads": int(st[5])}
+
+
+# ---- float32 rows (rows_f32.hip) ----------------------------------------------------------------------------
+def _check_rows_f32(X: torch.Tensor, name: str = "X") -> None:
+    if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous() or X.shape[1] % 16:
+        raise ValueError(f"{name} must be a contiguous 2-D float32 tensor with a row length that is a multiple of 16, "
+                         f"got {X.dtype} {tuple(X.shape)}")
+
+
+def upload_rows_f32(X: np.ndarray, device) -> torch.Tensor:
+    """Host (n, d) rows -> device (n, padded_dim(d)) zero-padded float32 rows.  A float32 array crosses PCIe as it
+    is; any other dtype (uint8 included, exactly) is cast to float32 on the host once."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    n, d = X.shape
+    out = device_empty((n, padded_dim(d)), torch.float32, device)
+    ctx = DeviceContext.get(out.device)
+    N.check(ctx.lib.svmd_upload_rows_f32(ctx.bind(), N.ptr(X), n, d, N.ptr(out), out.shape[1]), "svmd_upload_rows_f32")
+    return out
+
+
+def minmax_scale_f32_(X: torch.Tensor, d: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """In-place min-max scaling of float32 rows by ``float32((float64(x) - mn) / range)`` (one rounding; a range below
+    1e-12 divides by 1); returns (min, max, FP64 squared norms of the rounded rows).  min and max are the halves of
+    one 2 d buffer, as ``minmax_scale_``'s."""
+    _check_rows_f32(X)
+    ctx = _ctx_for(X)
+    mm = torch.empty(2 * d, dtype=torch.float64, device=X.device)
+    sqn = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+    N.check(ctx.lib.svmd_preprocess_f32(ctx.bind(), N.ptr(X), X.shape[0], d, X.shape[1], N.ptr(mm[:d]), N.ptr(mm[d:]),
+                                        N.ptr(sqn)), "svmd_preprocess_f32")
+    return mm[:d], mm[d:], sqn
+
+
+def rbf_block_f32(A: torch.Tensor, B: torch.Tensor, gamma: float, epilogue: str = "store",
+                  coef: Optional[torch.Tensor] = None, f: Optional[torch.Tensor] = None, count: int = -1,
+                  gate: int = 0, ida: Optional[torch.Tensor] = None, idb: Optional[torch.Tensor] = None,
+                  row_off: int = 0, twin_nrow: int = 0) -> torch.Tensor:
+    """The float32 RBF block (svmd_rbf_block_f32) on padded float32 device rows A (m, ld) and B (nb <= 1024, ld).
+    "store": returns K (m, nb) float64.  "sum" / "sum_twin": f[i] += sum_j coef[j] K_ij in place (twin: also
+    f[i + m]) and returns f.  count >= 0: a device-side column count; gate != 0: a no-op.  ida / idb (int32): the
+    rows' training ids (A's default to row_off + i), taken modulo twin_nrow when that is > 0; equal ids give 1.0."""
+    _check_rows_f32(A, "A")
+    _check_rows_f32(B, "B")
+    if A.shape[1] != B.shape[1]:
+        raise ValueError("A and B row lengths differ")
+    epi = ("store", "sum", "sum_twin").index(epilogue)
+    m, nb = A.shape[0], B.shape[0]
+    for name, t, k in (("ida", ida, m), ("idb", idb, nb)):
+        if t is not None and (t.dtype != torch.int32 or t.shape != (k,) or not t.is_contiguous()):
+            raise ValueError(f"{name} must be contiguous int32 of shape ({k},)")
+    K = None
+    if epi == 0:
+        K = torch.zeros((m, nb), dtype=torch.float64, device=A.device)
+    elif (coef is None or f is None or coef.shape != (nb,) or f.shape != (m * epi,) or coef.dtype != torch.float64
+          or f.dtype != torch.float64 or not coef.is_contiguous() or not f.is_contiguous()):
+        raise ValueError(f"{epilogue}: coef ({nb},) and f ({m * epi},), contiguous float64")
+    ctx = _ctx_for(A)
+    N.check(ctx.lib.svmd_rbf_block_f32(ctx.bind(), N.ptr(A), m, A.shape[1], N.ptr(B), nb, B.shape[1], A.shape[1],
+                                       N.ptr(ida), int(row_off), N.ptr(idb), int(twin_nrow), float(gamma), epi,
+                                       int(count), int(gate), N.ptr(K), nb, N.ptr(coef), N.ptr(f)),
+            "svmd_rbf_block_f32")
+    return K if epi == 0 else f
+
+
+def rows_f32_dense(X: torch.Tensor, sqn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(Xs, ns): the float32 rows ``idx`` (int64, device) widened to padded FP64 rows (k, ld) and their norms."""
+    _check_rows_f32(X)
+    idx = idx.to(device=X.device, dtype=torch.int64).contiguous()
+    k, ld = idx.numel(), X.shape[1]
+    Xs = device_empty((k, ld), torch.float64, X.device)
+    ns = torch.empty(k, dtype=torch.float64, device=X.device)
+    if k:
+        ctx = _ctx_for(X)
+        N.check(ctx.lib.svmd_rows_f32_dense(ctx.bind(), N.ptr(X), N.ptr(sqn), X.shape[0], ld, N.ptr(idx), k, N.ptr(Xs),
+                                            N.ptr(ns)), "svmd_rows_f32_dense")
+    return Xs, ns
+
+
+def train_decomp_f32(X: torch.Tensor, sqn: torch.Tensor, d: int, alpha: torch.Tensor, params: SVMParams,
+                     y: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, epsilon: float = 0.1,
+                     working_set: int = 1024, trace: Optional["N.DecompTrace"] = None) -> Tuple[SMOResult, dict]:
+    """The decomposition solver on scaled float32 rows (svmd_train_decomp_f32): the classifier over the int32 labels
+    ``y`` (alpha: n, out) or epsilon-SVR over the float64 targets ``z`` (alpha: 2n, a then a*).  Kernel values come
+    from the FP32-MFMA block; the RBF, cold start, one GPU; shrinking and the Newton polish raise."""
+    _check_rows_f32(X)
+    n = X.shape[0]
+    if (y is None) == (z is None):
+        raise ValueError("train_decomp_f32 takes labels y or targets z")
+    t = y if z is None else z
+    want = n if z is None else 2 * n
+    if t.shape != (n,) or not t.is_contiguous() or t.dtype != (torch.int32 if z is None else torch.float64):
+        raise ValueError(f"y must be int32 / z float64, contiguous, of shape ({n},)")
+    if alpha.dtype != torch.float64 or alpha.shape != (want,) or not alpha.is_contiguous():
+        raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({want},)")
+    if sqn.dtype != torch.float64 or sqn.shape != (n,) or not sqn.is_contiguous():
+        raise ValueError(f"sqn must be a contiguous float64 tensor of shape ({n},)")
+    ctx = _ctx_for(X)
+    r, tm = N.SvmResult(), N.SvmdTiming()
+    st = (ctypes.c_int64 * 16)()
+    p = params.to_struct()
+    rc = ctx.lib.svmd_train_decomp_f32(ctx.bind(), N.ptr(X), N.ptr(sqn), n, X.shape[1], int(d), 0 if z is None else 1,
+                                       N.ptr(y), N.ptr(z), float(epsilon), N.ptr(alpha), ctypes.byref(p),
+                                       int(working_set), ctypes.byref(r), ctypes.byref(tm), st,
+                                       ctypes.byref(trace.struct) if trace is not None else None)
+    if rc == 2:  # SVM_ERR_ARG: a refusal (the native table next to csr_rows_check, decomp.hip) or a bad argument
+        raise ValueError(f"svmd_train_decomp_f32: {N.last_error()}")
+    N.check(rc, "svmd_train_decomp_f32")
+    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
+                                      "kcache": "none", "gram_path": "f32-mfma", "rows": "f32",
+                                      "solver": "decomp" if z is None else "decomp-svr",
+                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
+                                      "working_set": int(st[2]), "update_columns": int(st[4]),
+                                      "inner_threads": int(st[5])}
