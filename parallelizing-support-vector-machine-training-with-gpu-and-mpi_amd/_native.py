@@ -223,6 +223,13 @@ _CORE_SIGS = {
     "svm_decomp_train_gram_svr": (c_int32, [_P, c_int64, _P, c_int64, c_double, _P, POINTER(SvmParams), c_int32,
                                             c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
                                             POINTER(SvmDecompTrace)]),
+    "svm_smo_train_sw": (c_int32, [_P, _P, c_int64, c_int64, _P, _P, POINTER(SvmParams), POINTER(SvmResult)]),
+    "svm_decomp_train_gram_sw": (c_int32, [_P, c_int64, _P, c_int64, _P, _P, POINTER(SvmParams), c_int32, c_double,
+                                           c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
+                                           POINTER(SvmDecompTrace)]),
+    "svm_decomp_train_gram_svr_sw": (c_int32, [_P, c_int64, _P, c_int64, c_double, _P, _P, POINTER(SvmParams), c_int32,
+                                               c_double, c_int32, c_int32, POINTER(SvmResult), POINTER(c_int64),
+                                               POINTER(SvmDecompTrace)]),
     "svm_oneclass_start": (c_int32, [c_double, c_int64, POINTER(c_int64), POINTER(c_double)]),
     "svm_smo_train_oneclass": (c_int32, [_P, c_int64, c_int64, c_double, _P, POINTER(SvmParams), POINTER(SvmResult)]),
     "svm_decomp_train_gram_oneclass": (c_int32, [_P, c_int64, c_int64, c_double, _P, POINTER(SvmParams), c_int32,
@@ -342,6 +349,12 @@ _HIP_SIGS = {
     "svmd_train_decomp_svr": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, c_double, _P,
                                         POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                         POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
+    "svmd_train_decomp_sw": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P,
+                                       POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
+                                       POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
+    "svmd_train_decomp_svr_sw": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, _P, c_double, _P,
+                                           _P, POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
+                                           POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),
     "svmd_train_decomp_oneclass": (c_int32, [c_void_p, _P, c_int32, c_int64, c_int64, c_int64, _P, _P, c_double, _P,
                                              POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                              POINTER(c_int64), POINTER(c_int32), POINTER(SvmDecompTrace)]),

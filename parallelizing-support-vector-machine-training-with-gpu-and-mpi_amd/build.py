@@ -48,6 +48,7 @@ HIP_EXTRA: dict = {
     "decomp_nu.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "csr_rbf.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "decomp_kfun.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "decomp_box.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 CORE_SRCS = sorted((CSRC / "core").glob("*.cpp")) + sorted((CSRC / "cascade").glob("*.cpp"))

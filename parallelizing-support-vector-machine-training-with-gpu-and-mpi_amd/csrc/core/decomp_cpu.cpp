@@ -40,6 +40,10 @@
 //     larger class gap, the inner solve by LIBSVM's Solver_NU rule (nu_inner) -- from LIBSVM's start walk
 //     (nu_start_walk), and r and rho at the end (nu-SVC: alpha / r).  One rank, cold start, no shrinking, no Newton
 //     polish, no class weights.
+//   * sample weights (svm_decomp_train_gram_sw / _svr_sw; decomp_box.hip): a box per kernel row, (class box) * w, in
+//     the set membership of every selection and in the pair clip (DecompMode::sample_w; with it null every expression
+//     is the class-weight one).  The device runs inner_wss = 2 (ws_inner_box_kernel); the arm itself takes any rule.
+//     One rank, cold start, no shrinking, no Newton polish.
 // The kernel values themselves come from the caller (the device Gram on the exact-integer path).
 #include <chrono>
 #include <climits>
@@ -365,8 +369,10 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   if (const int rc = svm_class_boxes(&p, &Cp, &Cn)) return rc;
   const auto set = [](double w) { return w != 0.0 && w != 1.0; };
   const DecompFeatures asked = decomp_features(
-      p, world, warm != 0, mode.kind == DecompModeKind::classify ? Cp != Cn : set(p.weight_pos) || set(p.weight_neg));
+      p, world, warm != 0, mode.kind == DecompModeKind::classify ? Cp != Cn : set(p.weight_pos) || set(p.weight_neg),
+      mode.boxed());
   if (const int rc = decomp_mode_check(who, mode, y, asked, n, DecompBackend::cpu_oracle)) return rc;
+  if (const int rc = decomp_box_check(who, p, mode.kind, asked, false, false)) return rc;
   // a dot-product kernel (p.kernel != 0): K_ii comes from the Gram, the rule is the second-order single pair
   // (ws_inner_kfun_kernel) and the f update sums in the sum epilogue's order, whatever f64_rows says
   const bool kf = p.kernel != kKernelRbf;
@@ -378,6 +384,11 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   const auto f_sum = kf ? rowsum_update_kfun : f64_rows ? rowsum_update_f64 : gemv_update;
   const int64_t nr = n;  // kernel rows: point id's row is id mod nr (twin mode), id itself otherwise
   n = mode.points(nr);
+  // sample weights (ws_box_kernel): row k's box, the class box times the weight; twin mode has one class box
+  std::vector<double> box(mode.boxed() ? size_t(nr) : 0);
+  for (int64_t k = 0; k < int64_t(box.size()); ++k)
+    box[size_t(k)] = ((mode.twin() || y[k] == 1) ? Cp : Cn) * mode.sample_w[k];
+  const bool boxed = mode.boxed();
   // the solve's signs: the init kernels' analogue (ws_twin_init_kernel, ws_oneclass_init_kernel,
   // ws_heldout_init_kernel)
   std::vector<int32_t> sgn(mode.own_signs() ? size_t(n) : 0);
@@ -438,8 +449,11 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   WorkerTeam team(std::max<int32_t>(1, std::min<int32_t>(resolve_threads(p.n_threads), int32_t(n / 256) + 1)));
   const double C = p.C, eps = p.eps, tau = p.tau, chp = Cp - eps, chn = Cn - eps, c_lo = 0.0 + eps;
   const double inf = std::numeric_limits<double>::infinity();
-  auto in_high = [&](int32_t yi, double a) { return (yi == 1 && a < chp) || (yi == -1 && a > c_lo); };
-  auto in_low = [&](int32_t yi, double a) { return (yi == 1 && a > c_lo) || (yi == -1 && a < chn); };
+  // a point's box and its upper threshold: the class's (Cp / Cn, chp / chn), or its own with sample weights
+  auto box_of = [&](int64_t id, int32_t yi) { return boxed ? box[size_t(id % nr)] : (yi == 1 ? Cp : Cn); };
+  auto hi_of = [&](int64_t id, int32_t yi) { return boxed ? box[size_t(id % nr)] - eps : (yi == 1 ? chp : chn); };
+  auto in_high = [&](int32_t yi, double a, double ch) { return (yi == 1 && a < ch) || (yi == -1 && a > c_lo); };
+  auto in_low = [&](int32_t yi, double a, double ch) { return (yi == 1 && a > c_lo) || (yi == -1 && a < ch); };
 
   // ---- start: cold (alpha = 0, f = -y: ws_init_kernel) or warm (f = -y + K (alpha y) over the
   // nonzero alphas, ascending, in chunks of kMaxWS columns: decomp.hip's warm start); f of this
@@ -511,7 +525,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
   double nub[4] = {inf, inf, -inf, -inf};  // the nu modes' extremes {b_high +, b_high -, b_low +, b_low -}
   std::vector<Cand> cown(size_t(std::max<int64_t>(Lr, 1))), call(size_t(sh.L));
   std::vector<int32_t> W, Wr;  // the working set's point ids and their kernel rows (id mod nr)
-  std::vector<double> a, a0, ft, kh, kl;
+  std::vector<double> a, a0, ft, kh, kl, cw, hw;  // cw / hw: the working set's boxes and upper thresholds
   std::vector<int32_t> yw, cols, fcols;
   std::vector<double> coef, fcoef;
   if (tr) tr->count = 0;
@@ -537,12 +551,12 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
           int64_t mi = -1, xi = -1;
           for (int64_t i = b0; i < b1; ++i) {
             if (shr[size_t(i - lo)]) continue;
-            const double ai = alpha[i], fi = f[size_t(i - lo)];
-            if (!th[size_t(i - b0)] && in_high(y[i], ai) && fi < mv) {
+            const double ai = alpha[i], fi = f[size_t(i - lo)], ch = hi_of(i, y[i]);
+            if (!th[size_t(i - b0)] && in_high(y[i], ai, ch) && fi < mv) {
               mv = fi;
               mi = i;
             }
-            if (!tl[size_t(i - b0)] && in_low(y[i], ai) && fi > xv) {
+            if (!tl[size_t(i - b0)] && in_low(y[i], ai, ch) && fi > xv) {
               xv = fi;
               xi = i;
             }
@@ -629,9 +643,13 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
     a.assign(size_t(m), 0.0);
     yw.assign(size_t(m), 0);
     ft.assign(Wf.begin(), Wf.end());
+    cw.assign(size_t(m), 0.0);
+    hw.assign(size_t(m), 0.0);
     for (int k = 0; k < m; ++k) {
       a[size_t(k)] = alpha[W[size_t(k)]];
       yw[size_t(k)] = y[W[size_t(k)]];
+      cw[size_t(k)] = box_of(W[size_t(k)], yw[size_t(k)]);
+      hw[size_t(k)] = hi_of(W[size_t(k)], yw[size_t(k)]);
     }
     a0 = a;
     kh.assign(size_t(m), 0.0);
@@ -648,11 +666,11 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       double hv = inf, lv = -inf;
       int ih = -1, il = -1;
       for (int k = 0; k < m; ++k) {
-        if (in_high(yw[size_t(k)], a[size_t(k)]) && ft[size_t(k)] < hv) {
+        if (in_high(yw[size_t(k)], a[size_t(k)], hw[size_t(k)]) && ft[size_t(k)] < hv) {
           hv = ft[size_t(k)];
           ih = k;
         }
-        if (in_low(yw[size_t(k)], a[size_t(k)]) && ft[size_t(k)] > lv) {
+        if (in_low(yw[size_t(k)], a[size_t(k)], hw[size_t(k)]) && ft[size_t(k)] > lv) {
           lv = ft[size_t(k)];
           il = k;
         }
@@ -693,7 +711,8 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         const int wih = (ih % (2 * inner_threads)) / 128;
         double v2 = inf;
         for (int k = 0; k < m; ++k)
-          if ((k % (2 * inner_threads)) / 128 != wih && in_high(yw[size_t(k)], a[size_t(k)]) && ft[size_t(k)] < v2) {
+          if ((k % (2 * inner_threads)) / 128 != wih && in_high(yw[size_t(k)], a[size_t(k)], hw[size_t(k)]) &&
+              ft[size_t(k)] < v2) {
             v2 = ft[size_t(k)];
             i2 = k;
           }
@@ -705,7 +724,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
           const double h2 = ft[size_t(i2)];
           double gv2 = inf;
           for (int k = 0; k < m; ++k) {
-            if (!in_low(yw[size_t(k)], a[size_t(k)]) || !(ft[size_t(k)] > h2)) continue;
+            if (!in_low(yw[size_t(k)], a[size_t(k)], hw[size_t(k)]) || !(ft[size_t(k)] > h2)) continue;
             const double bb = ft[size_t(k)] - h2;
             double at = 2.0 - 2.0 * K2[Wr[size_t(k)]];
             at = at <= 0.0 ? eps : at;
@@ -725,7 +744,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         double gv = inf;
         int gj = -1;
         for (int k = 0; k < m; ++k) {
-          if (!in_low(yw[size_t(k)], a[size_t(k)]) || !(ft[size_t(k)] > hv)) continue;
+          if (!in_low(yw[size_t(k)], a[size_t(k)], hw[size_t(k)]) || !(ft[size_t(k)] > hv)) continue;
           const double bb = ft[size_t(k)] - hv;
           double at = kf ? Kii + K[int64_t(Wr[size_t(k)]) * (ldk + 1)] - 2.0 * kh[size_t(k)]
                          : 2.0 - 2.0 * kh[size_t(k)];
@@ -750,7 +769,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
       const int32_t yh = yw[size_t(ih)], yl = yw[size_t(il)];
       const int s = yh * yl;
       double eta = kf ? Kii + Kj[Wr[size_t(il)]] - 2.0 * K12 : 1.0 + 1.0 - 2.0 * K12;
-      const double Ch = yh == 1 ? Cp : Cn, Cl = yl == 1 ? Cp : Cn;
+      const double Ch = cw[size_t(ih)], Cl = cw[size_t(il)];
       double U, V;
       if (s == -1) {
         U = std::fmax(0.0, al - ah);
@@ -790,7 +809,7 @@ int decomp_solve(const double* K, int64_t ldk, const int32_t* y, int64_t n, doub
         const int32_t yh2 = yw[size_t(i2)], yl2 = yw[size_t(j2)];
         const int s2 = yh2 * yl2;
         const double eta2 = 1.0 + 1.0 - 2.0 * K[int64_t(Wr[size_t(i2)]) * ldk + Wr[size_t(j2)]];
-        const double Ch2 = yh2 == 1 ? Cp : Cn, Cl2 = yl2 == 1 ? Cp : Cn;
+        const double Ch2 = cw[size_t(i2)], Cl2 = cw[size_t(j2)];
         double U2, V2;
         if (s2 == -1) {
           U2 = std::fmax(0.0, a2l - a2h);
@@ -967,6 +986,39 @@ extern "C" SVM_API int svm_decomp_train_gram_svr(const double* K, int64_t ldk, c
   mode.kind = DecompModeKind::twin;
   mode.twin_z = z;
   mode.twin_eps = epsilon;
+  return decomp_solve(K, ldk, nullptr, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
+                      nullptr, mode, f64_rows != 0);
+}
+
+// svm_decomp_train_gram_rows and svm_decomp_train_gram_svr with sample weights (svm355.h): a box per kernel row.
+extern "C" SVM_API int svm_decomp_train_gram_sw(const double* K, int64_t ldk, const int32_t* y, int64_t n,
+                                                const double* w, double* alpha, const svm_params* pp, int32_t qws,
+                                                double tau_frac, int32_t inner_wss, int32_t f64_rows, svm_result* res,
+                                                int64_t* stats, svm_decomp_trace* tr) {
+  if (!w) {
+    set_error("svm_decomp_train_gram_sw: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  DecompMode mode;
+  mode.sample_w = w;
+  return decomp_solve(K, ldk, y, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr, nullptr,
+                      mode, f64_rows != 0);
+}
+
+extern "C" SVM_API int svm_decomp_train_gram_svr_sw(const double* K, int64_t ldk, const double* z, int64_t n,
+                                                    double epsilon, const double* w, double* alpha,
+                                                    const svm_params* pp, int32_t qws, double tau_frac,
+                                                    int32_t inner_wss, int32_t f64_rows, svm_result* res,
+                                                    int64_t* stats, svm_decomp_trace* tr) {
+  if (!w) {
+    set_error("svm_decomp_train_gram_svr_sw: bad arguments");
+    return SVM_ERR_ARG;
+  }
+  DecompMode mode;
+  mode.kind = DecompModeKind::twin;
+  mode.twin_z = z;
+  mode.twin_eps = epsilon;
+  mode.sample_w = w;
   return decomp_solve(K, ldk, nullptr, n, alpha, 0, params_or_default(pp), qws, tau_frac, inner_wss, res, stats, tr,
                       nullptr, mode, f64_rows != 0);
 }

@@ -66,7 +66,8 @@ template <class Rows>
 int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int32_t warm,
               const svm_params* pp, svm_result* res, int64_t* trace, int64_t trace_cap,
               const double* f0 = nullptr,  // f0: a cold start's f instead of -y (a linear term: epsilon-SVR)
-              bool no_linear = false) {    // a warm start's f without the -y term (p = 0: one-class)
+              bool no_linear = false,      // a warm start's f without the -y term (p = 0: one-class)
+              const double* sw = nullptr) {  // sample weights: row i's box is (its class box) * sw[i]
   svm_params p;
   if (pp)
     p = *pp;
@@ -87,6 +88,12 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
   WorkerTeam team(nt);
   const double eps = p.eps, tau = p.tau, chp = Cp - eps, chn = Cn - eps;
   std::vector<double> f(size_t(n), 0.0);
+  // the per-point box arm: with sw null every expression below is the class-weight one (box_of / hi_of return the
+  // class's Cp / Cn and chp / chn themselves)
+  std::vector<double> box(sw ? size_t(n) : 0);
+  for (size_t i = 0; i < box.size(); ++i) box[i] = (y[i] == 1 ? Cp : Cn) * sw[i];
+  auto box_of = [&](int64_t i) { return sw ? box[size_t(i)] : (y[i] == 1 ? Cp : Cn); };
+  auto hi_of = [&](int64_t i) { return sw ? box[size_t(i)] - eps : (y[i] == 1 ? chp : chn); };
 
   if (!warm) {
     for (int64_t i = 0; i < n; ++i) alpha[i] = 0.0;
@@ -124,8 +131,9 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
       Pick l{-std::numeric_limits<double>::infinity(), n};
       for (int64_t i = lo; i < hi; ++i) {
         const double a = alpha[i], fi = f[size_t(i)];
-        const bool in_high = (y[i] == 1 && a < chp) || (y[i] == -1 && a > 0.0 + eps);
-        const bool in_low = (y[i] == 1 && a > 0.0 + eps) || (y[i] == -1 && a < chn);
+        const double ch = hi_of(i);
+        const bool in_high = (y[i] == 1 && a < ch) || (y[i] == -1 && a > 0.0 + eps);
+        const bool in_low = (y[i] == 1 && a > 0.0 + eps) || (y[i] == -1 && a < ch);
         if (in_high && fi < h.v) h = {fi, i};
         if (in_low && fi > l.v) l = {fi, i};
       }
@@ -169,7 +177,7 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
         Pick g{std::numeric_limits<double>::infinity(), n};
         for (int64_t t = lo; t < hi; ++t) {
           const double a = alpha[t], ft = f[size_t(t)];
-          const bool in_low = (y[t] == 1 && a > 0.0 + eps) || (y[t] == -1 && a < chn);
+          const bool in_low = (y[t] == 1 && a > 0.0 + eps) || (y[t] == -1 && a < hi_of(t));
           if (!in_low || !(ft > b_high)) continue;
           const double bb = ft - b_high;
           double at = K11 + 1.0 - 2.0 * Kh[size_t(t)];
@@ -203,7 +211,7 @@ int smo_solve(const Rows& rows, const int32_t* y, int64_t n, double* alpha, int3
     const double K12 = Kh[size_t(i_low_upd)];
     const double eta = K11 + K22 - 2.0 * K12;
     const double ah = alpha[i_high], al = alpha[i_low_upd];
-    const double Ch = y[i_high] == 1 ? Cp : Cn, Cl = y[i_low_upd] == 1 ? Cp : Cn;
+    const double Ch = box_of(i_high), Cl = box_of(i_low_upd);
     double U, V;
     if (s == -1) {
       U = std::max(0.0, al - ah);
@@ -292,6 +300,21 @@ SVM_API int svm_smo_train_gram(const double* K, int64_t ldk, const int32_t* y, i
   }
   GramRows rows{K, ldk};
   return smo_solve(rows, y, n, alpha, warm, p, r, trace, trace_cap);
+}
+
+// svm_smo_train from a cold start with sample weights (svm355.h): row i's box is (C w_class(y_i)) w[i].
+SVM_API int svm_smo_train_sw(const double* X, const int32_t* y, int64_t n, int64_t d, const double* w, double* alpha,
+                             const svm_params* p, svm_result* r) {
+  if (!X || d <= 0 || !w) {
+    set_error("svm_smo_train_sw: bad X / d / w");
+    return SVM_ERR_ARG;
+  }
+  if (p && p->kernel != 0) {
+    set_error("svm_smo_train_sw: sample weights do not support a dot-product kernel (the RBF only)");
+    return SVM_ERR_ARG;
+  }
+  XRows rows{X, d, p ? p->gamma : 0.00125};
+  return smo_solve(rows, y, n, alpha, 0, p, r, nullptr, 0, nullptr, false, w);
 }
 
 // epsilon-SVR on the pairwise solver (the small-n oracle): the 2n-variable problem on duplicated rows -- row k

@@ -1151,6 +1151,7 @@ struct DecompWs {
   CsrPanel panel() const { return CsrPanel{PT, kMaxWS, nP, pprev, pcnt}; }
   // float32 rows: the working set's and the moved columns' rows gathered (kMaxWS x ld floats each; norms: nw, nc)
   float *Xw32 = nullptr, *Xc32 = nullptr;
+  double* box = nullptr;  // sample weights: the kernel rows' boxes (ws_box_kernel)
 };
 
 // The f update's kernel columns K(this GPU's rows, j) kept in HBM (size_col_cache); slab null: no cache.
@@ -1347,6 +1348,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
     w.nw = c.take<double>(kMaxWS);
     w.nc = c.take<double>(kMaxWS);
   }
+  w.box = c.take<double>(nr1, S.mode.boxed());
 }
 
 // The knob values a dot-product kernel's solve refuses (docs/KNOBS.md): its inner solve is one kernel, 256 threads
@@ -1365,12 +1367,28 @@ int kfun_knobs_check(const char* who, const svm_params& p) {
   return SVM_ERR_ARG;
 }
 
+// The knob values a solve with sample weights refuses (docs/KNOBS.md): its inner solve is one kernel, 256 threads x 4
+// points with SVM355_DECOMP_WSS=2's rule, and its selection is the register-resident one.  Reads the environment only.
+int box_knobs_check(const char* who, const DecompMode& m) {
+  if (!m.boxed()) return SVM_OK;
+  const char* wss = getenv("SVM355_DECOMP_WSS");
+  const char* nt = getenv("SVM355_DECOMP_NT");
+  const char* ws = getenv("SVM355_DECOMP_WIDE_SELECT");
+  const char* what = wss && atoi(wss) != 2  ? "SVM355_DECOMP_WSS other than 2 (its inner solve is the second-order single pair)"
+                     : nt && atoi(nt) != 256 ? "SVM355_DECOMP_NT other than 256"
+                     : ws && atoi(ws) == 1   ? "the streamed selection (SVM355_DECOMP_WIDE_SELECT=1)"
+                                             : nullptr;
+  if (!what) return SVM_OK;
+  set_error("%s: sample weights do not support %s", who, what);
+  return SVM_ERR_ARG;
+}
+
 // What the solve is asked to run with (decomp_mode.h); the class weights' range check comes with the boxes.
 int mode_features(const DecompOpts& o, const svm_params& p, DecompFeatures* f) {
   double cp = 0.0, cn = 0.0;
   if (const int rc = svm_class_boxes(&p, &cp, &cn)) return rc;
   const bool classify = o.mode.kind == DecompModeKind::classify;
-  *f = decomp_features(p, o.world, o.warm, classify ? cp != cn : cp != p.C || cn != p.C);
+  *f = decomp_features(p, o.world, o.warm, classify ? cp != cn : cp != p.C || cn != p.C, o.mode.boxed());
   return SVM_OK;
 }
 
@@ -1414,6 +1432,9 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   if (rc || (rc = decomp_mode_check("decomposition SMO", o.mode, y, ft, nrow, DecompBackend::device))) return rc;
   if ((rc = decomp_kfun_check("decomposition SMO", p, o.mode.kind, ft, R.csr())) || (rc = kfun_knobs_check("decomposition SMO", p)))
     return rc;
+  if ((rc = decomp_box_check("decomposition SMO", p, o.mode.kind, ft, R.csr(), R.f32())) ||
+      (rc = box_knobs_check("decomposition SMO", o.mode)))
+    return rc;
   n = o.mode.points(nrow);
   svm_params p1 = p;  // the solve's parameters (one-class mode: the box is 1 whatever p.C says)
   int64_t oc_full = 0;
@@ -1451,6 +1472,11 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   if (!sh.ok) {
     set_error("decomposition SMO: n = %lld is outside the solver's shapes (2 <= n < 2^31 - 1, %lld candidates <= %d, "
               "world <= 64)", (long long)n, (long long)sh.L, kMaxWS);
+    return SVM_ERR_ARG;
+  }
+  if (o.mode.boxed() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64)) {  // ws_select_box_kernel's block
+    set_error("decomposition SMO: sample weights take at most %lld points (%lld here): a selection block of at most "
+              "%d points", (long long)(int64_t(kMaxWS / 2) * kSelNT * kSelE), (long long)n, kSelNT * kSelE);
     return SVM_ERR_ARG;
   }
   if ((rc = read_knobs(sh, &S.k))) return rc;
@@ -1494,7 +1520,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   if (o.mode.kind == DecompModeKind::nu_twin)
     nu_start_walk(p1.C * o.mode.nu * double(nrow) / 2.0, p1.C, nrow, &S.nu_full, &S.nu_frac);
   S.nchunks = (n + kMaxWS - 1) / kMaxWS;
-  S.wide_select = !o.mode.nu_pairs() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select);
+  S.wide_select = !o.mode.nu_pairs() && !o.mode.boxed() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select);
   S.kww_narrow = !f64 && !csr && !f32 && !S.k.kww_sym && S.kq <= 1536;
   S.shc = shrink_cfg(p);
   S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
@@ -1751,6 +1777,10 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
       break;
   }
   SVMD_LAUNCH_CHECK();
+  if (S.mode.boxed()) {  // the boxes, once per fit (twin mode: no labels, one class box)
+    launch_ws_box(s, S.mode.twin() ? nullptr : S.y_in, S.mode.sample_w, S.nrow, S.Cp, S.Cn, w.box);
+    SVMD_LAUNCH_CHECK();
+  }
   if (S.mode.chunked_start(warm) && (rc = nz_update(S, ps, warm_cols))) return rc;
   return SVM_OK;
 }
@@ -1998,7 +2028,10 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
     ++ps.o_dev;
     return solo.end(1);
   }
-  if (NBr > 0)
+  if (S.mode.boxed())  // one GPU, no packed rows: decomp_box.hip's selection with a box per point
+    launch_ws_select_box(s, BoxSelectArgs{w.f, S.alpha, S.y, w.box, S.n, S.nrow, S.sh.per, int(NBr), T, p.eps, w.own,
+                                          w.own + NBr * T, w.ctl});
+  else if (NBr > 0)
     hipLaunchKernelGGL(S.wide_select ? ws_select_wide_kernel : ws_select_kernel, dim3(unsigned(NBr)), dim3(kSelNT), 0, s,
                        w.f, S.alpha, S.y, lo, nloc, S.sh.per, T, S.Cp, S.Cn, p.eps, w.own, w.own + NBr * T, w.ctl, act,
                        packed ? w.boff[ps.pk] : nullptr, w.shr);
@@ -2014,7 +2047,9 @@ int enqueue_outer(const Solve& S, PackState& ps, SoloTimer& solo, int64_t index,
   const InnerArgs ia{w.Kw, kLdw, w.W, w.ctl, S.y, S.alpha, w.Wf, S.Cp, p.eps, w.cols, w.coef, w.mcount,
                      S.hs, pub, packed ? w.pos_of : nullptr, lo, nloc, packed ? w.cdiag : nullptr,
                      w.gAw, w.Wf, w.nAmat, S.nwd, S.Cn};
-  if (S.kfun)
+  if (S.mode.boxed())
+    launch_ws_inner_box(s, ia, w.box, S.nrow);
+  else if (S.kfun)
     launch_ws_inner_kfun(s, ia);
   else if ((rc = launch_ws_inner(s, S.inner, ia)))
     return rc;
@@ -2404,7 +2439,8 @@ int train_decomp(DeviceCtx* ctx, const char* who, const void* X_d, bool is_u8, i
   DecompFeatures ft;
   int rc = mode_features(o, p, &ft);
   if (rc || (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device)) ||
-      (rc = decomp_kfun_check(who, p, o.mode.kind, ft, false)) || (rc = kfun_knobs_check(who, p)))
+      (rc = decomp_kfun_check(who, p, o.mode.kind, ft, false)) || (rc = kfun_knobs_check(who, p)) ||
+      (rc = decomp_box_check(who, p, o.mode.kind, ft, false, false)) || (rc = box_knobs_check(who, o.mode)))
     return rc;
   if (p.kernel != kKernelRbf && is_u8) {
     set_error("%s: the dot-product kernels take FP64 rows (widen and scale the uint8 rows on the device first)", who);
@@ -2511,6 +2547,32 @@ SVM_API int svmd_train_decomp_svr(void* h, const void* X_d, int32_t is_u8, int64
   o.mode.twin_z = z_d;
   o.mode.twin_eps = epsilon;
   return train_decomp_entry("svmd_train_decomp_svr", h, X_d, is_u8, n, ld, d, mn_h, mx_h, z_d != nullptr, nullptr,
+                            alpha_d, pp, q, o, r, timing, stats, used_out, trace);
+}
+
+// svmd_train_decomp and svmd_train_decomp_svr with sample weights (svm355_device.h): w_d = n FP64 weights >= 0 on the
+// device, one per row; row i's box is (C w_class(y_i)) w_i (the regression solve: C w_k for both points of row k).
+// Cold start, one GPU, the RBF kernel; the kernels of the selection and the inner solve are decomp_box.hip's.
+SVM_API int svmd_train_decomp_sw(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                 const double* mn_h, const double* mx_h, const int32_t* y_d, const double* w_d,
+                                 double* alpha_d, const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
+                                 int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
+  DecompOpts o;
+  o.mode.sample_w = w_d;
+  return train_decomp_entry("svmd_train_decomp_sw", h, X_d, is_u8, n, ld, d, mn_h, mx_h, y_d && w_d, y_d, alpha_d, pp, q,
+                            o, r, timing, stats, used_out, trace);
+}
+
+SVM_API int svmd_train_decomp_svr_sw(void* h, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                     const double* mn_h, const double* mx_h, const double* z_d, double epsilon,
+                                     const double* w_d, double* alpha_d, const svm_params* pp, int32_t q, svm_result* r,
+                                     svmd_timing* timing, int64_t* stats, int32_t* used_out, svm_decomp_trace* trace) {
+  DecompOpts o;
+  o.mode.kind = DecompModeKind::twin;
+  o.mode.twin_z = z_d;
+  o.mode.twin_eps = epsilon;
+  o.mode.sample_w = w_d;
+  return train_decomp_entry("svmd_train_decomp_svr_sw", h, X_d, is_u8, n, ld, d, mn_h, mx_h, z_d && w_d, nullptr,
                             alpha_d, pp, q, o, r, timing, stats, used_out, trace);
 }
 

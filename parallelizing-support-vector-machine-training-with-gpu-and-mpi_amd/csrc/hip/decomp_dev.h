@@ -147,4 +147,24 @@ void launch_ws_nu_start_twin(hipStream_t s, const NuArgs& a, double* f, const do
 // with `rescale` and r > 0, alpha_i /= r over the n points.
 void launch_ws_nu_finish(hipStream_t s, const NuArgs& a, int rescale, double* out);
 
+// ---- a box per point (decomp_box.hip): sample weights for the classifier and the regression (twin) solve ---------
+// box[k] = (y && y[k] != 1 ? Cn : Cp) * w[k] over the nrow kernel rows (twin mode: y = nullptr, every box Cp w[k]).
+void launch_ws_box(hipStream_t s, const int32_t* y, const double* w, int64_t nrow, double Cp, double Cn, double* box);
+// ws_select_box_kernel's arguments: n points in NB blocks of per <= kSelNT x kSelE, T <= 64 picks per side and block
+// (the caller has checked both); point k's box is box[k mod nrow]; y: the solve's signs.
+struct BoxSelectArgs {
+  const double *f, *alpha;
+  const int32_t* y;
+  const double* box;
+  int64_t n, nrow, per;
+  int NB, T;
+  double eps;
+  CandRec *cand_h, *cand_l;
+  const DecompCtl* ctl;
+};
+void launch_ws_select_box(hipStream_t s, const BoxSelectArgs& a);
+// One inner solve (256 threads x 4 points, the second-order single pair).  Of `a` it reads Kw, ldw, W, ctl, y (the
+// signs), alpha, Wf, eps, cols, coef, mcount and pub.
+void launch_ws_inner_box(hipStream_t s, const InnerArgs& a, const double* box, int64_t nrow);
+
 }  // namespace svm355

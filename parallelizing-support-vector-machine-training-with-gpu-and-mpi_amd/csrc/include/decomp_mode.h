@@ -50,6 +50,12 @@ struct DecompMode {
   double* nu_out = nullptr;
   const uint8_t* heldout = nullptr;
   double* heldout_out = nullptr;
+  // sample weights (classify and twin only): one weight >= 0 per kernel row, on the device for the device solver.
+  // Row k's box is (C w_class(y_k)) w_k -- the class box of svm_class_boxes times the weight, in that order -- and in
+  // twin mode both points of row k have it.  A weight of 0 freezes the point at alpha = 0 (it is on neither side
+  // of any selection) while its f still collects every update.  The device's kernels are decomp_box.hip's.
+  const double* sample_w = nullptr;
+  bool boxed() const { return sample_w != nullptr; }
   bool twin() const { return kind == DecompModeKind::twin || kind == DecompModeKind::nu_twin; }
   // the same-sign-pair modes: four candidate lists, two gaps, decomp_nu.hip's select / build / inner kernels
   bool nu_pairs() const { return kind == DecompModeKind::nu_classify || kind == DecompModeKind::nu_twin; }
@@ -67,9 +73,10 @@ struct DecompMode {
 // C); for the other kinds, any class weight is set.
 struct DecompFeatures {
   bool distributed = false, warm = false, shrinking = false, newton = false, weighted = false;
+  bool boxed = false;  // sample weights: a box per point (DecompMode::sample_w)
 };
-inline DecompFeatures decomp_features(const svm_params& p, int world, bool warm, bool weighted) {
-  return {world != 1, warm, shrink_cfg(p).on, newton_cfg(p).on, weighted};
+inline DecompFeatures decomp_features(const svm_params& p, int world, bool warm, bool weighted, bool boxed = false) {
+  return {world != 1, warm, shrink_cfg(p).on, newton_cfg(p).on, weighted, boxed};
 }
 
 // What each kind refuses, per backend {device, CPU oracle}: distributed, warm, shrinking, newton, weighted.
@@ -116,6 +123,32 @@ inline int decomp_kfun_check(const char* who, const svm_params& p, DecompModeKin
                                                       : nullptr;
   if (!what) return SVM_OK;
   set_error("%s: the %s kernel does not support %s", who, name[p.kernel], what);
+  return SVM_ERR_ARG;
+}
+
+// Sample weights (a box per point; hip/decomp_box.hip): the kinds that run with them (the classifier, class weights
+// included, and the regression (twin) solve) and what such a solve refuses whatever its kind, on both backends: one
+// GPU, a cold start, no shrinking, no polish -- and the RBF kernel on dense uint8 or FP64 rows only.
+constexpr bool kDecompBoxKinds[6] = {true, true, false, false, false, false};
+constexpr DecompFeatures kDecompBoxRefuses = {true, true, true, true, false};
+
+// Everything a solve with sample weights does not cover (csr / f32: the row source): SVM_ERR_ARG with `who` as the
+// message's prefix, before the caller does any work.  SVM_OK at once without weights.
+inline int decomp_box_check(const char* who, const svm_params& p, DecompModeKind kind, const DecompFeatures& f, bool csr,
+                            bool f32) {
+  if (!f.boxed) return SVM_OK;
+  const DecompFeatures& r = kDecompBoxRefuses;
+  const char* what = !kDecompBoxKinds[int(kind)] ? "this mode (the classifier and the regression (twin) solve only)"
+                     : p.kernel != kKernelRbf     ? "a dot-product kernel (the RBF only)"
+                     : csr                        ? "sparse (CSR) rows"
+                     : f32                        ? "float32 rows"
+                     : f.distributed && r.distributed ? "the distributed solve (world > 1)"
+                     : f.warm && r.warm               ? "a warm start"
+                     : f.shrinking && r.shrinking     ? "shrinking"
+                     : f.newton && r.newton           ? "the Newton polish (SVM355_DECOMP_NEWTON)"
+                                                      : nullptr;
+  if (!what) return SVM_OK;
+  set_error("%s: sample weights do not support %s", who, what);
   return SVM_ERR_ARG;
 }
 

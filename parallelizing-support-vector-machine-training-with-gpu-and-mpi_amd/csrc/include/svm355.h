@@ -192,6 +192,20 @@ SVM_API int svm_decomp_train_gram_svr(const double* K, int64_t ldk, const double
                                       double* alpha, const svm_params* p, int32_t q, double tau_frac,
                                       int32_t inner_wss, int32_t f64_rows, svm_result* r, int64_t* stats,
                                       svm_decomp_trace* trace);
+// Sample weights: w = n weights >= 0 (the caller validates them), row i's box (C w_class(y_i)) w_i -- the class box of
+// svm_class_boxes times the weight -- in the set membership of every selection and in the pair clip; a weight of 0
+// keeps alpha_i = 0.  The pairwise oracle on rows (cold start), and the decomposition oracle's classifier and twin
+// forms from a cold start (the device's trajectory with svmd_train_decomp_sw / _svr_sw at inner_wss = 2; twin: both
+// points of row k have the box C w_k).  One rank, no shrinking, no Newton polish, the RBF's unit diagonal.
+SVM_API int svm_smo_train_sw(const double* X, const int32_t* y, int64_t n, int64_t d, const double* w, double* alpha,
+                             const svm_params* p, svm_result* r);
+SVM_API int svm_decomp_train_gram_sw(const double* K, int64_t ldk, const int32_t* y, int64_t n, const double* w,
+                                     double* alpha, const svm_params* p, int32_t q, double tau_frac, int32_t inner_wss,
+                                     int32_t f64_rows, svm_result* r, int64_t* stats, svm_decomp_trace* trace);
+SVM_API int svm_decomp_train_gram_svr_sw(const double* K, int64_t ldk, const double* z, int64_t n, double epsilon,
+                                         const double* w, double* alpha, const svm_params* p, int32_t q, double tau_frac,
+                                         int32_t inner_wss, int32_t f64_rows, svm_result* r, int64_t* stats,
+                                         svm_decomp_trace* trace);
 // The twin mode's moved-column fold alone (tests): cnt <= 1024 virtual ids in [0, 2n) with their coefficients
 // become one entry per kernel row, at the position of the row's first occurrence; where both twins are listed
 // the coefficient is coef_k + coef_{k+n}.  out_cols / out_coef: room for cnt entries; *out_cnt: entries written.

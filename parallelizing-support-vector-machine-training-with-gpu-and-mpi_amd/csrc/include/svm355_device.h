@@ -80,6 +80,21 @@ SVM_API int svmd_train_decomp_svr(void* ctx, const void* X_d, int32_t is_u8, int
                                   const double* mn_h, const double* mx_h, const double* z_d, double epsilon,
                                   double* alpha_d, const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
                                   int64_t* stats, int32_t* used, svm_decomp_trace* trace);
+// Sample weights (a box per point; hip/decomp_box.hip): svmd_train_decomp from a cold start and svmd_train_decomp_svr
+// with w_d, n FP64 weights >= 0 on the device, one per row.  Row i's box is (C w_class(y_i)) w_i -- the class box of
+// svm_class_boxes times the weight; the regression solve: C w_k for both points of row k.  A weight of 0 keeps the
+// point at alpha = 0 exactly.  Selection and the inner solve (256 threads x 4 points, the second-order single pair)
+// are kernels of their own; everything else in an outer iteration is the unweighted solve's.  One GPU, the RBF kernel,
+// uint8 or FP64 rows; shrinking, the Newton polish, SVM355_DECOMP_WSS other than 2, SVM355_DECOMP_NT other than 256 and
+// more than 2,097,152 points are SVM_ERR_ARG naming the combination (decomp_mode.h).  The caller validates the weights.
+SVM_API int svmd_train_decomp_sw(void* ctx, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                 const double* mn_h, const double* mx_h, const int32_t* y_d, const double* w_d,
+                                 double* alpha_d, const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
+                                 int64_t* stats, int32_t* used, svm_decomp_trace* trace);
+SVM_API int svmd_train_decomp_svr_sw(void* ctx, const void* X_d, int32_t is_u8, int64_t n, int64_t ld, int64_t d,
+                                     const double* mn_h, const double* mx_h, const double* z_d, double epsilon,
+                                     const double* w_d, double* alpha_d, const svm_params* p, int32_t q, svm_result* r,
+                                     svmd_timing* timing, int64_t* stats, int32_t* used, svm_decomp_trace* trace);
 // One-class SVM (LIBSVM's -s 2, svm355.h) on the decomposition solver: uint8 pixel rows or min-max scaled FP64
 // rows as above.  alpha_d: n doubles, out; r->b is rho.  The solver's one-class mode: y = +1, box 1 (p->C is not
 // read), no linear term, LIBSVM's feasible start written on the device and its f summed by the chunked start

@@ -335,6 +335,33 @@ def check_dot_kernel(params, **off) -> None:
                 raise ValueError(f"kernel={params.kernel!r} is not supported with {name.replace('_', ' ')} (the RBF only)")
 
 
+def check_sample_weight(w, n: int, class_box: np.ndarray, eps: float, y=None, **off) -> np.ndarray:
+    """``fit(..., sample_weight=w)`` checked before any device work; returns w as n contiguous float64.  ``off`` maps
+    each option a weighted fit does not cover to whether it was asked for.  w: shape (n,), finite, >= 0; with labels
+    y at least one positive weight in each class; every positive weight's box ``class_box_i * w_i`` above 2 eps, so a
+    point is either frozen at 0 (weight 0) or can be at both bounds (below box - eps, above eps)."""
+    for name, on in off.items():
+        if on:
+            raise ValueError(f"sample_weight is not supported with {name} (sample weights run on the CPU oracles and "
+                             "on the one-GPU RBF decomposition solver from a cold start, on dense float64 or uint8 "
+                             "rows)")
+    w = np.asarray(w)
+    if w.shape != (n,):
+        raise ValueError(f"sample_weight must have shape ({n},), got {w.shape}")
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("sample_weight must be finite and >= 0")
+    if y is not None and not (np.any(w[y == 1] > 0) and np.any(w[y == -1] > 0)):
+        raise ValueError("sample_weight leaves a class without a point of positive weight")
+    box = class_box * w
+    small = (w > 0) & ~(box > 2 * eps)
+    if np.any(small):
+        i = int(np.flatnonzero(small)[0])
+        raise ValueError(f"sample_weight[{i}] = {w[i]!r} gives a box of {box[i]!r}, not above 2 eps = {2 * eps!r}: use "
+                         "0 to leave the row out")
+    return w
+
+
 def host_kernel_decision(est, Xq: np.ndarray, coef: np.ndarray) -> np.ndarray:
     """sum_k coef_k kfun(x_k . q) - b on the host for a dot-product kernel model, summed in support-vector order."""
     from ..ops import cpu as C

@@ -28,8 +28,8 @@ from ..utils.config import SVMParams, default_threads
 from ..utils.data import check_folds, check_warm_start, resolve_class_weight, stratified_folds
 from ..utils.sparse import is_sparse, toarray
 from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
-                      check_f32_rows, check_row_dtype, host_kernel_decision, platt_probability, scaled_cpu,
-                      solve_on_rows)
+                      check_f32_rows, check_row_dtype, check_sample_weight, host_kernel_decision, platt_probability,
+                      scaled_cpu, solve_on_rows)
 
 
 class SVC(KernelEstimator):
@@ -94,10 +94,17 @@ class SVC(KernelEstimator):
 
     # ------------------------------------------------------------------ fit
     def fit(self, X: np.ndarray, y: np.ndarray, alpha0: Optional[np.ndarray] = None,
-            folds: Optional[np.ndarray] = None) -> "SVC":
-        """folds (probability=True only): an explicit fold id per row instead of stratified_folds(y, cv, cv_seed)."""
+            folds: Optional[np.ndarray] = None, sample_weight: Optional[np.ndarray] = None) -> "SVC":
+        """folds (probability=True only): an explicit fold id per row instead of stratified_folds(y, cv, cv_seed).
+        sample_weight (scikit-learn's, LIBSVM's per-instance weights): n weights >= 0; row i's box is
+        [0, C * class_weight(y_i) * w_i], and a weight of 0 leaves the row out (alpha_i = 0, never a support vector).
+        The CPU pairwise oracle, or on a GPU the decomposition solver with a box per point (decomp_box.hip: one GPU,
+        RBF, cold start); the weights are not stored in the model.  None is the unweighted fit."""
         dev = _resolve_device(self.device)
         sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
+        weighted_fit = sample_weight is not None
+        if weighted_fit and sparse:
+            check_sample_weight(sample_weight, 0, None, 0.0, **{"sparse input": True})
         if sparse and dev == "cpu":
             X, sparse = toarray(X), False
         # what the estimator itself rules out; the solver's own refusals (a warm start, shrinking, the knobs, CSR rows)
@@ -127,6 +134,17 @@ class SVC(KernelEstimator):
         self.class_weight_ = {1: wp, -1: wn}
         if self.params.weighted:
             self._check_weighted(dev)
+        sw = None
+        if weighted_fit:
+            gpu = dev != "cpu"
+            sw = check_sample_weight(
+                sample_weight, y.shape[0], self.params.box(y), self.params.eps, y,
+                **{"probability=True": self.probability, "a warm start (alpha0)": alpha0 is not None,
+                   "row_dtype='float32'": f32, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                   "shrinking": self.params._shrink_code() > 0, "wss='second'": self.params.wss == 2,
+                   "solver='smo' on a GPU": gpu and self.solver == "smo",
+                   f"gram={self.gram!r}": gpu and self.gram != "auto", f"kcache={self.kcache!r}": gpu and self.kcache != "auto",
+                   "scale=False on a GPU": gpu and not self.scale})
         if alpha0 is not None:
             alpha0 = check_warm_start(alpha0, y, self.params.box(y) if self.params.weighted else self.params.C)
         if folds is not None and not self.probability:
@@ -143,7 +161,9 @@ class SVC(KernelEstimator):
             else:
                 self._fit_cuda_probability(X, y, folds, dev)
         elif dev == "cpu":
-            self._fit_cpu(X, y, alpha0)
+            self._fit_cpu(X, y, alpha0, sw)
+        elif sw is not None:
+            self._fit_cuda_weighted(X, y, sw, dev)
         elif f32:
             self._fit_cuda_f32(X, y, dev)
         elif sparse:
@@ -305,12 +325,15 @@ class SVC(KernelEstimator):
                          "concurrent_solves": cv["width"]}
 
     def cross_val_decision(self, X: np.ndarray, y: np.ndarray, cv: int = 5, seed: int = 0,
-                           folds: Optional[np.ndarray] = None, concurrent_solves: Optional[int] = None) -> np.ndarray:
+                           folds: Optional[np.ndarray] = None, concurrent_solves: Optional[int] = None,
+                           sample_weight=None) -> np.ndarray:
         """The n held-out decision values of k-fold cross-validation with this estimator's options: row i's value
         comes from the model fitted without row i's fold.  folds: an explicit fold id per row instead of
         ``stratified_folds(y, cv, seed)``.  Min-max scaling is that of all rows, and class_weight="balanced"
         resolves on all labels.  Fits no sigmoid and leaves the estimator's own model alone.  On a GPU the folds
         run ``concurrent_solves`` at a time (default: all of them while the rows fit the last-level cache)."""
+        if sample_weight is not None:  # the held-out solve has one box per class
+            check_sample_weight(sample_weight, 0, None, 0.0, **{"cross_val_decision / cross_val_score": True})
         dev = _resolve_device(self.device)
         check_dot_kernel(self.params, cross_validation=True)
         if is_sparse(X):
@@ -339,10 +362,10 @@ class SVC(KernelEstimator):
         return out["dec"].cpu().numpy()
 
     def cross_val_score(self, X: np.ndarray, y: np.ndarray, cv: int = 5, seed: int = 0,
-                        folds: Optional[np.ndarray] = None) -> float:
+                        folds: Optional[np.ndarray] = None, sample_weight=None) -> float:
         """The held-out accuracy of k-fold cross-validation (LIBSVM's -v k): the share of rows whose held-out
         decision value has their label's sign (``zero_is_positive`` as in predict)."""
-        dec = self.cross_val_decision(X, y, cv, seed, folds)
+        dec = self.cross_val_decision(X, y, cv, seed, folds, sample_weight=sample_weight)
         pos = dec >= 0 if self.zero_is_positive else dec > 0
         return float(np.mean(np.where(pos, 1, -1) == np.asarray(y)))
 
@@ -368,7 +391,9 @@ class SVC(KernelEstimator):
             if on:
                 p.refuse_weights(f"{name} (the GPU pairwise solver)")
 
-    def _finish(self, alpha: np.ndarray, y: np.ndarray, res) -> None:
+    def _finish(self, alpha: np.ndarray, y: np.ndarray, res, box=None) -> None:
+        if box is not None:  # sample weights: no residue outside a point's own box (a weight of 0: exactly 0), as
+            alpha = np.clip(alpha, 0.0, box)  # SVR's split_twins -- the pair update can miss a bound by a few ulp
         self.alpha_ = alpha
         self.support_ = np.flatnonzero(alpha > self.params.sv_tol).astype(np.int64)
         self.dual_coef_ = alpha[self.support_] * y[self.support_]
@@ -379,13 +404,16 @@ class SVC(KernelEstimator):
         self.stop_reason_ = res.stop_reason
         self.result_ = res
 
-    def _fit_cpu(self, X, y, alpha0):
+    def _fit_cpu(self, X, y, alpha0, sw=None):
         from ..ops import cpu as C
 
         if self.solver == "decomp":
             raise ValueError("solver='decomp' runs on the GPU (device='cuda'); the CPU oracle is the pairwise SMO")
         Xs = self._scaled_cpu(X)
-        if self.params.dot_kernel:  # the pairwise oracle on the host Gram of the kernel (its first-order rule)
+        if sw is not None:  # the pairwise oracle with a box per point
+            alpha, res = C.smo_train_sw(Xs, y, sw, self.params)
+            alpha = np.clip(alpha, 0.0, self.params.box(y) * sw)  # as _finish(box=) below, before the SV rows are cut
+        elif self.params.dot_kernel:  # the pairwise oracle on the host Gram of the kernel (its first-order rule)
             alpha, res, _ = C.smo_train_gram(C.kernel_gram(Xs, Xs, self.params), y, self.params, alpha=alpha0,
                                              warm=alpha0 is not None)
         else:
@@ -449,6 +477,27 @@ class SVC(KernelEstimator):
 
         rows, (res, tm) = solve_on_rows(X, device, solve, scale=self.scale, bytes_ok=bytes_ok)
         self._finish(alpha.cpu().numpy(), y, res)
+        self._adopt_rows(rows)
+        self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
+
+    def _fit_cuda_weighted(self, X, y, sw, dev):
+        """Sample weights: the decomposition solver with a box per point, on the byte rows or the scaled FP64 rows."""
+        import torch
+
+        from ..ops import device as D
+
+        if self.solver == "decomp" and not self.scale:
+            raise ValueError("solver='decomp' needs scale=True")
+        device = torch.device(dev)
+        yd, wd = torch.from_numpy(y).to(device), torch.from_numpy(sw).to(device)
+        alpha = torch.empty(X.shape[0], dtype=torch.float64, device=device)  # the cold start zeroes it
+        rows, out = solve_on_rows(X, device, lambda r: D.train_decomp_sw(
+            r.rows, yd, wd, alpha, self.params, r.mn_h, r.mx_h, working_set=self.working_set))
+        if out is None:
+            raise ValueError("sample_weight: the decomposition solver does not cover these rows (n beyond its shapes, "
+                             "or the FP64-row solve's workspace does not fit the device)")
+        res, tm = out
+        self._finish(alpha.cpu().numpy(), y, res, box=self.params.box(y) * sw)
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 

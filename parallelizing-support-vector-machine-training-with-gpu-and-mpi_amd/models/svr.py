@@ -17,19 +17,20 @@ from __future__ import annotations
 
 import os
 import time
+from typing import Optional
 
 import numpy as np
 
 from ..utils.config import SVMParams, default_threads
 from ..utils.sparse import is_sparse, toarray
 from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
-                      check_f32_rows, check_row_dtype, host_kernel_decision, solve_on_rows)
+                      check_f32_rows, check_row_dtype, check_sample_weight, host_kernel_decision, solve_on_rows)
 
 KIND = "svr"  # model files' kind marker (model_io)
 
 
-def split_twins(alpha2: np.ndarray, C: float):
-    """The solvers' 2n values as (a, a*), each clamped into the box [0, C].  The pair update clips one of its two
+def split_twins(alpha2: np.ndarray, C):
+    """The solvers' 2n values as (a, a*), each clamped into the box [0, C] (C: one box, or a box per row).  The pair update clips one of its two
     variables and moves the other by the same amount (the reference's arithmetic, which the classifier shares),
     so a variable that lands on a bound can miss it by a few ulp, on either side; the model keeps no such
     residue outside the box."""
@@ -54,9 +55,14 @@ class SVR(KernelEstimator):
         self.working_set = int(working_set)
 
     # ------------------------------------------------------------------ fit
-    def fit(self, X: np.ndarray, z: np.ndarray) -> "SVR":
+    def fit(self, X: np.ndarray, z: np.ndarray, sample_weight: Optional[np.ndarray] = None) -> "SVR":
+        """sample_weight (scikit-learn's): n weights >= 0; both variables of row k have the box [0, C * w_k], and a
+        weight of 0 leaves the row out.  The decomposition oracle's twin mode on the CPU, the decomposition solver
+        with a box per point on a GPU (decomp_box.hip: RBF only); not stored in the model.  None: the unweighted fit."""
         dev = _resolve_device(self.device)
         sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
+        if sample_weight is not None and sparse:
+            check_sample_weight(sample_weight, 0, None, 0.0, **{"sparse input": True})
         if sparse and dev == "cpu":
             X, sparse = toarray(X), False
         check_dot_kernel(self.params, sparse_rows=sparse)
@@ -75,16 +81,23 @@ class SVR(KernelEstimator):
             raise ValueError("the targets z hold NaN or infinite values")
         if 2 * X.shape[0] > 2**31 - 1:
             raise ValueError(f"n = {X.shape[0]} rows are 2 n > 2^31 - 1 variables")
+        sw = None
+        if sample_weight is not None:
+            sw = check_sample_weight(sample_weight, z.shape[0], np.full(z.shape[0], self.params.C), self.params.eps,
+                                     **{"row_dtype='float32'": f32, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                                        "scale=False on a GPU": dev != "cpu" and not self.scale})
         t0 = time.perf_counter()
         if dev == "cpu":
-            self._fit_cpu(X, z)
+            self._fit_cpu(X, z, sw)
         else:
             if not self.scale:
                 raise ValueError("SVR on a GPU needs scale=True (min-max scaled rows: the decomposition solver's "
                                  "exact-integer plan, or the FP64 rows it solves on)")
             if X.shape[0] < 2:
                 raise ValueError("SVR on a GPU needs at least 2 rows")
-            if f32:
+            if sw is not None:
+                self._fit_cuda(X, z, dev, sw)
+            elif f32:
                 self._fit_cuda_f32(X, z, dev)
             elif sparse:
                 self._fit_cuda_sparse(X, z, dev)
@@ -93,8 +106,9 @@ class SVR(KernelEstimator):
         self.fit_time_ = time.perf_counter() - t0
         return self
 
-    def _finish(self, alpha2: np.ndarray, res) -> None:
-        self.alpha_, self.alpha_star_ = split_twins(alpha2, self.params.C)
+    def _finish(self, alpha2: np.ndarray, res, sw=None) -> None:
+        # sample weights: row k's own box C w_k (split_twins clips elementwise)
+        self.alpha_, self.alpha_star_ = split_twins(alpha2, self.params.C if sw is None else self.params.C * sw)
         beta = self.alpha_ - self.alpha_star_
         self.support_ = np.flatnonzero(np.abs(beta) > self.params.sv_tol).astype(np.int64)
         self.dual_coef_ = beta[self.support_]
@@ -104,21 +118,25 @@ class SVR(KernelEstimator):
         self.stop_reason_ = res.stop_reason
         self.result_ = res
 
-    def _fit_cpu(self, X, z):
+    def _fit_cpu(self, X, z, sw=None):
         from ..ops import cpu as C
 
         Xs = self._scaled_cpu(X)
-        if self.params.dot_kernel:  # the decomposition oracle's twin mode on the host Gram (its second-order pair)
+        if sw is not None:  # the decomposition oracle's twin mode with a box per row, on the host RBF Gram
+            K = C.rbf_matrix(Xs, Xs, self.params.gamma, self.params.n_threads)
+            alpha2, res, _, _ = C.decomp_train_gram_sw(K, z, sw, self.params, epsilon=self.epsilon, q=self.working_set,
+                                                       fp64_rows=True)
+        elif self.params.dot_kernel:  # the decomposition oracle's twin mode on the host Gram (its second-order pair)
             alpha2, res, _, _ = C.decomp_train_gram_svr(C.kernel_gram(Xs, Xs, self.params), z, self.params,
                                                         self.epsilon, q=self.working_set, inner_wss=2)
         else:
             alpha2, res = C.smo_train_svr(Xs, z, self.params, self.epsilon)
-        self._finish(alpha2, res)
+        self._finish(alpha2, res, sw)
         self._dev = None
         self.support_vectors_ = Xs[self.support_].copy()
         self.timings_ = {"smo_ms": res.seconds * 1e3}
 
-    def _fit_cuda(self, X, z, dev):
+    def _fit_cuda(self, X, z, dev, sw=None):
         import torch
 
         from ..ops import device as D
@@ -128,14 +146,17 @@ class SVR(KernelEstimator):
         alpha = torch.empty(2 * X.shape[0], dtype=torch.float64, device=device)  # the cold start zeroes it
         # pixel rows stay bytes on the device (the exact-integer plan reads them); FP64 rows are scaled there and
         # quantised when they admit the plan, else solved with FP64-MFMA kernel values
+        wd = torch.from_numpy(sw).to(device) if sw is not None else None
         rows, out = solve_on_rows(X, device, lambda r: D.train_decomp_svr(
-            r.rows, zd, alpha, self.params, r.mn_h, r.mx_h, epsilon=self.epsilon, working_set=self.working_set),
+            r.rows, zd, alpha, self.params, r.mn_h, r.mx_h, epsilon=self.epsilon, working_set=self.working_set)
+            if wd is None else D.train_decomp_sw(r.rows, zd, wd, alpha, self.params, r.mn_h, r.mx_h, epsilon=self.epsilon,
+                                                 working_set=self.working_set),
             bytes_ok=not self.params.dot_kernel)  # a dot-product kernel: the FP64 rows, scaled on the device
         if out is None:
             raise ValueError("SVR: the decomposition solver does not cover these rows (its FP64-row workspace, "
                              "n x 1024 doubles, does not fit the device)")
         res, tm = out
-        self._finish(alpha.cpu().numpy(), res)
+        self._finish(alpha.cpu().numpy(), res, sw)
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 

@@ -175,6 +175,56 @@ def decomp_train_gram_svr(K: np.ndarray, z: np.ndarray, params: SVMParams, epsil
     return a, SMOResult.from_struct(r), _decomp_stats(st), tr
 
 
+def _weights(w, n: int) -> np.ndarray:
+    w = _c64(w)
+    if w.shape != (n,):
+        raise ValueError(f"sample_weight must have shape ({n},), got {w.shape}")
+    return w
+
+
+def smo_train_sw(X: np.ndarray, y: np.ndarray, w: np.ndarray, params: SVMParams) -> Tuple[np.ndarray, SMOResult]:
+    """``smo_train`` from a cold start with sample weights (svm_smo_train_sw): row i's box is
+    (C class_weight(y_i)) w_i.  Returns (alpha, result)."""
+    X = _c64(X)
+    y = _c32(y)
+    n, d = X.shape
+    if y.shape != (n,):
+        raise ValueError(f"y must have shape ({n},), got {y.shape}")
+    w = _weights(w, n)
+    a = np.zeros(n)
+    r = N.SvmResult()
+    p = params.to_struct()
+    N.check(N.core().svm_smo_train_sw(N.ptr(X), N.ptr(y), n, d, N.ptr(w), N.ptr(a), ctypes.byref(p), ctypes.byref(r)),
+            "svm_smo_train_sw")
+    return a, SMOResult.from_struct(r)
+
+
+def decomp_train_gram_sw(K: np.ndarray, target: np.ndarray, w: np.ndarray, params: SVMParams, epsilon=None,
+                         q: int = 1024, tau_frac: float = 0.1, inner_wss: int = 2, trace_cap: int = 0,
+                         snapshots: bool = False, fp64_rows: bool = False):
+    """The decomposition oracle with sample weights w (a box per kernel row; the device's trajectory at inner_wss =
+    2).  epsilon None: the classifier over the labels ``target`` (svm_decomp_train_gram_sw); else the twin mode over
+    the targets (svm_decomp_train_gram_svr_sw; alpha of 2n entries).  Returns as ``decomp_train_gram``."""
+    K = _c64(K)
+    n = np.shape(target)[0]
+    _gram_shape(K, n)
+    w = _weights(w, n)
+    twin = epsilon is not None
+    target = _targets(target, n) if twin else _c32(target)
+    pts = 2 * n if twin else n
+    a = np.zeros(pts)
+    r = N.SvmResult()
+    st = (ctypes.c_int64 * 16)()
+    tr = N.DecompTrace(trace_cap, pts if snapshots else 0) if trace_cap > 0 else None
+    p = params.to_struct()
+    entry = "svm_decomp_train_gram_svr_sw" if twin else "svm_decomp_train_gram_sw"
+    N.check(getattr(N.core(), entry)(N.ptr(K), K.shape[1], N.ptr(target), n, *((float(epsilon),) if twin else ()),
+                                     N.ptr(w), N.ptr(a), ctypes.byref(p), int(q), float(tau_frac), int(inner_wss),
+                                     int(bool(fp64_rows)), ctypes.byref(r), st,
+                                     ctypes.byref(tr.struct) if tr is not None else None), entry)
+    return a, SMOResult.from_struct(r), _decomp_stats(st), tr
+
+
 def twin_fold(cols: np.ndarray, coef: np.ndarray, n: int) -> Tuple[np.ndarray, np.ndarray]:
     """The twin mode's moved-column fold (svm_decomp_twin_fold): virtual ids in [0, 2n) and their coefficients
     to one entry per kernel row.  Returns (rows, coefficients)."""

@@ -510,6 +510,31 @@ def train_decomp_svr(X: torch.Tensor, z: torch.Tensor, alpha: torch.Tensor, para
                          params, working_set, trace)
 
 
+def train_decomp_sw(X: torch.Tensor, target: torch.Tensor, w: torch.Tensor, alpha: torch.Tensor, params: SVMParams,
+                    mn, mx, epsilon: Optional[float] = None, working_set: int = 1024,
+                    trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:
+    """``train_decomp`` (epsilon None: ``target`` the int32 labels, alpha n values) or ``train_decomp_svr`` (``target``
+    the float64 targets, alpha 2n values) from a cold start with sample weights w (n float64 >= 0 on the device):
+    row i's box is (C class_weight(y_i)) w_i, a weight of 0 keeps the point at alpha = 0 (svmd_train_decomp_sw /
+    svmd_train_decomp_svr_sw; the selection and inner-solve kernels of decomp_box.hip).  What the solve refuses
+    (SVM_ERR_ARG: the native refusal table and knob check) is a ``ValueError`` with its message."""
+    n = _decomp_rows(X)
+    twin = epsilon is not None
+    pts = 2 * n if twin else n
+    for name, t, dt, shape in (("target", target, torch.float64 if twin else torch.int32, (n,)),
+                               ("sample_weight", w, torch.float64, (n,)), ("alpha", alpha, torch.float64, (pts,))):
+        if t.dtype != dt or t.shape != shape or not t.is_contiguous() or t.device != X.device:
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on the rows' device")
+    entry = "svmd_train_decomp_svr_sw" if twin else "svmd_train_decomp_sw"
+    args = (N.ptr(target), float(epsilon), N.ptr(w), N.ptr(alpha)) if twin else (N.ptr(target), N.ptr(w), N.ptr(alpha))
+    try:
+        return _train_decomp(entry, "decomp-svr-sw" if twin else "decomp-sw", X, mn, mx, args, params, working_set, trace)
+    except RuntimeError as e:
+        if "sample weights do not support" in str(e):
+            raise ValueError(str(e)) from None
+        raise
+
+
 def train_decomp_oneclass(X: torch.Tensor, alpha: torch.Tensor, params: SVMParams, mn, mx, nu: float = 0.5,
                           working_set: int = 1024,
                           trace: Optional["N.DecompTrace"] = None) -> Optional[Tuple[SMOResult, dict]]:
