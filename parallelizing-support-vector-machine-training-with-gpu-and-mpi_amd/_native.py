@@ -324,6 +324,12 @@ _HIP_SIGS = {
     "svmd_train_decomp_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_double, _P,
                                         POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                         POINTER(c_int64), POINTER(SvmDecompTrace)]),
+    "svmd_linear_block_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P,
+                                        c_int64]),
+    "svmd_linear_fupdate_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P,
+                                          c_int32, c_int32, _P]),
+    "svmd_linear_w": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P]),
+    "svmd_decision_csr_linear": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, c_double, _P]),
     "svmd_upload_rows_f32": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int64]),
     "svmd_preprocess_f32": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, _P, _P, _P]),
     "svmd_rbf_block_f32": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, c_int64, _P,

@@ -10,7 +10,8 @@ Targets
                                  and the device-resident SMO driver (hipGraph replay); every csrc/hip/*.hip
                                  (platt.hip, the one-workgroup sigmoid fit and its batch of P,
                                  ovo_proba.hip, the one-wave-per-row pairwise coupling, csr_rbf.hip,
-                                 sparse rows against a transposed panel, and rows_f32.hip, float32 rows on
+                                 sparse rows against a transposed panel, csr_linear.hip, the linear kernel on
+                                 sparse rows as a weight-vector update, and rows_f32.hip, float32 rows on
                                  FP32 MFMA under an FP64 epilogue, among them)
   bin/svm_serial          g++   main3.cpp-equivalent CLI
   bin/svm_gpu             hipcc gpu_svm_main3/4-equivalent CLI (--n-limit sweep)
@@ -47,6 +48,7 @@ HIP_EXTRA: dict = {
     # FP64 and integer code only: packed FP32 instructions are switched off for the file, not relied on to be absent
     "decomp_nu.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "csr_rbf.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "csr_linear.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "decomp_kfun.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "decomp_box.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }

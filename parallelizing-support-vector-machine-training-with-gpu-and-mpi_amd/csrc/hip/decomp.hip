@@ -32,6 +32,7 @@
 #include <mutex>
 #include <vector>
 
+#include "csr_linear.h"
 #include "csr_rbf.h"
 #include "decomp.h"
 #include "decomp_dev.h"
@@ -1149,6 +1150,7 @@ struct DecompWs {
   double *PT = nullptr, *nP = nullptr;
   int32_t *pprev = nullptr, *pcnt = nullptr;
   CsrPanel panel() const { return CsrPanel{PT, kMaxWS, nP, pprev, pcnt}; }
+  double* dw = nullptr;  // sparse rows under the linear kernel (csr_linear.hip): the f update's weight-vector delta (dpad)
   // float32 rows: the working set's and the moved columns' rows gathered (kMaxWS x ld floats each; norms: nw, nc)
   float *Xw32 = nullptr, *Xc32 = nullptr;
   double* box = nullptr;  // sample weights: the kernel rows' boxes (ws_box_kernel)
@@ -1349,6 +1351,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
     w.nc = c.take<double>(kMaxWS);
   }
   w.box = c.take<double>(nr1, S.mode.boxed());
+  w.dw = c.take<double>(size_t(S.R.dpad), S.csr && S.kfun);
 }
 
 // The knob values a dot-product kernel's solve refuses (docs/KNOBS.md): its inner solve is one kernel, 256 threads
@@ -1493,7 +1496,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.csr = csr;
   S.f32 = f32;
   S.kfun = p.kernel != kKernelRbf;
-  if (S.kfun && !f64) {
+  if (S.kfun && !f64 && !(csr && p.kernel == kKernelLinear)) {  // sparse rows: the linear kernel only (csr_linear.hip)
     set_error("decomposition SMO: the dot-product kernels run on FP64 rows");
     return SVM_ERR_ARG;
   }
@@ -1585,6 +1588,10 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
     const CsrRows A = csr_rows(R, S.rows());
     int rc = launch_csr_panel_scatter(s, A, cl, cnt, nullptr, 0, w.panel());
     if (rc) return rc;
+    if (S.kfun) {  // the linear kernel: dw = X_moved' coef from the panel, then f += X dw (no block at all)
+      if ((rc = launch_csr_panel_reduce(s, w.PT, kMaxWS, R.dpad, cf, kMaxWS, cnt, false, w.dw))) return rc;
+      return launch_csr_matvec(s, A, lo, nloc, w.dw, twin, cnt, w.f);
+    }
     CsrBlock b;
     b.arow0 = b.row_off = lo;
     b.m = nloc;
@@ -1905,6 +1912,8 @@ int enqueue_kww(const Solve& S) {
     b.gamma = S.p.gamma;
     b.K = w.Kw;
     b.ldk = kLdw;
+    // the linear kernel: the dot block, symmetric to the bit, and two twins get their row's |x|^2 (no ws_twin_kww_kernel)
+    if (S.kfun) return launch_csr_dot_block(s, A, w.panel(), b);
     b.sym = true;
     rc = launch_csr_rbf(s, CsrEpilogue::store, A, w.panel(), b);
     return rc ? rc : twin_diag();
@@ -2632,7 +2641,9 @@ SVM_API int svmd_train_decomp_nusvr(void* h, const void* X_d, int32_t is_u8, int
 // column maxima (svmd_csr_prepare) with their norms.  kind 0: the classifier over the labels y_d (alpha_d: n
 // doubles, out; class weights in *pp allowed); kind 1: epsilon-SVR over the targets z_d (alpha_d: 2n doubles, a
 // then a*, as svmd_train_decomp_svr).  Kernel values come from csr_rbf.hip against a d x 1024 panel; no rows x
-// 1024 block is stored.  One GPU, cold start; shrinking and the Newton polish are SVM_ERR_ARG.
+// 1024 block is stored.  The linear kernel (p.kernel = 1) runs csr_linear.hip on the same panel: K(W, W) as a dot
+// block, the f update as a weight-vector delta and one CSR x vector product.  One GPU, cold start; shrinking and
+// the Newton polish are SVM_ERR_ARG.
 SVM_API int svmd_train_decomp_csr(void* h, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
                                   const double* nrm_d, int64_t n, int64_t d, int32_t kind, const int32_t* y_d,
                                   const double* z_d, double epsilon, double* alpha_d, const svm_params* pp, int32_t q,

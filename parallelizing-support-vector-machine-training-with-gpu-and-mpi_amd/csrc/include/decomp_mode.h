@@ -101,8 +101,9 @@ constexpr DecompFeatures kDecompRefuses[6][2] = {
 constexpr bool kDecompKfunKinds[6] = {true, true, false, false, false, false};
 constexpr DecompFeatures kDecompKfunRefuses = {true, true, true, true, false};
 
-// A dot-product kernel's own arguments and everything such a solve does not cover (csr: sparse rows): SVM_ERR_ARG
-// with `who` as the message's prefix, before the caller does any work.  SVM_OK at once for the RBF.
+// A dot-product kernel's own arguments and everything such a solve does not cover (csr: sparse rows, which only the
+// linear kernel takes: hip/csr_linear.hip): SVM_ERR_ARG with `who` as the message's prefix, before the caller does
+// any work.  SVM_OK at once for the RBF.
 inline int decomp_kfun_check(const char* who, const svm_params& p, DecompModeKind kind, const DecompFeatures& f,
                              bool csr) {
   if (p.kernel == kKernelRbf) return SVM_OK;
@@ -115,7 +116,7 @@ inline int decomp_kfun_check(const char* who, const svm_params& p, DecompModeKin
   }
   const DecompFeatures& r = kDecompKfunRefuses;
   const char* what = !kDecompKfunKinds[int(kind)] ? "this mode (the classifier and the regression (twin) solve only)"
-                     : csr                        ? "sparse (CSR) rows"
+                     : csr && p.kernel != kKernelLinear ? "sparse (CSR) rows"
                      : f.distributed && r.distributed ? "the distributed solve (world > 1)"
                      : f.warm && r.warm               ? "a warm start"
                      : f.shrinking && r.shrinking     ? "shrinking"

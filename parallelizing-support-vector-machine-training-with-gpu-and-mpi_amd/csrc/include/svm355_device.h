@@ -314,9 +314,31 @@ SVM_API int svmd_decision_kfun(void* ctx, const double* Xs_d, const double* coef
 SVM_API int svmd_csr_rows_dense(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
                                 const double* nrm_d, int64_t n, int64_t d, const int64_t* ids_d, int64_t k,
                                 double* Xs_d, int64_t ld, double* ns_d);
+// ---- the linear kernel on sparse rows (csrc/hip/csr_linear.hip): K(x, z) = x . z, so f += K(:, moved) coef is
+// f += X (X_moved' coef): one weight-vector delta, then one CSR x vector product.  CSR operands as above.
+// K_d[i * ldk + j] = (row i of A) . (row j of B), m rows of A, 1 <= nb <= 1024 rows of B; no diagonal rule.
+SVM_API int svmd_linear_block_csr(void* ctx, const int64_t* a_indptr_d, const int32_t* a_indices_d,
+                                  const double* a_values_d, const double* a_nrm_d, int64_t m,
+                                  const int64_t* b_indptr_d, const int32_t* b_indices_d, const double* b_values_d,
+                                  const double* b_nrm_d, int64_t nb, int64_t d, double* K_d, int64_t ldk);
+// f_d[i] += a_i . (B[0 : count]' coef_d), as the solver's f update runs it (scatter, panel reduce, product); count
+// < 0: all nb <= 1024 rows; count = 0: f_d keeps its bits.  twin != 0: f_d holds 2 m values, f_d[i + m] += the same.
+SVM_API int svmd_linear_fupdate_csr(void* ctx, const int64_t* a_indptr_d, const int32_t* a_indices_d,
+                                    const double* a_values_d, const double* a_nrm_d, int64_t m,
+                                    const int64_t* b_indptr_d, const int32_t* b_indices_d, const double* b_values_d,
+                                    const double* b_nrm_d, int64_t nb, int64_t d, const double* coef_d, int32_t count,
+                                    int32_t twin, double* f_d);
+// w_d[0 : lds] = sum_k coef_d[k] Xs_d[k * lds + :], a linear model's weight vector from its dense support vectors
+// (nsv x lds), 1024 at a time in order.
+SVM_API int svmd_linear_w(void* ctx, const double* Xs_d, const double* coef_d, int64_t nsv, int64_t lds, double* w_d);
+// out_d[i] = (CSR query row i) . w_d - b, m scaled queries of d features (w_d: at least d doubles).
+SVM_API int svmd_decision_csr_linear(void* ctx, const int64_t* indptr_d, const int32_t* indices_d,
+                                     const double* values_d, const double* nq_d, int64_t m, int64_t d,
+                                     const double* w_d, double b, double* out_d);
 // The decomposition solver on prepared (mode 1) sparse rows.  kind 0: the classifier over y_d (alpha_d: n doubles,
-// out; class weights allowed); kind 1: epsilon-SVR over z_d (alpha_d: 2n doubles, a then a*).  One GPU, cold
-// start; shrinking, the Newton polish and a forced column cache are SVM_ERR_ARG.  stats[6] = 2.
+// out; class weights allowed); kind 1: epsilon-SVR over z_d (alpha_d: 2n doubles, a then a*).  The RBF or the
+// linear kernel (p->kernel 0 or 1).  One GPU, cold start; shrinking, the Newton polish and a forced column cache
+// are SVM_ERR_ARG.  stats[6] = 2.
 SVM_API int svmd_train_decomp_csr(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
                                   const double* nrm_d, int64_t n, int64_t d, int32_t kind, const int32_t* y_d,
                                   const double* z_d, double epsilon, double* alpha_d, const svm_params* p, int32_t q,

@@ -421,6 +421,25 @@ class KernelEstimator:
     def _device_queries(self, X):
         return scale_queries(self._dev, X, self.scale)
 
+    def _linear_w(self):
+        """A linear device model's weight vector sum_k coef_k Xs_k (padded, on the device), built once per device
+        model by the panel reduce (csr_linear.hip) and kept in it."""
+        from ..ops import device as D
+
+        if "w" not in self._dev:
+            self._dev["w"] = D.linear_w(self._dev["Xs"], self._dev["coef"])
+        return self._dev["w"]
+
+    @property
+    def coef_(self) -> np.ndarray:
+        """The linear kernel's weight vector in scaled-feature space, shape (d,): ``dual_coef_ @ support_vectors_``
+        (the decision function is ``x_scaled @ coef_ - b_``).  AttributeError for any other kernel."""
+        if self.params.kernel != "linear":
+            raise AttributeError("coef_ is only available when using a linear kernel")
+        if self._dev is not None:
+            return self._linear_w()[: self._dev["d"]].cpu().numpy()
+        return np.asarray(self.dual_coef_, dtype=np.float64) @ self.support_vectors_
+
     def _device_decide(self, X):
         """sum_k coef_k K(x_k, x) - b_ on the device model, as a device tensor: dense queries on the MFMA cross
         kernel, CSR queries on the CSR x panel kernel against the same dense support vectors."""
@@ -428,6 +447,8 @@ class KernelEstimator:
 
         dv = self._dev
         if self.params.dot_kernel:  # the model's kernel: the fused dot-product block and sum
+            if is_sparse(X) and self.params.kernel == "linear":  # one sparse dot product per row with w
+                return D.decision_csr_linear(self._linear_w(), sparse_queries(dv, X, self.scale), self.b_)
             if is_sparse(X):
                 raise ValueError(f"sparse queries are not supported with kernel={self.params.kernel!r} (densify them)")
             return D.decision_kfun(dv["Xs"], dv["coef"], self._device_queries(X)[0], self.params, self.b_)

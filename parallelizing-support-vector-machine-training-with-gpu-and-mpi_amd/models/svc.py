@@ -55,7 +55,8 @@ class SVC(KernelEstimator):
         # kernel (scikit-learn's, LIBSVM's -t): "rbf" (the default, and the only one of everything but SVC and SVR),
         # "linear", "poly" or "sigmoid" with degree and coef0 -- on the CPU the pairwise oracle on the host Gram, on
         # a GPU the decomposition solver's dot-product kernels (decomp_kfun.hip) from a cold start; probability=True,
-        # cross-validation, sparse rows, shrinking, a warm start and the pairwise GPU solver raise with them.
+        # cross-validation, sparse rows, shrinking, a warm start and the pairwise GPU solver raise with them -- except
+        # that the linear kernel takes sparse rows and sparse queries (csr_linear.hip), and a linear model has coef_.
         # class weights (scikit-learn's class_weight, LIBSVM's -wi): None, "balanced" (n / (2 n_c), resolved
         # per fit from the labels) or {1: w_pos, -1: w_neg}; row i's box is [0, C * w(y_i)].  The CPU oracle
         # and the GPU decomposition solver take them; the pairwise GPU solver, shrinking and the knobs that
@@ -110,7 +111,9 @@ class SVC(KernelEstimator):
         # what the estimator itself rules out; the solver's own refusals (a warm start, shrinking, the knobs, CSR rows)
         # come from the native table as ValueError.  wss='second' is the pairwise solvers' RBF-only second-order arm,
         # and on a GPU solver='smo', gram=, kcache= and scale=False all select the pairwise solver, which is RBF only.
-        check_dot_kernel(self.params, probability=self.probability, sparse_rows=sparse, **{"wss='second'": self.params.wss == 2},
+        # (CSR rows take the linear kernel: csr_linear.hip's weight-vector update.)
+        check_dot_kernel(self.params, probability=self.probability, sparse_rows=sparse and self.params.kernel != "linear",
+                         **{"wss='second'": self.params.wss == 2},
                          **({} if dev == "cpu" else {"solver='smo'": self.solver == "smo",
                                                      f"gram={self.gram!r}": self.gram != "auto",
                                                      f"kcache={self.kcache!r}": self.kcache != "auto",

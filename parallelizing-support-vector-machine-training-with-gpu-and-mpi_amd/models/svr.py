@@ -65,7 +65,7 @@ class SVR(KernelEstimator):
             check_sample_weight(sample_weight, 0, None, 0.0, **{"sparse input": True})
         if sparse and dev == "cpu":
             X, sparse = toarray(X), False
-        check_dot_kernel(self.params, sparse_rows=sparse)
+        check_dot_kernel(self.params, sparse_rows=sparse and self.params.kernel != "linear")  # csr_linear.hip
         f32 = self.row_dtype == "float32"
         if f32:  # what float32 rows do not cover, before any device work
             check_f32_rows(**{"sparse (CSR) rows": sparse, f"kernel={self.params.kernel!r}": self.params.dot_kernel,

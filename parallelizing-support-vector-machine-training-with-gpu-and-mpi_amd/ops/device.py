@@ -1092,6 +1092,61 @@ def train_decomp_csr(A: DeviceCSR, alpha: torch.Tensor, params: SVMParams, y: Op
                                       "inner_threads": int(st[5])}
 
 
+# ---- the linear kernel on sparse rows (csr_linear.hip) ------------------------------------------------------
+def linear_block_csr(A: DeviceCSR, B: DeviceCSR) -> torch.Tensor:
+    """K (m, nb) = A's rows . B's rows (nb <= 1024, both prepared): B's rows scattered into the transposed panel,
+    then the dot block (no norms, no diagonal rule; K(R, R) equals its transpose bit for bit)."""
+    if A.d != B.d or not (1 <= B.n <= 1024) or A.n < 1 or A.nrm is None or B.nrm is None:
+        raise ValueError("linear_block_csr: prepared rows of one d, 1 <= nb <= 1024")
+    K = torch.empty((A.n, B.n), dtype=torch.float64, device=A.values.device)
+    ctx = _ctx_for(A.values)
+    N.check(ctx.lib.svmd_linear_block_csr(ctx.bind(), *A.args(), A.n, *B.args(), B.n, A.d, N.ptr(K), B.n),
+            "svmd_linear_block_csr")
+    return K
+
+
+def linear_fupdate_csr(A: DeviceCSR, B: DeviceCSR, coef: torch.Tensor, f: torch.Tensor, twin: bool = False,
+                       count: int = -1) -> torch.Tensor:
+    """f[i] += A_i . (B[:count]' coef) in place, as the solver's f update runs it: the panel scatter, the panel reduce
+    into a weight-vector delta, the CSR x vector product.  twin: f holds 2 m values and f[i + m] gets the same sum.
+    count: a device-side count of that value (-1: all of B's nb <= 1024 rows; 0 leaves f bit-identical)."""
+    if A.d != B.d or not (1 <= B.n <= 1024) or A.n < 1 or A.nrm is None or B.nrm is None or count > B.n:
+        raise ValueError("linear_fupdate_csr: prepared rows of one d, 1 <= nb <= 1024, count <= nb")
+    want = A.n * (2 if twin else 1)
+    for name, t, k in (("coef", coef, B.n), ("f", f, want)):
+        if t.dtype != torch.float64 or t.shape != (k,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous float64 of shape ({k},)")
+    ctx = _ctx_for(A.values)
+    N.check(ctx.lib.svmd_linear_fupdate_csr(ctx.bind(), *A.args(), A.n, *B.args(), B.n, A.d, N.ptr(coef), int(count),
+                                            int(twin), N.ptr(f)), "svmd_linear_fupdate_csr")
+    return f
+
+
+def linear_w(Xs: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
+    """w (ld,) = coef @ Xs for a linear model's dense padded support vectors Xs (nsv, ld): 1024 rows at a time through
+    the transposed panel and the accumulating reduce, in order (bit-identical run to run)."""
+    _check_rows(Xs, "Xs")
+    nsv, ld = Xs.shape
+    if coef.dtype != torch.float64 or coef.shape != (nsv,) or not coef.is_contiguous():
+        raise ValueError(f"coef must be contiguous float64 of shape ({nsv},)")
+    w = torch.empty(ld, dtype=torch.float64, device=Xs.device)
+    ctx = _ctx_for(Xs)
+    N.check(ctx.lib.svmd_linear_w(ctx.bind(), N.ptr(Xs) if nsv else None, N.ptr(coef) if nsv else None, nsv, ld,
+                                  N.ptr(w)), "svmd_linear_w")
+    return w
+
+
+def decision_csr_linear(w: torch.Tensor, Q: DeviceCSR, b: float) -> torch.Tensor:
+    """out[i] = Q_i . w - b for prepared CSR queries against a linear model's weight vector (at least d values)."""
+    if w.dtype != torch.float64 or w.dim() != 1 or w.numel() < Q.d or not w.is_contiguous():
+        raise ValueError(f"w must be contiguous float64 with at least {Q.d} values")
+    out = torch.empty(Q.n, dtype=torch.float64, device=Q.values.device)
+    ctx = _ctx_for(Q.values)
+    N.check(ctx.lib.svmd_decision_csr_linear(ctx.bind(), *Q.args(), Q.n, Q.d, N.ptr(w), float(b), N.ptr(out)),
+            "svmd_decision_csr_linear")
+    return out
+
+
 # ---- float32 rows (rows_f32.hip) ----------------------------------------------------------------------------
 def _check_rows_f32(X: torch.Tensor, name: str = "X") -> None:
     if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous() or X.shape[1] % 16:

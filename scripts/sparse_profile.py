@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--dense", action="store_true", help="also fit the dense FP64 rows (toarray) of the same set")
     ap.add_argument("--gamma", type=float, default=0.05)
+    ap.add_argument("--kernel", default="rbf", choices=("rbf", "linear"),
+                    help="linear: the CSR fit runs csr_linear.hip's weight-vector update, the dense one decomp_kfun.hip")
+    ap.add_argument("--C", type=float, default=10.0)
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     import svm355
@@ -66,8 +69,8 @@ def main():
     cut = a.n * per
     Xtr = svm355.CSR(X.data[:cut], X.indices[:cut], X.indptr[:a.n + 1], (a.n, a.d))
     Xte = svm355.CSR(X.data[cut:], X.indices[cut:], X.indptr[a.n:] - cut, (a.heldout, a.d))
-    kw = dict(C=10.0, gamma=a.gamma, tol=1e-3, device="cuda:0", solver="decomp")
-    out = {"n": a.n, "d": a.d, "density": a.density, "nnz_per_row": per}
+    kw = dict(C=a.C, gamma=a.gamma, tol=1e-3, device="cuda:0", solver="decomp", kernel=a.kernel)
+    out = {"n": a.n, "d": a.d, "density": a.density, "nnz_per_row": per, "kernel": a.kernel, "C": a.C}
     sp = svm355.SVC(**kw)
     t, used, peak = fit_timed(sp, Xtr, y[:a.n], a.repeats)
     out["sparse"] = {"fit_ms": t, "device_bytes_grown": int(used), "torch_peak_bytes": int(peak),
