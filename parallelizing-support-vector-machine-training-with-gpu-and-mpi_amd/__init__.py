@@ -18,7 +18,8 @@ re-designed for gfx950:
                                      is taken, ``scipy.sparse.csr_matrix`` too): the solver's kernel values come
                                      from the CSR rows against a transposed panel of the working set
                                      ``SVC`` / ``SVR(row_dtype="float32")``: float32 device rows, kernel values from
-                                     FP32-MFMA dot products under an FP64 epilogue (rows_f32.hip)
+                                     FP32-MFMA dot products under an FP64 epilogue (rows_f32.hip);
+                                     ``row_dtype="float16"``: float16 device rows on FP16 MFMA (rows_f16.hip)
 * ``svm355.OneClassSVM``           one-class SVM (novelty detection on unlabelled rows, LIBSVM's -s 2): the
                                      classifier's dual with every sign +1, box 1 and no linear term, solved by
                                      the decomposition solver's one-class mode from LIBSVM's feasible start

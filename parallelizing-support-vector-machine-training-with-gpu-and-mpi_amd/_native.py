@@ -338,6 +338,14 @@ _HIP_SIGS = {
     "svmd_train_decomp_f32": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P, c_double, _P,
                                         POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
                                         POINTER(c_int64), POINTER(SvmDecompTrace)]),
+    "svmd_upload_rows_f16": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int64]),
+    "svmd_preprocess_f16": (c_int32, [c_void_p, _P, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, _P]),
+    "svmd_rbf_block_f16": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, c_int64, _P,
+                                     c_int64, c_double, c_int32, c_int32, c_int32, _P, c_int64, _P, _P]),
+    "svmd_rows_f16_dense": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P]),
+    "svmd_train_decomp_f16": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, c_int64, c_int32, _P, _P, c_double, _P,
+                                        POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),
+                                        POINTER(c_int64), POINTER(SvmDecompTrace)]),
     "svmd_ovo_votes": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P]),
     "svmd_ovo_predict": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, c_double,
                                    c_int64, _P, _P, c_int64, _P, c_int64, _P, _P]),

@@ -11,8 +11,9 @@ Targets
                                  (platt.hip, the one-workgroup sigmoid fit and its batch of P,
                                  ovo_proba.hip, the one-wave-per-row pairwise coupling, csr_rbf.hip,
                                  sparse rows against a transposed panel, csr_linear.hip, the linear kernel on
-                                 sparse rows as a weight-vector update, and rows_f32.hip, float32 rows on
-                                 FP32 MFMA under an FP64 epilogue, among them)
+                                 sparse rows as a weight-vector update, rows_f32.hip, float32 rows on
+                                 FP32 MFMA under an FP64 epilogue, and rows_f16.hip, float16 rows on FP16
+                                 MFMA under the same epilogue, among them)
   bin/svm_serial          g++   main3.cpp-equivalent CLI
   bin/svm_gpu             hipcc gpu_svm_main3/4-equivalent CLI (--n-limit sweep)
   bin/svm_cascade         hipcc mpi_svm_main2/3-equivalent: one process, a thread per GPU, RCCL

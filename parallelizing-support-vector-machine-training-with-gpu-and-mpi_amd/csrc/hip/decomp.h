@@ -61,7 +61,9 @@ struct DecompOpts {
 // form (indptr n + 1, indices sorted and in [0, d), values min-max scaled so that zeros stay zeros, and nrm;
 // csr_rbf.hip: kernel values against a d x 1024 transposed panel of the working set; one GPU, cold start) -- or the
 // rows as float32 (X32, n x ld floats, ld a multiple of 16, scaled and rounded once, with the FP64 norms nrm of the
-// rounded values; rows_f32.hip: FP32-MFMA dot products under an FP64 epilogue; one GPU, cold start).
+// rounded values; rows_f32.hip: FP32-MFMA dot products under an FP64 epilogue; one GPU, cold start) -- or as float16
+// (X16, n x ld halves, ld a multiple of 64, scaled and rounded to float32 and then to float16, with the FP64 norms of
+// those values; rows_f16.hip: FP16-MFMA dot products under the same epilogue, and the float32 rows' limits).
 struct DecompRows {
   const int8_t* Q = nullptr;
   const int32_t* N0 = nullptr;
@@ -79,6 +81,8 @@ struct DecompRows {
   const float* X32 = nullptr;
   bool csr() const { return indptr != nullptr; }
   bool f32() const { return X32 != nullptr; }
+  const _Float16* X16 = nullptr;
+  bool f16() const { return X16 != nullptr; }
 };
 
 // stats: SVM_DECOMP_STATS int64 (see run_decomp).

@@ -40,6 +40,7 @@
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
 #include "persist.h"
+#include "rows_f16.h"
 #include "rows_f32.h"
 #include "svm355_device.h"
 #include "trace.h"
@@ -1153,6 +1154,7 @@ struct DecompWs {
   double* dw = nullptr;  // sparse rows under the linear kernel (csr_linear.hip): the f update's weight-vector delta (dpad)
   // float32 rows: the working set's and the moved columns' rows gathered (kMaxWS x ld floats each; norms: nw, nc)
   float *Xw32 = nullptr, *Xc32 = nullptr;
+  half_t *Xw16 = nullptr, *Xc16 = nullptr;  // float16 rows: the same two panels in halves
   double* box = nullptr;  // sample weights: the kernel rows' boxes (ws_box_kernel)
 };
 
@@ -1171,6 +1173,8 @@ struct Solve {
   bool f64 = false;
   bool csr = false;  // sparse rows (csr_rbf.hip): neither of the two dense formats
   bool f32 = false;  // float32 rows (rows_f32.hip): no rows x 1024 block, no column cache, no quantisation plan
+  bool f16 = false;  // float16 rows (rows_f16.hip): the same
+  bool frows() const { return f32 || f16; }
   bool kfun = false;  // a dot-product kernel (p.kernel != 0, decomp_kfun.hip): FP64 rows, no norms, no unit diagonal
   int kq = 0;  // the quantised rows' bytes (exact-integer rows)
   const int32_t* y = nullptr;
@@ -1291,7 +1295,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   DecompWs& w = S.w;
   const size_t nl1 = size_t(std::max<int64_t>(S.nloc, 1)), n = size_t(S.n), kq = size_t(S.kq), ld = size_t(S.R.ld);
   const size_t nr1 = size_t(std::max<int64_t>(S.rows(), 1)), ncol = size_t(S.cols());  // kernel rows / columns
-  const bool f64 = S.f64, q8 = !f64 && !S.csr && !S.f32, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
+  const bool f64 = S.f64, q8 = !f64 && !S.csr && !S.frows(), cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
   w.f = c.take<double>(nl1);
   w.own = c.take<CandRec>(size_t(S.Lr));
   w.all = c.take<CandRec>(size_t(S.sh.L));
@@ -1346,7 +1350,9 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.pcnt = c.take<int32_t>(64, S.csr);
   w.Xw32 = c.take<float>(size_t(kMaxWS) * ld, S.f32);
   w.Xc32 = c.take<float>(size_t(kMaxWS) * ld, S.f32);
-  if (S.f32) {
+  w.Xw16 = c.take<half_t>(size_t(kMaxWS) * ld, S.f16);
+  w.Xc16 = c.take<half_t>(size_t(kMaxWS) * ld, S.f16);
+  if (S.frows()) {
     w.nw = c.take<double>(kMaxWS);
     w.nc = c.take<double>(kMaxWS);
   }
@@ -1413,16 +1419,19 @@ int fused_rows_check(const char* who, const char* rows, const DecompOpts& o, con
 }
 constexpr const char* kCsrRowsName = "sparse (CSR) rows";
 constexpr const char* kF32RowsName = "float32 rows";
+constexpr const char* kF16RowsName = "float16 rows";
 int csr_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& ft) {
   return fused_rows_check(who, kCsrRowsName, o, ft);
 }
-// float32 rows: the same limits, and the RBF kernel only (the dot-product kernels read FP64 rows).
-int f32_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& ft, const svm_params& p) {
+// float32 and float16 rows (`rows` naming which): the same limits, and the RBF kernel only (the dot-product kernels
+// read FP64 rows).
+int f32_rows_check(const char* who, const DecompOpts& o, const DecompFeatures& ft, const svm_params& p,
+                   const char* rows = kF32RowsName) {
   if (p.kernel != kKernelRbf) {
-    set_error("%s: %s do not support a dot-product kernel (kernel = %d; the RBF only)", who, kF32RowsName, p.kernel);
+    set_error("%s: %s do not support a dot-product kernel (kernel = %d; the RBF only)", who, rows, p.kernel);
     return SVM_ERR_ARG;
   }
-  return fused_rows_check(who, kF32RowsName, o, ft);
+  return fused_rows_check(who, rows, o, ft);
 }
 
 // The checks, the shape and this GPU's slice of it, the knobs and what follows from them.
@@ -1435,7 +1444,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   if (rc || (rc = decomp_mode_check("decomposition SMO", o.mode, y, ft, nrow, DecompBackend::device))) return rc;
   if ((rc = decomp_kfun_check("decomposition SMO", p, o.mode.kind, ft, R.csr())) || (rc = kfun_knobs_check("decomposition SMO", p)))
     return rc;
-  if ((rc = decomp_box_check("decomposition SMO", p, o.mode.kind, ft, R.csr(), R.f32())) ||
+  if ((rc = decomp_box_check("decomposition SMO", p, o.mode.kind, ft, R.csr(), R.f32(), R.f16())) ||
       (rc = box_knobs_check("decomposition SMO", o.mode)))
     return rc;
   n = o.mode.points(nrow);
@@ -1452,15 +1461,17 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
   }
-  const bool f64 = R.fp64(), csr = R.csr(), f32 = R.f32();
-  if (csr ? (f64 || f32 || !R.indices || !R.values || !R.nrm || R.d < 1 || R.dpad < R.d || R.d >= int64_t(INT32_MAX))
-      : f32 ? (f64 || R.ld < 16 || R.ld % 16 != 0 || !R.nrm)
+  const bool f64 = R.fp64(), csr = R.csr(), f32 = R.f32(), f16 = R.f16();
+  if (csr ? (f64 || f32 || f16 || !R.indices || !R.values || !R.nrm || R.d < 1 || R.dpad < R.d || R.d >= int64_t(INT32_MAX))
+      : f32 ? (f64 || f16 || R.ld < 16 || R.ld % 16 != 0 || !R.nrm)
+      : f16 ? (f64 || R.ld < kF16RowQuantum || R.ld % kF16RowQuantum != 0 || !R.nrm)
       : f64 ? (R.ld % 16 != 0 || !R.nrm) : (!R.Q || !R.P)) {
     set_error("decomposition SMO: bad row source");
     return SVM_ERR_ARG;
   }
   if (csr && (rc = csr_rows_check("decomposition SMO", o, ft))) return rc;
   if (f32 && (rc = f32_rows_check("decomposition SMO", o, ft, p))) return rc;
+  if (f16 && (rc = f32_rows_check("decomposition SMO", o, ft, p, kF16RowsName))) return rc;
   svm_decomp_trace* tr = o.trace;
   if (tr && (world != 1 || tr->cap < 0 || (tr->n != 0 && tr->n != n))) {
     set_error("decomposition SMO: a trace needs one GPU and snapshots of n = %lld", (long long)n);
@@ -1483,9 +1494,9 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     return SVM_ERR_ARG;
   }
   if ((rc = read_knobs(sh, &S.k))) return rc;
-  if ((csr || f32) && S.k.ccache == 1) {
+  if ((csr || f32 || f16) && S.k.ccache == 1) {
     set_error("decomposition SMO: %s do not support the column cache (SVM355_DECOMP_CCACHE=1)",
-              csr ? kCsrRowsName : kF32RowsName);
+              csr ? kCsrRowsName : f32 ? kF32RowsName : kF16RowsName);
     return SVM_ERR_ARG;
   }
   if ((rc = svm_class_boxes(&p1, &S.Cp, &S.Cn))) return rc;
@@ -1495,12 +1506,13 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.f64 = f64;
   S.csr = csr;
   S.f32 = f32;
+  S.f16 = f16;
   S.kfun = p.kernel != kKernelRbf;
   if (S.kfun && !f64 && !(csr && p.kernel == kKernelLinear)) {  // sparse rows: the linear kernel only (csr_linear.hip)
     set_error("decomposition SMO: the dot-product kernels run on FP64 rows");
     return SVM_ERR_ARG;
   }
-  S.kq = (f64 || csr || f32) ? 0 : R.P->kq;
+  S.kq = (f64 || csr || f32 || f16) ? 0 : R.P->kq;
   S.y = y;  // a mode with its own signs: those, in the workspace (alloc_solve)
   S.alpha = alpha;
   S.mode = o.mode;
@@ -1524,7 +1536,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     nu_start_walk(p1.C * o.mode.nu * double(nrow) / 2.0, p1.C, nrow, &S.nu_full, &S.nu_frac);
   S.nchunks = (n + kMaxWS - 1) / kMaxWS;
   S.wide_select = !o.mode.nu_pairs() && !o.mode.boxed() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select);
-  S.kww_narrow = !f64 && !csr && !f32 && !S.k.kww_sym && S.kq <= 1536;
+  S.kww_narrow = !f64 && !csr && !f32 && !f16 && !S.k.kww_sym && S.kq <= 1536;
   S.shc = shrink_cfg(p);
   S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
   const NewtonCfg nwc = newton_cfg(p);
@@ -1547,7 +1559,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
 int alloc_solve(Solve& S, bool warm) {
   static std::mutex alloc_mu;
   std::lock_guard<std::mutex> alloc_lock(alloc_mu);
-  int rc = (S.csr || S.f32) ? SVM_OK : size_col_cache(S, warm, &S.cc);  // sparse / float32 rows: no cache (refused when forced)
+  int rc = (S.csr || S.frows()) ? SVM_OK : size_col_cache(S, warm, &S.cc);  // sparse / float32 / float16 rows: no cache (refused when forced)
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
   if (S.mode.own_signs()) S.y = S.w.sgn;
@@ -1564,6 +1576,74 @@ int alloc_solve(Solve& S, bool warm) {
 
 // The solve's sparse rows as csr_rbf.hip's launchers take them (n kernel rows).
 CsrRows csr_rows(const DecompRows& R, int64_t n) { return CsrRows{R.indptr, R.indices, R.values, R.nrm, n, R.d}; }
+
+// The two narrow dense row sources (rows_f32.hip, rows_f16.hip) behind one pair of arms: the element type, the block
+// descriptor with its epilogues, and the two launchers.
+struct F32Rows {
+  using T = float;
+  using Block = Rbf32Block;
+  using Epi = Rbf32Epilogue;
+  static constexpr auto gather = launch_ws_gather_f32;
+  static constexpr auto launch = launch_rbf32_block;
+};
+struct F16Rows {
+  using T = half_t;
+  using Block = Rbf16Block;
+  using Epi = Rbf16Epilogue;
+  static constexpr auto gather = launch_ws_gather_f16;
+  static constexpr auto launch = launch_rbf16_block;
+};
+
+// f_update on a narrow source: the moved columns' rows gathered into the panel Xc, then the fused block + sum -- no
+// rows x 1024 block in HBM.
+template <class Src>
+int narrow_f_update(const Solve& S, const typename Src::T* X, typename Src::T* Xc, const int32_t* cl, const double* cf,
+                    const int32_t* cnt) {
+  const DecompWs& w = S.w;
+  const DecompRows& R = S.R;
+  int rc = Src::gather(S.s, X, R.nrm, R.ld, cl, cnt, nullptr, 0, kMaxWS, Xc, w.nc);
+  if (rc) return rc;
+  typename Src::Block b;
+  b.A = X + S.lo * R.ld;
+  b.nA = R.nrm + S.lo;
+  b.m = S.rows();
+  b.B = Xc;
+  b.nB = w.nc;
+  b.ncap = kMaxWS;
+  b.lda = b.ldb = b.kdim = R.ld;
+  b.ncount = cnt;
+  b.row_off = S.lo;
+  b.idb = cl;
+  b.gamma = S.p.gamma;
+  b.coef = cf;
+  b.f = w.f;
+  return Src::launch(S.s, S.mode.twin() ? Src::Epi::sum_twin : Src::Epi::sum, b);
+}
+
+// enqueue_kww on a narrow source: W's rows gathered into the panel Xw, then a full launch with A = B: symmetric to
+// the bit, 1.0 by id (twins too).
+template <class Src>
+int narrow_kww(const Solve& S, const typename Src::T* X, typename Src::T* Xw) {
+  const DecompWs& w = S.w;
+  const DecompRows& R = S.R;
+  int32_t* gate = &w.ctl->stop;
+  const int64_t tw = S.mode.twin() ? S.nrow : 0;
+  int rc = Src::gather(S.s, X, R.nrm, R.ld, w.W, &w.ctl->m, gate, tw, kMaxWS, Xw, w.nw);
+  if (rc) return rc;
+  typename Src::Block b;
+  b.A = b.B = Xw;
+  b.nA = b.nB = w.nw;
+  b.m = b.ncap = kMaxWS;
+  b.lda = b.ldb = b.kdim = R.ld;
+  b.gate = gate;
+  b.ncount = &w.ctl->m;
+  b.ida = b.idb = w.W;
+  b.twin_nrow = tw;
+  b.gamma = S.p.gamma;
+  b.K = w.Kw;
+  b.ldk = kLdw;
+  return Src::launch(S.s, Src::Epi::store, b);
+}
 
 // f += K(this GPU's rows, cols[0:*cnt]) coef: the exact-integer GEMV (column-half partials summed in
 // order) or, for FP64 rows, the moved columns' rows gathered, their block on FP64 MFMA and a row sum
@@ -1603,25 +1683,8 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
     b.f = w.f;
     return launch_csr_rbf(s, twin ? CsrEpilogue::sum_twin : CsrEpilogue::sum, A, w.panel(), b);
   }
-  if (S.f32) {  // the moved columns' rows gathered, then the fused block + sum: no rows x 1024 block in HBM
-    int rc = launch_ws_gather_f32(s, R.X32, R.nrm, R.ld, cl, cnt, nullptr, 0, kMaxWS, w.Xc32, w.nc);
-    if (rc) return rc;
-    Rbf32Block b;
-    b.A = R.X32 + lo * R.ld;
-    b.nA = R.nrm + lo;
-    b.m = nloc;
-    b.B = w.Xc32;
-    b.nB = w.nc;
-    b.ncap = kMaxWS;
-    b.lda = b.ldb = b.kdim = R.ld;
-    b.ncount = cnt;
-    b.row_off = lo;
-    b.idb = cl;
-    b.gamma = S.p.gamma;
-    b.coef = cf;
-    b.f = w.f;
-    return launch_rbf32_block(s, twin ? Rbf32Epilogue::sum_twin : Rbf32Epilogue::sum, b);
-  }
+  if (S.f32) return narrow_f_update<F32Rows>(S, R.X32, w.Xc32, cl, cf, cnt);
+  if (S.f16) return narrow_f_update<F16Rows>(S, R.X16, w.Xc16, cl, cf, cnt);
   if (S.f64) {
     hipLaunchKernelGGL(ws_gather_f64_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, cl, cnt,
                        nullptr, w.Xc, w.nc);
@@ -1739,8 +1802,9 @@ int start_solve(const Solve& S, const PackState& ps, bool warm, int64_t* warm_co
   std::memset(S.hs, 0, sizeof(DecompHost));
   SVMD_CHECK(hipMemsetAsync(w.ctl, 0, sizeof(DecompCtl), s));  // stop = SVM_STOP_RUNNING, counters 0
   if (S.f64) SVMD_CHECK(hipMemsetAsync(w.Xw, 0, size_t(kMaxWS) * S.R.ld * 8, s));  // rows beyond m stay finite
-  if (S.f32) {  // rows beyond m stay finite
-    SVMD_CHECK(hipMemsetAsync(w.Xw32, 0, size_t(kMaxWS) * S.R.ld * 4, s));
+  if (S.f16) SVMD_CHECK(hipMemsetAsync(w.Xw16, 0, size_t(kMaxWS) * S.R.ld * 2, s));
+  if (S.frows()) {  // rows beyond m stay finite
+    if (S.f32) SVMD_CHECK(hipMemsetAsync(w.Xw32, 0, size_t(kMaxWS) * S.R.ld * 4, s));
     SVMD_CHECK(hipMemsetAsync(w.nw, 0, size_t(kMaxWS) * 8, s));
   }
   if (S.csr) {  // the panel is cleared whole once per fit; after that only by re-walking the rows it held
@@ -1918,24 +1982,8 @@ int enqueue_kww(const Solve& S) {
     rc = launch_csr_rbf(s, CsrEpilogue::store, A, w.panel(), b);
     return rc ? rc : twin_diag();
   }
-  if (S.f32) {  // W's rows gathered, then a full launch with A = B: symmetric to the bit, 1.0 by id (twins too)
-    const int64_t tw = S.mode.twin() ? S.nrow : 0;
-    int rc = launch_ws_gather_f32(s, R.X32, R.nrm, R.ld, w.W, &w.ctl->m, gate, tw, kMaxWS, w.Xw32, w.nw);
-    if (rc) return rc;
-    Rbf32Block b;
-    b.A = b.B = w.Xw32;
-    b.nA = b.nB = w.nw;
-    b.m = b.ncap = kMaxWS;
-    b.lda = b.ldb = b.kdim = R.ld;
-    b.gate = gate;
-    b.ncount = &w.ctl->m;
-    b.ida = b.idb = w.W;
-    b.twin_nrow = tw;
-    b.gamma = S.p.gamma;
-    b.K = w.Kw;
-    b.ldk = kLdw;
-    return launch_rbf32_block(s, Rbf32Epilogue::store, b);
-  }
+  if (S.f32) return narrow_kww<F32Rows>(S, R.X32, w.Xw32);
+  if (S.f16) return narrow_kww<F16Rows>(S, R.X16, w.Xw16);
   if (S.f64) {
     if (S.mode.twin())
       hipLaunchKernelGGL(ws_gather_f64_twin_kernel, dim3(unsigned(kMaxWS)), dim3(64), 0, s, R.X, R.nrm, R.ld, w.W,
@@ -2148,7 +2196,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
     stats[3] = int64_t(ms_since(S.t0) * 1000.0);
     stats[4] = fin.changed_total;
     stats[5] = S.k.inner_nt;
-    stats[6] = S.f32 ? 3 : S.csr ? 2 : S.f64 ? 1 : 0;
+    stats[6] = S.f16 ? 4 : S.f32 ? 3 : S.csr ? 2 : S.f64 ? 1 : 0;
     stats[7] = warm_cols;
     stats[8] = ps.unshrinks;
     stats[9] = fin.passes;
@@ -2181,7 +2229,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
 // updates f for its own points.  With world dividing 8 the trajectory is the one-GPU trajectory.
 // stats (kDecompStats = SVM_DECOMP_STATS int64, 13 written): outer iterations, inner iterations, working-set
 // capacity, solve microseconds, columns of the f updates (points moved, summed over the outer iterations),
-// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA, 2 sparse rows, 3 float32 rows), warm-start columns,
+// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA, 2 sparse rows, 3 float32 rows, 4 float16 rows), warm-start columns,
 // unshrinks, shrink passes, the fewest active rows, repacks, Newton polish steps.
 int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n, const svm_params& p,
                int qws, svm_result* r, int64_t* stats, const DecompOpts& o) {
@@ -2689,18 +2737,18 @@ SVM_API int svmd_train_decomp_csr(void* h, const int64_t* indptr_d, const int32_
   return ctx->end();
 }
 
-// The solve on float32 rows (svm355_device.h): n rows of ld floats on the device, scaled and rounded once
-// (svmd_preprocess_f32) with the FP64 norms of the rounded values.  kind 0 / kind 1, alpha_d and the limits as
-// svmd_train_decomp_csr; the RBF kernel only.  Kernel values come from rows_f32.hip; no rows x 1024 block is stored.
-SVM_API int svmd_train_decomp_f32(void* h, const float* X_d, const double* nrm_d, int64_t n, int64_t ld, int64_t d,
-                                  int32_t kind, const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d,
-                                  const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
-                                  svm_decomp_trace* trace) {
-  const char* who = "svmd_train_decomp_f32";
+// The solve on float32 or float16 rows (exactly one of X32_d / X16_d; `quantum`: what ld is a multiple of, `rows`:
+// the source's name in refusals) behind svmd_train_decomp_f32 and svmd_train_decomp_f16.
+static int train_decomp_frows(const char* who, void* h, const float* X32_d, const _Float16* X16_d, int quantum,
+                              const char* rows, const double* nrm_d, int64_t n, int64_t ld, int64_t d, int32_t kind,
+                              const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d,
+                              const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
+                              svm_decomp_trace* trace) {
   SVMD_CTX(h);
-  if (!X_d || !nrm_d || n < 2 || d < 1 || ld < d || ld % 16 != 0 || (reinterpret_cast<uintptr_t>(X_d) & 15) ||
+  const void* X_d = X32_d ? static_cast<const void*>(X32_d) : X16_d;
+  if (!X_d || !nrm_d || n < 2 || d < 1 || ld < d || ld % quantum != 0 || (reinterpret_cast<uintptr_t>(X_d) & 15) ||
       !alpha_d || (kind != 0 && kind != 1) || (kind == 0 ? !y_d : !z_d)) {
-    set_error("%s: bad arguments (ld a multiple of 16, rows 16-byte aligned)", who);
+    set_error("%s: bad arguments (ld a multiple of %d, rows 16-byte aligned)", who, quantum);
     return SVM_ERR_ARG;
   }
   const svm_params p = params_or_default(pp);
@@ -2713,7 +2761,7 @@ SVM_API int svmd_train_decomp_f32(void* h, const float* X_d, const double* nrm_d
   }
   DecompFeatures ft;
   int rc = mode_features(o, p, &ft);
-  if (rc || (rc = f32_rows_check(who, o, ft, p)) ||
+  if (rc || (rc = f32_rows_check(who, o, ft, p, rows)) ||
       (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device)))
     return rc;
   if (!decomp_shape(o.mode.points(n), q > 0 ? q : 1024, 1).ok) {
@@ -2721,7 +2769,8 @@ SVM_API int svmd_train_decomp_f32(void* h, const float* X_d, const double* nrm_d
     return SVM_ERR_ARG;
   }
   DecompRows R;
-  R.X32 = X_d;
+  R.X32 = X32_d;
+  R.X16 = X16_d;
   R.nrm = nrm_d;
   R.ld = ld;
   const auto t0 = std::chrono::steady_clock::now();
@@ -2732,6 +2781,27 @@ SVM_API int svmd_train_decomp_f32(void* h, const float* X_d, const double* nrm_d
     timing->total_ms = timing->smo_ms = ms_since(t0);
   }
   return ctx->end();
+}
+
+// The solve on float32 rows (svm355_device.h): n rows of ld floats on the device, scaled and rounded once
+// (svmd_preprocess_f32) with the FP64 norms of the rounded values.  kind 0 / kind 1, alpha_d and the limits as
+// svmd_train_decomp_csr; the RBF kernel only.  Kernel values come from rows_f32.hip; no rows x 1024 block is stored.
+SVM_API int svmd_train_decomp_f32(void* h, const float* X_d, const double* nrm_d, int64_t n, int64_t ld, int64_t d,
+                                  int32_t kind, const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d,
+                                  const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
+                                  svm_decomp_trace* trace) {
+  return train_decomp_frows("svmd_train_decomp_f32", h, X_d, nullptr, 16, kF32RowsName, nrm_d, n, ld, d, kind, y_d, z_d,
+                            epsilon, alpha_d, pp, q, r, timing, stats, trace);
+}
+
+// The same on float16 rows (svmd_preprocess_f16; ld a multiple of 64 halves): kernel values from rows_f16.hip.
+SVM_API int svmd_train_decomp_f16(void* h, const void* X_d, const double* nrm_d, int64_t n, int64_t ld, int64_t d,
+                                  int32_t kind, const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d,
+                                  const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
+                                  svm_decomp_trace* trace) {
+  return train_decomp_frows("svmd_train_decomp_f16", h, nullptr, static_cast<const _Float16*>(X_d), kF16RowQuantum,
+                            kF16RowsName, nrm_d, n, ld, d, kind, y_d, z_d, epsilon, alpha_d, pp, q, r, timing, stats,
+                            trace);
 }
 
 // The held-out form of svmd_train_decomp (svm355_device.h): held-out mode (decomp_mode.h) over the n rows.

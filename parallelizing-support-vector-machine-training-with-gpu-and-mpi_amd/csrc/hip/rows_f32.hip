@@ -44,6 +44,7 @@
 // padded FP64 rows every model keeps.
 #include "rows_f32.h"
 
+#include "rows_minmax.h"
 #include "svm355_device.h"
 
 namespace svm355 {
@@ -180,61 +181,7 @@ __global__ __launch_bounds__(64) void ws_gather_f32_kernel(const float* __restri
   if (threadIdx.x == 0) no[k] = nrm[src];
 }
 
-// ---- prep: column min / max of float32 rows in one streaming pass (per-block column partials, then a fold in
-// partial order), a NaN anywhere in a column making both of its bounds NaN as in the FP64 scaler.
-constexpr int kColsPerBlock = 64, kRowLanes = 4;
-
-__global__ __launch_bounds__(256) void f32_minmax_partial_kernel(const float* __restrict__ X, int64_t n, int64_t d,
-                                                                 int64_t ld, double* __restrict__ pmin,
-                                                                 double* __restrict__ pmax) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t c = int64_t(blockIdx.x) * kColsPerBlock + lane;
-  const int64_t rstride = int64_t(gridDim.y) * kRowLanes;
-  float lo = __builtin_inff(), hi = -__builtin_inff();
-  bool nan = false;
-  if (c < d) {
-    for (int64_t r = int64_t(blockIdx.y) * kRowLanes + wv; r < n; r += rstride) {
-      const float v = X[r * ld + c];
-      lo = fminf(lo, v);
-      hi = fmaxf(hi, v);
-      nan |= v != v;
-    }
-  }
-  __shared__ float smin[kRowLanes][kColsPerBlock], smax[kRowLanes][kColsPerBlock];
-  __shared__ bool snan[kRowLanes][kColsPerBlock];
-  smin[wv][lane] = lo;
-  smax[wv][lane] = hi;
-  snan[wv][lane] = nan;
-  __syncthreads();
-  if (wv == 0 && c < d) {
-#pragma unroll
-    for (int w = 1; w < kRowLanes; ++w) {
-      nan |= snan[w][lane];
-      lo = fminf(lo, smin[w][lane]);
-      hi = fmaxf(hi, smax[w][lane]);
-    }
-    pmin[int64_t(blockIdx.y) * d + c] = nan ? __builtin_nan("") : double(lo);
-    pmax[int64_t(blockIdx.y) * d + c] = nan ? __builtin_nan("") : double(hi);
-  }
-}
-
-__global__ __launch_bounds__(256) void f32_minmax_final_kernel(const double* __restrict__ pmin,
-                                                               const double* __restrict__ pmax, int parts, int64_t d,
-                                                               double* __restrict__ mn, double* __restrict__ mx) {
-  const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (c >= d) return;
-  double lo = pmin[c], hi = pmax[c];
-  bool nan = lo != lo;
-  for (int p = 1; p < parts; ++p) {
-    const double v = pmin[int64_t(p) * d + c];
-    nan |= v != v;
-    lo = fmin(lo, v);
-    hi = fmax(hi, pmax[int64_t(p) * d + c]);
-  }
-  mn[c] = nan ? __builtin_nan("") : lo;
-  mx[c] = nan ? __builtin_nan("") : hi;
-}
-
+// ---- prep: the column min / max pass is rows_minmax.h's, on float.
 // One wave per row: x' = float((double(x) - mn) / range) in place (range < 1e-12 divides by 1), the padding up to
 // ld zeroed, and sqn = the FP64 sum of the rounded values' squares in scale_norm_kernel's order (lane-strided,
 // then the wave butterfly), so the norms are row_norms' of the widened rows bit for bit.  mn == nullptr: norms only.
@@ -369,17 +316,8 @@ SVM_API int svmd_preprocess_f32(void* h, float* X_d, int64_t n, int64_t d, int64
   }
   int rc = ctx->begin();
   if (rc) return rc;
-  const int gx = int((d + kColsPerBlock - 1) / kColsPerBlock);
-  const int parts = int(std::min<int64_t>((n + kRowLanes - 1) / kRowLanes, std::max(1, 2048 / gx)));
-  if ((rc = ctx->ensure_ws(size_t(2) * size_t(d) * size_t(parts) * 8))) return rc;
-  double* pmin = static_cast<double*>(ctx->ws);
-  double* pmax = pmin + size_t(parts) * size_t(d);
+  if ((rc = launch_rows_minmax(ctx, X_d, n, d, ld, mn_d, mx_d))) return rc;
   hipStream_t s = ctx->stream;
-  hipLaunchKernelGGL(f32_minmax_partial_kernel, dim3(gx, parts), dim3(256), 0, s, X_d, n, d, ld, pmin, pmax);
-  SVMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(f32_minmax_final_kernel, dim3(unsigned((d + 255) / 256)), dim3(256), 0, s, pmin, pmax, parts, d,
-                     mn_d, mx_d);
-  SVMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(f32_scale_norm_kernel, dim3(wave_rows_grid(n)), dim3(256), 0, s, X_d, n, d, ld, mn_d, mx_d, sqn_d);
   SVMD_LAUNCH_CHECK();
   return ctx->end();

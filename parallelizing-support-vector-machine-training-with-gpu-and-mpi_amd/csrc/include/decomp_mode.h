@@ -133,16 +133,17 @@ inline int decomp_kfun_check(const char* who, const svm_params& p, DecompModeKin
 constexpr bool kDecompBoxKinds[6] = {true, true, false, false, false, false};
 constexpr DecompFeatures kDecompBoxRefuses = {true, true, true, true, false};
 
-// Everything a solve with sample weights does not cover (csr / f32: the row source): SVM_ERR_ARG with `who` as the
+// Everything a solve with sample weights does not cover (csr / f32 / f16: the row source): SVM_ERR_ARG with `who` as the
 // message's prefix, before the caller does any work.  SVM_OK at once without weights.
 inline int decomp_box_check(const char* who, const svm_params& p, DecompModeKind kind, const DecompFeatures& f, bool csr,
-                            bool f32) {
+                            bool f32, bool f16 = false) {
   if (!f.boxed) return SVM_OK;
   const DecompFeatures& r = kDecompBoxRefuses;
   const char* what = !kDecompBoxKinds[int(kind)] ? "this mode (the classifier and the regression (twin) solve only)"
                      : p.kernel != kKernelRbf     ? "a dot-product kernel (the RBF only)"
                      : csr                        ? "sparse (CSR) rows"
                      : f32                        ? "float32 rows"
+                     : f16                        ? "float16 rows"
                      : f.distributed && r.distributed ? "the distributed solve (world > 1)"
                      : f.warm && r.warm               ? "a warm start"
                      : f.shrinking && r.shrinking     ? "shrinking"

@@ -373,6 +373,33 @@ SVM_API int svmd_train_decomp_f32(void* ctx, const float* X_d, const double* nrm
                                   const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
                                   svm_decomp_trace* trace);
 
+// ---- Float16 rows (csrc/hip/rows_f16.hip).  Rows stay float16 on the device (n x ld halves, ld a multiple of 64,
+// zero padded, 16-byte aligned; `void*` here: C has no portable name for the type); the dot product of a kernel value
+// runs on FP16 MFMA -- exact products, float32 accumulation -- and everything after it is FP64.
+// Host float16 rows (n x d, contiguous) -> device rows (n x ld).
+SVM_API int svmd_upload_rows_f16(void* ctx, const void* X_host, int64_t n, int64_t d, void* X_d, int64_t ld);
+// Column min / max of the uploaded values into mn_d / mx_d (d doubles), then X_d = the rows scaled by x' =
+// float16(float((double(x) - mn) / (mx - mn))) -- FP64 subtract and divide, then two roundings to nearest-even; a
+// range below 1e-12 divides by 1; float16 subnormals are kept -- and sqn_d[i] = the FP64 sum of squares of row i's
+// rounded values.  src_d null: the values are X_d's own (float16 host rows), scaled in place.  Otherwise they are the
+// float32 staging rows src_d (n x ld_src floats, svmd_upload_rows_f32), which the caller releases afterwards.
+SVM_API int svmd_preprocess_f16(void* ctx, const float* src_d, int64_t ld_src, void* X_d, int64_t n, int64_t d,
+                                int64_t ld, double* mn_d, double* mx_d, double* sqn_d);
+// The kernel block on caller-given rows (tests): svmd_rbf_block_f32's arguments on float16 rows, kdim halves per row
+// (a multiple of 64).
+SVM_API int svmd_rbf_block_f16(void* ctx, const void* A_d, int64_t m, int64_t lda, const void* B_d, int64_t nb,
+                               int64_t ldb, int64_t kdim, const int32_t* ida_d, int64_t row_off, const int32_t* idb_d,
+                               int64_t twin_nrow, double gamma, int32_t epi, int32_t count, int32_t gate, double* K_d,
+                               int64_t ldk, const double* coef_d, double* f_d);
+// Xs_d (k x ldo doubles, written whole; d <= ldo <= ld) = the rows ids_d[0 : k] widened to FP64, ns_d[k] their norms.
+SVM_API int svmd_rows_f16_dense(void* ctx, const void* X_d, const double* nrm_d, int64_t n, int64_t ld,
+                                const int64_t* ids_d, int64_t k, double* Xs_d, int64_t ldo, double* ns_d);
+// The decomposition solver on preprocessed float16 rows: svmd_train_decomp_f32's arguments and limits.  stats[6] = 4.
+SVM_API int svmd_train_decomp_f16(void* ctx, const void* X_d, const double* nrm_d, int64_t n, int64_t ld, int64_t d,
+                                  int32_t kind, const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d,
+                                  const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats,
+                                  svm_decomp_trace* trace);
+
 // dst[k] = src[idx[k]] rows (device gather), for SV compaction and cascade training-set assembly.
 SVM_API int svmd_gather_rows(void* ctx, const double* src_d, int64_t ld, const int64_t* idx_d,
                              int64_t k, double* dst_d);

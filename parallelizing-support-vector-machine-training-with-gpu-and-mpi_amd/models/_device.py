@@ -4,6 +4,8 @@
 ``OneClassSVM`` share (``KernelEstimator``).  ``OneVsRestSVC`` and ``OneVsOneSVC`` use the functions."""
 from __future__ import annotations
 
+import os
+import re
 import time
 from typing import Optional
 
@@ -48,6 +50,13 @@ class TrainRows:
 
         return self.rows.dtype == torch.float32
 
+    @property
+    def f16(self) -> bool:
+        """float16 rows (``row_dtype="float16"``): scaled and rounded (to float32, then float16) on the device."""
+        import torch
+
+        return self.rows.dtype == torch.float16
+
     @classmethod
     def upload(cls, X: np.ndarray, device, scale: bool = True, widen: bool = False,
                row_dtype: str = "float64") -> "TrainRows":
@@ -57,7 +66,10 @@ class TrainRows:
         into the FP64 rows that float64 host rows become.  ``scale=False`` (FP64 rows only): unscaled rows and
         their norms, through which a NaN / inf anywhere shows.  ``row_dtype="float32"``: the rows cross PCIe and
         stay on the device as float32 (any dtype, uint8 too, cast on the host once), min-max scaled there by
-        ``float32((float64(x) - mn) / range)`` with the FP64 norms of the rounded values."""
+        ``float32((float64(x) - mn) / range)`` with the FP64 norms of the rounded values.  ``row_dtype="float16"``:
+        a float16 host array crosses PCIe as it is (2 bytes a value) and is scaled in place; any other dtype crosses as
+        float32 and is scaled into a float16 buffer, the float32 staging rows being released before the solve.  The
+        rule is ``float16(float32((float64(x) - mn) / range))``, norms again in FP64 of the rounded values."""
         import torch
 
         from ..ops import device as D
@@ -70,6 +82,17 @@ class TrainRows:
                 raise ValueError("float32 device rows are min-max scaled rows (scale=True)")
             rows = D.upload_rows_f32(X, device)
             mn, mx, sqn = D.minmax_scale_f32_(rows, d)
+        elif row_dtype == "float16":
+            if not scale:
+                raise ValueError("float16 device rows are min-max scaled rows (scale=True)")
+            if X.dtype == np.float16:
+                rows = D.upload_rows_f16(X, device)
+                mn, mx, sqn = D.minmax_scale_f16_(rows, d)
+            else:
+                staging = D.upload_rows_f32(X, device)
+                rows = D.device_empty((X.shape[0], D.padded_dim_f16(d)), torch.float16, device)
+                mn, mx, sqn = D.minmax_scale_f16_(rows, d, src=staging)
+                del staging  # released before the solve (stream-ordered: the caller's stream waits for the scaling)
         elif _is_u8(X) and not widen:
             if not scale:
                 raise ValueError("uint8 device rows are min-max scaled rows (scale=True)")
@@ -112,6 +135,8 @@ class TrainRows:
             return D.sv_rows_u8(self.rows, idx, self.mn, self.mx)
         if self.f32:  # widened: a model keeps FP64 support vectors, so everything after the fit is the FP64 code
             return D.rows_f32_dense(self.rows, self.sqn, idx)
+        if self.f16:
+            return D.rows_f16_dense(self.rows, self.sqn, idx, self.d)
         return self.take(idx), self.sqn[idx].contiguous()
 
     def model(self, support, coef, **extra) -> dict:
@@ -289,24 +314,30 @@ def scaled_cpu(X: np.ndarray, scale: bool = True):
     return X, None
 
 
-ROW_DTYPES = ("float64", "float32")
+ROW_DTYPES = ("float64", "float32", "float16")
 
 
 def check_row_dtype(row_dtype: str) -> str:
     if row_dtype not in ROW_DTYPES:
-        raise ValueError(f"row_dtype must be 'float64' (the default) or 'float32', got {row_dtype!r}")
+        raise ValueError(f"row_dtype must be 'float64' (the default), 'float32' or 'float16', got {row_dtype!r}")
     return row_dtype
 
 
-def check_f32_rows(**off) -> None:
-    """What ``row_dtype="float32"`` does not cover raises here, before any device work: ``off`` maps each
+def check_f32_rows(row_dtype: str = "float32", **off) -> None:
+    """What ``row_dtype="float32"`` (or ``"float16"``) does not cover raises here, before any device work: ``off`` maps each
     unsupported option's description to whether it was asked for.  The solver's own limits are the native table's
     (``fused_rows_check`` in decomp.hip, shared with sparse rows); these are the estimator-level options that would
     route a fit elsewhere."""
     for name, on in off.items():
         if on:
-            raise ValueError(f"row_dtype='float32' is not supported with {name} (float32 rows run on the RBF "
+            raise ValueError(f"row_dtype='{row_dtype}' is not supported with {name} ({row_dtype} rows run on the RBF "
                              "decomposition solver from a cold start, min-max scaled)")
+
+
+def newton_polish_on() -> bool:
+    """Whether SVM355_DECOMP_NEWTON asks for the Newton polish, read as the native knob reads it (C's atoi != 0)."""
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("SVM355_DECOMP_NEWTON", ""))
+    return bool(m) and int(m.group()) != 0
 
 
 def scaled_cpu_f32(X: np.ndarray):
@@ -315,6 +346,15 @@ def scaled_cpu_f32(X: np.ndarray):
     Returns (rows, scaler) as ``scaled_cpu``."""
     Xs, sc = scaled_cpu(np.ascontiguousarray(X, dtype=np.float32).astype(np.float64), True)
     return Xs.astype(np.float32).astype(np.float64), sc
+
+
+def scaled_cpu_f16(X: np.ndarray):
+    """``row_dtype="float16"`` on the CPU, the host twin of the device's float16 rows: a float16 array as it is, any
+    other rounded to float32; min / max of those values; ``float16(float32((float64(x) - mn) / range))`` -- the scaler's
+    FP64 arithmetic, then the two roundings (subnormal halves kept) -- widened.  Returns (rows, scaler)."""
+    X = X if X.dtype == np.float16 else np.ascontiguousarray(X, dtype=np.float32)
+    Xs, sc = scaled_cpu(np.ascontiguousarray(X, dtype=np.float64), True)
+    return Xs.astype(np.float32).astype(np.float16).astype(np.float64), sc
 
 
 def platt_probability(z: np.ndarray) -> np.ndarray:
@@ -374,7 +414,7 @@ class KernelEstimator:
     lazily fetched host copy of the support vectors."""
 
     scaler_ = None
-    row_dtype = "float64"  # SVC / SVR take "float32" (rows_f32.hip); the other estimators keep the default
+    row_dtype = "float64"  # SVC / SVR take "float32" (rows_f32.hip) and "float16" (rows_f16.hip); the others keep the default
     _dev = None  # device-side model state (device_model's dict)
     _sv_host = None
 
@@ -401,7 +441,8 @@ class KernelEstimator:
         check_query_shape(X, self._n_features())
 
     def _scaled_cpu(self, X: np.ndarray) -> np.ndarray:
-        Xs, self.scaler_ = scaled_cpu_f32(X) if self.row_dtype == "float32" else scaled_cpu(X, self.scale)
+        Xs, self.scaler_ = (scaled_cpu_f32(X) if self.row_dtype == "float32" else scaled_cpu_f16(X)
+                            if self.row_dtype == "float16" else scaled_cpu(X, self.scale))
         return Xs
 
     def _adopt_rows(self, rows: TrainRows) -> None:

@@ -28,7 +28,7 @@ from ..utils.config import SVMParams, default_threads
 from ..utils.data import check_folds, check_warm_start, resolve_class_weight, stratified_folds
 from ..utils.sparse import is_sparse, toarray
 from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
-                      check_f32_rows, check_row_dtype, check_sample_weight, host_kernel_decision, platt_probability,
+                      check_f32_rows, check_row_dtype, newton_polish_on, check_sample_weight, host_kernel_decision, platt_probability,
                       scaled_cpu, solve_on_rows)
 
 
@@ -41,7 +41,8 @@ class SVC(KernelEstimator):
                  degree: int = 3, coef0: float = 0.0, row_dtype: str = "float64"):
         # row_dtype="float32": the training rows cross PCIe and stay on the device as float32, scaled there and
         # rounded once; kernel values come from FP32-MFMA dot products under an FP64 epilogue (rows_f32.hip) with no
-        # rows x 1024 block in HBM.  The model (FP64 support vectors) and everything after the fit are unchanged.
+        # rows x 1024 block in HBM.  row_dtype="float16": the same with float16 rows (a float16 array crosses PCIe as it is),
+        # rounded float32 -> float16 after scaling, on FP16 MFMA (rows_f16.hip): 11 significant bits per feature.  The model (FP64 support vectors) and everything after the fit are unchanged.
         self.row_dtype = check_row_dtype(row_dtype)
         if wss not in ("first", "second"):
             raise ValueError("wss must be 'first' (the reference's selection) or 'second'")
@@ -118,12 +119,14 @@ class SVC(KernelEstimator):
                                                      f"gram={self.gram!r}": self.gram != "auto",
                                                      f"kcache={self.kcache!r}": self.kcache != "auto",
                                                      "scale=False": not self.scale}))
-        f32 = self.row_dtype == "float32"
-        if f32:
+        f32, f16 = self.row_dtype == "float32", self.row_dtype == "float16"
+        if f32 or f16:
             self._check_f32(dev, sparse, alpha0)
         if sparse:
             self._check_sparse(alpha0)
-        elif f32 and dev != "cpu":  # as it is when it is float32; any other dtype (uint8 exactly) cast once
+        elif f16 and getattr(X, "dtype", None) == np.float16:  # as it is, on either device (2 bytes a value over PCIe)
+            X = np.ascontiguousarray(X)
+        elif (f32 or f16) and dev != "cpu":  # as it is when it is float32; any other dtype (uint8 exactly) cast once
             X = np.ascontiguousarray(X, dtype=np.float32)
         else:  # uint8 pixel rows stay compact up to the device (8x less H2D; widened to FP64 there)
             X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
@@ -143,7 +146,7 @@ class SVC(KernelEstimator):
             sw = check_sample_weight(
                 sample_weight, y.shape[0], self.params.box(y), self.params.eps, y,
                 **{"probability=True": self.probability, "a warm start (alpha0)": alpha0 is not None,
-                   "row_dtype='float32'": f32, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                   "row_dtype='float32'": f32, "row_dtype='float16'": f16, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
                    "shrinking": self.params._shrink_code() > 0, "wss='second'": self.params.wss == 2,
                    "solver='smo' on a GPU": gpu and self.solver == "smo",
                    f"gram={self.gram!r}": gpu and self.gram != "auto", f"kcache={self.kcache!r}": gpu and self.kcache != "auto",
@@ -169,6 +172,8 @@ class SVC(KernelEstimator):
             self._fit_cuda_weighted(X, y, sw, dev)
         elif f32:
             self._fit_cuda_f32(X, y, dev)
+        elif f16:
+            self._fit_cuda_f16(X, y, dev)
         elif sparse:
             self._fit_cuda_sparse(X, y, dev)
         else:
@@ -177,11 +182,11 @@ class SVC(KernelEstimator):
         return self
 
     def _check_f32(self, dev: str, sparse: bool = False, alpha0=None, cv: bool = False) -> None:
-        """What row_dtype='float32' does not cover raises here, before any device work."""
+        """What row_dtype='float32' / 'float16' does not cover raises here, before any device work."""
         gpu = dev != "cpu"
-        check_f32_rows(**{"sparse (CSR) rows": sparse, "a warm start (alpha0)": alpha0 is not None,
+        check_f32_rows(self.row_dtype, **{"sparse (CSR) rows": sparse, "a warm start (alpha0)": alpha0 is not None,
                           "shrinking": self.params._shrink_code() > 0, "probability=True": self.probability,
-                          "cross-validation": cv, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                          "the Newton polish (SVM355_DECOMP_NEWTON)": gpu and newton_polish_on(), "cross-validation": cv, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
                           "scale=False": not self.scale, "wss='second'": self.params.wss == 2,
                           "solver='smo'": gpu and self.solver == "smo", f"gram={self.gram!r}": gpu and self.gram != "auto",
                           f"kcache={self.kcache!r}": gpu and self.kcache != "auto"})
@@ -341,7 +346,7 @@ class SVC(KernelEstimator):
         check_dot_kernel(self.params, cross_validation=True)
         if is_sparse(X):
             raise ValueError("cross-validation does not take sparse rows (densify them: X.toarray())")
-        if self.row_dtype == "float32":
+        if self.row_dtype != "float64":
             self._check_f32(dev, cv=True)
         X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
         y = np.ascontiguousarray(y, dtype=np.int32)
@@ -519,20 +524,26 @@ class SVC(KernelEstimator):
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 
-    def _fit_cuda_f32(self, X, y, dev):
+    def _fit_cuda_f32(self, X, y, dev, row_dtype="float32"):
         """float32 rows: scaled and rounded once on the device, kernel values from the FP32-MFMA block."""
         import torch
 
         from ..ops import device as D
 
         device = torch.device(dev)
-        rows = TrainRows.upload(X, device, row_dtype="float32")
+        rows = TrainRows.upload(X, device, row_dtype=row_dtype)
         alpha = torch.empty(X.shape[0], dtype=torch.float64, device=device)  # the cold start zeroes it
-        res, tm = D.train_decomp_f32(rows.rows, rows.sqn, rows.d, alpha, self.params, y=torch.from_numpy(y).to(device),
-                                     working_set=self.working_set)
+        train = D.train_decomp_f16 if row_dtype == "float16" else D.train_decomp_f32
+        res, tm = train(rows.rows, rows.sqn, rows.d, alpha, self.params, y=torch.from_numpy(y).to(device),
+                        working_set=self.working_set)
         self._finish(alpha.cpu().numpy(), y, res)
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
+
+    def _fit_cuda_f16(self, X, y, dev):
+        """float16 rows: scaled, rounded to float32 and then float16 on the device, kernel values from the FP16-MFMA
+        block (rows_f16.hip); the float32 routing with the other row source."""
+        self._fit_cuda_f32(X, y, dev, row_dtype="float16")
 
     # ------------------------------------------------------------------ inference
     def decision_function(self, X: np.ndarray) -> np.ndarray:

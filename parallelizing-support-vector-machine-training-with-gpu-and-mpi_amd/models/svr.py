@@ -24,7 +24,7 @@ import numpy as np
 from ..utils.config import SVMParams, default_threads
 from ..utils.sparse import is_sparse, toarray
 from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
-                      check_f32_rows, check_row_dtype, check_sample_weight, host_kernel_decision, solve_on_rows)
+                      check_f32_rows, check_row_dtype, newton_polish_on, check_sample_weight, host_kernel_decision, solve_on_rows)
 
 KIND = "svr"  # model files' kind marker (model_io)
 
@@ -43,7 +43,7 @@ class SVR(KernelEstimator):
                  eps: float = 1e-12, sv_tol: float = 1e-8, max_iter: int = 100000, device: str = "auto",
                  n_threads: int = 0, scale: bool = True, working_set: int = 1024, kernel: str = "rbf", degree: int = 3,
                  coef0: float = 0.0, row_dtype: str = "float64"):
-        self.row_dtype = check_row_dtype(row_dtype)  # "float32": as SVC's (float32 device rows, rows_f32.hip)
+        self.row_dtype = check_row_dtype(row_dtype)  # "float32" / "float16": as SVC's (rows_f32.hip, rows_f16.hip)
         if not (np.isfinite(epsilon) and epsilon >= 0):
             raise ValueError(f"epsilon must be finite and >= 0, got {epsilon!r}")
         self.params = SVMParams(C=C, gamma=gamma, tau=tol, eps=eps, sv_tol=sv_tol, max_iter=max_iter,
@@ -66,11 +66,14 @@ class SVR(KernelEstimator):
         if sparse and dev == "cpu":
             X, sparse = toarray(X), False
         check_dot_kernel(self.params, sparse_rows=sparse and self.params.kernel != "linear")  # csr_linear.hip
-        f32 = self.row_dtype == "float32"
-        if f32:  # what float32 rows do not cover, before any device work
-            check_f32_rows(**{"sparse (CSR) rows": sparse, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
-                              "scale=False": not self.scale})
-        if f32 and dev != "cpu":  # as it is when it is float32; any other dtype (uint8 exactly) cast once
+        f32, f16 = self.row_dtype == "float32", self.row_dtype == "float16"
+        if f32 or f16:  # what float32 / float16 rows do not cover, before any device work
+            check_f32_rows(self.row_dtype, **{"sparse (CSR) rows": sparse, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                              "scale=False": not self.scale,
+                              "the Newton polish (SVM355_DECOMP_NEWTON)": dev != "cpu" and newton_polish_on()})
+        if f16 and getattr(X, "dtype", None) == np.float16:  # as it is, on either device (2 bytes a value over PCIe)
+            X = np.ascontiguousarray(X)
+        elif (f32 or f16) and dev != "cpu":  # as it is when it is float32; any other dtype (uint8 exactly) cast once
             X = np.ascontiguousarray(X, dtype=np.float32)
         elif not sparse:
             X = np.ascontiguousarray(X, dtype=np.uint8 if (dev != "cpu" and _is_u8(X)) else np.float64)
@@ -84,7 +87,7 @@ class SVR(KernelEstimator):
         sw = None
         if sample_weight is not None:
             sw = check_sample_weight(sample_weight, z.shape[0], np.full(z.shape[0], self.params.C), self.params.eps,
-                                     **{"row_dtype='float32'": f32, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                                     **{"row_dtype='float32'": f32, "row_dtype='float16'": f16, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
                                         "scale=False on a GPU": dev != "cpu" and not self.scale})
         t0 = time.perf_counter()
         if dev == "cpu":
@@ -99,6 +102,8 @@ class SVR(KernelEstimator):
                 self._fit_cuda(X, z, dev, sw)
             elif f32:
                 self._fit_cuda_f32(X, z, dev)
+            elif f16:
+                self._fit_cuda_f16(X, z, dev)
             elif sparse:
                 self._fit_cuda_sparse(X, z, dev)
             else:
@@ -175,20 +180,25 @@ class SVR(KernelEstimator):
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
 
-    def _fit_cuda_f32(self, X, z, dev):
+    def _fit_cuda_f32(self, X, z, dev, row_dtype="float32"):
         """float32 rows: scaled and rounded once on the device, kernel values from the FP32-MFMA block."""
         import torch
 
         from ..ops import device as D
 
         device = torch.device(dev)
-        rows = TrainRows.upload(X, device, row_dtype="float32")
+        rows = TrainRows.upload(X, device, row_dtype=row_dtype)
         alpha = torch.empty(2 * X.shape[0], dtype=torch.float64, device=device)
-        res, tm = D.train_decomp_f32(rows.rows, rows.sqn, rows.d, alpha, self.params, z=torch.from_numpy(z).to(device),
-                                     epsilon=self.epsilon, working_set=self.working_set)
+        train = D.train_decomp_f16 if row_dtype == "float16" else D.train_decomp_f32
+        res, tm = train(rows.rows, rows.sqn, rows.d, alpha, self.params, z=torch.from_numpy(z).to(device),
+                        epsilon=self.epsilon, working_set=self.working_set)
         self._finish(alpha.cpu().numpy(), res)
         self._adopt_rows(rows)
         self.timings_ = {"upload_preprocess_ms": rows.upload_ms, **tm}
+
+    def _fit_cuda_f16(self, X, z, dev):
+        """float16 rows (rows_f16.hip): the float32 routing with the other row source."""
+        self._fit_cuda_f32(X, z, dev, row_dtype="float16")
 
     # ------------------------------------------------------------------ inference
     def predict(self, X: np.ndarray) -> np.ndarray:

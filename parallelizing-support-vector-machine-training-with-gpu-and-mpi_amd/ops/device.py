@@ -1147,11 +1147,24 @@ def decision_csr_linear(w: torch.Tensor, Q: DeviceCSR, b: float) -> torch.Tensor
     return out
 
 
-# ---- float32 rows (rows_f32.hip) ----------------------------------------------------------------------------
-def _check_rows_f32(X: torch.Tensor, name: str = "X") -> None:
-    if X.dtype != torch.float32 or X.dim() != 2 or not X.is_contiguous() or X.shape[1] % 16:
-        raise ValueError(f"{name} must be a contiguous 2-D float32 tensor with a row length that is a multiple of 16, "
+# ---- float32 rows (rows_f32.hip) and float16 rows (rows_f16.hip): one set of wrappers, keyed "f32" / "f16" ----------
+_NARROW = {"f32": (torch.float32, 16, "float32"), "f16": (torch.float16, 64, "float16")}  # dtype, row quantum, name
+
+
+def padded_dim_f16(d: int) -> int:
+    """A float16 row's length: d rounded up to the FP16 block kernel's k stage of 64 halves."""
+    return (int(d) + 63) // 64 * 64
+
+
+def _check_rows_narrow(tag: str, X: torch.Tensor, name: str = "X") -> None:
+    dtype, q, dname = _NARROW[tag]
+    if X.dtype != dtype or X.dim() != 2 or not X.is_contiguous() or X.shape[1] % q:
+        raise ValueError(f"{name} must be a contiguous 2-D {dname} tensor with a row length that is a multiple of {q}, "
                          f"got {X.dtype} {tuple(X.shape)}")
+
+
+def _check_rows_f32(X: torch.Tensor, name: str = "X") -> None:
+    _check_rows_narrow("f32", X, name)
 
 
 def upload_rows_f32(X: np.ndarray, device) -> torch.Tensor:
@@ -1162,6 +1175,20 @@ def upload_rows_f32(X: np.ndarray, device) -> torch.Tensor:
     out = device_empty((n, padded_dim(d)), torch.float32, device)
     ctx = DeviceContext.get(out.device)
     N.check(ctx.lib.svmd_upload_rows_f32(ctx.bind(), N.ptr(X), n, d, N.ptr(out), out.shape[1]), "svmd_upload_rows_f32")
+    return out
+
+
+def upload_rows_f16(X: np.ndarray, device) -> torch.Tensor:
+    """Host (n, d) rows -> device (n, padded_dim_f16(d)) zero-padded float16 rows, 2 bytes a value over PCIe.  A
+    float16 array crosses as it is; any other dtype is rounded to float32 and then to float16 on the host (the
+    estimators send those as float32 instead and round on the device after scaling)."""
+    if X.dtype != np.float16:
+        X = np.ascontiguousarray(X, dtype=np.float32).astype(np.float16)
+    X = np.ascontiguousarray(X)
+    n, d = X.shape
+    out = device_empty((n, padded_dim_f16(d)), torch.float16, device)
+    ctx = DeviceContext.get(out.device)
+    N.check(ctx.lib.svmd_upload_rows_f16(ctx.bind(), N.ptr(X), n, d, N.ptr(out), out.shape[1]), "svmd_upload_rows_f16")
     return out
 
 
@@ -1178,16 +1205,29 @@ def minmax_scale_f32_(X: torch.Tensor, d: int) -> Tuple[torch.Tensor, torch.Tens
     return mm[:d], mm[d:], sqn
 
 
-def rbf_block_f32(A: torch.Tensor, B: torch.Tensor, gamma: float, epilogue: str = "store",
-                  coef: Optional[torch.Tensor] = None, f: Optional[torch.Tensor] = None, count: int = -1,
-                  gate: int = 0, ida: Optional[torch.Tensor] = None, idb: Optional[torch.Tensor] = None,
-                  row_off: int = 0, twin_nrow: int = 0) -> torch.Tensor:
-    """The float32 RBF block (svmd_rbf_block_f32) on padded float32 device rows A (m, ld) and B (nb <= 1024, ld).
-    "store": returns K (m, nb) float64.  "sum" / "sum_twin": f[i] += sum_j coef[j] K_ij in place (twin: also
-    f[i + m]) and returns f.  count >= 0: a device-side column count; gate != 0: a no-op.  ida / idb (int32): the
-    rows' training ids (A's default to row_off + i), taken modulo twin_nrow when that is > 0; equal ids give 1.0."""
-    _check_rows_f32(A, "A")
-    _check_rows_f32(B, "B")
+def minmax_scale_f16_(X: torch.Tensor, d: int, src: Optional[torch.Tensor] = None):
+    """Min-max scaling into float16 rows X by ``float16(float32((float64(x) - mn) / range))`` (FP64 subtract and divide,
+    two roundings to nearest-even, subnormal halves kept; a range below 1e-12 divides by 1).  Without ``src`` the
+    values are X's own, scaled in place; with it they are the float32 staging rows ``src`` (``upload_rows_f32``), left
+    as they are, and X is written whole.  Returns (min, max, FP64 squared norms of the rounded rows) as
+    ``minmax_scale_f32_``."""
+    _check_rows_narrow("f16", X)
+    if src is not None:
+        _check_rows_f32(src, "src")
+        if src.shape[0] != X.shape[0] or src.shape[1] < d or src.device != X.device:
+            raise ValueError("src must hold X's rows as float32 on X's device")
+    ctx = _ctx_for(X)
+    mm = torch.empty(2 * d, dtype=torch.float64, device=X.device)
+    sqn = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
+    N.check(ctx.lib.svmd_preprocess_f16(ctx.bind(), N.ptr(src), src.shape[1] if src is not None else 0, N.ptr(X),
+                                        X.shape[0], d, X.shape[1], N.ptr(mm[:d]), N.ptr(mm[d:]), N.ptr(sqn)),
+            "svmd_preprocess_f16")
+    return mm[:d], mm[d:], sqn
+
+
+def _rbf_block_narrow(tag, A, B, gamma, epilogue, coef, f, count, gate, ida, idb, row_off, twin_nrow) -> torch.Tensor:
+    _check_rows_narrow(tag, A, "A")
+    _check_rows_narrow(tag, B, "B")
     if A.shape[1] != B.shape[1]:
         raise ValueError("A and B row lengths differ")
     epi = ("store", "sum", "sum_twin").index(epilogue)
@@ -1202,11 +1242,31 @@ def rbf_block_f32(A: torch.Tensor, B: torch.Tensor, gamma: float, epilogue: str 
           or f.dtype != torch.float64 or not coef.is_contiguous() or not f.is_contiguous()):
         raise ValueError(f"{epilogue}: coef ({nb},) and f ({m * epi},), contiguous float64")
     ctx = _ctx_for(A)
-    N.check(ctx.lib.svmd_rbf_block_f32(ctx.bind(), N.ptr(A), m, A.shape[1], N.ptr(B), nb, B.shape[1], A.shape[1],
-                                       N.ptr(ida), int(row_off), N.ptr(idb), int(twin_nrow), float(gamma), epi,
-                                       int(count), int(gate), N.ptr(K), nb, N.ptr(coef), N.ptr(f)),
-            "svmd_rbf_block_f32")
+    entry = f"svmd_rbf_block_{tag}"
+    N.check(getattr(ctx.lib, entry)(ctx.bind(), N.ptr(A), m, A.shape[1], N.ptr(B), nb, B.shape[1], A.shape[1],
+                                    N.ptr(ida), int(row_off), N.ptr(idb), int(twin_nrow), float(gamma), epi,
+                                    int(count), int(gate), N.ptr(K), nb, N.ptr(coef), N.ptr(f)), entry)
     return K if epi == 0 else f
+
+
+def rbf_block_f32(A: torch.Tensor, B: torch.Tensor, gamma: float, epilogue: str = "store",
+                  coef: Optional[torch.Tensor] = None, f: Optional[torch.Tensor] = None, count: int = -1,
+                  gate: int = 0, ida: Optional[torch.Tensor] = None, idb: Optional[torch.Tensor] = None,
+                  row_off: int = 0, twin_nrow: int = 0) -> torch.Tensor:
+    """The float32 RBF block (svmd_rbf_block_f32) on padded float32 device rows A (m, ld) and B (nb <= 1024, ld).
+    "store": returns K (m, nb) float64.  "sum" / "sum_twin": f[i] += sum_j coef[j] K_ij in place (twin: also
+    f[i + m]) and returns f.  count >= 0: a device-side column count; gate != 0: a no-op.  ida / idb (int32): the
+    rows' training ids (A's default to row_off + i), taken modulo twin_nrow when that is > 0; equal ids give 1.0."""
+    return _rbf_block_narrow("f32", A, B, gamma, epilogue, coef, f, count, gate, ida, idb, row_off, twin_nrow)
+
+
+def rbf_block_f16(A: torch.Tensor, B: torch.Tensor, gamma: float, epilogue: str = "store",
+                  coef: Optional[torch.Tensor] = None, f: Optional[torch.Tensor] = None, count: int = -1,
+                  gate: int = 0, ida: Optional[torch.Tensor] = None, idb: Optional[torch.Tensor] = None,
+                  row_off: int = 0, twin_nrow: int = 0) -> torch.Tensor:
+    """The float16 RBF block (svmd_rbf_block_f16) on padded float16 device rows (row length a multiple of 64):
+    ``rbf_block_f32``'s arguments and results, the dot products on FP16 MFMA."""
+    return _rbf_block_narrow("f16", A, B, gamma, epilogue, coef, f, count, gate, ida, idb, row_off, twin_nrow)
 
 
 def rows_f32_dense(X: torch.Tensor, sqn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1223,16 +1283,27 @@ def rows_f32_dense(X: torch.Tensor, sqn: torch.Tensor, idx: torch.Tensor) -> Tup
     return Xs, ns
 
 
-def train_decomp_f32(X: torch.Tensor, sqn: torch.Tensor, d: int, alpha: torch.Tensor, params: SVMParams,
-                     y: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, epsilon: float = 0.1,
-                     working_set: int = 1024, trace: Optional["N.DecompTrace"] = None) -> Tuple[SMOResult, dict]:
-    """The decomposition solver on scaled float32 rows (svmd_train_decomp_f32): the classifier over the int32 labels
-    ``y`` (alpha: n, out) or epsilon-SVR over the float64 targets ``z`` (alpha: 2n, a then a*).  Kernel values come
-    from the FP32-MFMA block; the RBF, cold start, one GPU; shrinking and the Newton polish raise."""
-    _check_rows_f32(X)
+def rows_f16_dense(X: torch.Tensor, sqn: torch.Tensor, idx: torch.Tensor, d: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(Xs, ns): the float16 rows ``idx`` (int64, device) widened to FP64 rows (k, padded_dim(d)) -- the dense models'
+    row length, not the float16 rows' multiple of 64 -- and their norms."""
+    _check_rows_narrow("f16", X)
+    idx = idx.to(device=X.device, dtype=torch.int64).contiguous()
+    k, ldo = idx.numel(), padded_dim(d)
+    Xs = device_empty((k, ldo), torch.float64, X.device)
+    ns = torch.empty(k, dtype=torch.float64, device=X.device)
+    if k:
+        ctx = _ctx_for(X)
+        N.check(ctx.lib.svmd_rows_f16_dense(ctx.bind(), N.ptr(X), N.ptr(sqn), X.shape[0], X.shape[1], N.ptr(idx), k,
+                                            N.ptr(Xs), ldo, N.ptr(ns)), "svmd_rows_f16_dense")
+    return Xs, ns
+
+
+def _train_decomp_narrow(tag, X, sqn, d, alpha, params, y, z, epsilon, working_set, trace) -> Tuple[SMOResult, dict]:
+    entry = f"svmd_train_decomp_{tag}"
+    _check_rows_narrow(tag, X)
     n = X.shape[0]
     if (y is None) == (z is None):
-        raise ValueError("train_decomp_f32 takes labels y or targets z")
+        raise ValueError(f"train_decomp_{tag} takes labels y or targets z")
     t = y if z is None else z
     want = n if z is None else 2 * n
     if t.shape != (n,) or not t.is_contiguous() or t.dtype != (torch.int32 if z is None else torch.float64):
@@ -1245,16 +1316,33 @@ def train_decomp_f32(X: torch.Tensor, sqn: torch.Tensor, d: int, alpha: torch.Te
     r, tm = N.SvmResult(), N.SvmdTiming()
     st = (ctypes.c_int64 * 16)()
     p = params.to_struct()
-    rc = ctx.lib.svmd_train_decomp_f32(ctx.bind(), N.ptr(X), N.ptr(sqn), n, X.shape[1], int(d), 0 if z is None else 1,
-                                       N.ptr(y), N.ptr(z), float(epsilon), N.ptr(alpha), ctypes.byref(p),
-                                       int(working_set), ctypes.byref(r), ctypes.byref(tm), st,
-                                       ctypes.byref(trace.struct) if trace is not None else None)
+    rc = getattr(ctx.lib, entry)(ctx.bind(), N.ptr(X), N.ptr(sqn), n, X.shape[1], int(d), 0 if z is None else 1,
+                                 N.ptr(y), N.ptr(z), float(epsilon), N.ptr(alpha), ctypes.byref(p),
+                                 int(working_set), ctypes.byref(r), ctypes.byref(tm), st,
+                                 ctypes.byref(trace.struct) if trace is not None else None)
     if rc == 2:  # SVM_ERR_ARG: a refusal (the native table next to csr_rows_check, decomp.hip) or a bad argument
-        raise ValueError(f"svmd_train_decomp_f32: {N.last_error()}")
-    N.check(rc, "svmd_train_decomp_f32")
+        raise ValueError(f"{entry}: {N.last_error()}")
+    N.check(rc, entry)
     return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
-                                      "kcache": "none", "gram_path": "f32-mfma", "rows": "f32",
+                                      "kcache": "none", "gram_path": f"{tag}-mfma", "rows": tag,
                                       "solver": "decomp" if z is None else "decomp-svr",
                                       "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
                                       "working_set": int(st[2]), "update_columns": int(st[4]),
                                       "inner_threads": int(st[5])}
+
+
+def train_decomp_f32(X: torch.Tensor, sqn: torch.Tensor, d: int, alpha: torch.Tensor, params: SVMParams,
+                     y: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, epsilon: float = 0.1,
+                     working_set: int = 1024, trace: Optional["N.DecompTrace"] = None) -> Tuple[SMOResult, dict]:
+    """The decomposition solver on scaled float32 rows (svmd_train_decomp_f32): the classifier over the int32 labels
+    ``y`` (alpha: n, out) or epsilon-SVR over the float64 targets ``z`` (alpha: 2n, a then a*).  Kernel values come
+    from the FP32-MFMA block; the RBF, cold start, one GPU; shrinking and the Newton polish raise."""
+    return _train_decomp_narrow("f32", X, sqn, d, alpha, params, y, z, epsilon, working_set, trace)
+
+
+def train_decomp_f16(X: torch.Tensor, sqn: torch.Tensor, d: int, alpha: torch.Tensor, params: SVMParams,
+                     y: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, epsilon: float = 0.1,
+                     working_set: int = 1024, trace: Optional["N.DecompTrace"] = None) -> Tuple[SMOResult, dict]:
+    """The same on scaled float16 rows (svmd_train_decomp_f16): kernel values from the FP16-MFMA block, the limits
+    those of float32 rows."""
+    return _train_decomp_narrow("f16", X, sqn, d, alpha, params, y, z, epsilon, working_set, trace)

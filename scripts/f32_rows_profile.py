@@ -1,12 +1,14 @@
-"""row_dtype="float32" against the FP64-row path on the same real-valued rows: profiles/f32_rows.md's numbers.
+"""row_dtype="float32" against the FP64-row path on the same real-valued rows: profiles/f32_rows.md's numbers; with
+``--dtypes float32 float16``, float16 rows against float32 rows by the same protocol: profiles/f16_rows.md's.
 
 The rows are bench.py's --input f64-real rows (the synthetic MNIST-shaped pixels plus a uniform [0, 0.5) offset per
 value, the digit-1 one-vs-rest labels) with the headline parameters (C = 10, gamma = 0.00125, tol = 1e-5).  For
-each --n it fits SVC with row_dtype="float64" and "float32" in one process, alternating them: one warm-up fit each,
+each --n it fits SVC with each of --dtypes (default float64 float32) in one process, alternating them: one warm-up fit each,
 then --repeats timed fits each (a host clock around fits that end in a device-to-host copy).  Reports fit time,
 upload + preprocess time, solve time, the device memory the fit grew (the library's workspace is outside torch's
 allocator, so it is read from the free memory), support-vector counts, |b|, and the largest difference of the two
-models' decision values on --heldout held-out rows.  One JSON line per n on stdout.  For per-kernel times run one
+models' decision values on --heldout held-out rows (every dtype against the first of the list).  float32 and float16
+fits are both given the float32 array.  One JSON line per n on stdout.  For per-kernel times run one
 dtype under ``rocprofv3 --kernel-trace --stats -- python scripts/f32_rows_profile.py --only float32 --repeats 1``
 in a run of its own; ``flop`` in the output is the f update's 2 rows x columns x d of the whole fit.
 """
@@ -44,7 +46,8 @@ def main():
     ap.add_argument("--n", type=int, nargs="+", default=[60_000, 250_000])
     ap.add_argument("--heldout", type=int, default=10_000)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--only", choices=["float64", "float32"], default=None)
+    ap.add_argument("--dtypes", nargs="+", choices=["float64", "float32", "float16"], default=["float64", "float32"])
+    ap.add_argument("--only", choices=["float64", "float32", "float16"], default=None)
     ap.add_argument("--seed", type=int, default=2024)
     a = ap.parse_args()
     import torch
@@ -59,13 +62,13 @@ def main():
         d = X.shape[1]
         out = {"n": n, "d": d, "repeats": a.repeats}
         dec = {}
-        dtypes = [a.only] if a.only else ["float64", "float32"]
+        dtypes = [a.only] if a.only else a.dtypes
         est = {t: svm355.SVC(C=10.0, gamma=0.00125, tol=1e-5, device="cuda:0", solver="decomp", row_dtype=t)
                for t in dtypes}
         rec = {t: {"fit_ms": [], "upload_ms": [], "solve_ms": []} for t in dtypes}
         for rep in range(a.repeats + 1):  # rep 0 warms up; the dtypes alternate
             for t in dtypes:
-                Xin = X.astype(np.float32) if t == "float32" else X  # float32 data arrives as float32
+                Xin = X if t == "float64" else X.astype(np.float32)  # float32 data arrives as float32
                 ms, grown = fit_once(est[t], Xin, y)
                 if rep == 0:
                     rec[t]["device_bytes_grown_first_fit"] = int(grown)
@@ -82,9 +85,10 @@ def main():
             dec[t] = m.decision_function(Xte)
             out[t] = rec[t]
         if len(dtypes) == 2:
-            out["max_decision_diff"] = float(np.abs(dec["float64"] - dec["float32"]).max())
-            out["b_diff"] = abs(out["float64"]["b"] - out["float32"]["b"])
-            out["sign_flips"] = int(np.sum(np.sign(dec["float64"]) != np.sign(dec["float32"])))
+            p, q = dtypes
+            out["max_decision_diff"] = float(np.abs(dec[p] - dec[q]).max())
+            out["b_diff"] = abs(out[p]["b"] - out[q]["b"])
+            out["sign_flips"] = int(np.sum(np.sign(dec[p]) != np.sign(dec[q])))
         print(json.dumps(out), flush=True)
         del X, Xte, est
         torch.cuda.empty_cache()
