@@ -210,6 +210,7 @@ _CORE_SIGS = {
     "svm_scale": (c_int32, [_P, c_int64, c_int64, _P, _P]),
     "svm_rbf": (c_double, [_P, _P, c_int64, c_double]),
     "svm_rbf_matrix": (c_int32, [_P, c_int64, _P, c_int64, c_int64, c_double, _P, c_int32]),
+    "svm_kernel_gram": (c_int32, [_P, c_int64, _P, c_int64, c_int64, POINTER(SvmParams), _P, c_int32]),
     "svm_smo_train": (c_int32, [_P, _P, c_int64, c_int64, _P, c_int32, POINTER(SvmParams),
                                 POINTER(SvmResult), _P, c_int64]),
     "svm_smo_train_gram": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int32, POINTER(SvmParams),
@@ -319,6 +320,10 @@ _HIP_SIGS = {
     "svmd_kfun_block": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, POINTER(SvmParams),
                                   c_int32, c_int32, c_int32, _P, c_int64, _P, _P]),
     "svmd_decision_kfun": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64,
+                                     POINTER(SvmParams), c_double, _P]),
+    "svmd_dist_block": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, POINTER(SvmParams),
+                                  c_int32, c_int32, c_int32, _P, c_int64, _P, _P]),
+    "svmd_decision_dist": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64,
                                      POINTER(SvmParams), c_double, _P]),
     "svmd_csr_rows_dense": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P]),
     "svmd_train_decomp_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_double, _P,

@@ -12,8 +12,9 @@ Targets
                                  ovo_proba.hip, the one-wave-per-row pairwise coupling, csr_rbf.hip,
                                  sparse rows against a transposed panel, csr_linear.hip, the linear kernel on
                                  sparse rows as a weight-vector update, rows_f32.hip, float32 rows on
-                                 FP32 MFMA under an FP64 epilogue, and rows_f16.hip, float16 rows on FP16
-                                 MFMA under the same epilogue, among them)
+                                 FP32 MFMA under an FP64 epilogue, rows_f16.hip, float16 rows on FP16
+                                 MFMA under the same epilogue, and decomp_dist.hip, the laplacian / chi2
+                                 distance block on the FP64 VALU with a scalar-loaded B operand, among them)
   bin/svm_serial          g++   main3.cpp-equivalent CLI
   bin/svm_gpu             hipcc gpu_svm_main3/4-equivalent CLI (--n-limit sweep)
   bin/svm_cascade         hipcc mpi_svm_main2/3-equivalent: one process, a thread per GPU, RCCL
@@ -52,6 +53,7 @@ HIP_EXTRA: dict = {
     "csr_linear.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "decomp_kfun.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "decomp_box.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "decomp_dist.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 CORE_SRCS = sorted((CSRC / "core").glob("*.cpp")) + sorted((CSRC / "cascade").glob("*.cpp"))

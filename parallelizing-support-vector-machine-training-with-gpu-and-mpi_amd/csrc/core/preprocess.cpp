@@ -12,6 +12,7 @@
 #include <sys/stat.h>
 
 #include "internal.h"
+#include "kfun.h"
 
 using namespace svm355;
 
@@ -72,6 +73,21 @@ SVM_API int svm_rbf_matrix(const double* A, int64_t m, const double* B, int64_t 
   parallel_for(m, resolve_threads(n_threads), [&](int64_t lo, int64_t hi) {
     for (int64_t i = lo; i < hi; ++i)
       for (int64_t j = 0; j < n; ++j) K[i * n + j] = rbf_direct(A + i * d, B + j * d, d, gamma);
+  });
+  return SVM_OK;
+}
+
+SVM_API int svm_kernel_gram(const double* A, int64_t m, const double* B, int64_t n, int64_t d, const svm_params* p,
+                            double* K, int32_t n_threads) {
+  if (m < 0 || n < 0 || d <= 0 || !K || !p || !kernel_is_dist(p->kernel) || !kfun_params_ok(*p)) {
+    set_error("svm_kernel_gram: bad arguments (kernel 4 (laplacian) or 5 (chi2) with gamma > 0)");
+    return SVM_ERR_ARG;
+  }
+  const int32_t kind = p->kernel;
+  const double gamma = p->gamma;
+  parallel_for(m, resolve_threads(n_threads), [&](int64_t lo, int64_t hi) {
+    for (int64_t i = lo; i < hi; ++i)
+      for (int64_t j = 0; j < n; ++j) K[i * n + j] = dist_kernel_value(kind, gamma, A + i * d, B + j * d, d);
   });
   return SVM_OK;
 }

@@ -36,6 +36,7 @@
 #include "csr_rbf.h"
 #include "decomp.h"
 #include "decomp_dev.h"
+#include "decomp_dist.h"
 #include "decomp_kfun.h"
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
@@ -1175,7 +1176,8 @@ struct Solve {
   bool f32 = false;  // float32 rows (rows_f32.hip): no rows x 1024 block, no column cache, no quantisation plan
   bool f16 = false;  // float16 rows (rows_f16.hip): the same
   bool frows() const { return f32 || f16; }
-  bool kfun = false;  // a dot-product kernel (p.kernel != 0, decomp_kfun.hip): FP64 rows, no norms, no unit diagonal
+  bool kfun = false;  // a dot-product kernel (p.kernel 1..3, decomp_kfun.hip): FP64 rows, no norms, no unit diagonal
+  bool dist = false;  // a distance kernel (p.kernel 4, 5, decomp_dist.hip): FP64 rows, no norms, the RBF's unit diagonal
   int kq = 0;  // the quantised rows' bytes (exact-integer rows)
   const int32_t* y = nullptr;
   double* alpha = nullptr;
@@ -1314,7 +1316,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   w.nw = c.take<double>(kMaxWS, f64);
   w.Xc = c.take<double>(size_t(kMaxWS) * ld, f64);
   w.nc = c.take<double>(kMaxWS, f64);
-  w.Kc = c.take<double>(nr1 * kMaxWS, f64 && !S.kfun);  // the dot-product kernels sum their block in registers
+  w.Kc = c.take<double>(nr1 * kMaxWS, f64 && !S.kfun && !S.dist);  // those kernels sum their block in registers
   w.cslot = c.take<int32_t>(ncol, cache);
   w.crd = c.take<int32_t>(kMaxWS, cache);
   w.cmid = c.take<int32_t>(kMaxWS, cache);
@@ -1361,12 +1363,20 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
 }
 
 // The knob values a dot-product kernel's solve refuses (docs/KNOBS.md): its inner solve is one kernel, 256 threads
-// x 4 points with SVM355_DECOMP_WSS=2's rule, and it keeps no column cache.  Reads the environment only.
+// x 4 points with SVM355_DECOMP_WSS=2's rule, and it keeps no column cache.  A distance kernel's solve (kernel 4, 5)
+// refuses only the forced column cache: its inner solve is the RBF's, with every WSS / NT that is built for.  Reads the
+// environment only.
 int kfun_knobs_check(const char* who, const svm_params& p) {
   if (p.kernel == kKernelRbf) return SVM_OK;
   const char* wss = getenv("SVM355_DECOMP_WSS");
   const char* nt = getenv("SVM355_DECOMP_NT");
   const char* cc = getenv("SVM355_DECOMP_CCACHE");
+  if (kernel_is_dist(p.kernel)) {
+    if (!cc || atoi(cc) == 0) return SVM_OK;
+    set_error("%s: a distance kernel (kernel = %d) does not support a forced column cache (SVM355_DECOMP_CCACHE=1)", who,
+              p.kernel);
+    return SVM_ERR_ARG;
+  }
   const char* what = wss && atoi(wss) != 2  ? "SVM355_DECOMP_WSS other than 2 (its inner solve is the second-order single pair)"
                      : nt && atoi(nt) != 256 ? "SVM355_DECOMP_NT other than 256"
                      : cc && atoi(cc) != 0   ? "a forced column cache (SVM355_DECOMP_CCACHE=1)"
@@ -1507,9 +1517,10 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.csr = csr;
   S.f32 = f32;
   S.f16 = f16;
-  S.kfun = p.kernel != kKernelRbf;
-  if (S.kfun && !f64 && !(csr && p.kernel == kKernelLinear)) {  // sparse rows: the linear kernel only (csr_linear.hip)
-    set_error("decomposition SMO: the dot-product kernels run on FP64 rows");
+  S.dist = kernel_is_dist(p.kernel);
+  S.kfun = p.kernel != kKernelRbf && !S.dist;
+  if ((S.kfun || S.dist) && !f64 && !(csr && p.kernel == kKernelLinear)) {  // sparse rows: the linear kernel only (csr_linear.hip)
+    set_error("decomposition SMO: the dot-product and distance kernels run on FP64 rows");
     return SVM_ERR_ARG;
   }
   S.kq = (f64 || csr || f32 || f16) ? 0 : R.P->kq;
@@ -1703,6 +1714,22 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
       b.coef = cf;
       b.f = w.f;
       return launch_kfun_block(s, twin ? KfunEpilogue::sum_twin : KfunEpilogue::sum, b);
+    }
+    if (S.dist) {  // the same on the distance block (decomp_dist.hip)
+      DistBlock b;
+      b.A = R.X + lo * R.ld;
+      b.m = nloc;
+      b.lda = R.ld;
+      b.B = w.Xc;
+      b.ncap = kMaxWS;
+      b.ldb = R.ld;
+      b.kdim = R.ld;
+      b.kind = S.p.kernel;
+      b.gamma = S.p.gamma;
+      b.ncount = cnt;
+      b.coef = cf;
+      b.f = w.f;
+      return launch_dist_block(s, twin ? DistEpilogue::sum_twin : DistEpilogue::sum, b);
     }
     const int rc = launch_rbf_block_dev(s, R.X + lo * R.ld, R.nrm + lo, nloc, R.ld, w.Xc, w.nc, kMaxWS, R.ld, R.ld,
                                         S.p.gamma, w.Kc, kMaxWS, false, nullptr, cnt, cl, lo);
@@ -2003,6 +2030,19 @@ int enqueue_kww(const Solve& S) {
       b.K = w.Kw;
       b.ldk = kLdw;
       return launch_kfun_block(s, KfunEpilogue::store, b);
+    }
+    if (S.dist) {  // a full launch: symmetric to the bit, a diagonal of exactly 1, and two twins (one row) get 1 too
+      DistBlock b;
+      b.A = b.B = w.Xw;
+      b.m = b.ncap = kMaxWS;
+      b.lda = b.ldb = b.kdim = R.ld;
+      b.kind = S.p.kernel;
+      b.gamma = S.p.gamma;
+      b.gate = gate;
+      b.ncount = &w.ctl->m;
+      b.K = w.Kw;
+      b.ldk = kLdw;
+      return launch_dist_block(s, DistEpilogue::store, b);
     }
     // K(W, W) on FP64 MFMA, columns bounded by m, unit diagonal; skipped once stopped
     const int rc = launch_rbf_block_dev(s, w.Xw, w.nw, kMaxWS, R.ld, w.Xw, w.nw, kMaxWS, R.ld, R.ld, S.p.gamma, w.Kw,
@@ -2408,8 +2448,8 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
   const char* fe = getenv("SVM355_DECOMP_F64");
   const bool force_f64 = fe && atoi(fe) == 1;
   QuantPlan P;
-  const bool kfun = p.kernel != kKernelRbf;  // the dot-product kernels: the FP64 rows, and no rows x 1024 block
-  if (!kfun && !force_f64 && mn_h && mx_h && plan_quant(mn_h, mx_h, d, &P) && P.kq <= 32 * 128) {
+  const bool fp64_only = p.kernel != kKernelRbf;  // the dot-product and distance kernels: the FP64 rows, and no rows x 1024 block
+  if (!fp64_only && !force_f64 && mn_h && mx_h && plan_quant(mn_h, mx_h, d, &P) && P.kq <= 32 * 128) {
     QuantBufs b;
     int rc = decomp_quant_buffers(ctx, n, P, quantize_aux_bytes(P), &b);
     if (rc) return rc;
@@ -2432,7 +2472,7 @@ int decomp_fit_rows(DeviceCtx* ctx, const double* X_d, int64_t n, int64_t ld, in
   // doubles of workspace (8 GB at 1M rows).  When that does not fit 80 % of what the device has free
   // (plus the context's current workspace, which it would replace), nothing runs (*used = false) and
   // the caller takes the pairwise solver (SVC(solver="auto")).
-  if (!kfun) {
+  if (!fp64_only) {
     size_t free_b = 0, total_b = 0;
     SVMD_CHECK(hipMemGetInfo(&free_b, &total_b));
     const double need = double(n) / double(std::max(1, o.world)) * double(kMaxWS) * 8.0 +
@@ -2499,7 +2539,7 @@ int train_decomp(DeviceCtx* ctx, const char* who, const void* X_d, bool is_u8, i
       (rc = decomp_kfun_check(who, p, o.mode.kind, ft, false)) || (rc = kfun_knobs_check(who, p)) ||
       (rc = decomp_box_check(who, p, o.mode.kind, ft, false, false)) || (rc = box_knobs_check(who, o.mode)))
     return rc;
-  if (p.kernel != kKernelRbf && is_u8) {
+  if (p.kernel != kKernelRbf && is_u8) {  // the distance kernels with them
     set_error("%s: the dot-product kernels take FP64 rows (widen and scale the uint8 rows on the device first)", who);
     return SVM_ERR_ARG;
   }

@@ -5,6 +5,11 @@
 //   sigmoid     tanh(gamma x.z + coef0)
 // The integer power is LIBSVM's powi (repeated squaring): one fixed multiplication order, so the device and the
 // host multiply in the same order.  tanh is each side's own library function.
+// The additive distance kernels (svm_params.kernel = 4, 5; hip/decomp_dist.hip), K = exp(-gamma D) with a unit diagonal:
+//   laplacian   D = sum_k |x_k - z_k|
+//   chi2        D = sum_k (x_k - z_k)^2 / (x_k + z_k) over the k with x_k + z_k > 0 (scikit-learn's chi2_kernel;
+//               non-negative inputs)
+// D accumulates over k ascending in one chain on both sides; exp is each side's own library function.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -19,7 +24,9 @@
 
 namespace svm355 {
 
-enum : int32_t { kKernelRbf = 0, kKernelLinear = 1, kKernelPoly = 2, kKernelSigmoid = 3 };
+enum : int32_t {
+  kKernelRbf = 0, kKernelLinear = 1, kKernelPoly = 2, kKernelSigmoid = 3, kKernelLaplacian = 4, kKernelChi2 = 5
+};
 constexpr int32_t kMaxDegree = 16;
 
 struct KFun {
@@ -42,11 +49,35 @@ SVM_KFUN_HD inline double kfun_apply(const KFun& k, double dot) {
   return k.kind == kKernelSigmoid ? tanh(t) : kfun_powi(t, k.degree);
 }
 
+inline bool kernel_is_dist(int32_t kind) { return kind == kKernelLaplacian || kind == kKernelChi2; }
+
+// One term of D.  |a - b|, (a - b)^2 and a + b commute to the bit, so D(x, z) and D(z, x) are the same bits, equal
+// operands (and zero padding) give exactly 0, and the division is IEEE on both sides.
+template <bool CHI2>
+SVM_KFUN_HD inline double dist_term(double a, double b) {
+  const double t = a - b;
+  if (!CHI2) return fabs(t);
+  const double s = a + b;
+  return s > 0.0 ? (t * t) / s : 0.0;
+}
+
+// K(a, b) over d features on the host (the host Gram, svm_kernel_gram): the device block's chain and expression.
+inline double dist_kernel_value(int32_t kind, double gamma, const double* a, const double* b, int64_t d) {
+  double D = 0.0;
+  if (kind == kKernelChi2)
+    for (int64_t k = 0; k < d; ++k) D += dist_term<true>(a[k], b[k]);
+  else
+    for (int64_t k = 0; k < d; ++k) D += dist_term<false>(a[k], b[k]);
+  return std::exp(-gamma * D);
+}
+
 inline KFun kfun_of(const svm_params& p) { return KFun{p.kernel, p.degree, p.gamma, p.coef0}; }
 
-// kernel in 0..3, and for the polynomial 1 <= degree <= 16, a finite coef0.
+// kernel in 0..5, and for the polynomial 1 <= degree <= 16, a finite coef0 for it and the sigmoid; the distance
+// kernels need gamma > 0 and read neither degree nor coef0.
 inline bool kfun_params_ok(const svm_params& p) {
-  if (p.kernel < kKernelRbf || p.kernel > kKernelSigmoid) return false;
+  if (p.kernel < kKernelRbf || p.kernel > kKernelChi2) return false;
+  if (kernel_is_dist(p.kernel)) return p.gamma > 0.0;
   if (p.kernel == kKernelPoly && (p.degree < 1 || p.degree > kMaxDegree)) return false;
   return p.kernel == kKernelRbf || p.kernel == kKernelLinear || std::isfinite(p.coef0);
 }

@@ -59,7 +59,8 @@ typedef struct svm_params {
   double weight_neg; //   [0, C * weight_neg] where y_i = -1 (LIBSVM's -wi); 0 reads as 1 (a zero-filled
                      //   struct from an older caller), negative or non-finite values are SVM_ERR_ARG
   int32_t kernel;    // 0 = RBF exp(-gamma |x - z|^2) (a zero-filled struct from an older caller), 1 = linear x.z,
-                     //   2 = polynomial (gamma x.z + coef0)^degree, 3 = sigmoid tanh(gamma x.z + coef0) (kfun.h)
+                     //   2 = polynomial (gamma x.z + coef0)^degree, 3 = sigmoid tanh(gamma x.z + coef0),
+                     //   4 = laplacian exp(-gamma |x - z|_1), 5 = chi2 exp(-gamma sum (x - z)^2 / (x + z)) (kfun.h)
   int32_t degree;    // the polynomial's, 1..16 (LIBSVM's repeated squaring)
   double coef0;
 } svm_params;
@@ -106,6 +107,11 @@ SVM_API int svm_scale(double* X, int64_t n, int64_t d, const double* mn, const d
 SVM_API double svm_rbf(const double* a, const double* b, int64_t d, double gamma);
 SVM_API int svm_rbf_matrix(const double* A, int64_t m, const double* B, int64_t n, int64_t d,
                            double gamma, double* K, int32_t n_threads);
+// K (m x n, contiguous) of the additive distance kernels: p->kernel = 4 (laplacian) exp(-gamma sum_k |a_k - b_k|)
+// or 5 (chi2) exp(-gamma sum_k (a_k - b_k)^2 / (a_k + b_k)), a term with a_k + b_k = 0 being 0 (kfun.h).  Any
+// other kernel is SVM_ERR_ARG.
+SVM_API int svm_kernel_gram(const double* A, int64_t m, const double* B, int64_t n, int64_t d, const svm_params* p,
+                            double* K, int32_t n_threads);
 
 // ---------------------------------------------------------------- SMO (L3)
 // alpha: in/out length n. warm=0: alpha reset to 0 and f = -y (main3.cpp:165-172).

@@ -310,6 +310,17 @@ SVM_API int svmd_kfun_block(void* ctx, const double* A_d, int64_t m, int64_t lda
 SVM_API int svmd_decision_kfun(void* ctx, const double* Xs_d, const double* coef_d, int64_t nsv, int64_t lds,
                                const double* Xq_d, int64_t m, int64_t ldq, int64_t kdim, const svm_params* p, double b,
                                double* out_d);
+// ---- the additive distance kernels (svm_params.kernel = 4, 5: laplacian, chi2; hip/decomp_dist.hip) ----
+// K = exp(-gamma D), D = sum_k |a_k - b_k| or sum_k (a_k - b_k)^2 / (a_k + b_k) (terms with a_k + b_k = 0 are 0;
+// non-negative rows).  The svmd_train_decomp and svmd_train_decomp_svr entries take them on FP64 rows and refuse what
+// they refuse for the dot-product kernels.  The two entries below take svmd_kfun_block's and svmd_decision_kfun's
+// arguments.
+SVM_API int svmd_dist_block(void* ctx, const double* A_d, int64_t m, int64_t lda, const double* B_d, int64_t nb,
+                            int64_t ldb, int64_t kdim, const svm_params* p, int32_t epi, int32_t count, int32_t gate,
+                            double* K_d, int64_t ldk, const double* coef_d, double* f_d);
+SVM_API int svmd_decision_dist(void* ctx, const double* Xs_d, const double* coef_d, int64_t nsv, int64_t lds,
+                               const double* Xq_d, int64_t m, int64_t ldq, int64_t kdim, const svm_params* p, double b,
+                               double* out_d);
 // Xs_d (k x ld, ld >= d, written whole) = the CSR rows ids_d[0 : k] as dense rows, ns_d[k] their norms.
 SVM_API int svmd_csr_rows_dense(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
                                 const double* nrm_d, int64_t n, int64_t d, const int64_t* ids_d, int64_t k,

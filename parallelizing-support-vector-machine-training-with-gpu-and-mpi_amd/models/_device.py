@@ -368,11 +368,21 @@ def platt_probability(z: np.ndarray) -> np.ndarray:
 
 def check_dot_kernel(params, **off) -> None:
     """What a dot-product kernel (linear, poly, sigmoid) does not cover raises here, before any device work: ``off``
-    maps each unsupported option's description to whether it was asked for."""
-    if params.dot_kernel:
+    maps each unsupported option's description to whether it was asked for.  The distance kernels (laplacian, chi2)
+    cover the same and refuse the same."""
+    if params.gram_kernel:
         for name, on in off.items():
             if on:
                 raise ValueError(f"kernel={params.kernel!r} is not supported with {name.replace('_', ' ')} (the RBF only)")
+
+
+def check_chi2_rows(params, Xs: np.ndarray, what: str = "training rows") -> None:
+    """The chi2 kernel's domain: rows >= 0 after scaling (min-max scaled training rows are by construction; unscaled
+    rows and queries outside the training range need not be).  ValueError naming the first negative column."""
+    if params.kernel == "chi2" and Xs.size and Xs.min() < 0:
+        j = int(np.flatnonzero((Xs < 0).any(0))[0])
+        raise ValueError(f"kernel='chi2' needs non-negative values: column {j} of the {what} holds {Xs[:, j].min()!r}"
+                         + (" after scaling" if what == "queries" else ""))
 
 
 def check_sample_weight(w, n: int, class_box: np.ndarray, eps: float, y=None, **off) -> np.ndarray:
@@ -403,9 +413,11 @@ def check_sample_weight(w, n: int, class_box: np.ndarray, eps: float, y=None, **
 
 
 def host_kernel_decision(est, Xq: np.ndarray, coef: np.ndarray) -> np.ndarray:
-    """sum_k coef_k kfun(x_k . q) - b on the host for a dot-product kernel model, summed in support-vector order."""
+    """sum_k coef_k kfun(x_k . q) - b on the host for a dot-product or distance kernel model, summed in
+    support-vector order."""
     from ..ops import cpu as C
 
+    check_chi2_rows(est.params, Xq, "queries")
     return C.kernel_gram(Xq, est.support_vectors_, est.params) @ coef - est.b_
 
 
@@ -487,6 +499,15 @@ class KernelEstimator:
         from ..ops import device as D
 
         dv = self._dev
+        if self.params.dist_kernel:  # the fused distance block and sum (decomp_dist.hip)
+            if is_sparse(X):
+                raise ValueError(f"sparse queries are not supported with kernel={self.params.kernel!r} (densify them)")
+            Xq = self._device_queries(X)[0]
+            # chi2's domain by one min over the scaled queries (padding is 0, so a negative min is a feature's); the
+            # error path alone looks for the column, and words it as the host's check_chi2_rows does
+            if self.params.kernel == "chi2" and Xq.numel() and float(Xq.min()) < 0:
+                check_chi2_rows(self.params, Xq[:, : dv["d"]].cpu().numpy(), "queries")
+            return D.decision_dist(dv["Xs"], dv["coef"], Xq, self.params, self.b_)
         if self.params.dot_kernel:  # the model's kernel: the fused dot-product block and sum
             if is_sparse(X) and self.params.kernel == "linear":  # one sparse dot product per row with w
                 return D.decision_csr_linear(self._linear_w(), sparse_queries(dv, X, self.scale), self.b_)

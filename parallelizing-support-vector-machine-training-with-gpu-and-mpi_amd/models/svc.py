@@ -27,7 +27,7 @@ import numpy as np
 from ..utils.config import SVMParams, default_threads
 from ..utils.data import check_folds, check_warm_start, resolve_class_weight, stratified_folds
 from ..utils.sparse import is_sparse, toarray
-from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
+from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_chi2_rows, check_dot_kernel,
                       check_f32_rows, check_row_dtype, newton_polish_on, check_sample_weight, host_kernel_decision, platt_probability,
                       scaled_cpu, solve_on_rows)
 
@@ -146,7 +146,7 @@ class SVC(KernelEstimator):
             sw = check_sample_weight(
                 sample_weight, y.shape[0], self.params.box(y), self.params.eps, y,
                 **{"probability=True": self.probability, "a warm start (alpha0)": alpha0 is not None,
-                   "row_dtype='float32'": f32, "row_dtype='float16'": f16, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                   "row_dtype='float32'": f32, "row_dtype='float16'": f16, f"kernel={self.params.kernel!r}": self.params.gram_kernel,
                    "shrinking": self.params._shrink_code() > 0, "wss='second'": self.params.wss == 2,
                    "solver='smo' on a GPU": gpu and self.solver == "smo",
                    f"gram={self.gram!r}": gpu and self.gram != "auto", f"kcache={self.kcache!r}": gpu and self.kcache != "auto",
@@ -186,7 +186,7 @@ class SVC(KernelEstimator):
         gpu = dev != "cpu"
         check_f32_rows(self.row_dtype, **{"sparse (CSR) rows": sparse, "a warm start (alpha0)": alpha0 is not None,
                           "shrinking": self.params._shrink_code() > 0, "probability=True": self.probability,
-                          "the Newton polish (SVM355_DECOMP_NEWTON)": gpu and newton_polish_on(), "cross-validation": cv, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                          "the Newton polish (SVM355_DECOMP_NEWTON)": gpu and newton_polish_on(), "cross-validation": cv, f"kernel={self.params.kernel!r}": self.params.gram_kernel,
                           "scale=False": not self.scale, "wss='second'": self.params.wss == 2,
                           "solver='smo'": gpu and self.solver == "smo", f"gram={self.gram!r}": gpu and self.gram != "auto",
                           f"kcache={self.kcache!r}": gpu and self.kcache != "auto"})
@@ -418,10 +418,11 @@ class SVC(KernelEstimator):
         if self.solver == "decomp":
             raise ValueError("solver='decomp' runs on the GPU (device='cuda'); the CPU oracle is the pairwise SMO")
         Xs = self._scaled_cpu(X)
+        check_chi2_rows(self.params, Xs)  # scale=False: the rows as they came
         if sw is not None:  # the pairwise oracle with a box per point
             alpha, res = C.smo_train_sw(Xs, y, sw, self.params)
             alpha = np.clip(alpha, 0.0, self.params.box(y) * sw)  # as _finish(box=) below, before the SV rows are cut
-        elif self.params.dot_kernel:  # the pairwise oracle on the host Gram of the kernel (its first-order rule)
+        elif self.params.gram_kernel:  # the pairwise oracle on the host Gram of the kernel (its first-order rule)
             alpha, res, _ = C.smo_train_gram(C.kernel_gram(Xs, Xs, self.params), y, self.params, alpha=alpha0,
                                              warm=alpha0 is not None)
         else:
@@ -451,7 +452,7 @@ class SVC(KernelEstimator):
         # the FP64 rows, minus their widen / scale / FP64-quantise passes.  FP64 host rows (the reference's
         # format), and bytes the solver declined, are scaled on the device, then quantised into the same integers
         # or -- real-valued data -- solved with FP64-MFMA kernel values.
-        bytes_ok = X.dtype == np.uint8 and self.scale and not self.params.dot_kernel and (decomp or (
+        bytes_ok = X.dtype == np.uint8 and self.scale and not self.params.gram_kernel and (decomp or (
             self.gram in ("auto", "int") and self.kcache in ("auto", "full")
             and os.environ.get("SVM355_U8_TRAIN", "1") != "0"
             and (self.kcache != "auto" or D.gram_fits(X.shape[0], device))))
@@ -561,7 +562,7 @@ class SVC(KernelEstimator):
 
         X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
-        if self.params.dot_kernel:
+        if self.params.gram_kernel:
             return host_kernel_decision(self, Xq, self.dual_coef_)
         return C.decision(self.support_vectors_, self.support_labels_, self.alpha_[self.support_], Xq,
                           self.params.gamma, self.b_, self.params.n_threads)

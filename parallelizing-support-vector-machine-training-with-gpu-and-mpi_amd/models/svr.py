@@ -23,7 +23,7 @@ import numpy as np
 
 from ..utils.config import SVMParams, default_threads
 from ..utils.sparse import is_sparse, toarray
-from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_dot_kernel,
+from ._device import (KernelEstimator, SparseTrainRows, TrainRows, _is_u8, _resolve_device, check_chi2_rows, check_dot_kernel,
                       check_f32_rows, check_row_dtype, newton_polish_on, check_sample_weight, host_kernel_decision, solve_on_rows)
 
 KIND = "svr"  # model files' kind marker (model_io)
@@ -68,7 +68,7 @@ class SVR(KernelEstimator):
         check_dot_kernel(self.params, sparse_rows=sparse and self.params.kernel != "linear")  # csr_linear.hip
         f32, f16 = self.row_dtype == "float32", self.row_dtype == "float16"
         if f32 or f16:  # what float32 / float16 rows do not cover, before any device work
-            check_f32_rows(self.row_dtype, **{"sparse (CSR) rows": sparse, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+            check_f32_rows(self.row_dtype, **{"sparse (CSR) rows": sparse, f"kernel={self.params.kernel!r}": self.params.gram_kernel,
                               "scale=False": not self.scale,
                               "the Newton polish (SVM355_DECOMP_NEWTON)": dev != "cpu" and newton_polish_on()})
         if f16 and getattr(X, "dtype", None) == np.float16:  # as it is, on either device (2 bytes a value over PCIe)
@@ -87,7 +87,7 @@ class SVR(KernelEstimator):
         sw = None
         if sample_weight is not None:
             sw = check_sample_weight(sample_weight, z.shape[0], np.full(z.shape[0], self.params.C), self.params.eps,
-                                     **{"row_dtype='float32'": f32, "row_dtype='float16'": f16, f"kernel={self.params.kernel!r}": self.params.dot_kernel,
+                                     **{"row_dtype='float32'": f32, "row_dtype='float16'": f16, f"kernel={self.params.kernel!r}": self.params.gram_kernel,
                                         "scale=False on a GPU": dev != "cpu" and not self.scale})
         t0 = time.perf_counter()
         if dev == "cpu":
@@ -127,11 +127,12 @@ class SVR(KernelEstimator):
         from ..ops import cpu as C
 
         Xs = self._scaled_cpu(X)
+        check_chi2_rows(self.params, Xs)  # scale=False: the rows as they came
         if sw is not None:  # the decomposition oracle's twin mode with a box per row, on the host RBF Gram
             K = C.rbf_matrix(Xs, Xs, self.params.gamma, self.params.n_threads)
             alpha2, res, _, _ = C.decomp_train_gram_sw(K, z, sw, self.params, epsilon=self.epsilon, q=self.working_set,
                                                        fp64_rows=True)
-        elif self.params.dot_kernel:  # the decomposition oracle's twin mode on the host Gram (its second-order pair)
+        elif self.params.gram_kernel:  # the decomposition oracle's twin mode on the host Gram (its second-order pair)
             alpha2, res, _, _ = C.decomp_train_gram_svr(C.kernel_gram(Xs, Xs, self.params), z, self.params,
                                                         self.epsilon, q=self.working_set, inner_wss=2)
         else:
@@ -156,7 +157,7 @@ class SVR(KernelEstimator):
             r.rows, zd, alpha, self.params, r.mn_h, r.mx_h, epsilon=self.epsilon, working_set=self.working_set)
             if wd is None else D.train_decomp_sw(r.rows, zd, wd, alpha, self.params, r.mn_h, r.mx_h, epsilon=self.epsilon,
                                                  working_set=self.working_set),
-            bytes_ok=not self.params.dot_kernel)  # a dot-product kernel: the FP64 rows, scaled on the device
+            bytes_ok=not self.params.gram_kernel)  # a dot-product kernel: the FP64 rows, scaled on the device
         if out is None:
             raise ValueError("SVR: the decomposition solver does not cover these rows (its FP64-row workspace, "
                              "n x 1024 doubles, does not fit the device)")
@@ -210,7 +211,7 @@ class SVR(KernelEstimator):
 
         X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
-        if self.params.dot_kernel:
+        if self.params.gram_kernel:
             return host_kernel_decision(self, Xq, self.dual_coef_)
         return C.decision(self.support_vectors_, np.where(self.dual_coef_ > 0, 1, -1), np.abs(self.dual_coef_), Xq,
                           self.params.gamma, self.b_, self.params.n_threads)

@@ -62,7 +62,17 @@ def smo_train(X: np.ndarray, y: np.ndarray, params: SVMParams, alpha: Optional[n
 
 def kernel_gram(A: np.ndarray, B: np.ndarray, params: SVMParams) -> np.ndarray:
     """The host Gram K(A, B) of params' dot-product kernel (linear, poly, sigmoid) in float64; the polynomial's
-    integer power by LIBSVM's repeated squaring, as the native code multiplies."""
+    integer power by LIBSVM's repeated squaring, as the native code multiplies.  The distance kernels (laplacian,
+    chi2) come from the core library (svm_kernel_gram): the device block's accumulation chain, on the host."""
+    if params.dist_kernel:
+        A, B = _c64(A), _c64(B)
+        if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
+            raise ValueError("kernel_gram: A (m, d) and B (n, d)")
+        K = np.empty((A.shape[0], B.shape[0]))
+        p = params.to_struct()
+        N.check(N.core().svm_kernel_gram(N.ptr(A), A.shape[0], N.ptr(B), B.shape[0], A.shape[1], ctypes.byref(p),
+                                         N.ptr(K), int(params.n_threads)), "svm_kernel_gram")
+        return K
     dot = _c64(A) @ _c64(B).T
     if params.kernel == "linear":
         return dot

@@ -443,7 +443,7 @@ def _decomp_rows(X: torch.Tensor) -> int:
 def _check_dot(params: SVMParams, rc: int, entry: str) -> None:
     """``N.check``; what a solve with a dot-product kernel refuses (SVM_ERR_ARG: the native refusal table and
     knob check, decomp_mode.h / decomp.hip -- the one copy of those rules) is a ``ValueError`` with its message."""
-    if rc == 2 and params.dot_kernel:
+    if rc == 2 and params.gram_kernel:  # the distance kernels share the table
         raise ValueError(f"{entry}: {N.last_error()}")
     N.check(rc, entry)
 
@@ -854,6 +854,49 @@ def decision_kfun(Xs: torch.Tensor, coef: torch.Tensor, Xq: torch.Tensor, params
     N.check(ctx.lib.svmd_decision_kfun(ctx.bind(), N.ptr(Xs) if nsv else None, N.ptr(coef) if nsv else None, nsv,
                                        Xs.shape[1], N.ptr(Xq), m, Xq.shape[1], Xq.shape[1], ctypes.byref(p), float(b),
                                        N.ptr(out)), "svmd_decision_kfun")
+    return out
+
+
+def dist_block(A: torch.Tensor, B: torch.Tensor, params: SVMParams, epilogue: str = "store",
+               coef: Optional[torch.Tensor] = None, f: Optional[torch.Tensor] = None, count: int = -1,
+               gate: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The distance kernel block (svmd_dist_block, decomp_dist.hip; kernel "laplacian" or "chi2") on padded FP64
+    device rows A (m, ld) and B (nb, ld), ``kfun_block``'s arguments.  "store": returns K (m, nb), or writes the
+    leading (m, nb) part of ``out`` (contiguous float64, at least m rows and nb columns).  "sum" / "sum_twin": f[i] +=
+    sum_j coef[j] K_ij in place (twin: also f[i + m]) and returns f."""
+    _check_rows(A, "A")
+    _check_rows(B, "B")
+    if A.shape[1] != B.shape[1]:
+        raise ValueError("A and B row lengths differ")
+    epi = ("store", "sum", "sum_twin").index(epilogue)
+    m, nb = A.shape[0], B.shape[0]
+    K = None
+    if epi == 0:
+        K = torch.zeros((m, nb), dtype=torch.float64, device=A.device) if out is None else out
+        if K.dtype != torch.float64 or not K.is_contiguous() or K.shape[0] < m or K.shape[1] < nb:
+            raise ValueError(f"store: out must be contiguous float64 of at least ({m}, {nb})")
+    elif (coef is None or f is None or coef.shape != (nb,) or f.shape != (m * epi,) or coef.dtype != torch.float64
+          or f.dtype != torch.float64 or not coef.is_contiguous() or not f.is_contiguous()):
+        raise ValueError(f"{epilogue}: coef ({nb},) and f ({m * epi},), contiguous float64")
+    ctx = _ctx_for(A)
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_dist_block(ctx.bind(), N.ptr(A), m, A.shape[1], N.ptr(B), nb, B.shape[1], A.shape[1],
+                                    ctypes.byref(p), epi, int(count), int(gate), N.ptr(K),
+                                    K.shape[1] if epi == 0 else nb, N.ptr(coef), N.ptr(f)), "svmd_dist_block")
+    return K if epi == 0 else f
+
+
+def decision_dist(Xs: torch.Tensor, coef: torch.Tensor, Xq: torch.Tensor, params: SVMParams, b: float) -> torch.Tensor:
+    """out[i] = sum_k coef[k] K(Xs_k, Xq_i) - b for a distance kernel (svmd_decision_dist): the fused block and sum
+    over chunks of 1,024 support vectors in order; bit-identical run to run."""
+    _check_rows(Xq, "Xq")
+    m, nsv = Xq.shape[0], Xs.shape[0]
+    out = torch.empty(m, dtype=torch.float64, device=Xq.device)
+    ctx = _ctx_for(Xq)
+    p = params.to_struct()
+    N.check(ctx.lib.svmd_decision_dist(ctx.bind(), N.ptr(Xs) if nsv else None, N.ptr(coef) if nsv else None, nsv,
+                                       Xs.shape[1], N.ptr(Xq), m, Xq.shape[1], Xq.shape[1], ctypes.byref(p), float(b),
+                                       N.ptr(out)), "svmd_decision_dist")
     return out
 
 

@@ -33,7 +33,7 @@ def default_threads(cap: int = 16) -> int:
     return max(1, min(cap, n))
 
 
-KERNELS = ("rbf", "linear", "poly", "sigmoid")  # svm_params.kernel = the index
+KERNELS = ("rbf", "linear", "poly", "sigmoid", "laplacian", "chi2")  # svm_params.kernel = the index
 
 
 @dataclass
@@ -61,6 +61,8 @@ class SVMParams:
     # the kernel function (LIBSVM's -t, scikit-learn's kernel=): "rbf" exp(-gamma |x - z|^2), "linear" x.z,
     # "poly" (gamma x.z + coef0)^degree with 1 <= degree <= 16, "sigmoid" tanh(gamma x.z + coef0).  SVC and SVR
     # take the last three on the CPU and on the one-GPU decomposition solver; everything else is RBF only.
+    # "laplacian" exp(-gamma sum |x - z|) and "chi2" exp(-gamma sum (x - z)^2 / (x + z)) (non-negative rows; a 0 / 0
+    # term is 0) run where those three run; they read neither degree nor coef0.
     kernel: str = "rbf"
     degree: int = 3
     coef0: float = 0.0
@@ -121,6 +123,17 @@ class SVMParams:
     @property
     def dot_kernel(self) -> bool:
         """A kernel of x.z (linear, poly, sigmoid): its diagonal is not 1."""
+        return self.kernel in ("linear", "poly", "sigmoid")
+
+    @property
+    def dist_kernel(self) -> bool:
+        """An additive distance kernel exp(-gamma D) (laplacian, chi2): a unit diagonal, no matrix product."""
+        return self.kernel in ("laplacian", "chi2")
+
+    @property
+    def gram_kernel(self) -> bool:
+        """Any kernel but the RBF: on the CPU the solvers take its host Gram, on a GPU the decomposition solver's
+        FP64-row block kernels (decomp_kfun.hip, decomp_dist.hip)."""
         return self.kernel != "rbf"
 
     def replace(self, **kw) -> "SVMParams":
