@@ -325,6 +325,14 @@ _HIP_SIGS = {
                                   c_int32, c_int32, c_int32, _P, c_int64, _P, _P]),
     "svmd_decision_dist": (c_int32, [c_void_p, _P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64,
                                      POINTER(SvmParams), c_double, _P]),
+    "svmd_train_decomp_gram": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, POINTER(SvmParams), c_int32,
+                                         POINTER(SvmResult), POINTER(SvmdTiming), _P, _P]),
+    "svmd_train_decomp_svr_gram": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_double, _P, POINTER(SvmParams),
+                                             c_int32, POINTER(SvmResult), POINTER(SvmdTiming), _P, _P]),
+    "svmd_gram_check": (c_int32, [c_void_p, _P, c_int64, c_int64, POINTER(c_int64)]),
+    "svmd_decision_gram": (c_int32, [c_void_p, _P, c_int64, c_int64, c_int64, _P, _P, c_int64, c_double, _P]),
+    "svmd_gram_rowsum": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, _P, c_int64, c_int32, c_int32, c_int32, _P]),
+    "svmd_gram_kww": (c_int32, [c_void_p, _P, c_int64, c_int64, _P, c_int32, c_int32, _P, c_int64]),
     "svmd_csr_rows_dense": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P]),
     "svmd_train_decomp_csr": (c_int32, [c_void_p, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_double, _P,
                                         POINTER(SvmParams), c_int32, POINTER(SvmResult), POINTER(SvmdTiming),

@@ -13,8 +13,10 @@ Targets
                                  sparse rows against a transposed panel, csr_linear.hip, the linear kernel on
                                  sparse rows as a weight-vector update, rows_f32.hip, float32 rows on
                                  FP32 MFMA under an FP64 epilogue, rows_f16.hip, float16 rows on FP16
-                                 MFMA under the same epilogue, and decomp_dist.hip, the laplacian / chi2
-                                 distance block on the FP64 VALU with a scalar-loaded B operand, among them)
+                                 MFMA under the same epilogue, decomp_dist.hip, the laplacian / chi2
+                                 distance block on the FP64 VALU with a scalar-loaded B operand, and
+                                 decomp_gram.hip, a precomputed Gram as the row source: a streamed row sum,
+                                 a gather for K(W, W), the symmetry check and prediction, among them)
   bin/svm_serial          g++   main3.cpp-equivalent CLI
   bin/svm_gpu             hipcc gpu_svm_main3/4-equivalent CLI (--n-limit sweep)
   bin/svm_cascade         hipcc mpi_svm_main2/3-equivalent: one process, a thread per GPU, RCCL

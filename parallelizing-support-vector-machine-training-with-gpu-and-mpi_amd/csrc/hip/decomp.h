@@ -83,6 +83,10 @@ struct DecompRows {
   bool f32() const { return X32 != nullptr; }
   const _Float16* X16 = nullptr;
   bool f16() const { return X16 != nullptr; }
+  // a precomputed kernel (svm_params.kernel = 6; decomp_gram.hip): the n x n Gram itself, row stride ld (even, base
+  // 16-byte aligned), symmetric to the bit -- the f update streams its moved rows, K(W, W) is a gather; one GPU
+  const double* K = nullptr;
+  bool gram() const { return K != nullptr; }
 };
 
 // stats: SVM_DECOMP_STATS int64 (see run_decomp).

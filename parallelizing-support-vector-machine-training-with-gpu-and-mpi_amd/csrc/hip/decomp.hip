@@ -37,6 +37,7 @@
 #include "decomp.h"
 #include "decomp_dev.h"
 #include "decomp_dist.h"
+#include "decomp_gram.h"
 #include "decomp_kfun.h"
 #include "decomp_newton.h"
 #include "decomp_shrink.h"
@@ -1178,6 +1179,10 @@ struct Solve {
   bool frows() const { return f32 || f16; }
   bool kfun = false;  // a dot-product kernel (p.kernel 1..3, decomp_kfun.hip): FP64 rows, no norms, no unit diagonal
   bool dist = false;  // a distance kernel (p.kernel 4, 5, decomp_dist.hip): FP64 rows, no norms, the RBF's unit diagonal
+  // a precomputed kernel (p.kernel 6, decomp_gram.hip): the rows are the Gram itself -- no row panels, no column cache,
+  // no quantisation plan; kfun is set with it (the dot-product kernels' inner solve, which reads K_ii from K(W, W))
+  bool gram = false;
+  GramRows gram_rows() const { return GramRows{R.K, nrow, R.ld}; }
   int kq = 0;  // the quantised rows' bytes (exact-integer rows)
   const int32_t* y = nullptr;
   double* alpha = nullptr;
@@ -1297,7 +1302,7 @@ void layout_ws(Solve& S, bool warm, WsCarver& c) {
   DecompWs& w = S.w;
   const size_t nl1 = size_t(std::max<int64_t>(S.nloc, 1)), n = size_t(S.n), kq = size_t(S.kq), ld = size_t(S.R.ld);
   const size_t nr1 = size_t(std::max<int64_t>(S.rows(), 1)), ncol = size_t(S.cols());  // kernel rows / columns
-  const bool f64 = S.f64, q8 = !f64 && !S.csr && !S.frows(), cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
+  const bool f64 = S.f64, q8 = !f64 && !S.csr && !S.frows() && !S.gram, cache = S.cc.slab != nullptr, nzbuf = warm || S.shc.on, pack = S.pack_on;
   w.f = c.take<double>(nl1);
   w.own = c.take<CandRec>(size_t(S.Lr));
   w.all = c.take<CandRec>(size_t(S.sh.L));
@@ -1471,8 +1476,14 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     set_error("decomposition SMO: bad world / rank / exchange");
     return SVM_ERR_ARG;
   }
-  const bool f64 = R.fp64(), csr = R.csr(), f32 = R.f32(), f16 = R.f16();
-  if (csr ? (f64 || f32 || f16 || !R.indices || !R.values || !R.nrm || R.d < 1 || R.dpad < R.d || R.d >= int64_t(INT32_MAX))
+  const bool f64 = R.fp64(), csr = R.csr(), f32 = R.f32(), f16 = R.f16(), gram = R.gram();
+  if (gram != (p.kernel == kKernelPrecomputed)) {
+    set_error("decomposition SMO: a precomputed kernel (kernel = %d) and a Gram as the row source come together "
+              "(svmd_train_decomp_gram, svmd_train_decomp_svr_gram)", kKernelPrecomputed);
+    return SVM_ERR_ARG;
+  }
+  if (gram ? (f64 || csr || f32 || f16 || R.ld < nrow || R.ld % 2 != 0 || (reinterpret_cast<uintptr_t>(R.K) & 15))
+      : csr ? (f64 || f32 || f16 || !R.indices || !R.values || !R.nrm || R.d < 1 || R.dpad < R.d || R.d >= int64_t(INT32_MAX))
       : f32 ? (f64 || f16 || R.ld < 16 || R.ld % 16 != 0 || !R.nrm)
       : f16 ? (f64 || R.ld < kF16RowQuantum || R.ld % kF16RowQuantum != 0 || !R.nrm)
       : f64 ? (R.ld % 16 != 0 || !R.nrm) : (!R.Q || !R.P)) {
@@ -1519,11 +1530,12 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
   S.f16 = f16;
   S.dist = kernel_is_dist(p.kernel);
   S.kfun = p.kernel != kKernelRbf && !S.dist;
-  if ((S.kfun || S.dist) && !f64 && !(csr && p.kernel == kKernelLinear)) {  // sparse rows: the linear kernel only (csr_linear.hip)
+  S.gram = gram;
+  if ((S.kfun || S.dist) && !f64 && !gram && !(csr && p.kernel == kKernelLinear)) {  // sparse rows: the linear kernel only (csr_linear.hip)
     set_error("decomposition SMO: the dot-product and distance kernels run on FP64 rows");
     return SVM_ERR_ARG;
   }
-  S.kq = (f64 || csr || f32 || f16) ? 0 : R.P->kq;
+  S.kq = (f64 || csr || f32 || f16 || gram) ? 0 : R.P->kq;
   S.y = y;  // a mode with its own signs: those, in the workspace (alloc_solve)
   S.alpha = alpha;
   S.mode = o.mode;
@@ -1547,7 +1559,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
     nu_start_walk(p1.C * o.mode.nu * double(nrow) / 2.0, p1.C, nrow, &S.nu_full, &S.nu_frac);
   S.nchunks = (n + kMaxWS - 1) / kMaxWS;
   S.wide_select = !o.mode.nu_pairs() && !o.mode.boxed() && (sh.per > int64_t(kSelNT) * kSelE || sh.T > 64 || S.k.wide_select);
-  S.kww_narrow = !f64 && !csr && !f32 && !f16 && !S.k.kww_sym && S.kq <= 1536;
+  S.kww_narrow = !f64 && !csr && !f32 && !f16 && !gram && !S.k.kww_sym && S.kq <= 1536;
   S.shc = shrink_cfg(p);
   S.pack_on = S.shc.on && !f64 && S.nloc > 0 && S.k.pack;
   const NewtonCfg nwc = newton_cfg(p);
@@ -1570,7 +1582,7 @@ int setup_solve(Solve& S, DeviceCtx* ctx, const DecompRows& R, const int32_t* y,
 int alloc_solve(Solve& S, bool warm) {
   static std::mutex alloc_mu;
   std::lock_guard<std::mutex> alloc_lock(alloc_mu);
-  int rc = (S.csr || S.frows()) ? SVM_OK : size_col_cache(S, warm, &S.cc);  // sparse / float32 / float16 rows: no cache (refused when forced)
+  int rc = (S.csr || S.frows() || S.gram) ? SVM_OK : size_col_cache(S, warm, &S.cc);  // sparse / float32 / float16 rows: no cache (refused when forced)
   if (rc) return rc;
   if ((rc = carve_ws(S.ctx, [&](WsCarver& c) { layout_ws(S, warm, c); }))) return rc;
   if (S.mode.own_signs()) S.y = S.w.sgn;
@@ -1675,6 +1687,8 @@ int f_update(const Solve& S, const PackState& ps, const int32_t* cl, const doubl
   const bool twin = S.mode.twin();
   const int64_t lo = S.lo, nloc = S.rows();
   if (nloc <= 0) return SVM_OK;
+  if (S.gram)  // the moved rows of the Gram streamed once: nothing gathered, nothing computed (decomp_gram.hip)
+    return launch_gram_rowsum(s, S.gram_rows(), lo, nloc, cl, cf, cnt, &w.ctl->stop, twin, w.f);
   if (S.csr) {  // the moved columns' rows into the panel (the working set's leave it), then the fused block + sum
     const CsrRows A = csr_rows(R, S.rows());
     int rc = launch_csr_panel_scatter(s, A, cl, cnt, nullptr, 0, w.panel());
@@ -1987,6 +2001,8 @@ int enqueue_kww(const Solve& S) {
     SVMD_LAUNCH_CHECK();
     return SVM_OK;
   };
+  if (S.gram)  // a gather of the Gram: a point's row is its id mod nrow, so two twins get their row's diagonal
+    return launch_gram_kww(s, S.gram_rows(), w.W, &w.ctl->m, kMaxWS, gate, w.Kw, kLdw);
   if (S.csr) {  // W's rows into the panel, then K(W's rows, panel) stored with the unit diagonal by position
     const CsrRows A = csr_rows(R, S.rows());
     const int64_t tw = S.mode.twin() ? S.nrow : 0;
@@ -2236,7 +2252,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
     stats[3] = int64_t(ms_since(S.t0) * 1000.0);
     stats[4] = fin.changed_total;
     stats[5] = S.k.inner_nt;
-    stats[6] = S.f16 ? 4 : S.f32 ? 3 : S.csr ? 2 : S.f64 ? 1 : 0;
+    stats[6] = S.gram ? 5 : S.f16 ? 4 : S.f32 ? 3 : S.csr ? 2 : S.f64 ? 1 : 0;
     stats[7] = warm_cols;
     stats[8] = ps.unshrinks;
     stats[9] = fin.passes;
@@ -2269,7 +2285,7 @@ int finish_solve(const Solve& S, const PackState& ps, const DecompCtl& fin, int6
 // updates f for its own points.  With world dividing 8 the trajectory is the one-GPU trajectory.
 // stats (kDecompStats = SVM_DECOMP_STATS int64, 13 written): outer iterations, inner iterations, working-set
 // capacity, solve microseconds, columns of the f updates (points moved, summed over the outer iterations),
-// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA, 2 sparse rows, 3 float32 rows, 4 float16 rows), warm-start columns,
+// inner workgroup size, kernel-value path (0 exact-integer int8 MFMA, 1 FP64 MFMA, 2 sparse rows, 3 float32 rows, 4 float16 rows, 5 a precomputed Gram), warm-start columns,
 // unshrinks, shrink passes, the fewest active rows, repacks, Newton polish steps.
 int run_decomp(DeviceCtx* ctx, const DecompRows& R, const int32_t* y, double* alpha, int64_t n, const svm_params& p,
                int qws, svm_result* r, int64_t* stats, const DecompOpts& o) {
@@ -2842,6 +2858,66 @@ SVM_API int svmd_train_decomp_f16(void* h, const void* X_d, const double* nrm_d,
   return train_decomp_frows("svmd_train_decomp_f16", h, nullptr, static_cast<const _Float16*>(X_d), kF16RowQuantum,
                             kF16RowsName, nrm_d, n, ld, d, kind, y_d, z_d, epsilon, alpha_d, pp, q, r, timing, stats,
                             trace);
+}
+
+// The solve on a precomputed kernel (svm355_device.h): the n x n Gram K_d on the device is the row source
+// (decomp_gram.hip).  kind 0 / kind 1 and alpha_d as svmd_train_decomp_csr; the refusals are the dot-product kernels'
+// (decomp_kfun_check, kfun_knobs_check), and sample weights have no entry.
+static int train_decomp_gram(const char* who, void* h, const double* K_d, int64_t n, int64_t ld, int32_t kind,
+                             const int32_t* y_d, const double* z_d, double epsilon, double* alpha_d, const svm_params* pp,
+                             int32_t q, svm_result* r, svmd_timing* timing, int64_t* stats, svm_decomp_trace* trace) {
+  SVMD_CTX(h);
+  if (!K_d || n < 2 || ld < n || ld % 2 != 0 || (reinterpret_cast<uintptr_t>(K_d) & 15) || !alpha_d ||
+      (kind == 0 ? !y_d : !z_d)) {
+    set_error("%s: bad arguments (K n x n with an even row stride ld >= n, 16-byte aligned)", who);
+    return SVM_ERR_ARG;
+  }
+  const svm_params p = params_or_default(pp);
+  if (p.kernel != kKernelPrecomputed) {
+    set_error("%s: kernel must be %d (precomputed), got %d", who, kKernelPrecomputed, p.kernel);
+    return SVM_ERR_ARG;
+  }
+  DecompOpts o;
+  o.trace = trace;
+  if (kind == 1) {
+    o.mode.kind = DecompModeKind::twin;
+    o.mode.twin_z = z_d;
+    o.mode.twin_eps = epsilon;
+  }
+  DecompFeatures ft;
+  int rc = mode_features(o, p, &ft);
+  if (rc || (rc = decomp_mode_check(who, o.mode, y_d, ft, n, DecompBackend::device)) ||
+      (rc = decomp_kfun_check(who, p, o.mode.kind, ft, false)) || (rc = kfun_knobs_check(who, p)))
+    return rc;
+  if (!decomp_shape(o.mode.points(n), q > 0 ? q : 1024, 1).ok) {
+    set_error("%s: n = %lld is outside the solver's shapes", who, (long long)n);
+    return SVM_ERR_ARG;
+  }
+  DecompRows R;
+  R.K = K_d;
+  R.ld = ld;
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = ctx->begin())) return rc;
+  if ((rc = decomp_solve(ctx, R, kind == 0 ? y_d : nullptr, alpha_d, n, p, q, r, stats, o))) return rc;
+  if (timing) {
+    timing->gram_ms = 0.0;  // nothing is prepared here: the Gram arrives whole
+    timing->total_ms = timing->smo_ms = ms_since(t0);
+  }
+  return ctx->end();
+}
+
+SVM_API int svmd_train_decomp_gram(void* h, const double* K_d, int64_t n, int64_t ld, const int32_t* y_d,
+                                   double* alpha_d, const svm_params* pp, int32_t q, svm_result* r, svmd_timing* timing,
+                                   int64_t* stats, svm_decomp_trace* trace) {
+  return train_decomp_gram("svmd_train_decomp_gram", h, K_d, n, ld, 0, y_d, nullptr, 0.0, alpha_d, pp, q, r, timing,
+                           stats, trace);
+}
+
+SVM_API int svmd_train_decomp_svr_gram(void* h, const double* K_d, int64_t n, int64_t ld, const double* z_d,
+                                       double epsilon, double* alpha_d, const svm_params* pp, int32_t q, svm_result* r,
+                                       svmd_timing* timing, int64_t* stats, svm_decomp_trace* trace) {
+  return train_decomp_gram("svmd_train_decomp_svr_gram", h, K_d, n, ld, 1, nullptr, z_d, epsilon, alpha_d, pp, q, r,
+                           timing, stats, trace);
 }
 
 // The held-out form of svmd_train_decomp (svm355_device.h): held-out mode (decomp_mode.h) over the n rows.

@@ -438,8 +438,8 @@ SVM_API int svmd_kfun_block(void* h, const double* A_d, int64_t m, int64_t lda, 
                             int64_t ldb, int64_t kdim, const svm_params* pp, int32_t epi, int32_t count, int32_t gate,
                             double* K_d, int64_t ldk, const double* coef_d, double* f_d) {
   SVMD_CTX(h);
-  if (!pp || !kfun_params_ok(*pp) || pp->kernel == kKernelRbf || epi < 0 || epi > 2 || m < 1 || nb < 1) {
-    set_error("svmd_kfun_block: bad arguments (a dot-product kernel, epi 0..2, m, nb >= 1)");
+  if (!pp || !kfun_params_ok(*pp) || !kernel_is_dot(pp->kernel) || epi < 0 || epi > 2 || m < 1 || nb < 1) {
+    set_error("svmd_kfun_block: bad arguments (a dot-product kernel: 1 linear, 2 poly or 3 sigmoid; epi 0..2; m, nb >= 1)");
     return SVM_ERR_ARG;
   }
   int rc = ctx->begin();
@@ -474,8 +474,8 @@ SVM_API int svmd_decision_kfun(void* h, const double* Xs_d, const double* coef_d
                                const double* Xq_d, int64_t m, int64_t ldq, int64_t kdim, const svm_params* pp,
                                double b, double* out_d) {
   SVMD_CTX(h);
-  if (!pp || !kfun_params_ok(*pp) || pp->kernel == kKernelRbf || !out_d || m < 0 || nsv < 0) {
-    set_error("svmd_decision_kfun: bad arguments (a dot-product kernel)");
+  if (!pp || !kfun_params_ok(*pp) || !kernel_is_dot(pp->kernel) || !out_d || m < 0 || nsv < 0) {
+    set_error("svmd_decision_kfun: bad arguments (a dot-product kernel: 1 linear, 2 poly or 3 sigmoid)");
     return SVM_ERR_ARG;
   }
   int rc = ctx->begin();

@@ -104,15 +104,16 @@ constexpr DecompFeatures kDecompKfunRefuses = {true, true, true, true, false};
 // A dot-product kernel's own arguments and everything such a solve does not cover (csr: sparse rows, which only the
 // linear kernel takes: hip/csr_linear.hip): SVM_ERR_ARG with `who` as the message's prefix, before the caller does
 // any work.  SVM_OK at once for the RBF.  The additive distance kernels (kernel 4, 5: laplacian, chi2;
-// hip/decomp_dist.hip) run with the same kinds and refuse the same things, in the same sentences.
+// hip/decomp_dist.hip) run with the same kinds and refuse the same things, in the same sentences; so does a
+// precomputed kernel (kernel 6: hip/decomp_gram.hip), which reads no gamma.
 inline int decomp_kfun_check(const char* who, const svm_params& p, DecompModeKind kind, const DecompFeatures& f,
                              bool csr) {
   if (p.kernel == kKernelRbf) return SVM_OK;
-  static const char* const name[] = {"rbf", "linear", "poly", "sigmoid", "laplacian", "chi2"};
-  if (!kfun_params_ok(p) || !(p.gamma > 0.0) || !std::isfinite(p.gamma)) {
+  static const char* const name[] = {"rbf", "linear", "poly", "sigmoid", "laplacian", "chi2", "precomputed"};
+  if (!kfun_params_ok(p) || (p.kernel != kKernelPrecomputed && (!(p.gamma > 0.0) || !std::isfinite(p.gamma)))) {
     set_error("%s: kernel must be 0 (rbf), 1 (linear), 2 (poly, 1 <= degree <= %d) or 3 (sigmoid) with a finite "
-              "coef0, 4 (laplacian) or 5 (chi2), and gamma > 0 (kernel = %d, degree = %d, coef0 = %g, gamma = %g)", who,
-              kMaxDegree, p.kernel, p.degree, p.coef0, p.gamma);
+              "coef0, 4 (laplacian) or 5 (chi2), and gamma > 0, or 6 (precomputed: the caller's Gram) (kernel = %d, "
+              "degree = %d, coef0 = %g, gamma = %g)", who, kMaxDegree, p.kernel, p.degree, p.coef0, p.gamma);
     return SVM_ERR_ARG;
   }
   const DecompFeatures& r = kDecompKfunRefuses;

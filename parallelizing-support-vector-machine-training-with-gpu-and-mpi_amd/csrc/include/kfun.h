@@ -10,6 +10,8 @@
 //   chi2        D = sum_k (x_k - z_k)^2 / (x_k + z_k) over the k with x_k + z_k > 0 (scikit-learn's chi2_kernel;
 //               non-negative inputs)
 // D accumulates over k ascending in one chain on both sides; exp is each side's own library function.
+// A precomputed kernel (svm_params.kernel = 6; hip/decomp_gram.hip): no function at all, the solve reads the caller's
+// n x n Gram, which must be symmetric to the bit; gamma, degree and coef0 are not read.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -25,7 +27,8 @@
 namespace svm355 {
 
 enum : int32_t {
-  kKernelRbf = 0, kKernelLinear = 1, kKernelPoly = 2, kKernelSigmoid = 3, kKernelLaplacian = 4, kKernelChi2 = 5
+  kKernelRbf = 0, kKernelLinear = 1, kKernelPoly = 2, kKernelSigmoid = 3, kKernelLaplacian = 4, kKernelChi2 = 5,
+  kKernelPrecomputed = 6
 };
 constexpr int32_t kMaxDegree = 16;
 
@@ -49,6 +52,8 @@ SVM_KFUN_HD inline double kfun_apply(const KFun& k, double dot) {
   return k.kind == kKernelSigmoid ? tanh(t) : kfun_powi(t, k.degree);
 }
 
+// The kernels of x.z that kfun_apply evaluates (hip/decomp_kfun.hip's block): linear, polynomial, sigmoid.
+inline bool kernel_is_dot(int32_t kind) { return kind >= kKernelLinear && kind <= kKernelSigmoid; }
 inline bool kernel_is_dist(int32_t kind) { return kind == kKernelLaplacian || kind == kKernelChi2; }
 
 // One term of D.  |a - b|, (a - b)^2 and a + b commute to the bit, so D(x, z) and D(z, x) are the same bits, equal
@@ -73,10 +78,11 @@ inline double dist_kernel_value(int32_t kind, double gamma, const double* a, con
 
 inline KFun kfun_of(const svm_params& p) { return KFun{p.kernel, p.degree, p.gamma, p.coef0}; }
 
-// kernel in 0..5, and for the polynomial 1 <= degree <= 16, a finite coef0 for it and the sigmoid; the distance
-// kernels need gamma > 0 and read neither degree nor coef0.
+// kernel in 0..6, and for the polynomial 1 <= degree <= 16, a finite coef0 for it and the sigmoid; the distance
+// kernels need gamma > 0 and read neither degree nor coef0; a precomputed kernel reads none of the three.
 inline bool kfun_params_ok(const svm_params& p) {
-  if (p.kernel < kKernelRbf || p.kernel > kKernelChi2) return false;
+  if (p.kernel < kKernelRbf || p.kernel > kKernelPrecomputed) return false;
+  if (p.kernel == kKernelPrecomputed) return true;
   if (kernel_is_dist(p.kernel)) return p.gamma > 0.0;
   if (p.kernel == kKernelPoly && (p.degree < 1 || p.degree > kMaxDegree)) return false;
   return p.kernel == kKernelRbf || p.kernel == kKernelLinear || std::isfinite(p.coef0);

@@ -60,7 +60,8 @@ typedef struct svm_params {
                      //   struct from an older caller), negative or non-finite values are SVM_ERR_ARG
   int32_t kernel;    // 0 = RBF exp(-gamma |x - z|^2) (a zero-filled struct from an older caller), 1 = linear x.z,
                      //   2 = polynomial (gamma x.z + coef0)^degree, 3 = sigmoid tanh(gamma x.z + coef0),
-                     //   4 = laplacian exp(-gamma |x - z|_1), 5 = chi2 exp(-gamma sum (x - z)^2 / (x + z)) (kfun.h)
+                     //   4 = laplacian exp(-gamma |x - z|_1), 5 = chi2 exp(-gamma sum (x - z)^2 / (x + z)),
+                     //   6 = precomputed: the caller's n x n Gram, symmetric to the bit (kfun.h)
   int32_t degree;    // the polynomial's, 1..16 (LIBSVM's repeated squaring)
   double coef0;
 } svm_params;

@@ -321,6 +321,33 @@ SVM_API int svmd_dist_block(void* ctx, const double* A_d, int64_t m, int64_t lda
 SVM_API int svmd_decision_dist(void* ctx, const double* Xs_d, const double* coef_d, int64_t nsv, int64_t lds,
                                const double* Xq_d, int64_t m, int64_t ldq, int64_t kdim, const svm_params* p, double b,
                                double* out_d);
+// ---- a precomputed kernel (svm_params.kernel = 6; hip/decomp_gram.hip) ----
+// The row source is the caller's Gram on the device: K_d, n x n doubles with row stride ld >= n, ld even, K_d 16-byte
+// aligned, finite and symmetric to the bit (svmd_gram_check; the solver reads row j for column j).  The classifier
+// (class weights in *p allowed) over the labels y_d, alpha_d n doubles out; the regression (twin) solve over the
+// targets z_d, alpha_d 2n doubles out (a, then a*).  One GPU, cold start; p->kernel must be 6 and gamma, degree and
+// coef0 are not read; a warm start, shrinking, the Newton polish and sample weights are SVM_ERR_ARG (decomp_mode.h).
+SVM_API int svmd_train_decomp_gram(void* ctx, const double* K_d, int64_t n, int64_t ld, const int32_t* y_d,
+                                   double* alpha_d, const svm_params* p, int32_t q, svm_result* r, svmd_timing* timing,
+                                   int64_t* stats, svm_decomp_trace* trace);
+SVM_API int svmd_train_decomp_svr_gram(void* ctx, const double* K_d, int64_t n, int64_t ld, const double* z_d,
+                                       double epsilon, double* alpha_d, const svm_params* p, int32_t q, svm_result* r,
+                                       svmd_timing* timing, int64_t* stats, svm_decomp_trace* trace);
+// *bad_index (host) = -1 when K_d is finite and symmetric to the bit, else the smallest row-major index i * n + j of
+// an entry that is NaN / infinite or whose bits differ from K[j, i]'s (the same index on every run).
+SVM_API int svmd_gram_check(void* ctx, const double* K_d, int64_t n, int64_t ld, int64_t* bad_index);
+// out_d[q] = sum_s coef_d[s] Kq_d[q * ldq + sv_d[s]] - b for the m rows of a query Gram (m x n_fit, row stride ldq):
+// the support columns sv_d (nsv int32 ids, ascending) gathered, one wave per row, a fixed order.  nsv = 0: -b.
+SVM_API int svmd_decision_gram(void* ctx, const double* Kq_d, int64_t m, int64_t ncol, int64_t ldq, const int32_t* sv_d,
+                               const double* coef_d, int64_t nsv, double b, double* out_d);
+// The two steps alone (tests).  svmd_gram_rowsum: f_d[i] += sum_{k < count} coef_d[k] K_d[cols_d[k] * ld + i] for i <
+// n (twin != 0: also f_d[i + n]); cols_d / coef_d hold ncols <= 1024 entries, count <= ncols is a device-side count
+// of that value, gate the value of the device-side stop gate (non-zero: nothing is written).  svmd_gram_kww: Kw_d[a *
+// ldw + b] = K_d[(W_d[a] mod n) * ld + (W_d[b] mod n)] for a, b < m <= 1024 (W_d: point ids below 2 n).
+SVM_API int svmd_gram_rowsum(void* ctx, const double* K_d, int64_t n, int64_t ld, const int32_t* cols_d,
+                             const double* coef_d, int64_t ncols, int32_t count, int32_t gate, int32_t twin, double* f_d);
+SVM_API int svmd_gram_kww(void* ctx, const double* K_d, int64_t n, int64_t ld, const int32_t* W_d, int32_t m,
+                          int32_t gate, double* Kw_d, int64_t ldw);
 // Xs_d (k x ld, ld >= d, written whole) = the CSR rows ids_d[0 : k] as dense rows, ns_d[k] their norms.
 SVM_API int svmd_csr_rows_dense(void* ctx, const int64_t* indptr_d, const int32_t* indices_d, const double* values_d,
                                 const double* nrm_d, int64_t n, int64_t d, const int64_t* ids_d, int64_t k,

@@ -417,6 +417,10 @@ def host_kernel_decision(est, Xq: np.ndarray, coef: np.ndarray) -> np.ndarray:
     support-vector order."""
     from ..ops import cpu as C
 
+    if est.params.precomputed:  # Xq is the query Gram: its support columns
+        from ._precomputed import _host_f64
+
+        return _host_f64(Xq, "a precomputed kernel's queries")[:, est.support_] @ coef - est.b_
     check_chi2_rows(est.params, Xq, "queries")
     return C.kernel_gram(Xq, est.support_vectors_, est.params) @ coef - est.b_
 
@@ -442,6 +446,8 @@ class KernelEstimator:
         self._sv_host = value
 
     def _n_features(self) -> Optional[int]:
+        if self.params.precomputed:  # the queries' width: the training points
+            return getattr(self, "n_fit_", None)
         if self._dev is not None:
             return int(self._dev["d"])
         if self.scaler_ is not None and self.scaler_.min_ is not None:
@@ -450,6 +456,10 @@ class KernelEstimator:
         return int(sv.shape[1]) if sv is not None and np.ndim(sv) == 2 else None
 
     def _check_X(self, X) -> None:
+        if self.params.precomputed:  # a query Gram (numpy, or a tensor on the model's device)
+            from ._precomputed import check_queries
+
+            return check_queries(X, self._n_features(), self._dev is not None)
         check_query_shape(X, self._n_features())
 
     def _scaled_cpu(self, X: np.ndarray) -> np.ndarray:
@@ -464,6 +474,11 @@ class KernelEstimator:
         self._sv_host = None  # scaled SV rows stay on the device; copied to the host on first access
 
     def _upload_model(self, dev: str) -> None:
+        if self.params.precomputed:
+            from ._precomputed import device_model as gram_model
+
+            self._dev = gram_model(self.support_, self.dual_coef_, self.n_fit_, dev)
+            return
         self._dev = device_model_from_host(self.support_vectors_, self.scaler_, self.dual_coef_, dev)
 
     def _device_model_from_u8(self, X_sv: np.ndarray, dev: str) -> None:
@@ -499,6 +514,10 @@ class KernelEstimator:
         from ..ops import device as D
 
         dv = self._dev
+        if self.params.precomputed:  # X is the query Gram: its support columns gathered (decomp_gram.hip)
+            from ._precomputed import decide_device
+
+            return decide_device(self, X)
         if self.params.dist_kernel:  # the fused distance block and sum (decomp_dist.hip)
             if is_sparse(X):
                 raise ValueError(f"sparse queries are not supported with kernel={self.params.kernel!r} (densify them)")

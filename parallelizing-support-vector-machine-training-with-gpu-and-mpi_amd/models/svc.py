@@ -103,6 +103,8 @@ class SVC(KernelEstimator):
         The CPU pairwise oracle, or on a GPU the decomposition solver with a box per point (decomp_box.hip: one GPU,
         RBF, cold start); the weights are not stored in the model.  None is the unweighted fit."""
         dev = _resolve_device(self.device)
+        if self.params.precomputed:
+            return self._fit_precomputed(X, y, dev, alpha0, folds, sample_weight)
         sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
         weighted_fit = sample_weight is not None
         if weighted_fit and sparse:
@@ -178,6 +180,40 @@ class SVC(KernelEstimator):
             self._fit_cuda_sparse(X, y, dev)
         else:
             self._fit_cuda(X, y, alpha0, dev)
+        self.fit_time_ = time.perf_counter() - t0
+        return self
+
+    def _fit_precomputed(self, K, y, dev, alpha0, folds, sample_weight) -> "SVC":
+        """kernel="precomputed": K is the (n, n) Gram (models/_precomputed.py).  The pairwise oracle on it on the
+        CPU; on a GPU the decomposition solver with the Gram as its row source (decomp_gram.hip)."""
+        from . import _precomputed as G
+        from ..ops import cpu as C
+
+        gpu = dev != "cpu"
+        G.check_options(self, K, sample_weight, probability=self.probability or folds is not None,
+                        **{"a warm start (alpha0)": alpha0 is not None, "wss='second'": self.params.wss == 2,
+                           "shrinking": self.params._shrink_code() > 0, "solver='smo'": gpu and self.solver == "smo",
+                           "solver='decomp' on the CPU": not gpu and self.solver == "decomp",
+                           f"gram={self.gram!r}": gpu and self.gram != "auto",
+                           f"kcache={self.kcache!r}": gpu and self.kcache != "auto"})
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        if y.ndim != 1 or not np.all(np.abs(y) == 1):
+            raise ValueError("labels must be (n,) of +1/-1 (use svm355.utils.data.one_vs_rest)")
+        K = G.as_gram(K, y.shape[0], dev)
+        wp, wn = resolve_class_weight(self.class_weight, y)
+        self.params = self.params.replace(weight_pos=wp, weight_neg=wn)
+        self.class_weight_ = {1: wp, -1: wn}
+        self.probA_ = self.probB_ = self.cv_decision_ = self.cv_folds_ = self.platt_ = None
+        self.classes_ = np.array([-1, 1], dtype=np.int32)
+        t0 = time.perf_counter()
+        if gpu:
+            alpha, res, self.timings_ = G.fit_device(self, K, dev, y.shape[0], y=y)
+        else:
+            G.check_host(K)
+            alpha, res, _ = C.smo_train_gram(K, y, self.params)
+            self.timings_ = {"smo_ms": res.seconds * 1e3}
+        self._finish(alpha, y, res)
+        G.adopt(self, y.shape[0], dev)
         self.fit_time_ = time.perf_counter() - t0
         return self
 
@@ -560,7 +596,8 @@ class SVC(KernelEstimator):
     def _host_decision(self, X: np.ndarray) -> np.ndarray:
         from ..ops import cpu as C
 
-        X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
+        if not self.params.precomputed:  # a query Gram keeps its dtype: anything but float64 raises
+            X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
         if self.params.gram_kernel:
             return host_kernel_decision(self, Xq, self.dual_coef_)
@@ -591,6 +628,7 @@ class SVC(KernelEstimator):
                    alphas=self.alpha_[self.support_], b=self.b_, sv_rows=self.support_vectors_,
                    scaler=self.scaler_, params=self.params,
                    meta={"n_iter": self.n_iter_, "stop_reason": self.stop_reason_,
+                         **({"n_fit": self.n_fit_} if self.params.precomputed else {}),
                          **({"probA": self.probA_, "probB": self.probB_} if self.probA_ is not None else {})})
 
     @classmethod
@@ -619,6 +657,8 @@ class SVC(KernelEstimator):
         svc.alpha_[svc.support_] = alphas
         svc.dual_coef_ = alphas * svc.support_labels_
         svc.classes_ = np.array([-1, 1], dtype=np.int32)
+        if "n_fit" in m["meta"]:  # a precomputed kernel: the queries' width
+            svc.n_fit_ = int(m["meta"]["n_fit"])
         if "probA" in m["meta"] and "probB" in m["meta"]:
             svc.probability = True
             svc.probA_, svc.probB_ = float(m["meta"]["probA"]), float(m["meta"]["probB"])

@@ -60,6 +60,8 @@ class SVR(KernelEstimator):
         weight of 0 leaves the row out.  The decomposition oracle's twin mode on the CPU, the decomposition solver
         with a box per point on a GPU (decomp_box.hip: RBF only); not stored in the model.  None: the unweighted fit."""
         dev = _resolve_device(self.device)
+        if self.params.precomputed:
+            return self._fit_precomputed(X, z, dev, sample_weight)
         sparse = is_sparse(X)  # CSR rows: solved as they are on a GPU, densified for the CPU oracle
         if sample_weight is not None and sparse:
             check_sample_weight(sample_weight, 0, None, 0.0, **{"sparse input": True})
@@ -108,6 +110,31 @@ class SVR(KernelEstimator):
                 self._fit_cuda_sparse(X, z, dev)
             else:
                 self._fit_cuda(X, z, dev)
+        self.fit_time_ = time.perf_counter() - t0
+        return self
+
+    def _fit_precomputed(self, K, z, dev, sample_weight) -> "SVR":
+        """kernel="precomputed": K is the (n, n) Gram (models/_precomputed.py).  The decomposition oracle's twin mode
+        on it on the CPU; on a GPU the decomposition solver with the Gram as its row source (decomp_gram.hip)."""
+        from . import _precomputed as G
+        from ..ops import cpu as C
+
+        G.check_options(self, K, sample_weight)
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.ndim != 1 or not np.all(np.isfinite(z)):
+            raise ValueError("the targets z must be (n,) and finite")
+        K = G.as_gram(K, z.shape[0], dev)
+        if z.shape[0] < 2 or 2 * z.shape[0] > 2**31 - 1:
+            raise ValueError(f"n = {z.shape[0]} rows: SVR needs 2 <= n with 2 n <= 2^31 - 1 variables")
+        t0 = time.perf_counter()
+        if dev != "cpu":
+            alpha2, res, self.timings_ = G.fit_device(self, K, dev, 2 * z.shape[0], z=z, epsilon=self.epsilon)
+        else:
+            G.check_host(K)
+            alpha2, res, _, _ = C.decomp_train_gram_svr(K, z, self.params, self.epsilon, q=self.working_set, inner_wss=2)
+            self.timings_ = {"smo_ms": res.seconds * 1e3}
+        self._finish(alpha2, res)
+        G.adopt(self, z.shape[0], dev)
         self.fit_time_ = time.perf_counter() - t0
         return self
 
@@ -209,7 +236,8 @@ class SVR(KernelEstimator):
             return self._device_decide(X).cpu().numpy()
         from ..ops import cpu as C
 
-        X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
+        if not self.params.precomputed:  # a query Gram keeps its dtype: anything but float64 raises
+            X = np.ascontiguousarray(toarray(X) if is_sparse(X) else X, dtype=np.float64)
         Xq = self.scaler_.transform(X) if self.scaler_ is not None else X
         if self.params.gram_kernel:
             return host_kernel_decision(self, Xq, self.dual_coef_)
@@ -230,7 +258,8 @@ class SVR(KernelEstimator):
         save_model(directory, ids=self.support_, labels=np.where(self.dual_coef_ > 0, 1, -1),
                    alphas=np.abs(self.dual_coef_), b=self.b_, sv_rows=self.support_vectors_, scaler=self.scaler_,
                    params=self.params, kind=KIND,
-                   meta={"n_iter": self.n_iter_, "stop_reason": self.stop_reason_, "epsilon": self.epsilon})
+                   meta={"n_iter": self.n_iter_, "stop_reason": self.stop_reason_, "epsilon": self.epsilon,
+                         **({"n_fit": self.n_fit_} if self.params.precomputed else {})})
 
     @classmethod
     def load(cls, directory: str | os.PathLike, device: str = "cpu") -> "SVR":
@@ -251,11 +280,13 @@ class SVR(KernelEstimator):
         svr.n_iter_ = m["meta"].get("n_iter")
         svr.stop_reason_ = m["meta"].get("stop_reason")
         svr.support_vectors_ = m["sv_rows"]
+        if "n_fit" in m["meta"]:  # a precomputed kernel: the queries' width
+            svr.n_fit_ = int(m["meta"]["n_fit"])
         if _resolve_device(device) != "cpu":
             svr._upload_model(_resolve_device(device))
         return svr
 
     def _upload_model(self, dev: str) -> None:
-        if self.scaler_ is None:
+        if self.scaler_ is None and not self.params.precomputed:
             raise ValueError("SVR on a GPU needs a scaled model (scale=True)")
         super()._upload_model(dev)

@@ -1389,3 +1389,146 @@ def train_decomp_f16(X: torch.Tensor, sqn: torch.Tensor, d: int, alpha: torch.Te
     """The same on scaled float16 rows (svmd_train_decomp_f16): kernel values from the FP16-MFMA block, the limits
     those of float32 rows."""
     return _train_decomp_narrow("f16", X, sqn, d, alpha, params, y, z, epsilon, working_set, trace)
+
+
+# ---- a precomputed kernel (decomp_gram.hip): the Gram itself is the row source -------------------------------
+def padded_gram_dim(n: int) -> int:
+    """The row stride of an uploaded Gram: n rounded up to 8 doubles (64-byte rows: every row starts a 16-byte pair)."""
+    return (int(n) + 7) // 8 * 8
+
+
+def _gram_in_place(K: torch.Tensor) -> bool:
+    return (K.dim() == 2 and K.stride(1) == 1 and K.stride(0) >= K.shape[1] and K.stride(0) % 2 == 0
+            and K.data_ptr() % 16 == 0)
+
+
+def device_gram(K, device) -> torch.Tensor:
+    """A Gram (or query Gram) as the kernels read it: an (m, n) float64 device view with unit column stride, an even
+    row stride and a 16-byte-aligned base.  A float64 numpy array is uploaded once into a row-padded buffer (stride
+    ``padded_gram_dim(n)``); a float64 tensor on ``device`` is used in place when it already has that form, and is
+    copied into the padded buffer once otherwise."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:  # "cuda": the current device, as a tensor's own device names it
+        device = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(K, torch.Tensor):
+        if K.dtype != torch.float64 or K.dim() != 2 or K.device != device:
+            raise ValueError(f"a device Gram must be a 2-D float64 tensor on {device}, got {K.dtype} {tuple(K.shape)} "
+                             f"on {K.device}")
+        if _gram_in_place(K):
+            return K
+        buf = device_empty((K.shape[0], padded_gram_dim(K.shape[1])), torch.float64, device)
+        buf[:, : K.shape[1]].copy_(K)
+        return buf[:, : K.shape[1]]
+    K = np.asarray(K)
+    if K.dtype != np.float64 or K.ndim != 2:
+        raise ValueError(f"a precomputed kernel is a 2-D float64 array, got {K.dtype} {K.shape}")
+    return upload_rows(K, device, ld=padded_gram_dim(K.shape[1]))[:, : K.shape[1]]
+
+
+def gram_check(K: torch.Tensor) -> int:
+    """-1 when the square device Gram K (``device_gram``'s form) is finite and symmetric to the bit, else the
+    smallest row-major index i * n + j of an entry that is NaN / infinite or differs from K[j, i] in its bits
+    (svmd_gram_check: tile pairs through LDS, one 64-bit atomic minimum; the same index on every run)."""
+    n = K.shape[0]
+    if K.shape != (n, n) or not _gram_in_place(K) or K.dtype != torch.float64:
+        raise ValueError("gram_check: a square float64 device Gram (device_gram)")
+    ctx = _ctx_for(K)
+    bad = ctypes.c_int64(0)
+    N.check(ctx.lib.svmd_gram_check(ctx.bind(), N.ptr(K), n, K.stride(0), ctypes.byref(bad)), "svmd_gram_check")
+    return int(bad.value)
+
+
+def train_decomp_gram(K: torch.Tensor, alpha: torch.Tensor, params: SVMParams, y: Optional[torch.Tensor] = None,
+                      z: Optional[torch.Tensor] = None, epsilon: float = 0.1, working_set: int = 1024,
+                      trace: Optional["N.DecompTrace"] = None) -> Tuple[SMOResult, dict]:
+    """The decomposition solver on a precomputed kernel (svmd_train_decomp_gram / _svr_gram): K is the (n, n) device
+    Gram in ``device_gram``'s form, finite and symmetric to the bit (``gram_check``); the classifier over the int32
+    labels ``y`` (alpha: n, out) or epsilon-SVR over the float64 targets ``z`` (alpha: 2n, a then a*).  The f update
+    streams the moved rows of K, K(W, W) is a gather; params.kernel must be "precomputed".  One GPU, cold start; what
+    the dot-product kernels refuse raises here too."""
+    n = K.shape[0]
+    if K.shape != (n, n) or not _gram_in_place(K) or K.dtype != torch.float64:
+        raise ValueError("train_decomp_gram: a square float64 device Gram (device_gram)")
+    if (y is None) == (z is None):
+        raise ValueError("train_decomp_gram takes labels y or targets z")
+    t = y if z is None else z
+    want = n if z is None else 2 * n
+    if t.shape != (n,) or not t.is_contiguous() or t.dtype != (torch.int32 if z is None else torch.float64):
+        raise ValueError(f"y must be int32 / z float64, contiguous, of shape ({n},)")
+    if alpha.dtype != torch.float64 or alpha.shape != (want,) or not alpha.is_contiguous():
+        raise ValueError(f"alpha must be a contiguous float64 tensor of shape ({want},)")
+    ctx = _ctx_for(K)
+    r, tm = N.SvmResult(), N.SvmdTiming()
+    st = (ctypes.c_int64 * 16)()
+    p = params.to_struct()
+    trp = ctypes.byref(trace.struct) if trace is not None else None
+    if z is None:
+        entry = "svmd_train_decomp_gram"
+        rc = ctx.lib.svmd_train_decomp_gram(ctx.bind(), N.ptr(K), n, K.stride(0), N.ptr(y), N.ptr(alpha),
+                                            ctypes.byref(p), int(working_set), ctypes.byref(r), ctypes.byref(tm), st, trp)
+    else:
+        entry = "svmd_train_decomp_svr_gram"
+        rc = ctx.lib.svmd_train_decomp_svr_gram(ctx.bind(), N.ptr(K), n, K.stride(0), N.ptr(z), float(epsilon),
+                                                N.ptr(alpha), ctypes.byref(p), int(working_set), ctypes.byref(r),
+                                                ctypes.byref(tm), st, trp)
+    if rc == 2:  # SVM_ERR_ARG: a refusal of the native table (decomp_mode.h) or a bad argument
+        raise ValueError(f"{entry}: {N.last_error()}")
+    N.check(rc, entry)
+    return SMOResult.from_struct(r), {"gram_ms": tm.gram_ms, "smo_ms": tm.smo_ms, "total_ms": tm.total_ms,
+                                      "kcache": "none", "gram_path": "precomputed", "rows": "gram",
+                                      "solver": "decomp" if z is None else "decomp-svr",
+                                      "outer_iterations": int(st[0]), "inner_iterations": int(st[1]),
+                                      "working_set": int(st[2]), "update_columns": int(st[4]),
+                                      "inner_threads": int(st[5])}
+
+
+def decision_gram(Kq, sv: torch.Tensor, coef: torch.Tensor, b: float, chunk_rows: Optional[int] = None) -> torch.Tensor:
+    """out[q] = sum_s coef[s] Kq[q, sv[s]] - b on the device (svmd_decision_gram): the support columns ``sv`` (int32,
+    ascending) of a query Gram gathered, one wave per row, a fixed order.  Kq: a float64 numpy array, uploaded in row
+    chunks sized to a quarter of the free memory (``chunk_rows`` overrides), or a float64 tensor on sv's device, read
+    in place when ``device_gram`` takes it so."""
+    device = sv.device
+    m, ncol = Kq.shape
+    nsv = sv.shape[0]
+    if sv.dtype != torch.int32 or coef.dtype != torch.float64 or coef.shape != (nsv,) or not sv.is_contiguous() \
+            or not coef.is_contiguous():
+        raise ValueError("decision_gram: sv int32 and coef float64, contiguous, of one length")
+    out = torch.empty(m, dtype=torch.float64, device=device)
+    ctx = _ctx_for(sv)
+    if isinstance(Kq, torch.Tensor):
+        step = max(m, 1)
+    else:
+        free = torch.cuda.mem_get_info(device)[0]
+        step = chunk_rows or max(1, min(m, int(free // 4 // (8 * padded_gram_dim(ncol)))))
+    for q0 in range(0, m, step):
+        part = device_gram(Kq[q0:q0 + step], device)
+        N.check(ctx.lib.svmd_decision_gram(ctx.bind(), N.ptr(part), part.shape[0], ncol, part.stride(0),
+                                           N.ptr(sv) if nsv else None, N.ptr(coef) if nsv else None, nsv, float(b),
+                                           N.ptr(out[q0:q0 + step])), "svmd_decision_gram")
+    return out
+
+
+def gram_rowsum(K: torch.Tensor, cols: torch.Tensor, coef: torch.Tensor, f: torch.Tensor, count: int, gate: int = 0,
+                twin: bool = False) -> torch.Tensor:
+    """The f update's step alone (svmd_gram_rowsum; tests): f[i] += sum_{k < count} coef[k] K[cols[k], i] in place,
+    with ``twin`` also into f[i + n]; count and gate are the device-side values the kernel reads.  Returns f."""
+    n = K.shape[0]
+    if (not _gram_in_place(K) or cols.dtype != torch.int32 or coef.dtype != torch.float64 or cols.shape != coef.shape
+            or f.dtype != torch.float64 or f.shape != (n * (2 if twin else 1),) or not f.is_contiguous()):
+        raise ValueError("gram_rowsum: a device Gram, int32 cols and float64 coef of one length, f (n,) or (2n,)")
+    ctx = _ctx_for(K)
+    N.check(ctx.lib.svmd_gram_rowsum(ctx.bind(), N.ptr(K), n, K.stride(0), N.ptr(cols), N.ptr(coef), cols.shape[0],
+                                     int(count), int(gate), int(twin), N.ptr(f)), "svmd_gram_rowsum")
+    return f
+
+
+def gram_kww(K: torch.Tensor, W: torch.Tensor, gate: int = 0) -> torch.Tensor:
+    """K(W, W) alone (svmd_gram_kww; tests): the (m, m) gather K[W mod n][:, W mod n] of the int32 point ids W."""
+    m = W.shape[0]
+    if not _gram_in_place(K) or W.dtype != torch.int32 or not W.is_contiguous():
+        raise ValueError("gram_kww: a device Gram and int32 ids")
+    Kw = torch.zeros((m, m), dtype=torch.float64, device=K.device)
+    ctx = _ctx_for(K)
+    N.check(ctx.lib.svmd_gram_kww(ctx.bind(), N.ptr(K), K.shape[0], K.stride(0), N.ptr(W), m, int(gate), N.ptr(Kw), m),
+            "svmd_gram_kww")
+    return Kw

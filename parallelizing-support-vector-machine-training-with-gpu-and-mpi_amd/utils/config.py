@@ -33,7 +33,7 @@ def default_threads(cap: int = 16) -> int:
     return max(1, min(cap, n))
 
 
-KERNELS = ("rbf", "linear", "poly", "sigmoid", "laplacian", "chi2")  # svm_params.kernel = the index
+KERNELS = ("rbf", "linear", "poly", "sigmoid", "laplacian", "chi2", "precomputed")  # svm_params.kernel = the index
 
 
 @dataclass
@@ -62,7 +62,8 @@ class SVMParams:
     # "poly" (gamma x.z + coef0)^degree with 1 <= degree <= 16, "sigmoid" tanh(gamma x.z + coef0).  SVC and SVR
     # take the last three on the CPU and on the one-GPU decomposition solver; everything else is RBF only.
     # "laplacian" exp(-gamma sum |x - z|) and "chi2" exp(-gamma sum (x - z)^2 / (x + z)) (non-negative rows; a 0 / 0
-    # term is 0) run where those three run; they read neither degree nor coef0.
+    # term is 0) run where those three run; they read neither degree nor coef0.  "precomputed" (SVC and SVR): fit takes
+    # the (n, n) Gram, finite and symmetric to the bit, and the queries are (m, n); gamma, degree and coef0 are not read.
     kernel: str = "rbf"
     degree: int = 3
     coef0: float = 0.0
@@ -131,9 +132,14 @@ class SVMParams:
         return self.kernel in ("laplacian", "chi2")
 
     @property
+    def precomputed(self) -> bool:
+        """The caller's Gram is the kernel: no rows, no scaling (decomp_gram.hip on a GPU, the oracles as they are)."""
+        return self.kernel == "precomputed"
+
+    @property
     def gram_kernel(self) -> bool:
         """Any kernel but the RBF: on the CPU the solvers take its host Gram, on a GPU the decomposition solver's
-        FP64-row block kernels (decomp_kfun.hip, decomp_dist.hip)."""
+        FP64-row block kernels (decomp_kfun.hip, decomp_dist.hip) or, precomputed, the Gram itself (decomp_gram.hip)."""
         return self.kernel != "rbf"
 
     def replace(self, **kw) -> "SVMParams":
